@@ -2,9 +2,15 @@
 """Headline benchmark: BPR training triplets/s at dim=64 on a synthetic
 1M-user x 1M-item table (BASELINE.json configs[1]), MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the
+last timed step if --dump-outputs is given, and prints the line.  Everything
+else -- the profiled re-run behind the roofline figures, the streaming-copy
+yardstick, the "secondary" workloads, the CPU baseline, the sharded engine's
+diagnosis pass -- runs only with --full.
 
 A "step" = one fused train step (forward on the pre-step tables, gradients of
 loss + l2_loss, exact TF sparse SGD apply) over one batch of 65536 triplets
@@ -91,6 +97,29 @@ def cpu_baseline(args, budget_s=15.0, max_steps=2000):
                 sample=f"{done} steps of {args.batch} triplets on {args.users}x{args.items}x{args.dim} tables, {what}, {dt:.1f} s")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_ROWS = 32768
+DUMP_SEED = 20240917
+
+
+def dump_rows(n_rows, width, budget):
+    """the fixed, seeded sample of table rows --dump-outputs writes (at most `budget` bytes of fp32 rows of `width`
+    elements): int32 row ids, sorted, the same for every run with the same arguments"""
+    n = min(n_rows, DUMP_SAMPLE_ROWS, max(1, budget // (4 * width)))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, n, replace=False)).astype(np.int32)
+
+
+def dump_outputs(path, arrays):
+    """writes {name: array} as path/<name>.npy in float32 (what a caller of the timed path holds after its last step)"""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 CRITEO_KAGGLE_COUNTS = [1460, 583, 10131227, 2202608, 305, 24, 12517, 633, 3, 93145, 5683, 8351593, 3194, 27, 14992, 5461306, 10,
                         5652, 2173, 4, 7046547, 18, 15, 286181, 105, 142572]     # SURVEY.md 8(d) C5
 
@@ -127,12 +156,23 @@ def bench_dlrm(args, torch, rt, world, rank, local_rank, device, dist):
         ctx.synchronize(); torch.cuda.synchronize()
         dt = time.perf_counter() - t0
         par = "single-gpu"
-        # MLP products against the MFMA roofline: 3 products per Dense layer and step (forward, dX, dW;
-        # no dX for the first bottom layer), 2*B*in*out flops each; kernel time from dispatch-attached events
-        ctx.prof_reset(); ctx.prof_enable(True)
-        run(W, K)
-        ctx.prof_enable(False)
-        gp = ctx.prof_get().get("gemm", {})
+        if args.dump_outputs:
+            # the model's parameters after the last timed step: every MLP weight and bias, a fixed sample of embedding rows
+            emb = m.param("emb")
+            arrays = {"emb_rows": emb.gather(dump_rows(emb.rows, emb.dim, 32 << 20))}
+            for part, widths in (("bot", cfg["ln_bot"]), ("top", cfg["ln_top"])):
+                for layer in range(len(widths)):
+                    arrays[f"{part}_w{layer}"] = m.param(f"{part}_w", layer).read()
+                    arrays[f"{part}_b{layer}"] = m.param(f"{part}_b", layer).read()
+            dump_outputs(args.dump_outputs, arrays)
+        gp = {}
+        if args.full:
+            # MLP products against the MFMA roofline: 3 products per Dense layer and step (forward, dX, dW;
+            # no dX for the first bottom layer), 2*B*in*out flops each; kernel time from dispatch-attached events
+            ctx.prof_reset(); ctx.prof_enable(True)
+            run(W, K)
+            ctx.prof_enable(False)
+            gp = ctx.prof_get().get("gemm", {})
         dims = list(zip([13] + cfg["ln_bot"][:-1], cfg["ln_bot"])) + list(zip([128 + 27 * 26 // 2] + cfg["ln_top"][:-1], cfg["ln_top"]))
         flops = sum(2.0 * B * i * o * (2 if k == 0 else 3) for k, (i, o) in enumerate(dims))
         if gp.get("launches"):
@@ -269,7 +309,14 @@ def main():
     ap.add_argument("--users", type=int, default=1_000_000)
     ap.add_argument("--items", type=int, default=1_000_000)
     ap.add_argument("--batch", type=int, default=65536, help="triplets per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / per-kernel figures (a profiled re-run "
+                         "of the K steps), the streaming-copy yardstick, the \"secondary\" workloads, the CPU baseline, the "
+                         "sharded engine's diagnosis pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the trained parameters; a fixed, seeded sample "
+                         "of the rows of large tables) as DIR/<name>.npy in float32, at most 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--hogwild", action="store_true", help="racy non-reference mode (never the headline)")
     ap.add_argument("--sharded", action="store_true", help="use the row-sharded engine even on one GPU (debug)")
     ap.add_argument("--shard-dedup", choices=["auto", "on", "off"], default="auto",
@@ -283,8 +330,10 @@ def main():
     ap.add_argument("--censor", action="store_true",
                     help="UCML: LatentFactor.censor of the touched rows after every step (ucml.py:44-48)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the \"secondary\" block of the headline line (C3 = UCML D=128 + censor, C5 = DLRM with fp16 MLP products)")
+                    help="with --full: skip the \"secondary\" block of the headline line (C3 = UCML D=128 + censor, C5 = DLRM with fp16 MLP products)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.sharded):
+        raise SystemExit("--dump-outputs is implemented for the single-GPU paths only (--gpus 1, without --sharded)")
 
     import torch
     from openrec_amd import runtime as rt
@@ -359,12 +408,23 @@ def main():
         ctx.synchronize()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        # kernel-level timing of the same K steps (HIP events on the library's stream)
-        ctx.prof_reset()
-        ctx.prof_enable(True)
-        losses = run(W, K, want_loss=True)
-        ctx.prof_enable(False)
-        prof = ctx.prof_get()
+        if args.dump_outputs:
+            # the tables after the last timed step (the timed call returns no loss): a fixed sample of user rows, and of item
+            # rows with their biases; GMF's output weights whole
+            su = dump_rows(args.users, args.dim, 24 << 20)
+            si = dump_rows(args.items, args.dim + 1, 24 << 20)
+            arrays = {"user_rows": U.gather(su), "item_rows": V.gather(si), "item_bias": b.gather(si)}
+            if pointwise and wk is not None:
+                arrays["gmf_w"] = wk.read()
+            dump_outputs(args.dump_outputs, arrays)
+        prof, losses = {}, None
+        if args.full:
+            # kernel-level timing of the same K steps (HIP events on the library's stream)
+            ctx.prof_reset()
+            ctx.prof_enable(True)
+            losses = run(W, K, want_loss=True)
+            ctx.prof_enable(False)
+            prof = ctx.prof_get()
         parallelism = "single-gpu"
     else:
         from openrec_amd import sharded
@@ -406,64 +466,64 @@ def main():
         eng.check()
         # ---- diagnosis of the sharded step (after the timed region): the same K steps again with dispatch-attached events on the
         # kernels and HIP events around every exchange, and what a link delivers to the engine's own ncclSend / ncclRecv groups
-        sharded_extra = {}
-
-        def all_ranks_ok(ok):
-            # the diagnosis below makes COLLECTIVE calls: a rank that failed must take the others out with it, not leave them
-            # waiting inside an exchange
-            if dist is None:
-                return ok
-            t = torch.tensor([1 if ok else 0], device=device, dtype=torch.int32)
-            dist.all_reduce(t, op=dist.ReduceOp.MIN)
-            return bool(int(t.item()))
-        try:
-            ready = True
+        sharded_extra, prof = {}, {}
+        if args.full:
+            def all_ranks_ok(ok):
+                # the diagnosis below makes COLLECTIVE calls: a rank that failed must take the others out with it, not leave them
+                # waiting inside an exchange
+                if dist is None:
+                    return ok
+                t = torch.tensor([1 if ok else 0], device=device, dtype=torch.int32)
+                dist.all_reduce(t, op=dist.ReduceOp.MIN)
+                return bool(int(t.item()))
             try:
-                eng.check()
-            except Exception as e:                          # noqa: BLE001
-                ready = False
+                ready = True
+                try:
+                    eng.check()
+                except Exception as e:                          # noqa: BLE001
+                    ready = False
+                    sharded_extra["diagnosis_error"] = repr(e)
+                if not all_ranks_ok(ready):
+                    raise RuntimeError(sharded_extra.get("diagnosis_error", "another rank is not ready for the diagnosis pass"))
+                ping = eng.comm_ping(32 << 20, 5)              # (first: connections are up before anything is timed)
+                eng.be.ctx.prof_reset(); eng.be.ctx.prof_enable(True)
+                eng.comm_stats_start()
+                tq0 = time.perf_counter()
+                eng.steps(uid[W:W + K], pid[W:W + K], nid[W:W + K])
+                torch.cuda.synchronize()
+                tq = time.perf_counter() - tq0
+                st = eng.comm_stats_stop()
+                eng.be.ctx.prof_enable(False)
+                prof = eng.prof()
+                ovf = int(eng._ovf.item()) if eng._ovf is not None else 0
+                ker = {k: v for k, v in prof.items() if v.get("launches")}
+                ker_ms = sum(v["total_ms"] for v in ker.values())
+                bpt_alg = alg_bytes_per_triplet(args.dim, args.opt, args.model)
+                sharded_extra["phases_us"] = {
+                    **{"kernels:" + k: v["total_ms"] / K * 1e3 for k, v in ker.items()},
+                    "exchanges": (st["exchange_ms"] / K * 1e3) if st else None,
+                    "step_profiled": tq / K * 1e6}
+                if ker_ms > 0:
+                    # per rank: the rows of its B triplets are read and written once somewhere in the job -- the single-GPU step's algorithmic
+                    # bytes -- against the time of this rank's kernels (gathers, gradient kernels, applies; the exchanges are not HBM work)
+                    ach = args.batch * bpt_alg * K / (ker_ms * 1e-3) / 1e9
+                    sharded_extra["roofline"] = {"bound": "hbm", "kernel": "this rank's gather / gradient / apply kernels of the sharded step",
+                                                 "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
+                                                 "bytes_per_triplet": bpt_alg, "kernel_us_per_step": ker_ms / K * 1e3}
+                if st:
+                    sharded_extra["link_GBps"] = {
+                        "ping_out_all_links": ping["GBps_out"] if ping else None, "ping_per_link": ping["GBps_per_link"] if ping else None,
+                        "ping_us_per_all_to_all_of_32MiB": ping["us_per_all_to_all"] if ping else None,
+                        "in_step_out_all_links": (st["wire_bytes"] / (st["exchange_ms"] * 1e-3) / 1e9) if st["exchange_ms"] > 0 else None,
+                        "wire_bytes_per_step": st["wire_bytes"] / K, "self_bytes_per_step": st["self_bytes"] / K,
+                        "exchanges_per_step": st["exchanges"] / K}
+                sharded_extra["overflow"] = ovf
+                if args.hot_items:
+                    sharded_extra["hot_items"] = {"H": args.hot_items, "cold_fraction_of_item_references": cold,
+                                                  "allreduce_bytes_per_step": 2.0 * (world - 1) / world * args.hot_items * (args.dim + 4) * 4}
+            except Exception as e:                              # the diagnosis must never hide the number
                 sharded_extra["diagnosis_error"] = repr(e)
-            if not all_ranks_ok(ready):
-                raise RuntimeError(sharded_extra.get("diagnosis_error", "another rank is not ready for the diagnosis pass"))
-            ping = eng.comm_ping(32 << 20, 5)              # (first: connections are up before anything is timed)
-            eng.be.ctx.prof_reset(); eng.be.ctx.prof_enable(True)
-            eng.comm_stats_start()
-            tq0 = time.perf_counter()
-            eng.steps(uid[W:W + K], pid[W:W + K], nid[W:W + K])
-            torch.cuda.synchronize()
-            tq = time.perf_counter() - tq0
-            st = eng.comm_stats_stop()
-            eng.be.ctx.prof_enable(False)
-            prof = eng.prof()
-            ovf = int(eng._ovf.item()) if eng._ovf is not None else 0
-            ker = {k: v for k, v in prof.items() if v.get("launches")}
-            ker_ms = sum(v["total_ms"] for v in ker.values())
-            bpt_alg = alg_bytes_per_triplet(args.dim, args.opt, args.model)
-            sharded_extra["phases_us"] = {
-                **{"kernels:" + k: v["total_ms"] / K * 1e3 for k, v in ker.items()},
-                "exchanges": (st["exchange_ms"] / K * 1e3) if st else None,
-                "step_profiled": tq / K * 1e6}
-            if ker_ms > 0:
-                # per rank: the rows of its B triplets are read and written once somewhere in the job -- the single-GPU step's algorithmic
-                # bytes -- against the time of this rank's kernels (gathers, gradient kernels, applies; the exchanges are not HBM work)
-                ach = args.batch * bpt_alg * K / (ker_ms * 1e-3) / 1e9
-                sharded_extra["roofline"] = {"bound": "hbm", "kernel": "this rank's gather / gradient / apply kernels of the sharded step",
-                                             "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": None,
-                                             "bytes_per_triplet": bpt_alg, "kernel_us_per_step": ker_ms / K * 1e3}
-            if st:
-                sharded_extra["link_GBps"] = {
-                    "ping_out_all_links": ping["GBps_out"] if ping else None, "ping_per_link": ping["GBps_per_link"] if ping else None,
-                    "ping_us_per_all_to_all_of_32MiB": ping["us_per_all_to_all"] if ping else None,
-                    "in_step_out_all_links": (st["wire_bytes"] / (st["exchange_ms"] * 1e-3) / 1e9) if st["exchange_ms"] > 0 else None,
-                    "wire_bytes_per_step": st["wire_bytes"] / K, "self_bytes_per_step": st["self_bytes"] / K,
-                    "exchanges_per_step": st["exchanges"] / K}
-            sharded_extra["overflow"] = ovf
-            if args.hot_items:
-                sharded_extra["hot_items"] = {"H": args.hot_items, "cold_fraction_of_item_references": cold,
-                                              "allreduce_bytes_per_step": 2.0 * (world - 1) / world * args.hot_items * (args.dim + 4) * 4}
-        except Exception as e:                              # the diagnosis must never hide the number
-            sharded_extra["diagnosis_error"] = repr(e)
-            prof = eng.prof()
+                prof = eng.prof()
         losses = None
         parallelism = f"row-sharded x{world}, all-to-all"
 
@@ -533,7 +593,7 @@ def main():
             out["loss_first_last"] = [float(losses[0][0]), float(losses[0][-1])]
         headline = (args.model, args.dim, args.users, args.items, args.batch, args.opt, args.zipf, args.hogwild, args.host_ids, args.censor) == \
                    ("bpr", 64, 1_000_000, 1_000_000, 65536, "sgd", 0.0, False, False, False)
-        if world == 1 and not args.sharded and headline and not args.no_secondary:
+        if args.full and world == 1 and not args.sharded and headline and not args.no_secondary:
             # BASELINE.json configs[2] and configs[4] at the same protocol, after the timed C2 region (the headline tables are
             # released first); a failure here must never hide the headline
             sec = {}
@@ -546,7 +606,7 @@ def main():
                 except Exception as e:
                     sec[key] = {"error": repr(e)}
             out["secondary"] = sec
-        if world == 1 and not args.sharded and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.sharded and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args)
             except Exception as e:                      # the baseline must never hide the GPU number

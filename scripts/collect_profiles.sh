@@ -14,19 +14,19 @@ cd /tmp && export TMPDIR=/tmp
 
 run() {   # run <name> <pmc 0|1> <bench args...>
   local NAME=$1 PMC=$2; shift 2
-  local CMD="python $REPO/bench.py --no-cpu-baseline $*"
+  local CMD="python $REPO/bench.py --full --no-cpu-baseline $*"
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_${TAG}_$NAME -o b -- $CMD > $OUT/${TAG}_${NAME}_prof.log 2>&1
   if [ "$PMC" = "1" ]; then
     local SHORT=$(echo "$CMD" | sed -E 's/--steps [0-9]+/--steps 40/; s/--warmup [0-9]+/--warmup 5/')
     timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/pmcf_${TAG}_$NAME -o f -- $SHORT > /dev/null 2>&1
     timeout 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/pmcw_${TAG}_$NAME -o w -- $SHORT > /dev/null 2>&1
   fi
-  (cd $REPO && timeout 600 python bench.py --no-cpu-baseline "$@" > $OUT/${TAG}_${NAME}_bench.json 2> /dev/null)
+  (cd $REPO && timeout 600 python bench.py --full --no-cpu-baseline "$@" > $OUT/${TAG}_${NAME}_bench.json 2> /dev/null)
 }
 
 # the headline (configs[1]): the driver's protocol (20 steps) and the steady state (200 steps), with the CPU baseline once
 run c2 1 --steps 200 --warmup 20
-(cd $REPO && timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/${TAG}_c2_k20_bench.json 2> /dev/null)
+(cd $REPO && timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_c2_k20_bench.json 2> /dev/null)
 if [ "$WHAT" = "all" ]; then
   run c3_ucml128_censor 1 --model ucml --dim 128 --censor --steps 200 --warmup 20
   run bpr_adagrad 1 --opt adagrad --steps 200 --warmup 20

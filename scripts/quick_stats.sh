@@ -3,7 +3,7 @@
 TAG=$1; shift
 REPO=$(pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/q_$TAG -o q -- python $REPO/bench.py --no-cpu-baseline "$@" > $OUT/q_$TAG.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/q_$TAG -o q -- python $REPO/bench.py --full --no-cpu-baseline "$@" > $OUT/q_$TAG.log 2>&1
 cd $REPO
 python - <<PY
 import csv, glob

@@ -1,6 +1,6 @@
 """The host-only pieces of the TensorFlow shim the reference's example scripts touch (SURVEY.md Appendix C;
 tf2_examples/bpr_citeulike.py:1-67, dlrm_criteo.py:1-60): no device needed -- the train step itself is covered on the GPU
-(tests/test_gpu_reference_examples.py runs both scripts textually)."""
+(tests/test_gpu_reference_examples.py runs the example scripts of examples/)."""
 import sys
 
 import numpy as np

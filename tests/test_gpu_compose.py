@@ -1,39 +1,25 @@
-"""The reference's recommenders are COMPOSITIONS of its modules (openrec/tf2/recommenders/bpr.py:5-43, wrmf.py:5-40:
-`LatentFactor` lookups -> `PairwiseLogLoss` / `PointwiseMSELoss` -> `tf.nn.l2_loss`).  Here the reference's own class text
-is executed against this package's modules (`openrec.tf2.modules`, `tensorflow.keras.Model`, `tf.nn`, `tf.linalg` resolved by
-compat.install()) and trained with the example's train step (tf2_examples/bpr_citeulike.py:33-39): the composition must run
-as the fused device step -- the K-step queue of the native pairwise / pointwise entry points -- and give the oracle's
-tables, not a host-side forward without gradients.  The class text comes from /root/reference here and from the git-ignored
-blob __graft_entry__.build() writes on the GPU box."""
-import json
-import os
+"""The recommenders of the TF-2 API are COMPOSITIONS of its modules: `LatentFactor` lookups -> `PairwiseLogLoss` /
+`PointwiseMSELoss` / a hinge / BCE -> `tf.nn.l2_loss`.  The classes of tests/compose_models.py write the five compositions by hand
+against this package's modules (`openrec_amd.tf2.modules`, the `Model` / `tf.nn` / `tf.linalg` of openrec_amd.tf2.compat) and are
+trained here with a tape-style train step (`@tf.function`, `tf.GradientTape`, `optimizer.apply_gradients`): each composition must
+run as the fused device step -- the K-step queue of the native pairwise / pointwise / DLRM entry points -- and give the oracle's
+tables, not a host-side forward without gradients."""
 import warnings
-import zlib
 
 import numpy as np
 import pytest
 
+import compose_models
 from conftest import TOL, TOL_ADAM, rel_err
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _ref_class(fname, cls):
-    ref = os.path.join("/root/reference/openrec/tf2/recommenders", fname)
-    if os.path.exists(ref):
-        text = open(ref).read()
-    else:
-        blob = os.path.join(ROOT, "tests", "golden", "_ref_scripts.bin")
-        texts = json.loads(zlib.decompress(open(blob, "rb").read()).decode()) if os.path.exists(blob) else {}
-        if "recommenders/" + fname not in texts:
-            pytest.skip("reference recommender sources unavailable: neither /root/reference nor the blob of __graft_entry__.build()")
-        text = texts["recommenders/" + fname]
+def _composed(cls):
+    """the hand-written composition `cls` of tests/compose_models.py, with `import tensorflow` resolved to the shim"""
     from openrec_amd.tf2 import compat
     compat.install()
-    ns = {"__name__": "ref_" + fname[:-3]}
-    exec(compile(text, fname, "exec"), ns)
-    return ns[cls]
+    return getattr(compose_models, cls)
 
 
 def _train_step(model, optimizer):
@@ -58,7 +44,7 @@ def test_reference_bpr_class_text_trains_on_the_fused_path(optk):
     from openrec_amd.tf2.compat import optimizers
     from openrec_amd.tf2.modules._compose import _models
     from oracle import numpy_oracle as orc
-    BPR = _ref_class("bpr.py", "BPR")
+    BPR = _composed("BPR")
     NU, NI, D, B = 700, 900, 32, 1024
     model = BPR(dim_user_embed=D, dim_item_embed=D, total_users=NU, total_items=NI)
     names = [v.name for v in model.trainable_variables]
@@ -87,7 +73,7 @@ def test_reference_bpr_class_text_trains_on_the_fused_path(optk):
     Ud, Vd, bd = (v.numpy() for v in model.trainable_variables)
     assert rel_err(Ud, U) < tol and rel_err(Vd, V) < tol and rel_err(bd, b) < tol
     assert np.abs(Ud - U0).max() > 1e-4                                  # it trained
-    # inference (bpr.py:39-43) through tf.linalg.matmul(...) + tf.reshape(...): the device scorer
+    # inference through tf.linalg.matmul(...) + tf.reshape(...): the device scorer
     pred = model.inference(np.arange(16, dtype=np.int32))
     assert pred.shape == (16, NI) and rel_err(np.asarray(pred), orc.bpr_inference(U, V, b, np.arange(16))) < 1e-4
     # eager call outside a tape: forward only
@@ -106,7 +92,7 @@ def test_reference_bpr_class_text_trains_on_the_fused_path(optk):
 def test_reference_wrmf_class_text_trains_on_the_fused_path():
     from openrec_amd.tf2.compat import optimizers
     from oracle import numpy_oracle as orc
-    WRMF = _ref_class("wrmf.py", "WRMF")
+    WRMF = _composed("WRMF")
     NU, NI, D, B = 500, 800, 64, 2048
     model = WRMF(dim_user_embed=D, dim_item_embed=D, total_users=NU, total_items=NI, a=2.0, b=0.5)
     opt, oo = optimizers.Adagrad(0.02), orc.Adagrad(0.02)
@@ -129,11 +115,11 @@ def test_reference_wrmf_class_text_trains_on_the_fused_path():
 
 @pytest.mark.parametrize("optk", ["sgd", "adagrad"])
 def test_reference_ucml_class_text_trains_on_the_fused_path(optk):
-    """ucml.py:21-42 spells its score out in raw ops (tf.math.square(user_vec - item_vec) -> reduce_sum -> hinge): the lazy
-    expression tree of modules/_expr.py must match it onto the fused UCML step, censor_vec (ucml.py:44-48) included."""
+    """UCML spells its score out in raw ops (tf.math.square(user_vec - item_vec) -> reduce_sum -> hinge): the lazy
+    expression tree of modules/_expr.py must match it onto the fused UCML step, censor_vec included."""
     from openrec_amd.tf2.compat import optimizers
     from oracle import numpy_oracle as orc
-    UCML = _ref_class("ucml.py", "UCML")
+    UCML = _composed("UCML")
     NU, NI, D, B = 600, 800, 32, 1024
     model = UCML(dim_user_embed=D, dim_item_embed=D, total_users=NU, total_items=NI, margin=0.7)
     opt, oo = {"sgd": (optimizers.SGD(0.05), orc.SGD(0.05)), "adagrad": (optimizers.Adagrad(0.05), orc.Adagrad(0.05))}[optk]
@@ -152,17 +138,17 @@ def test_reference_ucml_class_text_trains_on_the_fused_path(optk):
         Ud, Vd, bd = (v.numpy() for v in model.trainable_variables)
         assert rel_err(Ud, U) < TOL and rel_err(Vd, V) < TOL and rel_err(bd, b) < TOL
         assert np.abs(Ud - U0).max() > 1e-4
-        # inference (ucml.py:50-53): -reduce_sum(square(expand_dims(user_vec, 1) - V), -1) + reshape(b): the device L2 scorer
+        # inference: -reduce_sum(square(expand_dims(user_vec, 1) - V), -1) + reshape(b): the device L2 scorer
         pred = model.inference(np.arange(16, dtype=np.int32))
     assert pred.shape == (16, NI) and rel_err(np.asarray(pred), orc.ucml_inference(U, V, b, np.arange(16))) < 1e-4
 
 
 def test_reference_gmf_class_text_trains_on_the_fused_path():
-    """gmf.py:22-34: MLP([1], no bias) of (user_vec * item_vec) + item_bias -> Keras BCE with logits; l2 over the lookups and the
+    """GMF: MLP([1], no bias) of (user_vec * item_vec) + item_bias -> Keras BCE with logits; l2 over the lookups and the
     Dense kernel.  The composition must run as the fused GMF step (the kernel is a device-resident dense parameter)."""
     from openrec_amd.tf2.compat import optimizers
     from oracle import numpy_oracle as orc
-    GMF = _ref_class("gmf.py", "GMF")
+    GMF = _composed("GMF")
     NU, NI, D, B = 500, 700, 32, 2048
     model = GMF(dim_user_embed=D, dim_item_embed=D, total_users=NU, total_items=NI)
     opt, oo = optimizers.SGD(0.05), orc.SGD(0.05)
@@ -190,7 +176,7 @@ def test_reference_gmf_class_text_trains_on_the_fused_path():
         Ud, Vd, bd, wd = (v.numpy() for v in model.trainable_variables)
         assert rel_err(Ud, U) < TOL and rel_err(Vd, V) < TOL and rel_err(bd, b) < TOL and rel_err(wd, w) < TOL
         assert np.abs(wd - W0).max() > 1e-5                              # the Dense kernel trained
-        # inference (gmf.py:36-41): squeeze(mlp(expand_dims(user_vec, 1) * V), -1) + reshape(b): the device GMF scorer
+        # inference: squeeze(mlp(expand_dims(user_vec, 1) * V), -1) + reshape(b): the device GMF scorer
         pred = model.inference(np.arange(8, dtype=np.int32))
     want = (U[:8, None, :] * V[None, :, :]) @ w.reshape(-1) + b.reshape(-1)
     assert pred.shape == (8, NI) and rel_err(np.asarray(pred), want) < 1e-4
@@ -327,9 +313,8 @@ def test_a_lookup_made_before_a_step_holds_the_pre_step_rows_and_a_scaled_l2_ter
 
 @pytest.mark.parametrize("optk,loss_func,compat", [("sgd", "mse", True), ("sgd", "bce", False), ("adagrad", "mse", False), ("adam", "bce", False)])
 def test_reference_dlrm_class_text_trains_on_the_fused_path(optk, loss_func, compat):
-    """recommenders/dlrm.py of the reference, executed as it stands: its `call` composes LatentFactor lookups, the bottom MLP,
-    SecondOrderFeatureInteraction, tf.concat, the top MLP, [tf.clip_by_value,] tf.reshape and a keras loss object
-    (dlrm.py:76-100, :63-74).  The loss object recognises the tree and the model trains through `orx_dlrm_step` -- the modules'
+    """The DLRM composition: its `call` composes LatentFactor lookups, the bottom MLP, SecondOrderFeatureInteraction, tf.concat,
+    the top MLP, [tf.clip_by_value,] tf.reshape and a keras loss object.  The loss object recognises the tree and the model trains through `orx_dlrm_step` -- the modules'
     tables become that step's parameters -- and gives the oracle's parameters, not a host forward without gradients."""
     from openrec_amd.tf2.compat import optimizers
     from openrec_amd.tf2.modules import SecondOrderFeatureInteraction
@@ -337,7 +322,7 @@ def test_reference_dlrm_class_text_trains_on_the_fused_path(optk, loss_func, com
     from oracle import numpy_oracle as orc
     from oracle.dlrm_oracle import DLRMOracle
     from dlrm_util import draw_batch
-    DLRM = _ref_class("dlrm.py", "DLRM")
+    DLRM = _composed("DLRM")
     cfg = dict(m_spa=16, ln_emb=[50, 7, 300, 3], ln_bot=[32, 16], ln_top=[64, 32, 1])
     model = DLRM(loss_func=loss_func, loss_threshold=0.0 if loss_func == "mse" else 0.01, **cfg)
     if not compat:      # (the module's own switch: the evidently intended interaction instead of the reference's all-zero one)
@@ -371,7 +356,7 @@ def test_reference_dlrm_class_text_trains_on_the_fused_path(optk, loss_func, com
             de, sp, la = draw_batch(o, rng, B, cfg["ln_emb"])              # (away from the network's relu ties: tests/dlrm_util.py)
             got.append(step(de, sp, la))
             want.append(float(o.step(de, sp, la, oo)))
-        pred = model.inference(d0, s0)                                    # dlrm.py:76-100 again, outside a tape: orx_dlrm_inference
+        pred = model.inference(d0, s0)                                    # the same graph outside a tape: orx_dlrm_inference
         assert np.asarray(pred).shape == (B,)
     assert len(model._latent_factors[0]._composed) == 1                   # one fused model for all of it
     tol = TOL_ADAM if optk == "adam" else 2e-5
