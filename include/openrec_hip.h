@@ -52,8 +52,15 @@ enum orx_status {
  * the rows it exposes up to date, so the result is the dense rule's at every observation.
  * Tables over caller-owned memory (orx_table_wrap) always take the literal whole-table sweeps, as does
  * everything with ORX_ADAM_DENSE=1 in the environment.  A pointer obtained from orx_table_device_ptr is
- * current when returned; after further Adam steps, ask again. */
-enum orx_opt_kind { ORX_SGD = 0, ORX_ADAGRAD = 1, ORX_ADAM = 2 };
+ * current when returned; after further Adam steps, ask again.
+ * ORX_MOMENTUM is keras.optimizers.SGD(lr, momentum > 0, nesterov) (ResourceSparseApplyKerasMomentum /
+ * ResourceApplyKerasMomentum): duplicates are summed first, then for each referenced row (every element of a
+ * dense variable) with summed gradient G and velocity a (slot 0, zero-initialised)
+ *     a = a*momentum - lr*G;   plain: w += a;   nesterov: w += a*momentum - lr*G
+ * Rows not referenced in a step are untouched, velocity included.  Momentum takes the exact (non-hogwild) routes of
+ * orx_pairwise_step, orx_pointwise_step, orx_apply_rows, orx_dlrm_step and orx_dlrm_dense_apply; ORX_HOGWILD, the
+ * sharded engines, orx_shard_grads_sgd and orx_apply_rows_flagged refuse it (ORX_ERR_ARG). */
+enum orx_opt_kind { ORX_SGD = 0, ORX_ADAGRAD = 1, ORX_ADAM = 2, ORX_MOMENTUM = 3 };
 
 /* pairwise recommenders: recommenders/bpr.py:5, recommenders/ucml.py:5 */
 enum orx_pair_model { ORX_BPR = 0, ORX_UCML = 1 };
@@ -131,7 +138,8 @@ int orx_table_censor(orx_table* t, const int32_t* ids, int64_t n, float min_norm
  * (tf2_examples/bpr_citeulike.py:31,38) with TF-2.0 sparse-apply semantics.
  *   SGD:     p0..p2 unused
  *   ADAGRAD: p0 = initial_accumulator_value, p1 = epsilon
- *   ADAM:    p0 = beta_1, p1 = beta_2, p2 = epsilon   (dense-decay sparse apply) */
+ *   ADAM:    p0 = beta_1, p1 = beta_2, p2 = epsilon   (dense-decay sparse apply)
+ *   MOMENTUM: p0 = momentum in [0, 1], p1 = nesterov (0 or 1), p2 unused */
 int orx_opt_create(orx_ctx* ctx, int kind, float lr, float p0, float p1, float p2, orx_opt** out);
 int orx_opt_destroy(orx_opt* opt);
 int orx_opt_set_lr(orx_opt* opt, float lr);
@@ -151,7 +159,7 @@ int orx_opt_get_step(orx_opt* opt, int64_t* step_out);
 int orx_opt_set_step(orx_opt* opt, int64_t step);
 int orx_opt_advance(orx_opt* opt, orx_table* const* tables, int32_t n_tables);
 /* read/write an optimizer slot of a table (checkpointing, parity):
- * slot 0 = Adagrad accumulator / Adam m, slot 1 = Adam v. */
+ * slot 0 = Adagrad accumulator / Adam m / momentum velocity, slot 1 = Adam v. */
 int orx_opt_slot_read(orx_opt* opt, orx_table* t, int slot, int64_t row0, int64_t nrows, float* host_dst);
 int orx_opt_slot_write(orx_opt* opt, orx_table* t, int slot, int64_t row0, int64_t nrows, const float* host_src);
 

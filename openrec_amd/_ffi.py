@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ORX_LIB_PATH") or os.path.join(HERE, "_lib", "libopenrec_hip.so")      # (ORX_LIB_PATH: A/B runs of two builds on one box)
 
 ORX_OK, ORX_ERR_ARG, ORX_ERR_HIP, ORX_ERR_OOM, ORX_ERR_INDEX, ORX_ERR_STATE = 0, -1, -2, -3, -4, -5
-ORX_SGD, ORX_ADAGRAD, ORX_ADAM = 0, 1, 2
+ORX_SGD, ORX_ADAGRAD, ORX_ADAM, ORX_MOMENTUM = 0, 1, 2, 3
 ORX_BPR, ORX_UCML = 0, 1
 ORX_GMF, ORX_WRMF = 0, 1
 ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID = 1, 2, 4, 8, 16

@@ -372,7 +372,9 @@ extern "C" int orx_table_censor(orx_table* t, const int32_t* ids, int64_t n, flo
 // ------------------------------------------------------------- optimizers ---
 extern "C" int orx_opt_create(orx_ctx* ctx, int kind, float lr, float p0, float p1, float p2, orx_opt** out) {
     ORX_ARG(ctx && out, "orx_opt_create: NULL context/out");
-    ORX_ARG(kind == ORX_SGD || kind == ORX_ADAGRAD || kind == ORX_ADAM, "orx_opt_create: unknown optimizer kind %d", kind);
+    ORX_ARG(kind == ORX_SGD || kind == ORX_ADAGRAD || kind == ORX_ADAM || kind == ORX_MOMENTUM, "orx_opt_create: unknown optimizer kind %d", kind);
+    ORX_ARG(kind != ORX_MOMENTUM || (p0 >= 0.f && p0 <= 1.f), "orx_opt_create: momentum must lie in [0, 1], got %g", (double)p0);
+    ORX_ARG(kind != ORX_MOMENTUM || p1 == 0.f || p1 == 1.f, "orx_opt_create: momentum's nesterov flag (p1) must be 0 or 1, got %g", (double)p1);
     orx_opt* o = new orx_opt();
     o->ctx = ctx; o->kind = kind; o->lr = lr; o->p0 = p0; o->p1 = p1; o->p2 = p2;
     ctx->opts.push_back(o);
@@ -458,6 +460,9 @@ int orx_opt_slots(orx_opt* o, orx_table* t, OptSlots* out) {
     if (o->kind == ORX_ADAGRAD) {
         ORX_HIP(hipMalloc((void**)&s.s0, n * sizeof(float)));
         CHECK(orx_launch_fill(o->ctx, s.s0, (int64_t)n, o->p0));      // initial_accumulator_value
+    } else if (o->kind == ORX_MOMENTUM) {
+        ORX_HIP(hipMalloc((void**)&s.s0, n * sizeof(float)));
+        ORX_HIP(hipMemsetAsync(s.s0, 0, n * sizeof(float), o->ctx->stream));      // the "momentum" slot starts at zero
     } else if (o->kind == ORX_ADAM) {
         ORX_HIP(hipMalloc((void**)&s.s0, n * sizeof(float)));
         ORX_HIP(hipMalloc((void**)&s.s1, n * sizeof(float)));
@@ -1003,6 +1008,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     CHECK(stage_triplets(c, uid, pid, nid, K, B, id_stride, flags, &du, &dp, &dn, &ds));
 
     const bool hogwild = (flags & ORX_HOGWILD) != 0;
+    ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pairwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
     // TF-2.0 Adam decays m, v and moves var on EVERY row every step.  On the float4 dims that is applied lazily and
     // exactly: a row's gradient-free steps are replayed when the row is next touched (or observed: orx_table_sync);
     // the dense form (every reference accumulates, then three whole-table sweeps per step) remains for the other
@@ -1071,7 +1077,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     a.aU = sU.s0; a.aV = sV.s0; a.ab = sb.s0;
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
     a.lr = opt->lr;
-    a.eps = opt->kind == ORX_ADAGRAD ? opt->p1 : 0.f;
+    a.eps = orx_rule_eps(opt);
     a.margin = margin;
     a.invB = 1.0f / (float)B;
     a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f;

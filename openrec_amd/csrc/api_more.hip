@@ -58,6 +58,7 @@ extern "C" int orx_pointwise_step(orx_ctx* c, int model, orx_opt* opt,
     const int32_t *du, *di; const float* dl; int64_t ds;
     CHECK(stage_point(c, uid, iid, label, K, B, id_stride, flags, &du, &di, &dl, &ds));
     const bool hogwild = (flags & ORX_HOGWILD) != 0;
+    ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pointwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
     const char* fb_env = getenv("ORX_FORCE_FALLBACK");
     const int fb = fb_env ? atoi(fb_env) : 0;
     // TF-2.0 Adam applied lazily, as in orx_pairwise_step: float4 dims with the exact-step plan; the
@@ -126,7 +127,7 @@ extern "C" int orx_pointwise_step(orx_ctx* c, int model, orx_opt* opt,
     a.gU = U->gsum; a.gV = V->gsum; a.gb = b->gsum;
     a.aU = sU.s0; a.aV = sV.s0; a.ab = sb.s0;
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = D;
-    a.lr = opt->lr; a.eps = opt->kind == ORX_ADAGRAD ? opt->p1 : 0.f;
+    a.lr = opt->lr; a.eps = orx_rule_eps(opt);
     a.invB = 1.0f / (float)B; a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f; a.a_w = a_w; a.b_w = b_w;
     a.sigmoid = (model == ORX_WRMF && (flags & ORX_POINT_SIGMOID)) ? 1 : 0;
     a.wpartial = c->d_wpart; a.err = c->d_err;
@@ -453,8 +454,8 @@ int orx_table_touch(orx_table* t, const int32_t* ids, int64_t n) {
     return orx_adam_rows_touch(t->ctx, t->lazy, t, ids, n, false);
 }
 
-// Adagrad on per-occurrence gradient rows: dedup-sum semantics (duplicate flags + gsum + dup_apply)
-int orx_adagrad_rows_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* bias, const int32_t* ids, int64_t n, const float* grads,
+// Adagrad / momentum on per-occurrence gradient rows: dedup-sum semantics (duplicate flags + gsum + dup_apply)
+int orx_summed_rows_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* bias, const int32_t* ids, int64_t n, const float* grads,
                            int64_t g_stride, ColWindows cw) {
     RowsArgs a;
     memset(&a, 0, sizeof(a));
@@ -481,15 +482,15 @@ int orx_adagrad_rows_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* 
     CHECK(orx_launch_dedup(ctx, d, 1));
     a.G = t->gsum; a.gb = bias ? bias->gsum : nullptr;
     a.A = st.s0; a.ab = bias ? sb.s0 : nullptr;
-    a.dflag = ctx->d_dflag; a.eps = opt->p1;
-    CHECK(orx_launch_apply_rows(ctx, ORX_ADAGRAD, true, a));
+    a.dflag = ctx->d_dflag; a.eps = orx_rule_eps(opt);
+    CHECK(orx_launch_apply_rows(ctx, opt->kind, true, a));
     PairArgs pa;
     memset(&pa, 0, sizeof(pa));
     pa.V = t->w; pa.gV = t->gsum; pa.aV = st.s0;
     pa.b = bias ? bias->w : nullptr; pa.gb = bias ? bias->gsum : nullptr; pa.ab = bias ? sb.s0 : nullptr;
     pa.dlist = ctx->d_dlist; pa.dcount = ctx->d_dcount;
-    pa.B = n; pa.D = t->dim; pa.lr = opt->lr; pa.eps = opt->p1;
-    return orx_launch_dup_apply(ctx, ORX_ADAGRAD, pa);
+    pa.B = n; pa.D = t->dim; pa.lr = opt->lr; pa.eps = a.eps;
+    return orx_launch_dup_apply(ctx, opt->kind, pa);
 }
 
 extern "C" int orx_apply_rows(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* bias,
@@ -498,7 +499,7 @@ extern "C" int orx_apply_rows(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_tabl
     if (t && !lazy) CHECK(orx_table_sync(t));
     if (bias && !lazy) CHECK(orx_table_sync(bias));
     ORX_ARG(ctx && opt && t && (n == 0 || (ids && grads)), "orx_apply_rows: NULL argument");
-    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || (opt->kind == ORX_ADAM && (!bias || lazy)),
+    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM || (opt->kind == ORX_ADAM && (!bias || lazy)),
             "orx_apply_rows: the whole-table-sweep form of Adam (ORX_ADAM_DENSE) takes no bias column");
     ORX_ARG(g_stride >= t->dim + (bias ? 1 : 0), "orx_apply_rows: g_stride too small");
     ORX_ARG(!bias || (bias->dim == 1 && bias->rows == t->rows), "orx_apply_rows: bias must be [%lld, 1]", (long long)t->rows);
@@ -537,7 +538,7 @@ extern "C" int orx_apply_rows(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_tabl
         return orx_launch_adam_sweep(ctx, t->w, st.s0, st.s1, t->gsum, t->rows * t->dim, lr_t, opt->p0, opt->p1, opt->p2);
     }
 
-    return orx_adagrad_rows_apply(ctx, opt, t, bias, ids, n, grads, g_stride);
+    return orx_summed_rows_apply(ctx, opt, t, bias, ids, n, grads, g_stride);
 }
 
 // ---- planned apply of K id lists against one table (see orx_internal.h) ------------------------------------------
@@ -559,6 +560,7 @@ int orx_apply_rows_plan(orx_ctx* c, orx_table* t, const int32_t* ids, int64_t K,
 
 int orx_apply_rows_planned_step(orx_ctx* c, orx_opt* opt, orx_table* t, orx_table* bias, const RowsPlan& rp, int64_t i,
                                 const int32_t* ids, const float* grads, int64_t g_stride) {
+    ORX_ARG(opt->kind != ORX_MOMENTUM, "apply_rows_planned_step: momentum is not supported here (the sharded engines are SGD / Adagrad / Adam)");
     ORX_ARG(rp.ready && (opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD), "apply_rows_planned_step: no plan, or not SGD / Adagrad");
     if (bias) CHECK(orx_table_scratch(bias, true));
     OptSlots st, sb;
@@ -612,6 +614,7 @@ extern "C" int orx_apply_rows_flagged(orx_ctx* ctx, orx_opt* opt, orx_table* t, 
 
 static int flagged_args(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* bias, const int32_t* ids, int64_t n,
                         const float* grads, int64_t g_stride, const float* gbias, const unsigned char* dflag, RowsArgs* out) {
+    ORX_ARG(!opt || opt->kind != ORX_MOMENTUM, "orx_apply_rows_flagged: SGD only, momentum is not supported (orx_apply_rows takes it)");
     if (t) CHECK(orx_table_sync(t));
     if (bias) CHECK(orx_table_sync(bias));
     ORX_ARG(ctx && opt && t && (n == 0 || (ids && grads && dflag)), "orx_apply_rows_flagged: NULL argument");
@@ -813,6 +816,7 @@ extern "C" int orx_shard_grads_sgd(orx_ctx* ctx, int model, orx_opt* opt, orx_ta
                                    const int32_t* slot, const uint8_t* dupref, const void* sorted, const void* seglist, const int32_t* segcount,
                                    float* gdup, const uint8_t* dup_u, int64_t T, int64_t row_stride, int64_t B_global,
                                    float margin, int flags, float* gu, int32_t* u_apply, float* send_g, double* loss_l2_accum) {
+    ORX_ARG(!opt || opt->kind != ORX_MOMENTUM, "orx_shard_grads_sgd: momentum is not supported by the sharded engines");
     ORX_ARG(opt && dup_u && u_apply, "orx_shard_grads_sgd: NULL argument");
     return orx_shard_grads_impl(ctx, model, opt, user, rows_in, nullptr, u_loc, slot, dupref, sorted, seglist, segcount, gdup, dup_u, T, row_stride,
                                 B_global, margin, flags, gu, u_apply, send_g, nullptr, loss_l2_accum);

@@ -577,7 +577,7 @@ static int dense_apply_all(orx_dlrm* m, orx_opt* opt, float lr_t = 0.f, bool fus
         m->pending_coljobs.clear();
         if (!rest.empty()) CHECK(orx_launch_colparts_reduce(c, rest.data(), (int)rest.size()));
         if (opt->kind == ORX_ADAM) CHECK(orx_launch_dense_apply_fused(c, m->d_fused, m->fused_tt, m->fused_tiles, ORX_ADAM, lr_t, opt->p2, opt->p0, opt->p1, slab_scale, finish));
-        else CHECK(orx_launch_dense_apply_fused(c, m->d_fused, m->fused_tt, m->fused_tiles, opt->kind, opt->lr, opt->p1, 0.f, 0.f, slab_scale, finish));
+        else CHECK(orx_launch_dense_apply_fused(c, m->d_fused, m->fused_tt, m->fused_tiles, opt->kind, opt->lr, orx_rule_eps(opt), 0.f, 0.f, slab_scale, finish));
         for (int k = 0; k < 2; ++k) for (auto& D : (k == 0 ? m->bot : m->top)) { D.W->version += 1; D.b->version += 1; D.shadow_version = D.W->version; }
         return ORX_OK;
     }
@@ -601,7 +601,7 @@ static int dense_apply_all(orx_dlrm* m, orx_opt* opt, float lr_t = 0.f, bool fus
         m->params_opt = opt;
     }
     if (opt->kind == ORX_ADAM) return orx_launch_dense_apply_multi(c, m->d_params, (int)h.size(), max_n, ORX_ADAM, lr_t, opt->p2, opt->p0, opt->p1);
-    return orx_launch_dense_apply_multi(c, m->d_params, (int)h.size(), max_n, opt->kind, opt->lr, opt->p1);
+    return orx_launch_dense_apply_multi(c, m->d_params, (int)h.size(), max_n, opt->kind, opt->lr, orx_rule_eps(opt));
 }
 
 // backward through one MLP; dy [B, last.out] is consumed (in place), returns d(input) in *dx_out.
@@ -969,10 +969,12 @@ extern "C" int orx_dlrm_step(orx_dlrm* m, orx_opt* opt, const float* dense, cons
         m->cur_hl = fold_loss ? &hl : nullptr; m->hl_used = false;
         const bool fuse_dense = m->gen2 && getenv("ORX_DLRM_NO_FUSED_DENSE") == nullptr;
         // (round 6) SGD / Adagrad with the fused dense optimizer launch behind it: the sorted apply's finish pass rides in THAT launch (kernels_dense.hip
-        // dense_apply_fused_kernel) instead of being the step's 24th.  ORX_DLRM_FINISH_LAUNCH=1: its own launch
+        // dense_apply_fused_kernel) instead of being the step's 24th; momentum's too (that launch's momentum instantiation).
+        // ORX_DLRM_FINISH_LAUNCH=1: its own launch
         CsrFinish fin;
         memset(&fin, 0, sizeof(fin));
-        const bool carry_finish = fuse_dense && sorted_apply && !lazy_adam && (opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD) && !no_carry;
+        const bool carry_finish = fuse_dense && sorted_apply && !lazy_adam && (opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM) &&
+                                  !no_carry;
         m->fuse_single = fuse_rows ? m->d_single + (s % PC) * B * F : nullptr; m->fuse_opt = opt;
         const int rc_bwd = backward(m, bt, B, gscale, fuse_dense);
         const bool rows_fused = m->fuse_single != nullptr && m->direct_idx != nullptr;      // (backward applied them: see there)
@@ -998,9 +1000,9 @@ extern "C" int orx_dlrm_step(orx_dlrm* m, orx_opt* opt, const float* dense, cons
             CHECK(orx_apply_rows_planned_step(c, opt, m->emb, nullptr, rp, s % PC, idx_s, m->dZ, d));
         } else if (lazy_adam) {
             CHECK(orx_adam_rows_apply(c, opt, m->emb, idx_s, B * F, m->dZ, d, deduped, cw));
-        } else if (opt->kind == ORX_ADAGRAD) {
+        } else if (opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM) {
             CHECK(orx_table_sync(m->emb));
-            CHECK(orx_adagrad_rows_apply(c, opt, m->emb, nullptr, m->d_idx, B * F, m->dZ, d, cw));
+            CHECK(orx_summed_rows_apply(c, opt, m->emb, nullptr, m->d_idx, B * F, m->dZ, d, cw));
         } else if (opt->kind == ORX_SGD && !m->tiny_f.empty()) {
             // tiny tables: per-slab LDS sums; the generic scatter then skips their slots
             CHECK(orx_launch_dlrm_tiny_apply(c, m->d_idx, m->dZ, m->d_tiny_f, (int)m->tiny_f.size(), m->tiny_max_rows, m->d_offset,

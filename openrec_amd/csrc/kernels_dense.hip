@@ -1125,14 +1125,20 @@ int orx_launch_rows_accum(orx_ctx* ctx, float* G, const int32_t* ids, const floa
 
 // ------------------------------------------------------- multi-tensor dense apply ---
 // The SGD / Adagrad / Adam rule of every dense parameter of a model in ONE launch (16 launches of a few microseconds
-// each otherwise): grid.y = parameter, grid.x covers the largest one.  Gradients are zeroed behind.
+// each otherwise): grid.y = parameter, grid.x covers the largest one.  Gradients are zeroed behind.  MOM: the momentum
+// instantiation (eps = the signed momentum of orx_rule_eps).
+template <bool MOM>
 __global__ __launch_bounds__(256) void dense_apply_multi_kernel(const DenseParam* ps, int optkind, float lr, float eps, float b1, float b2) {
     const DenseParam p = ps[blockIdx.y];
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += stride) {
         const float gi = p.g[i];
         p.g[i] = 0.0f;
-        if (optkind == ORX_ADAM) {          // lr = lr_t of this step; acc = m, acc2 = v
+        if (MOM) {
+            float a = p.acc[i];
+            p.w[i] = mom_elem(p.w[i], gi, a, lr, eps);
+            p.acc[i] = a;
+        } else if (optkind == ORX_ADAM) {          // lr = lr_t of this step; acc = m, acc2 = v
             float w = p.w[i], m = p.acc[i], v = p.acc2[i];
             adam_elem(w, m, v, gi, lr, b1, b2, eps);
             p.w[i] = w; p.acc[i] = m; p.acc2[i] = v;
@@ -1150,7 +1156,8 @@ int orx_launch_dense_apply_multi(orx_ctx* ctx, const DenseParam* ps_dev, int cou
                                  float b1, float b2) {
     if (count == 0) return ORX_OK;
     int64_t gx = (max_n + 255) / 256; if (gx > 1024) gx = 1024; if (gx < 1) gx = 1;
-    ORX_LAUNCH(ctx, dense_apply_multi_kernel, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, ps_dev, optkind, lr, eps, b1, b2);
+    if (optkind == ORX_MOMENTUM) ORX_LAUNCH(ctx, dense_apply_multi_kernel<true>, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, ps_dev, optkind, lr, eps, b1, b2);
+    else ORX_LAUNCH(ctx, dense_apply_multi_kernel<false>, dim3((unsigned)gx, (unsigned)count), dim3(256), 0, ps_dev, optkind, lr, eps, b1, b2);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }
@@ -1174,11 +1181,14 @@ __device__ __forceinline__ void csr_finish_any(const CsrArgs& a, int64_t b, int 
     }
 }
 
+// MOM: the momentum instantiation (eps = the signed momentum of orx_rule_eps; the finish pass it carries is momentum's)
+template <bool MOM>
 __global__ __launch_bounds__(256) void dense_apply_fused_kernel(const DenseFused* ps, DenseFusedTiles tt, int optkind, float lr, float eps, float b1, float b2,
                                                                 float slab_scale, CsrFinish fin) {
     if ((int)blockIdx.x < fin.blocks) {
         const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-        if (fin.mode == CSR_SGD) csr_finish_any<CSR_SGD>(fin.a, b, threadIdx.x & 63);
+        if (MOM) csr_finish_any<CSR_MOMENTUM>(fin.a, b, threadIdx.x & 63);
+        else if (fin.mode == CSR_SGD) csr_finish_any<CSR_SGD>(fin.a, b, threadIdx.x & 63);
         else csr_finish_any<CSR_ADAGRAD>(fin.a, b, threadIdx.x & 63);
         return;
     }
@@ -1259,7 +1269,8 @@ __global__ __launch_bounds__(256) void dense_apply_fused_kernel(const DenseFused
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            if (optkind == ORX_ADAM) adam_elem(wv[e], a1[e], a2[e], gi[e], lr, b1, b2, eps);
+            if (MOM) wv[e] = mom_elem(wv[e], gi[e], a1[e], lr, eps);
+            else if (optkind == ORX_ADAM) adam_elem(wv[e], a1[e], a2[e], gi[e], lr, b1, b2, eps);
             else if (optkind == ORX_ADAGRAD) { a1[e] += gi[e] * gi[e]; wv[e] -= lr * gi[e] / (sqrtf(a1[e]) + eps); }
             else wv[e] -= lr * gi[e];
         }
@@ -1302,8 +1313,11 @@ int orx_launch_dense_apply_fused(orx_ctx* ctx, const DenseFused* ps_dev, const D
     memset(&fin, 0, sizeof(fin));
     if (finish != nullptr) fin = *finish;
     if ((tt.count == 0 || total_tiles == 0) && fin.blocks == 0) return ORX_OK;
-    ORX_ARG(fin.blocks == 0 || fin.mode == CSR_SGD || fin.mode == CSR_ADAGRAD, "dense_apply_fused: the finish pass it carries is SGD / Adagrad");
-    ORX_LAUNCH(ctx, dense_apply_fused_kernel, dim3((unsigned)(total_tiles + fin.blocks)), dim3(256), 0, ps_dev, tt, optkind, lr, eps, b1, b2, slab_scale, fin);
+    const bool mom = optkind == ORX_MOMENTUM;
+    ORX_ARG(fin.blocks == 0 || (mom ? fin.mode == CSR_MOMENTUM : (fin.mode == CSR_SGD || fin.mode == CSR_ADAGRAD)),
+            "dense_apply_fused: the finish pass it carries is SGD / Adagrad, or momentum with the momentum rule");
+    if (mom) ORX_LAUNCH(ctx, dense_apply_fused_kernel<true>, dim3((unsigned)(total_tiles + fin.blocks)), dim3(256), 0, ps_dev, tt, optkind, lr, eps, b1, b2, slab_scale, fin);
+    else ORX_LAUNCH(ctx, dense_apply_fused_kernel<false>, dim3((unsigned)(total_tiles + fin.blocks)), dim3(256), 0, ps_dev, tt, optkind, lr, eps, b1, b2, slab_scale, fin);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }

@@ -1108,12 +1108,19 @@ int orx_launch_fused(orx_ctx* ctx, int model, int optkind, int mode, const PairA
         ORX_HIP(hipGetLastError());
         return ORX_OK;
     }
-    const int ok = (optkind == ORX_ADAGRAD) ? ORX_ADAGRAD : ORX_SGD;
+    const int ok = (optkind == ORX_ADAGRAD || optkind == ORX_MOMENTUM) ? optkind : ORX_SGD;
+    // momentum: exact mode only (the host refuses hogwild), the rest of its mode switch is never taken
+    if (ok == ORX_MOMENTUM && mode != MODE_EXACT) {
+        orx_set_error("fused: momentum takes the exact mode only (mode %d)", mode);
+        return ORX_ERR_ARG;
+    }
     if (model == ORX_BPR) {
         if (ok == ORX_ADAGRAD) launch_fused_lpr<ORX_BPR, ORX_ADAGRAD>(lpr, mode, g, ctx, a);
+        else if (ok == ORX_MOMENTUM) launch_fused_lpr<ORX_BPR, ORX_MOMENTUM>(lpr, mode, g, ctx, a);
         else launch_fused_lpr<ORX_BPR, ORX_SGD>(lpr, mode, g, ctx, a);
     } else {
         if (ok == ORX_ADAGRAD) launch_fused_lpr<ORX_UCML, ORX_ADAGRAD>(lpr, mode, g, ctx, a);
+        else if (ok == ORX_MOMENTUM) launch_fused_lpr<ORX_UCML, ORX_MOMENTUM>(lpr, mode, g, ctx, a);
         else launch_fused_lpr<ORX_UCML, ORX_SGD>(lpr, mode, g, ctx, a);
     }
     ORX_HIP(hipGetLastError());
@@ -1158,6 +1165,7 @@ bool orx_launch_tail(orx_ctx* ctx, int optkind, const PairArgs& a, const ReduceA
     if (want < 16) want = 16;
     const dim3 g((unsigned)(want + K));
 #define ORX_TL(L) do { if (optkind == ORX_ADAGRAD) ORX_LAUNCH(ctx, (tail_kernel<L, ORX_ADAGRAD>), g, dim3(1024), 0, a, r, (int)K); \
+                       else if (optkind == ORX_MOMENTUM) ORX_LAUNCH(ctx, (tail_kernel<L, ORX_MOMENTUM>), g, dim3(1024), 0, a, r, (int)K); \
                        else ORX_LAUNCH(ctx, (tail_kernel<L, ORX_SGD>), g, dim3(1024), 0, a, r, (int)K); } while (0)
     switch (lpr) {
         case 4: ORX_TL(4); break;
@@ -1189,6 +1197,7 @@ int orx_launch_dup_apply(orx_ctx* ctx, int optkind, const PairArgs& a) {
             default: ORX_LAUNCH(ctx, (dup_apply_kernel<64, ORX_ADAM>), g, dim3(256), 0, a); break;
         }
     } else if (optkind == ORX_ADAGRAD) launch_dup_apply_lpr<ORX_ADAGRAD>(lpr, g, ctx, a);
+    else if (optkind == ORX_MOMENTUM) launch_dup_apply_lpr<ORX_MOMENTUM>(lpr, g, ctx, a);
     else launch_dup_apply_lpr<ORX_SGD>(lpr, g, ctx, a);
     ORX_HIP(hipGetLastError());
     return ORX_OK;

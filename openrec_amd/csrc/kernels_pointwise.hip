@@ -50,7 +50,8 @@ constexpr int WT_GROUP = 64;
 constexpr uint32_t WT_EMPTY = 0xffffffffu;
 constexpr int WT_SPIN_MAX = 1 << 22;         // (a value that IS all ones -- only a NaN fed in from outside can be -- is taken after this many polls)
 
-template <int LPR>
+// MOM: the momentum instantiations (their launches carry wt_optkind = ORX_MOMENTUM); the others never test for it
+template <int LPR, bool MOM>
 __device__ __forceinline__ void dense_tail_reducer(const PointArgs& a, int red, int nwg) {
     constexpr int D = 4 * LPR, NSL = 256 / LPR, RB = 4;
     __shared__ f4 wt_red[256];
@@ -122,6 +123,11 @@ __device__ __forceinline__ void dense_tail_reducer(const PointArgs& a, int red, 
             for (int e = 0; e < 4; ++e) { a2[e] = a2[e] + g[e] * g[e]; wn[e] = we[e] - a.lr * g[e] / (sqrtf(a2[e]) + a.eps); }
             *reinterpret_cast<f4*>(a.wt_acc + 4 * sub) = a2;
             *reinterpret_cast<f4*>(wp) = wn;
+        } else if (MOM && a.wt_optkind == ORX_MOMENTUM) {
+            f4 a2 = *reinterpret_cast<const f4*>(a.wt_acc + 4 * sub);
+            const f4 wn = mom_elem4(we, g, a2, a.lr, a.eps);
+            *reinterpret_cast<f4*>(a.wt_acc + 4 * sub) = a2;
+            *reinterpret_cast<f4*>(wp) = wn;
         } else if (a.wt_gout != nullptr) {
             *reinterpret_cast<f4*>(a.wt_gout + 4 * sub) = g;
         }
@@ -155,7 +161,7 @@ __global__ __launch_bounds__(256) void point_fused_kernel(PointArgs a) {
     }
     const int nwg = (int)gridDim.x - nab - (MODEL == ORX_GMF ? a.wt_nred : 0);      // sample workgroups
     if (MODEL == ORX_GMF && MODE != MODE_LOSS && (int)blockIdx.x - nab >= nwg) {        // reducer role (block-uniform): see dense_tail_reducer
-        dense_tail_reducer<LPR>(a, (int)blockIdx.x - nab - nwg, nwg);
+        dense_tail_reducer<LPR, OPT == ORX_MOMENTUM>(a, (int)blockIdx.x - nab - nwg, nwg);
         return;
     }
     const int64_t wave_global = (int64_t)(blockIdx.x - nab) * 4 + (threadIdx.x >> 6);
@@ -408,7 +414,8 @@ __global__ __launch_bounds__(256) void dense_reduce1_kernel(const float* wpartia
 
 // final stage: gradient = sum of the partial rows + l2w * w; 0.5*||w||^2 of the PRE-step kernel joins
 // l2_loss (gmf.py:31-32); with optkind >= 0 the optimizer's dense rule is applied here as well (SGD /
-// Adagrad), otherwise the gradient is left in gout (Adam: adam_sweep_kernel follows).
+// Adagrad; momentum in the MOM instantiation), otherwise the gradient is left in gout (Adam: adam_sweep_kernel follows).
+template <bool MOM>
 __global__ __launch_bounds__(1024) void dense_reduce_kernel(const float* wpartial, int nwaves, int D, float* w,
                                                             float l2w, float* gout, float* l2slot,
                                                             float* acc, int optkind, float lr, float eps) {
@@ -434,6 +441,10 @@ __global__ __launch_bounds__(1024) void dense_reduce_kernel(const float* wpartia
                 const float a2 = acc[e] + g * g;
                 acc[e] = a2;
                 w[e] = we - lr * g / (sqrtf(a2) + eps);
+            } else if (MOM && optkind == ORX_MOMENTUM) {
+                float a2 = acc[e];
+                w[e] = mom_elem(we, g, a2, lr, eps);
+                acc[e] = a2;
             } else if (gout != nullptr) {
                 gout[e] = g;
             }
@@ -446,12 +457,17 @@ __global__ __launch_bounds__(1024) void dense_reduce_kernel(const float* wpartia
     }
 }
 
+template <bool MOM>
 __global__ __launch_bounds__(256) void dense_apply_kernel(float* w, float* acc, float* g, int n, int optkind, float lr, float eps) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float gi = g[i];
     g[i] = 0.0f;
-    if (optkind == ORX_ADAGRAD) {
+    if (MOM) {
+        float a2 = acc[i];
+        w[i] = mom_elem(w[i], gi, a2, lr, eps);
+        acc[i] = a2;
+    } else if (optkind == ORX_ADAGRAD) {
         const float a2 = acc[i] + gi * gi;
         acc[i] = a2;
         w[i] = w[i] - lr * gi / (sqrtf(a2) + eps);
@@ -593,7 +609,11 @@ int orx_launch_point_fused(orx_ctx* ctx, int model, int optkind, int mode, const
         return ORX_OK;
     }
     const bool ada = optkind == ORX_ADAGRAD;
-    if (model == ORX_GMF) {
+    if (optkind == ORX_MOMENTUM) {            // exact mode only (the host refuses hogwild)
+        ORX_ARG(mode == MODE_EXACT, "point_fused: momentum takes the exact mode only (mode %d)", mode);
+        if (model == ORX_GMF) launch_point_lpr<ORX_GMF, ORX_MOMENTUM>(lpr, mode, g, ctx, a);
+        else launch_point_lpr<ORX_WRMF, ORX_MOMENTUM>(lpr, mode, g, ctx, a);
+    } else if (model == ORX_GMF) {
         if (ada) launch_point_lpr<ORX_GMF, ORX_ADAGRAD>(lpr, mode, g, ctx, a);
         else launch_point_lpr<ORX_GMF, ORX_SGD>(lpr, mode, g, ctx, a);
     } else {
@@ -612,13 +632,15 @@ int orx_launch_dense_reduce(orx_ctx* ctx, const float* wpartial, int nwaves, int
         ORX_LAUNCH(ctx, dense_reduce1_kernel, dim3(G), dim3(256), 0, wpartial, nwaves, D, stage1);
         wpartial = stage1; nwaves = G;
     }
-    ORX_LAUNCH(ctx, dense_reduce_kernel, dim3(1), dim3(1024), 0, wpartial, nwaves, D, w, l2w, gout, l2slot, acc, optkind, lr, eps);
+    if (optkind == ORX_MOMENTUM) ORX_LAUNCH(ctx, dense_reduce_kernel<true>, dim3(1), dim3(1024), 0, wpartial, nwaves, D, w, l2w, gout, l2slot, acc, optkind, lr, eps);
+    else ORX_LAUNCH(ctx, dense_reduce_kernel<false>, dim3(1), dim3(1024), 0, wpartial, nwaves, D, w, l2w, gout, l2slot, acc, optkind, lr, eps);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }
 
 int orx_launch_dense_apply(orx_ctx* ctx, float* w, float* acc, float* g, int n, int optkind, float lr, float eps) {
-    ORX_LAUNCH(ctx, dense_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, w, acc, g, n, optkind, lr, eps);
+    if (optkind == ORX_MOMENTUM) ORX_LAUNCH(ctx, dense_apply_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, w, acc, g, n, optkind, lr, eps);
+    else ORX_LAUNCH(ctx, dense_apply_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, w, acc, g, n, optkind, lr, eps);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }

@@ -332,10 +332,10 @@ static int csr_args(orx_ctx* ctx, orx_table* t, const uint2* sorted, int64_t n, 
     return ORX_OK;
 }
 
-// SGD / Adagrad on the sorted list (one step)
+// SGD / Adagrad / momentum on the sorted list (one step)
 int orx_csr_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride, bool skip_single) {
     if (n == 0) return ORX_OK;
-    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD, "csr_apply: SGD / Adagrad (Adam: orx_csr_adam_apply)");
+    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM, "csr_apply: SGD / Adagrad / momentum (Adam: orx_csr_adam_apply)");
     ProfScope ps(ctx, ORX_K_DUPAPPLY);
     CsrArgs a;
     if (int rc = csr_args(ctx, t, sorted, n, grads, g_stride, &a)) return rc;
@@ -346,6 +346,12 @@ int orx_csr_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, const uint2* sorted,
         a.A = st.s0; a.eps = opt->p1;
         return launch_csr<CSR_ADAGRAD>(ctx, a);
     }
+    if (opt->kind == ORX_MOMENTUM) {
+        OptSlots st;
+        if (int rc = orx_opt_slots(opt, t, &st)) return rc;
+        a.A = st.s0; a.eps = orx_rule_eps(opt);
+        return launch_csr<CSR_MOMENTUM>(ctx, a);
+    }
     return launch_csr<CSR_SGD>(ctx, a);
 }
 
@@ -353,7 +359,7 @@ int orx_csr_apply_split(orx_ctx* ctx, orx_opt* opt, orx_table* t, const uint2* s
                         bool skip_single, CsrFinish* finish) {
     memset(finish, 0, sizeof(*finish));
     if (n == 0) return ORX_OK;
-    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD, "csr_apply: SGD / Adagrad (Adam: orx_csr_adam_apply)");
+    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM, "csr_apply: SGD / Adagrad / momentum (Adam: orx_csr_adam_apply)");
     ProfScope ps(ctx, ORX_K_DUPAPPLY);
     CsrArgs a;
     if (int rc = csr_args(ctx, t, sorted, n, grads, g_stride, &a)) return rc;
@@ -364,9 +370,14 @@ int orx_csr_apply_split(orx_ctx* ctx, orx_opt* opt, orx_table* t, const uint2* s
         if (int rc2 = orx_opt_slots(opt, t, &st)) return rc2;
         a.A = st.s0; a.eps = opt->p1;
         rc = launch_csr<CSR_ADAGRAD>(ctx, a, false);
+    } else if (opt->kind == ORX_MOMENTUM) {
+        OptSlots st;
+        if (int rc2 = orx_opt_slots(opt, t, &st)) return rc2;
+        a.A = st.s0; a.eps = orx_rule_eps(opt);
+        rc = launch_csr<CSR_MOMENTUM>(ctx, a, false);
     } else rc = launch_csr<CSR_SGD>(ctx, a, false);
     if (rc != ORX_OK) return rc;
-    finish->a = a; finish->mode = opt->kind == ORX_ADAGRAD ? CSR_ADAGRAD : CSR_SGD;
+    finish->a = a; finish->mode = opt->kind == ORX_ADAGRAD ? CSR_ADAGRAD : (opt->kind == ORX_MOMENTUM ? CSR_MOMENTUM : CSR_SGD);
     finish->blocks = (int)(((n + 63) / 64 + 3) / 4);
     return ORX_OK;
 }

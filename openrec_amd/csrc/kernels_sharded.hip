@@ -271,9 +271,10 @@ int orx_launch_rows_planned(orx_ctx* ctx, int optkind, const RowsArgs& a) {
     return ORX_OK;
 }
 
-// Adagrad: rows referenced once are updated in place, duplicated rows sum into
+// Adagrad / momentum: rows referenced once are updated in place, duplicated rows sum into
 // gsum first (dup_apply_kernel finishes them).  One wavefront per reference.
-__global__ __launch_bounds__(256) void apply_rows_adagrad_kernel(RowsArgs a) {
+template <int OPT>
+__global__ __launch_bounds__(256) void apply_rows_summed_kernel(RowsArgs a) {
     const int lane = threadIdx.x & 63;
     const int D = a.D;
     const int64_t stride = (int64_t)gridDim.x * 4;
@@ -286,11 +287,11 @@ __global__ __launch_bounds__(256) void apply_rows_adagrad_kernel(RowsArgs a) {
         for (int e = lane; e < D; e += 64) {
             const size_t i = (size_t)r * D + e;
             if (dup) unsafeAtomicAdd(a.G + i, g[e]);
-            else opt_apply1<ORX_ADAGRAD>(a.W + i, a.A + i, a.W[i], g[e], a.lr, a.eps);
+            else opt_apply1<OPT>(a.W + i, a.A + i, a.W[i], g[e], a.lr, a.eps);
         }
         if (a.bias != nullptr && lane == 0) {
             if (dup) unsafeAtomicAdd(a.gb + r, g[D]);
-            else opt_apply1<ORX_ADAGRAD>(a.bias + r, a.ab + r, a.bias[r], g[D], a.lr, a.eps);
+            else opt_apply1<OPT>(a.bias + r, a.ab + r, a.bias[r], g[D], a.lr, a.eps);
         }
     }
 }
@@ -390,7 +391,8 @@ int orx_launch_apply_rows(orx_ctx* ctx, int optkind, bool use_dflag, const RowsA
         ORX_LAUNCH(ctx, apply_rows_sgd_kernel, dim3((unsigned)g), dim3(256), 0, a);
     } else {
         (void)use_dflag;
-        ORX_LAUNCH(ctx, apply_rows_adagrad_kernel, dim3(grid_for_rows(0, a.n)), dim3(256), 0, a);
+        if (optkind == ORX_MOMENTUM) ORX_LAUNCH(ctx, apply_rows_summed_kernel<ORX_MOMENTUM>, dim3(grid_for_rows(0, a.n)), dim3(256), 0, a);
+        else ORX_LAUNCH(ctx, apply_rows_summed_kernel<ORX_ADAGRAD>, dim3(grid_for_rows(0, a.n)), dim3(256), 0, a);
     }
     ORX_HIP(hipGetLastError());
     return ORX_OK;

@@ -53,6 +53,7 @@ __device__ __forceinline__ void store_wt4(float* p, f4 v) {
 template <int OPT>
 __device__ __forceinline__ float opt_rule(float w, float g, float& acc, float lr, float eps) {
     if (OPT == ORX_ADAGRAD) { acc = acc + g * g; return w - lr * g / (sqrtf(acc) + eps); }
+    if (OPT == ORX_MOMENTUM) return mom_elem(w, g, acc, lr, eps);
     return w - lr * g;
 }
 
@@ -98,7 +99,7 @@ __device__ __forceinline__ void inline_apply(const PairArgs& a) {
         else g = *reinterpret_cast<const f4*>(g1) + *reinterpret_cast<const f4*>(g2);
         const f4 w = *reinterpret_cast<const f4*>(wp);
         f4 acc; acc.x = acc.y = acc.z = acc.w = 0.0f;
-        if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM) acc = *reinterpret_cast<const f4*>(A + row * D + 4 * sub);
+        if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM || OPT == ORX_MOMENTUM) acc = *reinterpret_cast<const f4*>(A + row * D + 4 * sub);
         float ac[4] = {acc.x, acc.y, acc.z, acc.w};
         f4 wn;
         f4 vv; vv.x = vv.y = vv.z = vv.w = 0.0f;           // Adam v (acc holds m)
@@ -125,12 +126,12 @@ __device__ __forceinline__ void inline_apply(const PairArgs& a) {
         f4 z; z.x = z.y = z.z = z.w = 0.0f;
         store_wt4(wp, wn);
         if (!STAGED || scnt <= 0) { store_wt4(g1, z); store_wt4(g2, z); }
-        if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM) store_wt4(A + row * D + 4 * sub, acc);
+        if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM || OPT == ORX_MOMENTUM) store_wt4(A + row * D + 4 * sub, acc);
         float gbs = 0.0f;
         if (STAGED && scnt > 0 && item) gbs = segment_sum1<LPR>(a.prev_stageb, sseg, scnt, sub);
         if (item && sub == 0) {
             const float gb = STAGED && scnt > 0 ? gbs : a.gb[row] + a.gb2[row];
-            float ab = (OPT == ORX_ADAGRAD || OPT == ORX_ADAM) ? a.ab[row] : 0.0f;
+            float ab = (OPT == ORX_ADAGRAD || OPT == ORX_ADAM || OPT == ORX_MOMENTUM) ? a.ab[row] : 0.0f;
             float bn;
             if (OPT == ORX_ADAM) {
                 float bw = a.b[row], bv = a.a2b[row];
@@ -145,7 +146,7 @@ __device__ __forceinline__ void inline_apply(const PairArgs& a) {
             }
             store_wt(a.b + row, bn);
             if (!STAGED || scnt <= 0) { store_wt(a.gb + row, 0.0f); store_wt(a.gb2 + row, 0.0f); }
-            if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM) store_wt(a.ab + row, ab);
+            if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM || OPT == ORX_MOMENTUM) store_wt(a.ab + row, ab);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every store of this wave has been written through
         if (sub == 0) __hip_atomic_store((item ? a.readyV : a.readyU) + row, a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

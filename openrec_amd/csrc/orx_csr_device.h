@@ -5,12 +5,12 @@
 
 constexpr uint32_t CSR_KEY_NONE = 0xffffffffu;
 
-enum { CSR_SGD = 0, CSR_ADAGRAD = 1, CSR_ADAM = 2, CSR_ACCUM = 3 };
+enum { CSR_SGD = 0, CSR_ADAGRAD = 1, CSR_ADAM = 2, CSR_ACCUM = 3, CSR_MOMENTUM = 4 };
 
 struct CsrArgs {
     const uint2* sorted; int64_t n; uint32_t rows; int D;
     const float* grads; int64_t g_stride;
-    float* W; float* A; float* V; int* last; float* G;      // table; Adagrad acc / Adam m; Adam v; lazy stamps; gsum (ACCUM)
+    float* W; float* A; float* V; int* last; float* G;      // table; Adagrad acc / Adam m / momentum velocity; Adam v; lazy stamps; gsum (ACCUM)
     float lr, eps, b1, b2, lr_T; const float* lrt; int T, newton; AdamCFParams cf;
     float* part_lo; float* part_hi;                          // [blocks][Dp]: sums of the runs open at a block's start / end
     int Dp;
@@ -37,7 +37,7 @@ struct RowState {
             w[e] = a[e] = v[e] = 0.0f;
             if (MODE == CSR_ACCUM) { if (ok) w[e] = c.G[i]; continue; }
             if (ok) w[e] = c.W[i];
-            if (MODE == CSR_ADAGRAD || MODE == CSR_ADAM) { if (ok) a[e] = c.A[i]; }
+            if (MODE == CSR_ADAGRAD || MODE == CSR_ADAM || MODE == CSR_MOMENTUM) { if (ok) a[e] = c.A[i]; }
             if (MODE == CSR_ADAM) { if (ok) v[e] = c.V[i]; }
         }
     }
@@ -60,6 +60,11 @@ __device__ __forceinline__ void csr_rule(const CsrArgs& a, uint32_t row, const f
             a.W[i] = st.w[e] - a.lr * s[e] / (sqrtf(acc) + a.eps);
         }
         else if (MODE == CSR_ACCUM) a.G[i] = st.w[e] + s[e];
+        else if (MODE == CSR_MOMENTUM) {
+            float acc = st.a[e];
+            a.W[i] = mom_elem(st.w[e], s[e], acc, a.lr, a.eps);
+            a.A[i] = acc;
+        }
         else {
             float w = st.w[e], m = st.a[e], v = st.v[e];
             adam_replay1<true>(w, m, v, from, a.T - 1, a.lrt, a.b1, a.b2, a.eps, a.newton != 0, a.cf);

@@ -141,6 +141,29 @@ __device__ __forceinline__ f4 slot_grad(int slot, f4 u, f4 p, f4 n, f4 row, floa
 }
 
 // ---------------------------------------------------------- optimizer rule ---
+// keras.optimizers.SGD(lr, momentum, nesterov) on one element (ResourceSparseApplyKerasMomentum for a row's summed
+// gradient, ResourceApplyKerasMomentum for a dense variable): a = a*m - lr*g, then w += a*c1 - c2*g with (c1, c2) =
+// (1, 0) plain and (m, lr) nesterov -- one expression, bit-exact for the plain form (a*1 and g*0 are exact).  The
+// momentum travels in the rules' `eps` argument, its sign bit flagging nesterov (orx_internal.h orx_rule_eps).
+// Contraction is off so that every product rounds on its own, as in TF's kernels.
+__device__ __forceinline__ float mom_elem(float w, float g, float& acc, float lr, float mc) {
+#pragma clang fp contract(off)
+    const float m = fabsf(mc);
+    const bool nest = __builtin_signbit(mc);
+    const float c1 = nest ? m : 1.0f, c2 = nest ? lr : 0.0f;
+    acc = acc * m - lr * g;
+    return w + (acc * c1 - c2 * g);
+}
+
+__device__ __forceinline__ f4 mom_elem4(f4 w, f4 g, f4& acc, float lr, float mc) {
+    float ax = acc.x, ay = acc.y, az = acc.z, aw = acc.w;
+    f4 r;
+    r.x = mom_elem(w.x, g.x, ax, lr, mc); r.y = mom_elem(w.y, g.y, ay, lr, mc);
+    r.z = mom_elem(w.z, g.z, az, lr, mc); r.w = mom_elem(w.w, g.w, aw, lr, mc);
+    acc.x = ax; acc.y = ay; acc.z = az; acc.w = aw;
+    return r;
+}
+
 template <int OPT>
 __device__ __forceinline__ void opt_apply4(float* w_ptr, float* a_ptr, f4 w_old, f4 grad, float lr, float eps) {
     if (OPT == ORX_ADAGRAD) {
@@ -150,6 +173,11 @@ __device__ __forceinline__ void opt_apply4(float* w_ptr, float* a_ptr, f4 w_old,
         f4 den;
         den.x = sqrtf(acc.x) + eps; den.y = sqrtf(acc.y) + eps; den.z = sqrtf(acc.z) + eps; den.w = sqrtf(acc.w) + eps;
         *reinterpret_cast<f4*>(w_ptr) = w_old - lr * grad / den;
+    } else if (OPT == ORX_MOMENTUM) {
+        f4 acc = *reinterpret_cast<f4*>(a_ptr);
+        const f4 wn = mom_elem4(w_old, grad, acc, lr, eps);
+        *reinterpret_cast<f4*>(a_ptr) = acc;
+        *reinterpret_cast<f4*>(w_ptr) = wn;
     } else {
         *reinterpret_cast<f4*>(w_ptr) = w_old - lr * grad;
     }
@@ -166,6 +194,12 @@ __device__ __forceinline__ f4 opt_new4(float* a_ptr, f4 w_old, f4 grad, float lr
         den.x = sqrtf(acc.x) + eps; den.y = sqrtf(acc.y) + eps; den.z = sqrtf(acc.z) + eps; den.w = sqrtf(acc.w) + eps;
         return w_old - lr * grad / den;
     }
+    if (OPT == ORX_MOMENTUM) {
+        f4 acc = *reinterpret_cast<f4*>(a_ptr);
+        const f4 wn = mom_elem4(w_old, grad, acc, lr, eps);
+        *reinterpret_cast<f4*>(a_ptr) = acc;
+        return wn;
+    }
     return w_old - lr * grad;
 }
 
@@ -175,6 +209,11 @@ __device__ __forceinline__ void opt_apply1(float* w_ptr, float* a_ptr, float w_o
         const float acc = *a_ptr + grad * grad;
         *a_ptr = acc;
         *w_ptr = w_old - lr * grad / (sqrtf(acc) + eps);
+    } else if (OPT == ORX_MOMENTUM) {
+        float acc = *a_ptr;
+        const float wn = mom_elem(w_old, grad, acc, lr, eps);
+        *a_ptr = acc;
+        *w_ptr = wn;
     } else {
         *w_ptr = w_old - lr * grad;
     }

@@ -134,7 +134,7 @@ struct orx_table {
 };
 
 struct OptSlots {
-    float* s0 = nullptr;              // Adagrad acc / Adam m
+    float* s0 = nullptr;              // Adagrad acc / Adam m / momentum velocity
     float* s1 = nullptr;              // Adam v
     int* last = nullptr;              // lazy Adam: optimizer step up to which (w, m, v) of the row are current
 };
@@ -151,6 +151,13 @@ struct orx_opt {
     // (float4 per step, w unused); entries [0, lrv_done) are final for the present learning rate
     std::vector<float> h_lrv; float* d_lrv = nullptr; size_t lrv_cap = 0; int64_t lrv_done = 0;
 };
+// the second scalar of the sum-then-apply rules (the kernels' `eps` argument): Adagrad's epsilon; for momentum the
+// momentum, its sign bit set for nesterov (orx_device.h mom_elem; -0.0f for nesterov with momentum 0)
+inline float orx_rule_eps(const orx_opt* o) {
+    if (o->kind == ORX_ADAGRAD) return o->p1;
+    if (o->kind == ORX_MOMENTUM) return o->p1 != 0.f ? -o->p0 : o->p0;
+    return 0.f;
+}
 constexpr int ORX_ADAM_CF_TERMS = 512;        // J: b1^J is negligible for b1 <= 0.95
 // what a kernel needs for the closed-form replay: the moments table and the constants (lrv NULL: the replay loops)
 struct AdamCFParams { const float4* lrv; float delta, lb1, lb2; };
@@ -335,7 +342,7 @@ int orx_adam_rows_dedup(orx_ctx* ctx, orx_table* t, const int32_t* ids, int64_t 
 int orx_adam_rows_touch(orx_ctx* ctx, orx_opt* opt, orx_table* t, const int32_t* ids, int64_t n, bool have_dedup, ColWindows cw = ColWindows());
 int orx_adam_rows_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, const int32_t* ids, int64_t n, const float* grads, int64_t g_stride,
                         bool have_dedup, ColWindows cw = ColWindows());
-int orx_adagrad_rows_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* bias, const int32_t* ids, int64_t n, const float* grads,
+int orx_summed_rows_apply(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_table* bias, const int32_t* ids, int64_t n, const float* grads,
                            int64_t g_stride, ColWindows cw = ColWindows());
 int orx_table_touch(orx_table* t, const int32_t* ids, int64_t n);       // no-op unless the table is lazy
 bool orx_adam_rows_lazy(const orx_opt* opt, const orx_table* t);

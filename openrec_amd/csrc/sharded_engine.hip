@@ -379,6 +379,7 @@ static int sharded_pairwise_impl(orx_comm* c, orx_opt* opt, int model, orx_table
                                  int64_t hot, float cold_fraction, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t K, int64_t B,
                                  int64_t id_stride, int64_t users_global, int64_t items_global, float margin, float slack,
                                  int32_t plan_chunk, int flags, double* loss_l2_accum, int32_t* overflow) {
+    ORX_ARG(!opt || opt->kind != ORX_MOMENTUM, "orx_sharded_pairwise_steps: momentum is not supported by the sharded engines");
     ORX_ARG(c && opt && U && V && b && uid && pid && nid && loss_l2_accum && overflow, "orx_sharded_pairwise_steps: NULL argument");
     ORX_ARG(hot >= 0 && hot <= items_global && hot < (1LL << 30), "orx_sharded_pairwise_steps: hot_items out of range");
     ORX_ARG(hot == 0 || (Vh && bh && Vh->ctx == c->ctx && bh->ctx == c->ctx && Vh->rows >= hot && bh->rows >= hot && Vh->dim == V->dim && bh->dim == 1),
@@ -679,6 +680,7 @@ static int all_reduce(orx_comm* c, float* x, int64_t n, Buf& tmp, Buf& ptrs) {
 
 extern "C" int orx_sharded_dlrm_steps(orx_comm* c, orx_dlrm* m, orx_opt* opt, orx_table* emb, const float* dense, const int32_t* sparse,
                                       const float* label, int64_t K, int64_t B, float slack, double* loss_accum, int32_t* overflow) {
+    ORX_ARG(!opt || opt->kind != ORX_MOMENTUM, "orx_sharded_dlrm_steps: momentum is not supported by the sharded engines");
     ORX_ARG(c && m && opt && emb && dense && sparse && label && loss_accum && overflow, "orx_sharded_dlrm_steps: NULL argument");
     ORX_ARG(K >= 0 && B > 0 && slack >= 1.0f, "orx_sharded_dlrm_steps: bad sizes");
     orx_ctx* ctx = c->ctx;

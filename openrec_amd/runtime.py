@@ -177,12 +177,14 @@ class Table:
 
 
 class Optimizer:
-    KINDS = {"sgd": _ffi.ORX_SGD, "adagrad": _ffi.ORX_ADAGRAD, "adam": _ffi.ORX_ADAM}
+    KINDS = {"sgd": _ffi.ORX_SGD, "adagrad": _ffi.ORX_ADAGRAD, "adam": _ffi.ORX_ADAM, "momentum": _ffi.ORX_MOMENTUM}
+    NSLOTS = {"sgd": 0, "adagrad": 1, "adam": 2, "momentum": 1}
 
     def __init__(self, kind, lr, p0=0.0, p1=0.0, p2=0.0, ctx=None):
         self.ctx = ctx or default_context()
         self._lib = self.ctx._lib
         self.kind = kind
+        self.params = (float(p0), float(p1), float(p2))
         h = c_void_p()
         check(self._lib.orx_opt_create(self.ctx._h, self.KINDS[kind], lr, p0, p1, p2, byref(h)))
         self._h = h
@@ -200,6 +202,11 @@ class Optimizer:
     @classmethod
     def adam(cls, lr=0.001, beta_1=0.9, beta_2=0.999, epsilon=1e-7, ctx=None):
         return cls("adam", lr, beta_1, beta_2, epsilon, ctx=ctx)
+
+    @classmethod
+    def momentum(cls, lr=0.01, momentum=0.9, nesterov=False, ctx=None):
+        """keras.optimizers.SGD(lr, momentum, nesterov): slot 0 is the velocity (Keras' "momentum" slot)"""
+        return cls("momentum", lr, momentum, 1.0 if nesterov else 0.0, ctx=ctx)
 
     def set_lr(self, lr):
         check(self._lib.orx_opt_set_lr(self._h, lr))
@@ -630,19 +637,21 @@ def save_checkpoint(path, tables, opt=None, shard=None):
         out = {}
         for name, t in tables.items():
             out["table/" + name] = t.read()
-            if opt is not None and opt.kind in ("adagrad", "adam"):
+            if opt is not None and opt.kind in ("adagrad", "adam", "momentum"):
                 out["slot0/" + name] = opt.slot(t, 0)
                 if opt.kind == "adam":
                     out["slot1/" + name] = opt.slot(t, 1)
         if opt is not None:
             out["opt/kind"] = np.array(opt.kind)
             out["opt/step"] = np.array(opt.step, np.int64)          # Adam's bias correction resumes where it stopped
+            if opt.kind == "momentum":
+                out["opt/momentum"] = np.array(opt.params[:2], np.float32)      # (momentum, nesterov)
         np.savez(path, **out)
         return
     os.makedirs(path, exist_ok=True)
     suffix = "" if shard is None else ".rank%dof%d" % (int(shard[0]), int(shard[1]))
     man = dict(format="openrec_amd-ckpt-1", tensors={}, shard=None if shard is None else dict(rank=int(shard[0]), world=int(shard[1])))
-    nslots = 0 if opt is None else {"sgd": 0, "adagrad": 1, "adam": 2}[opt.kind]
+    nslots = 0 if opt is None else Optimizer.NSLOTS[opt.kind]
     for name, t in tables.items():
         if hasattr(t, "_sync_pending"):
             t._sync_pending()
@@ -656,8 +665,18 @@ def save_checkpoint(path, tables, opt=None, shard=None):
             mm.flush(); del mm
     if opt is not None:
         man["opt"] = dict(kind=opt.kind, step=int(opt.step))
+        if opt.kind == "momentum":
+            man["opt"].update(momentum=opt.params[0], nesterov=bool(opt.params[1]))
     with open(os.path.join(path, f"manifest{suffix}.json"), "w") as f:
         json.dump(man, f, indent=1)
+
+
+def _check_momentum(path, saved, opt):
+    """a velocity only continues under the momentum and the nesterov flag it was accumulated with"""
+    want = (float(np.float32(opt.params[0])), opt.params[1])
+    if (float(np.float32(saved[0])), saved[1]) != want:
+        raise ValueError(f"{path}: saved with momentum={saved[0]:g}, nesterov={bool(saved[1])}; "
+                         f"the optimizer has momentum={opt.params[0]:g}, nesterov={bool(opt.params[1])}")
 
 
 def load_checkpoint(path, tables, opt=None, shard=None):
@@ -665,6 +684,11 @@ def load_checkpoint(path, tables, opt=None, shard=None):
     import json
     if str(path).endswith(".npz"):
         z = np.load(path)
+        saved = str(z["opt/kind"]) if "opt/kind" in z else None
+        if opt is not None and saved is not None and saved != opt.kind and "momentum" in (saved, opt.kind):
+            raise ValueError(f"{path}: saved with a {saved} optimizer, loading into {opt.kind}")     # (a velocity is no other slot)
+        if opt is not None and opt.kind == "momentum" and "opt/momentum" in z:
+            _check_momentum(path, tuple(float(v) for v in z["opt/momentum"]), opt)
         for name, t in tables.items():
             t.write(z["table/" + name])
             if opt is not None and ("slot0/" + name) in z:
@@ -684,6 +708,8 @@ def load_checkpoint(path, tables, opt=None, shard=None):
         raise ValueError(f"{path}: saved with shard={man.get('shard')}, asked for {want_shard}")
     if opt is not None and "opt" in man and man["opt"]["kind"] != opt.kind:
         raise ValueError(f"{path}: saved with a {man['opt']['kind']} optimizer, loading into {opt.kind}")
+    if opt is not None and opt.kind == "momentum" and "momentum" in man.get("opt", {}):
+        _check_momentum(path, (float(man["opt"]["momentum"]), 1.0 if man["opt"]["nesterov"] else 0.0), opt)
     for name, t in tables.items():
         info = man["tensors"].get(name)
         if info is None:
@@ -696,7 +722,7 @@ def load_checkpoint(path, tables, opt=None, shard=None):
             t.write(np.ascontiguousarray(mm[r0:r0 + step]), r0)
         del mm
         if opt is not None:
-            for k in range(min(info["slots"], {"sgd": 0, "adagrad": 1, "adam": 2}[opt.kind])):
+            for k in range(min(info["slots"], Optimizer.NSLOTS[opt.kind])):
                 mm = np.load(os.path.join(path, f"slot{k}.{name}{suffix}.npy"), mmap_mode="r")
                 for r0 in range(0, t.rows, step):
                     opt.set_slot_rows(t, np.ascontiguousarray(mm[r0:r0 + step]), k, r0)

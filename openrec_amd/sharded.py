@@ -122,6 +122,8 @@ class HipBackend:
             # TF-2.0 dense-decay Adam, applied lazily by the library (rows replay their gradient-free steps when
             # next gathered or given a gradient); the step counter advances once per step, see begin_step()
             self.opt = rt.Optimizer.adam(lr, kw.get("beta_1", 0.9), kw.get("beta_2", 0.999), kw.get("epsilon", 1e-7), ctx=self.ctx)
+        elif opt_kind == "momentum":
+            raise ValueError("momentum is not supported by the sharded engines (single-GPU steps only)")
         else:
             raise ValueError("sharded tables support sgd, adagrad and adam")
         self.opt_kind = opt_kind

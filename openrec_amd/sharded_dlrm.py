@@ -49,6 +49,8 @@ class HipDLRMBackend:
             self.opt = rt.Optimizer.adagrad(lr, kw.get("initial_accumulator_value", 0.1), kw.get("epsilon", 1e-7), ctx=self.ctx)
         elif opt_kind == "adam":
             self.opt = rt.Optimizer.adam(lr, kw.get("beta_1", 0.9), kw.get("beta_2", 0.999), kw.get("epsilon", 1e-7), ctx=self.ctx)
+        elif opt_kind == "momentum":
+            raise ValueError("momentum is not supported by the sharded engines (single-GPU steps only)")
         else:
             raise ValueError("unknown optimizer %r" % opt_kind)
         self.model = rt.DLRMModel(ctx=self.ctx, no_emb=True, seed=seed, fp16_mlp=fp16_mlp, **cfg)

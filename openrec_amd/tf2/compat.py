@@ -100,13 +100,20 @@ class _Optimizer:
 
 
 class SGD(_Optimizer):
-    def __init__(self, learning_rate=0.01, momentum=0.0, **_):
+    """keras.optimizers.SGD(learning_rate, momentum, nesterov).  momentum == 0: plain SGD (every occurrence accumulated);
+    momentum > 0: the momentum rule of TF 2.0 (duplicates summed first, one "momentum" slot per variable)."""
+
+    def __init__(self, learning_rate=0.01, momentum=0.0, nesterov=False, **_):
         super().__init__()
-        if momentum:
-            raise NotImplementedError("momentum SGD is not on the reference's hot path")
+        momentum = float(momentum)
+        if not 0.0 <= momentum <= 1.0:                  # (as keras raises it; a NaN is refused too)
+            raise ValueError("`momentum` must be between [0, 1].")
+        self.momentum, self.nesterov = momentum, bool(nesterov)
         self.learning_rate = learning_rate
 
     def _make(self, ctx):
+        if self.momentum > 0:
+            return rt.Optimizer.momentum(self.learning_rate, self.momentum, self.nesterov, ctx=ctx)
         return rt.Optimizer.sgd(self.learning_rate, ctx=ctx)
 
 
