@@ -167,7 +167,9 @@ int orx_opt_slot_write(orx_opt* opt, orx_table* t, int slot, int64_t row0, int64
  * K consecutive train steps of BPR.call / UCML.call + tape.gradient((loss,
  * l2_loss)) + optimizer.apply_gradients  (bpr.py:21-37, ucml.py:21-42,
  * pairwise_log_loss.py:15-34, tf2_examples/bpr_citeulike.py:33-39).
- *   user/item/bias : tables [NU,D], [NI,D], [NI,1]
+ *   user/item/bias : tables [NU,D], [NI,D], [NI,1].  bias may be NULL with ORX_BPR: BPR without item
+ *                    biases (pairwise_log_loss.py:26-30 with p_item_bias = n_item_bias = None, score
+ *                    u.p - u.n); ORX_UCML or ORX_CENSOR with a NULL bias returns ORX_ERR_ARG
  *   uid/pid/nid    : int32, step s uses elements [s*id_stride, s*id_stride+B)
  *   margin         : UCML margin (ucml.py:7); ignored for BPR
  *   loss_out/l2_out: host float[K] or NULL (NULL = fully asynchronous call)
@@ -182,12 +184,13 @@ int orx_pairwise_step(orx_ctx* ctx, int model, orx_opt* opt,
 
 /* Pre-size every per-call scratch buffer for calls of up to K steps of B triplets on these tables
  * (duplicate-detection outputs, rewritten ids, loss partials, scratch tables), so that a later
- * orx_pairwise_step performs no device allocation.  Optional: buffers also grow on demand. */
+ * orx_pairwise_step performs no device allocation.  Optional: buffers also grow on demand.
+ * bias may be NULL (the tables of a bias-free BPR). */
 int orx_pairwise_reserve(orx_ctx* ctx, orx_opt* opt, orx_table* user, orx_table* item, orx_table* bias,
                          int64_t K, int64_t B);
 
 /* Forward only: (loss, l2_loss) of one batch without touching the tables
- * (BPR.call / UCML.call outside a tape). */
+ * (BPR.call / UCML.call outside a tape).  bias may be NULL as in orx_pairwise_step. */
 int orx_pairwise_loss(orx_ctx* ctx, int model,
                       orx_table* user, orx_table* item, orx_table* bias,
                       const int32_t* uid, const int32_t* pid, const int32_t* nid,
@@ -210,7 +213,8 @@ int orx_pointwise_loss(orx_ctx* ctx, int model,
 
 /* Recommender.inference (bpr.py:39-43, wrmf.py:36-40: kind 0 = U[uid] . V^T + b;
  * ucml.py:50-53: kind 1 = -||U[uid] - V||^2 + b; gmf.py:36-41: kind 2 = sum_d w_d u_d v_d + b).
- * uid: host int32[n]; out: host float[n * item_rows], row-major [n, item_rows]. */
+ * uid: host int32[n]; out: host float[n * item_rows], row-major [n, item_rows].
+ * bias may be NULL (every kind): the same scores without the "+ b" (a model without item biases). */
 int orx_score_all_items(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
                         const int32_t* uid, int64_t n, float* out);
 
@@ -222,7 +226,8 @@ int orx_score_all_items_device(orx_ctx* ctx, int kind, orx_table* user, orx_tabl
  * tf2_examples/bpr_citeulike.py:41-46).  For each of n users: scores over ALL items (computed on the
  * device like orx_score_all_items when pred == NULL, else taken from the host array pred[n*items]),
  * pos_mask / excl_mask host uint8 [n*items]; at: host float[nat] cut-offs (nat <= 16).
- * Outputs (host): auc[n], ndcg[n*nat], recall[n*nat]; any of them may be NULL. */
+ * Outputs (host): auc[n], ndcg[n*nat], recall[n*nat]; any of them may be NULL.  bias may be NULL as in
+ * orx_score_all_items. */
 int orx_rank_metrics(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
                      const int32_t* uid, const float* pred, const uint8_t* pos_mask, const uint8_t* excl_mask,
                      int64_t n, int64_t items, const float* at, int32_t nat,
@@ -232,7 +237,7 @@ int orx_rank_metrics(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, o
  * in before openrec/tf2/data/dataset.py:60-82 _evaluation_generator densifies them): pos_ptr / excl_ptr host int64[n + 1]
  * starting at 0, pos_items / excl_items host int32, each user's list a set (a repeated positive is an error, an id outside
  * [0, items) an index error).  2 x n x items mask bytes become the lists; results equal orx_rank_metrics on the dense masks.
- * pred_on_device != 0: pred is device memory (what orx_score_all_items_device wrote). */
+ * pred_on_device != 0: pred is device memory (what orx_score_all_items_device wrote).  bias may be NULL as in orx_score_all_items. */
 int orx_rank_metrics_csr(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
                          const int32_t* uid, const float* pred, int32_t pred_on_device, int64_t n, int64_t items,
                          const int64_t* pos_ptr, const int32_t* pos_items, const int64_t* excl_ptr, const int32_t* excl_items,

@@ -598,8 +598,17 @@ extern "C" int orx_opt_slot_write(orx_opt* o, orx_table* t, int slot, int64_t ro
 }
 
 // ------------------------------------------------------------ the hot path ---
-static int check_pair_tables(orx_table* U, orx_table* V, orx_table* b) {
-    ORX_ARG(U && V && b, "pairwise: NULL table");
+// b == NULL: BPR without item biases (model < 0: any model may go without, as in orx_pairwise_reserve); UCML and the
+// censor always need the bias
+static int check_pair_tables(orx_table* U, orx_table* V, orx_table* b, int model = -1, int flags = 0) {
+    ORX_ARG(U && V, "pairwise: NULL table");
+    ORX_ARG(b || model != ORX_UCML, "pairwise: UCML needs the item bias table (bias may be NULL with ORX_BPR only)");
+    ORX_ARG(b || !(flags & ORX_CENSOR), "pairwise: ORX_CENSOR needs the item bias table (bias may be NULL with ORX_BPR only)");
+    if (b == nullptr) {
+        ORX_ARG(U->ctx == V->ctx, "pairwise: tables belong to different contexts");
+        ORX_ARG(U->dim == V->dim, "pairwise: user dim %d != item dim %d (every model multiplies them element-wise)", U->dim, V->dim);
+        return ORX_OK;
+    }
     ORX_ARG(U->ctx == V->ctx && V->ctx == b->ctx, "pairwise: tables belong to different contexts");
     ORX_ARG(U->dim == V->dim, "pairwise: user dim %d != item dim %d (every model multiplies them element-wise)", U->dim, V->dim);
     ORX_ARG(b->dim == 1 && b->rows == V->rows, "pairwise: item_bias must be [%lld, 1]", (long long)V->rows);
@@ -993,7 +1002,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
                                  float* loss_out, float* l2_out) {
     ORX_ARG(c && opt, "orx_pairwise_step: NULL context/optimizer");
     ORX_ARG(model == ORX_BPR || model == ORX_UCML, "orx_pairwise_step: unknown model %d", model);
-    CHECK(check_pair_tables(U, V, b));
+    CHECK(check_pair_tables(U, V, b, model, flags));
     ORX_ARG(U->ctx == c && opt->ctx == c, "orx_pairwise_step: objects belong to a different context");
     ORX_ARG(K >= 0 && B >= 0, "orx_pairwise_step: negative K or B");
     ORX_ARG(K == 0 || B == 0 || (uid && pid && nid), "orx_pairwise_step: NULL id pointer");
@@ -1013,13 +1022,15 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     // exactly: a row's gradient-free steps are replayed when the row is next touched (or observed: orx_table_sync);
     // the dense form (every reference accumulates, then three whole-table sweeps per step) remains for the other
     // cases and behind ORX_ADAM_DENSE=1.
-    const bool lazy_adam = lazy_adam_ok(opt, U, V, flags) && b->owned;
+    // b == NULL: BPR without item biases -- the kernels of MODEL_BPR_NB, every use of the bias table below is skipped
+    const int kmodel = b ? model : MODEL_BPR_NB;
+    const bool lazy_adam = lazy_adam_ok(opt, U, V, flags) && (!b || b->owned);
     const int mode = (opt->kind == ORX_ADAM && !lazy_adam) ? MODE_ACCUM : (hogwild ? MODE_HOGWILD : MODE_EXACT);
     // the three tables are lazy together under one optimizer (the item rows and their biases then share step stamps),
     // or not at all: anything else first brings every row up to date
-    const bool lazy_resume = lazy_adam && U->lazy == opt && V->lazy == opt && b->lazy == opt;
-    if (!lazy_resume) for (orx_table* t : {U, V, b}) CHECK(orx_table_sync(t));
-    { orx_table* mine[3] = {U, V, b}; CHECK(orx_opt_isolate(opt, mine, 3)); }      // (a shared optimizer: see orx_opt_isolate)
+    const bool lazy_resume = lazy_adam && U->lazy == opt && V->lazy == opt && (!b || b->lazy == opt);
+    if (!lazy_resume) for (orx_table* t : {U, V, b}) CHECK(orx_table_sync(t));      // (NULL: nothing to do)
+    { orx_table* mine[3] = {U, V, b}; CHECK(orx_opt_isolate(opt, mine, b ? 3 : 2)); }      // (a shared optimizer: see orx_opt_isolate)
     // rows referenced exactly twice get plain stores into two scratch rows; the role of a reference
     // travels in bits 30:29 of its id, which needs tables below 2^29 rows
     // ORX_FORCE_FALLBACK (debug / tests): bit 0 = behave as if the tables had >= 2^28 rows (no role bits: every
@@ -1038,7 +1049,8 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     // rows referenced >= 3 times in a step: private staging slots instead of atomics (fb bit 3: atomics)
     bool staging = role_bits && orx_fused_can_inline_apply(U->dim) && !(fb & 8);
     // no read-back (see plan_stats_poll): the previous call of this shape was quiet
-    const int64_t stats_key[5] = {B, U->rows, V->rows, (int64_t)model * 16 + opt->kind, (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (inline_apply ? 2 : 0)};
+    // (kmodel: a biased and a bias-free call of one shape run different kernels and keep apart)
+    const int64_t stats_key[5] = {B, U->rows, V->rows, (int64_t)kmodel * 16 + opt->kind, (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (inline_apply ? 2 : 0)};
     CHECK(plan_stats_poll(c));
     const bool plan_wait = getenv("ORX_PLAN_WAIT") != nullptr || getenv("ORX_PLAN_PIPE") != nullptr;      // (experiments / tests: always read back)
     bool nowait = mode == MODE_EXACT && orx_plan_v2(role_bits) && staging && !censor && opt->kind != ORX_ADAM && !plan_wait &&
@@ -1047,10 +1059,12 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     if (nowait) staging = false;
     const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
     if (mode != MODE_HOGWILD) {
-        CHECK(orx_table_scratch(U, role_bits)); CHECK(orx_table_scratch(V, role_bits)); CHECK(orx_table_scratch(b, role_bits));
+        CHECK(orx_table_scratch(U, role_bits)); CHECK(orx_table_scratch(V, role_bits));
+        if (b) CHECK(orx_table_scratch(b, role_bits));
     }
     OptSlots sU, sV, sb;
-    CHECK(orx_opt_slots(opt, U, &sU)); CHECK(orx_opt_slots(opt, V, &sV)); CHECK(orx_opt_slots(opt, b, &sb));
+    CHECK(orx_opt_slots(opt, U, &sU)); CHECK(orx_opt_slots(opt, V, &sV));
+    if (b) CHECK(orx_opt_slots(opt, b, &sb));
 
     PairPlan plan;
     CHECK(orx_exact_buffers(c, U, V, K, B, mode, role_bits, inline_apply, staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
@@ -1071,9 +1085,9 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
 
     PairArgs a;
     memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b->w;
-    a.gU = U->gsum; a.gV = V->gsum; a.gb = b->gsum;
-    if (role_bits) { a.gU2 = U->gsum2; a.gV2 = V->gsum2; a.gb2 = b->gsum2; a.role_bits = 1; a.readyU = U->ready; a.readyV = V->ready; }
+    a.U = U->w; a.V = V->w; a.b = b ? b->w : nullptr;
+    a.gU = U->gsum; a.gV = V->gsum; a.gb = b ? b->gsum : nullptr;
+    if (role_bits) { a.gU2 = U->gsum2; a.gV2 = V->gsum2; a.gb2 = b ? b->gsum2 : nullptr; a.role_bits = 1; a.readyU = U->ready; a.readyV = V->ready; }
     a.aU = sU.s0; a.aV = sV.s0; a.ab = sb.s0;
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
     a.lr = opt->lr;
@@ -1085,7 +1099,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     if (lazy_adam) {
         a.a2U = sU.s1; a.a2V = sV.s1; a.a2b = sb.s1;
         CHECK(orx_opt_last(opt, U, !lazy_resume, &a.lastU)); CHECK(orx_opt_last(opt, V, !lazy_resume, &a.lastV));
-        CHECK(orx_opt_last(opt, b, !lazy_resume, &a.lastb));
+        if (b) CHECK(orx_opt_last(opt, b, !lazy_resume, &a.lastb));
         CHECK(orx_adam_lrt(opt, opt->t + K));
         a.lrt = opt->d_lrt; a.b1 = opt->p0; a.b2 = opt->p1; a.eps = opt->p2;
         if (orx_adam_cf_ok(opt) && opt->d_lrv != nullptr) {      // closed-form replay (fused_kernel LONGGAP = 2)
@@ -1095,7 +1109,8 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
         a.newton = (1.0f - sqrtf(opt->p1)) <= 1e-3f && getenv("ORX_ADAM_NO_NEWTON") == nullptr;
         // expected steps between two references of a row = rows / references per step
         a.long_gap = (U->rows / B > 64 || V->rows / (2 * B) > 64) && getenv("ORX_ADAM_NO_LONGGAP") == nullptr;
-        U->lazy = opt; V->lazy = opt; b->lazy = opt;
+        U->lazy = opt; V->lazy = opt;
+        if (b) b->lazy = opt;
     }
     // epochs are consumed one per step; on wrap-around every table clears its epoch-tagged arrays
     if ((int64_t)c->epoch + K + 16 > 0x7fffffff) { c->epoch = 0; c->epoch_gen += 1; }
@@ -1120,6 +1135,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
                 a.uid = du + s * ds; a.pid = dp + s * ds; a.nid = dn + s * ds;
             }
             orx_exact_step_views(c, plan, i, B, U->dim, stage_views, &a);
+            if (!b) { a.stageb = nullptr; a.partb = nullptr; a.prev_stageb = nullptr; }      // (no bias: nothing is staged for it)
             a.ids4 = plan.pair_tpw > 1 ? c->d_ids4 + (size_t)i * B : nullptr;
             a.partial = c->d_partial + (size_t)i * nw * 2;
             a.epoch = ++c->epoch;           // one epoch per step: ready flags and censor side marks are tagged with it
@@ -1132,7 +1148,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
             } else {
                 a.n_apply_blocks = 0; a.prev_dlist = nullptr; a.prev_dcount = nullptr;
             }
-            return orx_launch_fused(c, model, opt->kind, mode, a);
+            return orx_launch_fused(c, kmodel, opt->kind, mode, a);
         };
         bool first_launched = false;
         bool tail_done = false;             // the chunk's loss sums left with the last step's duplicate apply
@@ -1245,7 +1261,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
                     const float lr_t = (float)(opt->lr * std::sqrt(1.0 - std::pow(b2, (double)opt->t)) / (1.0 - std::pow(b1, (double)opt->t)));
                     CHECK(orx_launch_adam_sweep(c, U->w, sU.s0, sU.s1, U->gsum, U->rows * U->dim, lr_t, opt->p0, opt->p1, opt->p2));
                     CHECK(orx_launch_adam_sweep(c, V->w, sV.s0, sV.s1, V->gsum, V->rows * V->dim, lr_t, opt->p0, opt->p1, opt->p2));
-                    CHECK(orx_launch_adam_sweep(c, b->w, sb.s0, sb.s1, b->gsum, b->rows, lr_t, opt->p0, opt->p1, opt->p2));
+                    if (b) CHECK(orx_launch_adam_sweep(c, b->w, sb.s0, sb.s1, b->gsum, b->rows, lr_t, opt->p0, opt->p1, opt->p2));
                 }
                 if (censor) {                   // ucml.py:44-48: users and pos items (two tables), then neg items
                     const unsigned char* fu = c->d_cflag + (size_t)i * B;
@@ -1289,9 +1305,11 @@ extern "C" int orx_pairwise_reserve(orx_ctx* c, orx_opt* opt, orx_table* U, orx_
     const bool inline_apply = role_bits && K > 1 && orx_fused_can_inline_apply(U->dim);
     const bool staging = role_bits && orx_fused_can_inline_apply(U->dim);
     const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-    CHECK(orx_table_scratch(U, role_bits)); CHECK(orx_table_scratch(V, role_bits)); CHECK(orx_table_scratch(b, role_bits));
+    CHECK(orx_table_scratch(U, role_bits)); CHECK(orx_table_scratch(V, role_bits));
+    if (b) CHECK(orx_table_scratch(b, role_bits));
     OptSlots s;
-    CHECK(orx_opt_slots(opt, U, &s)); CHECK(orx_opt_slots(opt, V, &s)); CHECK(orx_opt_slots(opt, b, &s));
+    CHECK(orx_opt_slots(opt, U, &s)); CHECK(orx_opt_slots(opt, V, &s));
+    if (b) CHECK(orx_opt_slots(opt, b, &s));
     PairPlan plan;
     CHECK(orx_exact_buffers(c, U, V, K, B, mode, role_bits, inline_apply, staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
     if (pairing_wanted(mode, role_bits, opt->kind, U->dim, B, 0)) CHECK(pairing_buffers(c, B, U->dim, &plan));
@@ -1307,7 +1325,7 @@ extern "C" int orx_pairwise_loss(orx_ctx* c, int model, orx_table* U, orx_table*
     if (b) CHECK(orx_table_sync(b));
     ORX_ARG(c, "orx_pairwise_loss: NULL context");
     ORX_ARG(model == ORX_BPR || model == ORX_UCML, "orx_pairwise_loss: unknown model %d", model);
-    CHECK(check_pair_tables(U, V, b));
+    CHECK(check_pair_tables(U, V, b, model, flags));
     ORX_ARG(B > 0 && uid && pid && nid, "orx_pairwise_loss: empty batch or NULL ids");
     ORX_HIP(hipSetDevice(c->device));
     const int32_t *du, *dp, *dn; int64_t ds;
@@ -1317,12 +1335,12 @@ extern "C" int orx_pairwise_loss(orx_ctx* c, int model, orx_table* U, orx_table*
     ENSURE(c->d_loss, c->d_loss_cap, 2 * sizeof(double));
     PairArgs a;
     memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b->w;
+    a.U = U->w; a.V = V->w; a.b = b ? b->w : nullptr;
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
     a.margin = margin; a.invB = 1.0f / (float)B; a.l2w = 1.f;
     a.partial = c->d_partial; a.err = c->d_err;
     a.uid = du; a.pid = dp; a.nid = dn;
-    CHECK(orx_launch_fused(c, model, ORX_SGD, MODE_LOSS, a));
+    CHECK(orx_launch_fused(c, b ? model : MODEL_BPR_NB, ORX_SGD, MODE_LOSS, a));
     ReduceArgs r;
     r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nw;
     CHECK(orx_launch_loss_reduce(c, r, 1));

@@ -280,9 +280,9 @@ extern "C" int orx_score_all_items(orx_ctx* c, int kind, orx_table* U, orx_table
     if (V) CHECK(orx_table_sync(V));
     if (b) CHECK(orx_table_sync(b));
     if (w) CHECK(orx_table_sync(w));
-    ORX_ARG(c && U && V && b && (n == 0 || (uid && out)), "orx_score_all_items: NULL argument");
+    ORX_ARG(c && U && V && (n == 0 || (uid && out)), "orx_score_all_items: NULL argument");
     ORX_ARG(kind >= 0 && kind <= 2, "orx_score_all_items: unknown kind %d", kind);
-    ORX_ARG(U->dim == V->dim && b->rows == V->rows && b->dim == 1, "orx_score_all_items: table shapes do not match");
+    ORX_ARG(U->dim == V->dim && (!b || (b->rows == V->rows && b->dim == 1)), "orx_score_all_items: table shapes do not match");
     ORX_ARG(kind != 2 || (w && w->rows == U->dim && w->dim == 1), "orx_score_all_items: GMF needs w [D, 1]");
     ORX_ARG(U->dim <= 1024, "orx_score_all_items: dim too large for the LDS user tile");
     if (n == 0) return ORX_OK;
@@ -290,7 +290,7 @@ extern "C" int orx_score_all_items(orx_ctx* c, int kind, orx_table* U, orx_table
     ENSURE(c->d_ids, c->d_ids_cap, (size_t)n * sizeof(int32_t));
     ENSURE(c->d_tmp, c->d_tmp_cap, (size_t)n * V->rows * sizeof(float));
     CHECK(stage_ids(c, uid, n, 0));
-    CHECK(orx_launch_score_all(c, U->w, V->w, b->w, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, c->d_tmp));
+    CHECK(orx_launch_score_all(c, U->w, V->w, b ? b->w : nullptr, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, c->d_tmp));
     ORX_HIP(hipMemcpyAsync(out, c->d_tmp, (size_t)n * V->rows * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     return orx_check_index_error(c);
 }
@@ -302,16 +302,16 @@ extern "C" int orx_score_all_items_device(orx_ctx* c, int kind, orx_table* U, or
     if (V) CHECK(orx_table_sync(V));
     if (b) CHECK(orx_table_sync(b));
     if (w) CHECK(orx_table_sync(w));
-    ORX_ARG(c && U && V && b && (n == 0 || (uid && out_dev)), "orx_score_all_items_device: NULL argument");
+    ORX_ARG(c && U && V && (n == 0 || (uid && out_dev)), "orx_score_all_items_device: NULL argument");
     ORX_ARG(kind >= 0 && kind <= 2, "orx_score_all_items_device: unknown kind %d", kind);
-    ORX_ARG(U->dim == V->dim && b->rows == V->rows && b->dim == 1, "orx_score_all_items_device: table shapes do not match");
+    ORX_ARG(U->dim == V->dim && (!b || (b->rows == V->rows && b->dim == 1)), "orx_score_all_items_device: table shapes do not match");
     ORX_ARG(kind != 2 || (w && w->rows == U->dim && w->dim == 1), "orx_score_all_items_device: GMF needs w [D, 1]");
     ORX_ARG(U->dim <= 1024, "orx_score_all_items_device: dim too large for the LDS user tile");
     if (n == 0) return ORX_OK;
     ORX_HIP(hipSetDevice(c->device));
     ENSURE(c->d_ids, c->d_ids_cap, (size_t)n * sizeof(int32_t));
     CHECK(stage_ids(c, uid, n, 0));
-    CHECK(orx_launch_score_all(c, U->w, V->w, b->w, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, out_dev));
+    CHECK(orx_launch_score_all(c, U->w, V->w, b ? b->w : nullptr, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, out_dev));
     return orx_check_index_error(c);
 }
 
@@ -833,7 +833,7 @@ extern "C" int orx_rank_metrics(orx_ctx* c, int kind, orx_table* U, orx_table* V
     if (w) CHECK(orx_table_sync(w));
     ORX_ARG(c && pos_mask && excl_mask && at, "orx_rank_metrics: NULL argument");
     ORX_ARG(nat >= 1 && nat <= 16, "orx_rank_metrics: nat must be in [1, 16]");
-    ORX_ARG(pred || (U && V && b && uid), "orx_rank_metrics: need either pred or tables + user ids");
+    ORX_ARG(pred || (U && V && uid), "orx_rank_metrics: need either pred or tables + user ids");
     ORX_ARG(pred || V->rows == items, "orx_rank_metrics: items must equal the item table's rows");
     if (n == 0) return ORX_OK;
     ORX_HIP(hipSetDevice(c->device));
@@ -854,7 +854,7 @@ extern "C" int orx_rank_metrics(orx_ctx* c, int kind, orx_table* U, orx_table* V
         ORX_ARG(kind >= 0 && kind <= 2 && U->dim == V->dim && U->dim <= 1024, "orx_rank_metrics: bad scorer arguments");
         ENSURE(c->d_ids, c->d_ids_cap, (size_t)n * sizeof(int32_t));
         CHECK(stage_ids(c, uid, n, 0));
-        CHECK(orx_launch_score_all(c, U->w, V->w, b->w, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, d_pred));
+        CHECK(orx_launch_score_all(c, U->w, V->w, b ? b->w : nullptr, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, d_pred));
     }
     EvalArgs a;
     a.pred = d_pred; a.pos = d_pos; a.excl = d_excl; a.NI = items; a.at = d_at; a.nat = nat;
@@ -885,7 +885,7 @@ extern "C" int orx_rank_metrics_csr(orx_ctx* c, int kind, orx_table* U, orx_tabl
     if (w) CHECK(orx_table_sync(w));
     ORX_ARG(c && pos_ptr && excl_ptr && at && n >= 0 && items > 0, "orx_rank_metrics_csr: NULL argument");
     ORX_ARG(nat >= 1 && nat <= 16, "orx_rank_metrics_csr: nat must be in [1, 16]");
-    ORX_ARG(pred || (U && V && b && uid), "orx_rank_metrics_csr: need either pred or tables + user ids");
+    ORX_ARG(pred || (U && V && uid), "orx_rank_metrics_csr: need either pred or tables + user ids");
     ORX_ARG(pred || V->rows == items, "orx_rank_metrics_csr: items must equal the item table's rows");
     if (n == 0) return ORX_OK;
     ORX_ARG(pos_ptr[0] == 0 && excl_ptr[0] == 0, "orx_rank_metrics_csr: the lists start at offset 0");
@@ -961,7 +961,7 @@ extern "C" int orx_rank_metrics_csr(orx_ctx* c, int kind, orx_table* U, orx_tabl
         } else {
             // (scoring and sweeping slices of the batch on two streams -- a write stream beside a read stream -- was measured and is
             // slower at every slice count: profiles/r3_eval_notes.txt)
-            CHECK(orx_launch_score_all(c, U->w, V->w, b->w, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, d_pred));
+            CHECK(orx_launch_score_all(c, U->w, V->w, b ? b->w : nullptr, w ? w->w : nullptr, c->d_ids, n, U->rows, V->rows, U->dim, kind, d_pred));
             CHECK(orx_launch_rank_sweeps(c, a, 0, n, max_pos));
         }
         return ORX_OK;

@@ -468,20 +468,23 @@ template <int LPR, int MODEL, int OPT, int MODE, bool CENSOR = false, bool STAGE
 __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
     constexpr int TPW = 64 / LPR;
     constexpr int D = 4 * LPR;
+    // MODEL_BPR_NB: BPR with bp = bn = 0 as constants; no bias memory is touched (the bias pointers are NULL)
+    constexpr bool NB = MODEL == MODEL_BPR_NB;
+    constexpr int SM = NB ? (int)ORX_BPR : MODEL;      // the model of the score and the gradients
     // (SGD only.  Adagrad: 111 VGPRs with the pairing tail against 84 without -- a wavefront of occupancy; bounded to 96 registers
     // (`__launch_bounds__(256, 5)`: no spills) the kernel with pairs still takes 51.5 us against 49.6 without and the step 62.1
     // against 57.7, K = 20, one box: profiles/r5_adagrad_pairing_ab.txt -- the pair tail reads and writes the accumulator row too)
     constexpr bool PAIRS = MODE == MODE_EXACT && OPT == ORX_SGD && TPW > 1;
     __shared__ f4 pair_xg[PAIRS ? 256 : 1];            // pairing: gradient exchange, one slot per lane
-    __shared__ float pair_xb[PAIRS ? 256 / LPR : 1];   // ... and per lane group (item bias)
+    __shared__ float pair_xb[PAIRS && !NB ? 256 / LPR : 1];   // ... and per lane group (item bias)
     __shared__ f4 pair_xw[PAIRS ? 256 : 1];            // the writer's copy of the shared row as read
-    __shared__ float pair_xwb[PAIRS ? 256 / LPR : 1];
+    __shared__ float pair_xwb[PAIRS && !NB ? 256 / LPR : 1];
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPR;
     const int grp = lane / LPR;
     const int nab = MODE == MODE_EXACT ? a.n_apply_blocks : 0;
     if (MODE == MODE_EXACT && (int)blockIdx.x < nab) {          // apply role (block-uniform)
-        inline_apply<LPR, OPT, CENSOR, STAGED>(a);
+        inline_apply<LPR, OPT, CENSOR, STAGED, !NB>(a);
         return;
     }
     const int64_t wave_global = (int64_t)(blockIdx.x - nab) * 4 + (threadIdx.x >> 6);
@@ -525,7 +528,7 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
                 if (pi & ORX_PAIR_VALID) {  // (its partner must not add what an earlier iteration left in LDS)
                     f4 z; z.x = z.y = z.z = z.w = 0.0f;
                     pair_xg[threadIdx.x] = z;
-                    if (sub == 0) pair_xb[threadIdx.x / LPR] = 0.0f;
+                    if (!NB && sub == 0) pair_xb[threadIdx.x / LPR] = 0.0f;
                 }
             }
             continue;
@@ -553,7 +556,8 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
         f4 ru = *reinterpret_cast<const f4*>(Up);
         f4 rp = *reinterpret_cast<const f4*>(Pp);
         f4 rn = *reinterpret_cast<const f4*>(Np);
-        float bp = a.b[p], bn = a.b[n];
+        float bp = 0.f, bn = 0.f;
+        if (!NB) { bp = a.b[p]; bn = a.b[n]; }
         // lazy Adam: (w, m, v) of the three rows and two biases, replayed up to the step before this one -- the
         // forward then sees exactly what the whole-table sweeps of TF 2.0 would have left
         f4 mu, vu, mp, vp, mn, vn;
@@ -563,15 +567,15 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
             mu = *reinterpret_cast<const f4*>(a.aU + (size_t)u * D + 4 * sub); vu = *reinterpret_cast<const f4*>(a.a2U + (size_t)u * D + 4 * sub);
             mp = *reinterpret_cast<const f4*>(a.aV + (size_t)p * D + 4 * sub); vp = *reinterpret_cast<const f4*>(a.a2V + (size_t)p * D + 4 * sub);
             mn = *reinterpret_cast<const f4*>(a.aV + (size_t)n * D + 4 * sub); vn = *reinterpret_cast<const f4*>(a.a2V + (size_t)n * D + 4 * sub);
-            mbp = a.ab[p]; vbp = a.a2b[p]; mbn = a.ab[n]; vbn = a.a2b[n];
+            if (!NB) { mbp = a.ab[p]; vbp = a.a2b[p]; mbn = a.ab[n]; vbn = a.a2b[n]; }
             // (the bias of an item shares the item row's stamp: the three tables are lazy together, api.hip)
             int lu = a.lastU[u], lp = a.lastV[p], ln = a.lastV[n];
             if (LONGGAP == 2) {
                 const float4 Vt = a.lrv[T1];                 // (wave-uniform)
                 AdamCF cf;
                 if (lu < T1) { cf.setup(a.lrv, lu, T1, Vt, a.cf_lb1, a.cf_lb2); cf.row4(ru, mu, vu, a.eps, a.cf_delta); }
-                if (lp < T1) { cf.setup(a.lrv, lp, T1, Vt, a.cf_lb1, a.cf_lb2); cf.row4(rp, mp, vp, a.eps, a.cf_delta); cf.elem(bp, mbp, vbp, a.eps, a.cf_delta); }
-                if (ln < T1) { cf.setup(a.lrv, ln, T1, Vt, a.cf_lb1, a.cf_lb2); cf.row4(rn, mn, vn, a.eps, a.cf_delta); cf.elem(bn, mbn, vbn, a.eps, a.cf_delta); }
+                if (lp < T1) { cf.setup(a.lrv, lp, T1, Vt, a.cf_lb1, a.cf_lb2); cf.row4(rp, mp, vp, a.eps, a.cf_delta); if (!NB) cf.elem(bp, mbp, vbp, a.eps, a.cf_delta); }
+                if (ln < T1) { cf.setup(a.lrv, ln, T1, Vt, a.cf_lb1, a.cf_lb2); cf.row4(rn, mn, vn, a.eps, a.cf_delta); if (!NB) cf.elem(bn, mbn, vbn, a.eps, a.cf_delta); }
                 lu = lp = ln = T1;
             }
             if (LONGGAP == 1) {      // large tables: rows that have waited very long take the bounded replay and leave the merged loop
@@ -588,15 +592,15 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
             else adam_catchup_triplet<false, LPR>(ru, mu, vu, lu, rp, mp, vp, lp, rn, mn, vn, ln, bp, mbp, vbp, bn, mbn, vbn, T1, a.lrt, a.b1, a.b2, a.eps);
         }
 
-        const float red = group_allreduce<LPR>(score_partial<MODEL>(ru, rp, rn));
+        const float red = group_allreduce<LPR>(score_partial<SM>(ru, rp, rn));
         float term, g;
-        score<MODEL>(red, bp, bn, a.invB, a.margin, term, g);
+        score<SM>(red, NB ? 0.f : bp, NB ? 0.f : bn, a.invB, a.margin, term, g);
         sq_acc += dot4(ru, ru) + dot4(rp, rp) + dot4(rn, rn);
         if (sub == 0) loss_acc += term;
         if (MODE == MODE_LOSS) continue;
 
         f4 gu, gp, gn; float gbp, gbn;
-        row_grads<MODEL>(ru, rp, rn, g, a.l2w, gu, gp, gn, gbp, gbn);
+        row_grads<SM>(ru, rp, rn, g, a.l2w, gu, gp, gn, gbp, gbn);
 
         // pairing: the two lane groups that share a row leave their gradient of it in LDS (one slot per lane; a wavefront's LDS
         // operations execute in order, so no barrier), the WRITER also the row and bias it read; for both the slot is then settled
@@ -607,7 +611,7 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
                 const int myslot = (pi >> 4) & 3;
                 pair_xg[threadIdx.x] = myslot == 0 ? gu : (myslot == 1 ? gp : gn);
                 if (pi & ORX_PAIR_WRITER) pair_xw[threadIdx.x] = myslot == 0 ? ru : (myslot == 1 ? rp : rn);
-                if (sub == 0) {
+                if (!NB && sub == 0) {
                     pair_xb[threadIdx.x / LPR] = myslot == 1 ? gbp : gbn;
                     if (pi & ORX_PAIR_WRITER) pair_xwb[threadIdx.x / LPR] = myslot == 1 ? bp : bn;
                 }
@@ -635,7 +639,7 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
             } else {
                 opt_apply4<OPT>(W + off, A + off, w, gs, a.lr, a.eps);
             }
-            if (myslot != 0 && sub == 0)
+            if (!NB && myslot != 0 && sub == 0)
                 opt_apply1<OPT>(a.b + id, a.ab + id, pair_xwb[threadIdx.x / LPR], pair_xb[threadIdx.x / LPR] + pair_xb[xsrc / LPR], a.lr, a.eps);
         };
 
@@ -655,13 +659,14 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
                 *reinterpret_cast<f4*>(Pp) = rp; *reinterpret_cast<f4*>(a.aV + (size_t)p * D + 4 * sub) = mp;
                 *reinterpret_cast<f4*>(a.a2V + (size_t)p * D + 4 * sub) = vp;
                 if (sub == 0) {
-                    adam_elem(bp, mbp, vbp, gbp, lrT, a.b1, a.b2, a.eps);
-                    a.b[p] = bp; a.ab[p] = mbp; a.a2b[p] = vbp; a.lastV[p] = a.step_t; a.lastb[p] = a.step_t;
+                    if (!NB) { adam_elem(bp, mbp, vbp, gbp, lrT, a.b1, a.b2, a.eps); a.b[p] = bp; a.ab[p] = mbp; a.a2b[p] = vbp; }
+                    a.lastV[p] = a.step_t;
+                    if (!NB) a.lastb[p] = a.step_t;
                 }
             } else {
                 const int sp = kp == 2 ? slot_of(Bp + t0) : -1;
                 dup_store4s(a.gV, a.gV2, (size_t)p * D + 4 * sub, gp, kp, a.stage, sp, D, sub);
-                if (sub == 0) { dup_store1s(a.gb, a.gb2, p, gbp, kp, a.stageb, sp); if (CENSOR) a.sideV[2 * (size_t)p] = a.epoch; }
+                if (sub == 0) { if (!NB) dup_store1s(a.gb, a.gb2, p, gbp, kp, a.stageb, sp); if (CENSOR) a.sideV[2 * (size_t)p] = a.epoch; }
             }
             if (dn == 0) {
                 adam_elem4(rn, mn, vn, gn, lrT, a.b1, a.b2, a.eps);
@@ -669,13 +674,14 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
                 *reinterpret_cast<f4*>(Np) = rn; *reinterpret_cast<f4*>(a.aV + (size_t)n * D + 4 * sub) = mn;
                 *reinterpret_cast<f4*>(a.a2V + (size_t)n * D + 4 * sub) = vn;
                 if (sub == 0) {
-                    adam_elem(bn, mbn, vbn, gbn, lrT, a.b1, a.b2, a.eps);
-                    a.b[n] = bn; a.ab[n] = mbn; a.a2b[n] = vbn; a.lastV[n] = a.step_t; a.lastb[n] = a.step_t;
+                    if (!NB) { adam_elem(bn, mbn, vbn, gbn, lrT, a.b1, a.b2, a.eps); a.b[n] = bn; a.ab[n] = mbn; a.a2b[n] = vbn; }
+                    a.lastV[n] = a.step_t;
+                    if (!NB) a.lastb[n] = a.step_t;
                 }
             } else {
                 const int sn = kn == 2 ? slot_of(2 * Bp + t0) : -1;
                 dup_store4s(a.gV, a.gV2, (size_t)n * D + 4 * sub, gn, kn, a.stage, sn, D, sub);
-                if (sub == 0) { dup_store1s(a.gb, a.gb2, n, gbn, kn, a.stageb, sn); if (CENSOR) a.sideV[2 * (size_t)n + 1] = a.epoch; }
+                if (sub == 0) { if (!NB) dup_store1s(a.gb, a.gb2, n, gbn, kn, a.stageb, sn); if (CENSOR) a.sideV[2 * (size_t)n + 1] = a.epoch; }
             }
             continue;
         }
@@ -713,19 +719,19 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
         else dup_store4s(a.gU, a.gU2, (size_t)u * D + 4 * sub, gu, ku, a.stage, ku == 2 ? slot_of(t0) : -1, D, sub);
         if (dp == 0) {
             opt_apply4<OPT>(Pp, a.aV + (size_t)p * D + 4 * sub, rp, gp, a.lr, a.eps);
-            if (sub == 0) opt_apply1<OPT>(a.b + p, a.ab + p, bp, gbp, a.lr, a.eps);
+            if (!NB && sub == 0) opt_apply1<OPT>(a.b + p, a.ab + p, bp, gbp, a.lr, a.eps);
         } else {
             const int sp = kp == 2 ? slot_of(Bp + t0) : -1;
             dup_store4s(a.gV, a.gV2, (size_t)p * D + 4 * sub, gp, kp, a.stage, sp, D, sub);
-            if (sub == 0) dup_store1s(a.gb, a.gb2, p, gbp, kp, a.stageb, sp);
+            if (!NB && sub == 0) dup_store1s(a.gb, a.gb2, p, gbp, kp, a.stageb, sp);
         }
         if (dn == 0) {
             opt_apply4<OPT>(Np, a.aV + (size_t)n * D + 4 * sub, rn, gn, a.lr, a.eps);
-            if (sub == 0) opt_apply1<OPT>(a.b + n, a.ab + n, bn, gbn, a.lr, a.eps);
+            if (!NB && sub == 0) opt_apply1<OPT>(a.b + n, a.ab + n, bn, gbn, a.lr, a.eps);
         } else {
             const int sn = kn == 2 ? slot_of(2 * Bp + t0) : -1;
             dup_store4s(a.gV, a.gV2, (size_t)n * D + 4 * sub, gn, kn, a.stage, sn, D, sub);
-            if (sub == 0) dup_store1s(a.gb, a.gb2, n, gbn, kn, a.stageb, sn);
+            if (!NB && sub == 0) dup_store1s(a.gb, a.gb2, n, gbn, kn, a.stageb, sn);
         }
         pair_tail();
     }
@@ -917,6 +923,8 @@ __global__ __launch_bounds__(256) void dup_apply_generic_kernel(PairArgs a) {
 // (e.g. the example's dim_embed = 50, tf2_examples/bpr_citeulike.py:12).
 template <int MODEL, int OPT, int MODE>
 __global__ __launch_bounds__(256) void fused_generic_kernel(PairArgs a) {
+    constexpr bool NB = MODEL == MODEL_BPR_NB;         // BPR without item biases (see fused_kernel)
+    constexpr int SM = NB ? (int)ORX_BPR : MODEL;
     const int lane = threadIdx.x & 63;
     const int D = a.D;
     const int64_t wave_global = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -945,23 +953,23 @@ __global__ __launch_bounds__(256) void fused_generic_kernel(PairArgs a) {
         float* Ur = a.U + (size_t)u * D;
         float* Pr = a.V + (size_t)p * D;
         float* Nr = a.V + (size_t)n * D;
-        const float bp = a.b[p], bn = a.b[n];
+        const float bp = NB ? 0.f : a.b[p], bn = NB ? 0.f : a.b[n];
         float part = 0.0f;
         for (int e = lane; e < D; e += 64) {
             const float x = Ur[e], y = Pr[e], z = Nr[e];
-            if (MODEL == ORX_BPR) part += x * (y - z);
+            if (SM == ORX_BPR) part += x * (y - z);
             else part += (x - z) * (x - z) - (x - y) * (x - y);
             sq_acc += x * x + y * y + z * z;
         }
         const float red = wave_sum(part);
         float term, g;
-        score<MODEL>(red, bp, bn, a.invB, a.margin, term, g);
+        score<SM>(red, bp, bn, a.invB, a.margin, term, g);
         if (lane == 0) loss_acc += term;
         if (MODE == MODE_LOSS) continue;
         for (int e = lane; e < D; e += 64) {
             const float x = Ur[e], y = Pr[e], z = Nr[e];
             float gu, gp, gn;
-            if (MODEL == ORX_BPR) {
+            if (SM == ORX_BPR) {
                 gu = g * (y - z) + a.l2w * x; gp = g * x + a.l2w * y; gn = -g * x + a.l2w * z;
             } else {
                 const float a2 = 2.0f * g;
@@ -974,8 +982,8 @@ __global__ __launch_bounds__(256) void fused_generic_kernel(PairArgs a) {
             if (dn == 0) opt_apply1<OPT>(Nr + e, a.aV + (size_t)n * D + e, z, gn, a.lr, a.eps);
             else dup_store1(a.gV, a.gV2, (size_t)n * D + e, gn, kn);
         }
-        const float gbp = MODEL == ORX_BPR ? g : -g, gbn = -gbp;
-        if (lane == 0) {
+        const float gbp = SM == ORX_BPR ? g : -g, gbn = -gbp;
+        if (!NB && lane == 0) {
             if (dp == 0) opt_apply1<OPT>(a.b + p, a.ab + p, bp, gbp, a.lr, a.eps);
             else dup_store1(a.gb, a.gb2, p, gbp, kp);
             if (dn == 0) opt_apply1<OPT>(a.b + n, a.ab + n, bn, gbn, a.lr, a.eps);
@@ -1016,10 +1024,11 @@ int orx_fused_nwaves(int D, int64_t B) { return (int)(fused_grid(D, B) * 4); }
 
 template <int LPR, int MODEL, int OPT>
 static void launch_fused_mode(int mode, dim3 g, orx_ctx* s, const PairArgs& a) {
+    constexpr bool CEN = MODEL != MODEL_BPR_NB;      // censor instantiations (UCML's censor_vec; bias-free BPR has none)
     switch (mode) {
         case MODE_EXACT:
-            if (a.censor && a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, true, true>), g, dim3(256), 0, a);
-            else if (a.censor) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, true, false>), g, dim3(256), 0, a);
+            if (CEN && a.censor && a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, CEN, true>), g, dim3(256), 0, a);
+            else if (CEN && a.censor) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, CEN, false>), g, dim3(256), 0, a);
             else if (a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, false, true>), g, dim3(256), 0, a);
             else ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT>), g, dim3(256), 0, a);
             break;
@@ -1083,8 +1092,9 @@ static void launch_fused_adam(int lpr, dim3 g, orx_ctx* s, const PairArgs& a) {
         return;
     }
 #undef ORX_FL
-#define ORX_FA(L) do { if (a.censor) { if (a.stage) ORX_LAUNCH(s, (fused_kernel<L, MODEL, ORX_ADAM, MODE_EXACT, true, true>), g, dim3(256), 0, a); \
-                                         else ORX_LAUNCH(s, (fused_kernel<L, MODEL, ORX_ADAM, MODE_EXACT, true, false>), g, dim3(256), 0, a); } \
+    constexpr bool CEN = MODEL != MODEL_BPR_NB;      // (see launch_fused_mode)
+#define ORX_FA(L) do { if (CEN && a.censor) { if (a.stage) ORX_LAUNCH(s, (fused_kernel<L, MODEL, ORX_ADAM, MODE_EXACT, CEN, true>), g, dim3(256), 0, a); \
+                                         else ORX_LAUNCH(s, (fused_kernel<L, MODEL, ORX_ADAM, MODE_EXACT, CEN, false>), g, dim3(256), 0, a); } \
                        else if (a.stage) ORX_LAUNCH(s, (fused_kernel<L, MODEL, ORX_ADAM, MODE_EXACT, false, true>), g, dim3(256), 0, a); \
                        else ORX_LAUNCH(s, (fused_kernel<L, MODEL, ORX_ADAM, MODE_EXACT, false, false>), g, dim3(256), 0, a); } while (0)
     switch (lpr) {
@@ -1104,6 +1114,7 @@ int orx_launch_fused(orx_ctx* ctx, int model, int optkind, int mode, const PairA
     if (optkind == ORX_ADAM && mode == MODE_EXACT) {
         ORX_ARG(lpr != 0 && a.lrt != nullptr, "fused: the lazy Adam path needs a float4 dim");
         if (model == ORX_BPR) launch_fused_adam<ORX_BPR>(lpr, g, ctx, a);
+        else if (model == MODEL_BPR_NB) launch_fused_adam<MODEL_BPR_NB>(lpr, g, ctx, a);
         else launch_fused_adam<ORX_UCML>(lpr, g, ctx, a);
         ORX_HIP(hipGetLastError());
         return ORX_OK;
@@ -1118,6 +1129,10 @@ int orx_launch_fused(orx_ctx* ctx, int model, int optkind, int mode, const PairA
         if (ok == ORX_ADAGRAD) launch_fused_lpr<ORX_BPR, ORX_ADAGRAD>(lpr, mode, g, ctx, a);
         else if (ok == ORX_MOMENTUM) launch_fused_lpr<ORX_BPR, ORX_MOMENTUM>(lpr, mode, g, ctx, a);
         else launch_fused_lpr<ORX_BPR, ORX_SGD>(lpr, mode, g, ctx, a);
+    } else if (model == MODEL_BPR_NB) {
+        if (ok == ORX_ADAGRAD) launch_fused_lpr<MODEL_BPR_NB, ORX_ADAGRAD>(lpr, mode, g, ctx, a);
+        else if (ok == ORX_MOMENTUM) launch_fused_lpr<MODEL_BPR_NB, ORX_MOMENTUM>(lpr, mode, g, ctx, a);
+        else launch_fused_lpr<MODEL_BPR_NB, ORX_SGD>(lpr, mode, g, ctx, a);
     } else {
         if (ok == ORX_ADAGRAD) launch_fused_lpr<ORX_UCML, ORX_ADAGRAD>(lpr, mode, g, ctx, a);
         else if (ok == ORX_MOMENTUM) launch_fused_lpr<ORX_UCML, ORX_MOMENTUM>(lpr, mode, g, ctx, a);

@@ -519,6 +519,46 @@ __global__ __launch_bounds__(256) void score_all_kernel(const float* __restrict_
     }
 }
 
+// score_all_kernel without the item bias (b == NULL: bias-free models); a copy rather than a shared body, which changed the
+// register allocation of score_all_kernel itself
+__global__ __launch_bounds__(256) void score_all_nb_kernel(const float* __restrict__ U, const float* __restrict__ V,
+                                                           const float* __restrict__ w,
+                                                           const int32_t* __restrict__ uid, int64_t nq, int64_t NU,
+                                                           int64_t NI, int D, int kind, float* __restrict__ out, int* err) {
+    extern __shared__ float urow[];                 // [16][D]
+    const int64_t q0 = (int64_t)blockIdx.y * 16;
+    const int64_t j = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+    const int qs = threadIdx.x >> 6;                // this thread scores users qs, qs+4, qs+8, qs+12
+    for (int k = threadIdx.x; k < 16 * D; k += 256) {
+        const int64_t q = q0 + k / D;
+        float v = 0.0f;
+        if (q < nq) {
+            const int u = uid[q];
+            if ((uint32_t)u >= (uint64_t)NU) *err = 1; else v = U[(size_t)u * D + k % D];
+        }
+        urow[k] = v;
+    }
+    __syncthreads();
+    if (j >= NI) return;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    const float* vr = V + (size_t)j * D;
+    for (int e = 0; e < D; ++e) {
+        const float v = vr[e];
+        const float we = kind == 2 ? w[e] : 1.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float x = urow[(qs + 4 * k) * D + e];
+            if (kind == 1) { const float d = x - v; acc[k] -= d * d; }
+            else acc[k] += x * v * we;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t q = q0 + qs + 4 * k;
+        if (q < nq) out[q * NI + j] = acc[k];
+    }
+}
+
 // ---------------------------------------------------------------- launchers ---
 static inline int lpr_for_dim_p(int D) {
     switch (D) { case 16: return 4; case 32: return 8; case 64: return 16; case 128: return 32; case 256: return 64; default: return 0; }
@@ -654,7 +694,8 @@ int orx_launch_score_all(orx_ctx* ctx, const float* U, const float* V, const flo
         if (rc != ORX_OK || launched) return rc;
     }
     const dim3 g((unsigned)((NI + 63) / 64), (unsigned)((nq + 15) / 16));
-    ORX_LAUNCH(ctx, score_all_kernel, g, dim3(256), (size_t)16 * D * sizeof(float), U, V, b, w, uid, nq, NU, NI, D, kind, out, ctx->d_err);
+    if (b == nullptr) ORX_LAUNCH(ctx, score_all_nb_kernel, g, dim3(256), (size_t)16 * D * sizeof(float), U, V, w, uid, nq, NU, NI, D, kind, out, ctx->d_err);
+    else ORX_LAUNCH(ctx, score_all_kernel, g, dim3(256), (size_t)16 * D * sizeof(float), U, V, b, w, uid, nq, NU, NI, D, kind, out, ctx->d_err);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }

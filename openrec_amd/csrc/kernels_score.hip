@@ -2,6 +2,7 @@
 //   BPR / WRMF   out[q, j] =  U[uid[q]] . V[j] + b[j]                      (bpr.py:39-43, wrmf.py:36-40)
 //   UCML         out[q, j] = -|U[uid[q]] - V[j]|^2 + b[j]                   (ucml.py:50-53)
 //   GMF          out[q, j] =  sum_e w[e] U[uid[q], e] V[j, e] + b[j]        (gmf.py:36-41: Dense(1, no bias) of the products)
+// With b == NULL (a model without item biases, e.g. bias-free BPR) the same scores without the "+ b[j]".
 // The reference materialises a [B, N, D] broadcast for UCML / GMF and a GEMM for BPR; the caller on the other side is
 // eval_step (tf2_examples/bpr_citeulike.py:41-46), 1000 users x every item per call.
 //
@@ -28,6 +29,9 @@ struct ScoreArgs {
 
 template <int KIND, int NSUB, int UW, int KB>
 __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
+    // KIND 0 / 1 / 2: dot / L2 / GMF plus the item bias; 4 / 5 / 6: the same without a bias (b is NULL and never read)
+    constexpr int K3 = KIND & 3;
+    constexpr bool BIAS = KIND < 4;
     extern __shared__ __attribute__((aligned(16))) float sc_lds[];
     const int D = a.D;
     constexpr int Dp = 16 * KB, pitch = Dp + 4;           // the k loop is unrolled completely: with a back-edge the compiler drains the
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
         if (q0 + r < a.nq && c < D) {
             const int u = a.uid[q0 + r];
             if ((uint32_t)u >= (uint64_t)a.NU) *a.err = 1;
-            else { v = a.U[(size_t)u * D + c]; if (KIND == 2) v *= a.w[c]; }
+            else { v = a.U[(size_t)u * D + c]; if (K3 == 2) v *= a.w[c]; }
         }
         As[r * pitch + c] = v;
     }
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
     f32x4 stage[8];
     float bstage = 0.f;
     auto fetch = [&](int64_t j0) {
-        bstage = (tid < TI && j0 + tid < a.NI) ? a.b[j0 + tid] : 0.f;
+        bstage = (BIAS && tid < TI && j0 + tid < a.NI) ? a.b[j0 + tid] : 0.f;
         if (vec) {
             const f32x4* src = reinterpret_cast<const f32x4*>(a.V + (size_t)j0 * D);
             const int64_t lim = (a.NI - j0) * (int64_t)(D / 4);   // float4 of the rows that exist
@@ -75,7 +79,7 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
         }
     };
     auto put = [&](float* B, int64_t j0, int buf) {
-        if (tid < TI) bt[buf * TI + tid] = bstage;
+        if (BIAS && tid < TI) bt[buf * TI + tid] = bstage;
         if (vec) {
             const int q4 = D / 4;
 #pragma unroll
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
     fetch(jbeg);
     put(Bsel(0), jbeg, 0);
     __syncthreads();
-    if (KIND == 1) {
+    if (K3 == 1) {
         for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s += x * x; } un2[r] = s; }
         if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s += x * x; } vn2[r] = s; }
         __syncthreads();
@@ -138,23 +142,23 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
             const int ul = 16 * (UW * wave + g) + (lane & 15);
             const int64_t q = q0 + ul;
             if (q >= a.nq) continue;
-            const float un = KIND == 1 ? un2[ul] : 0.f;
+            const float un = K3 == 1 ? un2[ul] : 0.f;
             float* orow = a.out + (size_t)q * a.NI;
 #pragma unroll
             for (int s = 0; s < NSUB; ++s) {
                 const int64_t j = j0 + 16 * s + 4 * (lane >> 4);
                 f32x4 v = acc[g][s];
                 if (j + 3 < jend && ((a.NI | j) & 3) == 0) {           // four consecutive items, 16-byte aligned in the output row
-                    const f32x4 bj = *reinterpret_cast<const f32x4*>(bt + (t & 1) * TI + 16 * s + 4 * (lane >> 4));
-                    if (KIND == 1) { const f32x4 vn = *reinterpret_cast<const f32x4*>(vn2 + (t & 1) * TI + 16 * s + 4 * (lane >> 4)); v = 2.0f * v - un - vn; }
-                    *reinterpret_cast<f32x4*>(orow + j) = v + bj;
+                    const f32x4 bj = BIAS ? *reinterpret_cast<const f32x4*>(bt + (t & 1) * TI + 16 * s + 4 * (lane >> 4)) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (K3 == 1) { const f32x4 vn = *reinterpret_cast<const f32x4*>(vn2 + (t & 1) * TI + 16 * s + 4 * (lane >> 4)); v = 2.0f * v - un - vn; }
+                    *reinterpret_cast<f32x4*>(orow + j) = BIAS ? v + bj : v;
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         if (j + r < jend) {
                             float x = v[r];
-                            if (KIND == 1) x = 2.0f * x - un - vn2[(t & 1) * TI + 16 * s + 4 * (lane >> 4) + r];
-                            orow[j + r] = x + bt[(t & 1) * TI + 16 * s + 4 * (lane >> 4) + r];
+                            if (K3 == 1) x = 2.0f * x - un - vn2[(t & 1) * TI + 16 * s + 4 * (lane >> 4) + r];
+                            orow[j + r] = BIAS ? x + bt[(t & 1) * TI + 16 * s + 4 * (lane >> 4) + r] : x;
                         }
                     }
                 }
@@ -162,7 +166,7 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
         }
         if (more) {
             put(Bsel((t + 1) & 1), j0 + TI, (t + 1) & 1);
-            if (KIND == 1) {
+            if (K3 == 1) {
                 __syncthreads();
                 if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s += x * x; } vn2[((t + 1) & 1) * TI + tid] = s; }
             }
@@ -206,7 +210,9 @@ int orx_launch_score_mfma(orx_ctx* ctx, const float* U, const float* V, const fl
 #define ORX_SCW(K, B) do { if (UW == 2) ORX_SC(K, 4, 2, B); else ORX_SC(K, 4, 1, B); } while (0)
 #define ORX_SCK(K) do { switch (KB) { case 1: ORX_SCW(K, 1); break; case 2: ORX_SCW(K, 2); break; case 4: ORX_SCW(K, 4); break; \
                                       case 8: ORX_SCW(K, 8); break; default: ORX_SC(K, 2, 1, 16); break; } } while (0)
-    if (kind == 0) ORX_SCK(0); else if (kind == 1) ORX_SCK(1); else ORX_SCK(2);
+    if (b == nullptr) {              // no item bias (bias-free BPR): the kinds without the bias epilogue
+        if (kind == 0) ORX_SCK(4); else if (kind == 1) ORX_SCK(5); else ORX_SCK(6);
+    } else if (kind == 0) ORX_SCK(0); else if (kind == 1) ORX_SCK(1); else ORX_SCK(2);
 #undef ORX_SCK
 #undef ORX_SCW
 #undef ORX_SC

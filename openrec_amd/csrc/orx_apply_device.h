@@ -72,7 +72,8 @@ __device__ __forceinline__ bool censored_twice(const PairArgs& a, size_t row, in
     return m.x == ep && m.y == ep;
 }
 
-template <int LPR, int OPT, bool CENSOR, bool STAGED>
+// BIAS = false: the rows carry no item bias (bias-free BPR: the bias pointers are NULL and never read)
+template <int LPR, int OPT, bool CENSOR, bool STAGED, bool BIAS = true>
 __device__ __forceinline__ void inline_apply(const PairArgs& a) {
     constexpr int TPW = 64 / LPR;
     constexpr int D = 4 * LPR;
@@ -128,8 +129,8 @@ __device__ __forceinline__ void inline_apply(const PairArgs& a) {
         if (!STAGED || scnt <= 0) { store_wt4(g1, z); store_wt4(g2, z); }
         if (OPT == ORX_ADAGRAD || OPT == ORX_ADAM || OPT == ORX_MOMENTUM) store_wt4(A + row * D + 4 * sub, acc);
         float gbs = 0.0f;
-        if (STAGED && scnt > 0 && item) gbs = segment_sum1<LPR>(a.prev_stageb, sseg, scnt, sub);
-        if (item && sub == 0) {
+        if (BIAS && STAGED && scnt > 0 && item) gbs = segment_sum1<LPR>(a.prev_stageb, sseg, scnt, sub);
+        if (BIAS && item && sub == 0) {
             const float gb = STAGED && scnt > 0 ? gbs : a.gb[row] + a.gb2[row];
             float ab = (OPT == ORX_ADAGRAD || OPT == ORX_ADAM || OPT == ORX_MOMENTUM) ? a.ab[row] : 0.0f;
             float bn;

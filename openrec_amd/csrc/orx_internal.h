@@ -468,6 +468,11 @@ enum { MODE_EXACT = 0,     // unique rows in place; duplicate rows -> gsum, appl
        MODE_ACCUM = 2,     // everything -> gsum (Adam: dense sweep follows)
        MODE_LOSS = 3 };    // forward only
 
+// Internal model value of the pairwise kernels (not part of the public orx_pair_model): BPR without item biases
+// (PairwiseLogLoss with p_item_bias = n_item_bias = None).  The score is u.p - u.n; no kernel built for it loads or stores
+// b / gb / gb2 / ab / a2b / lastb / stageb / partb, which are NULL on this route.
+enum { MODEL_BPR_NB = 16 };
+
 // kernels_misc.hip
 int orx_launch_init_uniform(orx_ctx* ctx, float* w, int64_t n, float lo, float hi, uint64_t seed);
 int orx_launch_fill(orx_ctx* ctx, float* w, int64_t n, float v);

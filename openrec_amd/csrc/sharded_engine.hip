@@ -380,6 +380,7 @@ static int sharded_pairwise_impl(orx_comm* c, orx_opt* opt, int model, orx_table
                                  int64_t id_stride, int64_t users_global, int64_t items_global, float margin, float slack,
                                  int32_t plan_chunk, int flags, double* loss_l2_accum, int32_t* overflow) {
     ORX_ARG(!opt || opt->kind != ORX_MOMENTUM, "orx_sharded_pairwise_steps: momentum is not supported by the sharded engines");
+    ORX_ARG(b != nullptr, "orx_sharded_pairwise_steps: the item bias table is required (bias-free BPR runs on the single-GPU orx_pairwise_step only)");
     ORX_ARG(c && opt && U && V && b && uid && pid && nid && loss_l2_accum && overflow, "orx_sharded_pairwise_steps: NULL argument");
     ORX_ARG(hot >= 0 && hot <= items_global && hot < (1LL << 30), "orx_sharded_pairwise_steps: hot_items out of range");
     ORX_ARG(hot == 0 || (Vh && bh && Vh->ctx == c->ctx && bh->ctx == c->ctx && Vh->rows >= hot && bh->rows >= hot && Vh->dim == V->dim && bh->dim == 1),

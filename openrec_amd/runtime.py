@@ -253,10 +253,21 @@ class Optimizer:
         check(self._lib.orx_opt_slot_write(self._h, table._h, int(slot), int(row0), a.shape[0], a.ctypes.data))
 
 
+def _bias_h(bias):
+    """the C handle of an optional item-bias table (None: a model without item biases -- bias-free BPR)"""
+    return None if bias is None else bias._h
+
+
+def _keep_tables(opt, tables):
+    """the optimizer keeps the tables it holds slots for alive (never None)"""
+    opt._tables = list({id(t): t for t in (opt._tables + [t for t in tables if t is not None])}.values())
+
+
 def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None,
                   margin=0.5, hogwild=False, no_l2=False, want_loss=True, censor=False):
     """K fused train steps.  Returns (loss[K], l2[K]) as numpy float32 when
-    want_loss, else None (fully asynchronous)."""
+    want_loss, else None (fully asynchronous).  bias=None: BPR without item biases (score u.p - u.n); UCML and
+    censor need the bias (ValueError)."""
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pp, npn, dp, k1 = _ids_arg(pid)
@@ -278,16 +289,16 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
     else:
         loss = l2 = None
         lp = l2p = None
-    check(lib.orx_pairwise_step(user.ctx._h, mid, opt._h, user._h, item._h, bias._h, pu, pp, pn,
+    check(lib.orx_pairwise_step(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
                                 int(K), int(B), int(id_stride), float(margin), flags, lp, l2p))
-    opt._tables = list({id(t): t for t in (opt._tables + [user, item, bias])}.values())
+    _keep_tables(opt, (user, item, bias))
     return (loss, l2) if want_loss else None
 
 
 def pairwise_reserve(opt, user, item, bias, K, B):
-    """Pre-size every per-call device buffer for calls of up to K steps of B triplets."""
-    check(user.ctx._lib.orx_pairwise_reserve(user.ctx._h, opt._h, user._h, item._h, bias._h, int(K), int(B)))
-    opt._tables = list({id(t): t for t in (opt._tables + [user, item, bias])}.values())
+    """Pre-size every per-call device buffer for calls of up to K steps of B triplets (bias may be None)."""
+    check(user.ctx._lib.orx_pairwise_reserve(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), int(K), int(B)))
+    _keep_tables(opt, (user, item, bias))
 
 
 def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5):
@@ -298,7 +309,7 @@ def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5):
     mid = {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
     loss = np.empty(1, np.float32)
     l2 = np.empty(1, np.float32)
-    check(lib.orx_pairwise_loss(user.ctx._h, mid, user._h, item._h, bias._h, pu, pp, pn, nu, float(margin),
+    check(lib.orx_pairwise_loss(user.ctx._h, mid, user._h, item._h, _bias_h(bias), pu, pp, pn, nu, float(margin),
                                 _ffi.ORX_IDS_DEVICE if du else 0, loss.ctypes.data, l2.ctypes.data))
     return float(loss[0]), float(l2[0])
 
@@ -437,7 +448,7 @@ class SparseMask(_HostView):
 
 def score_all_items(kind, user, item, bias, uid, w=None, device=False):
     """Recommender.inference: scores of the given users against ALL items -> [n, item_rows] (host array, or with
-    `device=True` a DeviceScores that stays in HBM until someone reads it)."""
+    `device=True` a DeviceScores that stays in HBM until someone reads it).  bias=None: no "+ b" (bias-free models)."""
     lib = user.ctx._lib
     ptr, n, dev, keep = _ids_arg(uid)
     if dev:
@@ -451,11 +462,11 @@ def score_all_items(kind, user, item, bias, uid, w=None, device=False):
     if device and torch is not None:
         out = torch.empty((n, item.rows), dtype=torch.float32, device=torch.device("cuda", user.ctx.device))
         user.ctx.after_torch(out)            # (a cached block may still have work of torch's stream pending: the library's stream waits for it)
-        check(lib.orx_score_all_items_device(user.ctx._h, k, user._h, item._h, bias._h, w._h if w is not None else None,
+        check(lib.orx_score_all_items_device(user.ctx._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None,
                                              ptr, n, out.data_ptr()))
         return DeviceScores(user.ctx, out)
     out = np.empty((n, item.rows), np.float32)
-    check(lib.orx_score_all_items(user.ctx._h, k, user._h, item._h, bias._h, w._h if w is not None else None,
+    check(lib.orx_score_all_items(user.ctx._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None,
                                   ptr, n, out.ctypes.data))
     return out
 
@@ -577,7 +588,7 @@ def rank_metrics(pos_mask, excl_mask, at, pred=None, kind=None, user=None, item=
         ptr, nn, dev, keep = _ids_arg(uid)
         assert nn == n and not dev
         k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
-        check(c._lib.orx_rank_metrics(c._h, k, user._h, item._h, bias._h, w._h if w is not None else None, ptr, None,
+        check(c._lib.orx_rank_metrics(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, None,
                                       pos.ctypes.data, excl.ctypes.data, n, items, atv.ctypes.data, atv.size,
                                       auc.ctypes.data, ndcg.ctypes.data, rec.ctypes.data))
     return dict(auc=auc, ndcg=ndcg, recall=rec)
@@ -606,7 +617,7 @@ def rank_metrics_csr(pos, excl, at, pred=None, kind=None, user=None, item=None, 
         ptr, nn, dev, keep = _ids_arg(uid)
         assert nn == n and not dev
         k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
-        check(c._lib.orx_rank_metrics_csr(c._h, k, user._h, item._h, bias._h, w._h if w is not None else None, ptr, None, 0, *tail))
+        check(c._lib.orx_rank_metrics_csr(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, None, 0, *tail))
     return dict(auc=auc, ndcg=ndcg, recall=rec)
 
 

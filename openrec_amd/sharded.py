@@ -248,6 +248,9 @@ class HipBackend:
     def sharded_steps(self, comm, model, U, V, b, uid, pid, nid, n_users, n_items, margin, slack, plan_chunk, overlap, accum, ovf, dedup=True,
                       hot=None):
         """hot = (hot_items, Vh, bh): the K steps with the replicated hot items (orx_sharded_pairwise_steps_hot)"""
+        if b is None:
+            raise ValueError("sharded_steps: the item bias table is required (bias-free BPR runs on the single-GPU "
+                             "runtime.pairwise_step only)")
         mid = {"bpr": self._ffi.ORX_BPR, "ucml": self._ffi.ORX_UCML}[model]
         K, B = uid.shape
         assert uid.stride(1) == 1 and pid.stride() == uid.stride() and nid.stride() == uid.stride()

@@ -84,9 +84,10 @@ def _ids(x):
 
 class Recommender:
     """Base of BPR / UCML / GMF / WRMF: three tables exactly as in the reference
-    constructors (user_latent_factor, item_latent_factor, item_bias)."""
+    constructors (user_latent_factor, item_latent_factor, item_bias); `item_bias` is None in a model built
+    without item biases (BPR(use_item_bias=False))."""
 
-    def _build_tables(self, dim_user_embed, dim_item_embed, total_users, total_items, ctx=None):
+    def _build_tables(self, dim_user_embed, dim_item_embed, total_users, total_items, ctx=None, item_bias=True):
         from ..modules import LatentFactor
         if dim_user_embed != dim_item_embed:
             # the reference multiplies / subtracts the two vectors element-wise, so unequal
@@ -96,10 +97,14 @@ class Recommender:
                                                name='user_latent_factor', ctx=ctx)
         self.item_latent_factor = LatentFactor(num_instances=total_items, dim=dim_item_embed,
                                                name='item_latent_factor', ctx=ctx)
-        self.item_bias = LatentFactor(num_instances=total_items, dim=1, name='item_bias', ctx=ctx)
+        self.item_bias = LatentFactor(num_instances=total_items, dim=1, name='item_bias', ctx=ctx) if item_bias else None
         self._queue = _StepQueue()
-        for lf in (self.user_latent_factor, self.item_latent_factor, self.item_bias):
+        for lf in self._factors():
             lf.table.pre_access = self.flush          # any host-visible access to a table first runs the queued steps
+
+    def _factors(self):
+        """the model's LatentFactor modules (item_bias left out where the model has none)"""
+        return [lf for lf in (self.user_latent_factor, self.item_latent_factor, self.item_bias) if lf is not None]
 
     def flush(self):
         """Run the queued train steps now (called automatically whenever their effect could be observed)."""
@@ -120,8 +125,7 @@ class Recommender:
 
     @property
     def trainable_variables(self):
-        return (self.user_latent_factor.variables + self.item_latent_factor.variables
-                + self.item_bias.variables)
+        return [v for lf in self._factors() for v in lf.variables]
 
     @property
     def variables(self):           # (every variable of these models is trainable; a subclass that adds some is followed)
@@ -130,7 +134,8 @@ class Recommender:
     def _tables(self, flush=True):
         if flush:
             self.flush()
-        return self.user_latent_factor.table, self.item_latent_factor.table, self.item_bias.table
+        return (self.user_latent_factor.table, self.item_latent_factor.table,
+                self.item_bias.table if self.item_bias is not None else None)
 
     _score_kind = "dot"
 
@@ -147,7 +152,7 @@ class Recommender:
         return rt.rank_metrics(pos_mask, excl_mask, list(at), **kw)
 
     def _record(self, run_forward, run_train):
-        for lf in (self.user_latent_factor, self.item_latent_factor, self.item_bias):
+        for lf in self._factors():
             lf.snapshot_pending()               # lookups made before this step see the rows as they are now (TF gathers at call time)
         step = PendingStep(self, run_forward, run_train)
         tape = active_tape()
