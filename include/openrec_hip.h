@@ -76,9 +76,10 @@ enum orx_flags {
     ORX_CENSOR = 8,       /* orx_pairwise_step: after every step, UCML.censor_vec
                              (ucml.py:44-48) on that step's ids: users, then pos
                              items, then neg items, min_norm 0.1                */
-    ORX_POINT_SIGMOID = 16 /* orx_pointwise_step / _loss with ORX_WRMF: PointwiseMSELoss(sigmoid=True),
+    ORX_POINT_SIGMOID = 16, /* orx_pointwise_step / _loss with ORX_WRMF: PointwiseMSELoss(sigmoid=True),
                              the prediction goes through a sigmoid before the weighted squared
                              error (modules/pointwise_mse_loss.py:24-25)        */
+    ORX_OUT_DEVICE = 32   /* orx_recommend_topk: the outputs are device pointers */
 };
 
 /* kernels whose device time can be sampled with orx_prof_* */
@@ -242,6 +243,28 @@ int orx_rank_metrics_csr(orx_ctx* ctx, int kind, orx_table* user, orx_table* ite
                          const int32_t* uid, const float* pred, int32_t pred_on_device, int64_t n, int64_t items,
                          const int64_t* pos_ptr, const int32_t* pos_items, const int64_t* excl_ptr, const int32_t* excl_items,
                          const float* at, int32_t nat, float* auc, float* ndcg, float* recall);
+
+/* ---- top-K recommendation (beyond the reference API: what `Recommender.inference` is used for after training).
+ * For each user q of uid[n] (host int32) the k items with the largest orx_score_all_items score s(q, j) -- the same kinds,
+ * bias may be NULL, w for GMF -- without materialising the [n, item_rows] score matrix.
+ *   order     score descending, then item id ascending (tf.math.top_k's tie rule)
+ *   scores    bit-identical to orx_score_all_items for that (q, j)
+ *   eligible  not in the user's exclusion list and not NaN (-inf is an ordinary score); fewer than k eligible items leave
+ *             the rest of the row as item -1, score -inf
+ *   excl_ptr  host int64[n + 1] from 0 and excl_items host int32: each user's excluded items (the orx_rank_metrics_csr
+ *             form; either may be NULL for none)
+ * 1 <= k <= 1024 (else ORX_ERR_ARG); a uid outside [0, user rows) or an excluded id outside [0, item rows) is ORX_ERR_INDEX.
+ * Outputs out_items int32[n * k], out_scores float[n * k]: host memory, device memory with flags = ORX_OUT_DEVICE.
+ * The result does not depend on launch shapes or atomics: a repeated call gives the same bits.  Lazy tables are synced. */
+int orx_recommend_topk(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
+                       const int32_t* uid, int64_t n, const int64_t* excl_ptr, const int32_t* excl_items, int32_t k, int flags,
+                       int32_t* out_items, float* out_scores);
+
+/* The same selection and rules over scores that exist already: scores float[n * m] row-major, in device memory when
+ * scores_on_device != 0 (e.g. what orx_score_all_items_device wrote), else on the host.  excl_ptr / excl_items as in
+ * orx_recommend_topk with ids in [0, m); outputs on the host. */
+int orx_topk_rows(orx_ctx* ctx, const float* scores, int32_t scores_on_device, int64_t n, int64_t m,
+                  const int64_t* excl_ptr, const int32_t* excl_items, int32_t k, int32_t* out_items, float* out_scores);
 
 /* ---- on-device triplet sampler: the producer of the train step
  * (openrec/tf2/data/dataset.py:7-16 _pairwise_generator; utils.py:82-87, 102-116).

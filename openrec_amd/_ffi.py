@@ -14,7 +14,7 @@ ORX_OK, ORX_ERR_ARG, ORX_ERR_HIP, ORX_ERR_OOM, ORX_ERR_INDEX, ORX_ERR_STATE = 0,
 ORX_SGD, ORX_ADAGRAD, ORX_ADAM, ORX_MOMENTUM = 0, 1, 2, 3
 ORX_BPR, ORX_UCML = 0, 1
 ORX_GMF, ORX_WRMF = 0, 1
-ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID = 1, 2, 4, 8, 16
+ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID, ORX_OUT_DEVICE = 1, 2, 4, 8, 16, 32
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
 ORX_DLRM_FP16_MLP = 32
@@ -68,6 +68,8 @@ SIGNATURES = {
     "orx_score_all_items_device": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _fp]),
     "orx_rank_metrics": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _fp, _p, _p, c_int64, c_int64, _fp, c_int32, _fp, _fp, _fp]),
     "orx_rank_metrics_csr": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _fp, c_int32, c_int64, c_int64, _p, _p, _p, _p, _fp, c_int32, _fp, _fp, _fp]),
+    "orx_recommend_topk": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _p, _ip, c_int32, c_int, _ip, _fp]),
+    "orx_topk_rows": (c_int, [_p, _fp, c_int32, c_int64, c_int64, _p, _ip, c_int32, _ip, _fp]),
     "orx_sampler_create": (c_int, [_p, _ip, _ip, c_int64, _p, _ip, c_int64, c_int64, _pp]),
     "orx_sampler_destroy": (c_int, [_p]),
     "orx_sampler_pairwise": (c_int, [_p, c_uint64, c_int64, c_int64, _ip, _ip, _ip]),

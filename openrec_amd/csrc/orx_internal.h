@@ -102,6 +102,7 @@ struct orx_ctx {
     float* d_partial = nullptr; size_t d_partial_cap = 0;   // [K][nwaves][2] loss partials
     double* d_loss = nullptr;  size_t d_loss_cap = 0;       // [K][2] step results
     float* d_tmp = nullptr;    size_t d_tmp_cap = 0;        // misc fp32 scratch
+    unsigned char* d_topk = nullptr; size_t d_topk_cap = 0;  // top-K: thresholds, candidate lists, exclusion rows, staged outputs
     float* d_wpart = nullptr;  size_t d_wpart_cap = 0;      // [nwaves][D] dense-kernel gradient partials
     // deterministic row apply (kernels_rowsort.hip): ping-pong buffers of the radix sort, its histograms, partial sums of runs
     // that cross a 64-entry block
@@ -410,6 +411,25 @@ bool orx_point_dense_tail_ok(int D);
 int orx_point_reducers(int D, int64_t B);
 int orx_launch_score_mfma(orx_ctx* ctx, const float* U, const float* V, const float* b, const float* w, const int32_t* uid,
                           int64_t nq, int64_t NU, int64_t NI, int D, int kind, float* out, bool* launched);
+
+// top-K selection (kernels_topk.hip)
+struct TopkSelectArgs {
+    // dense rows (scores != NULL): row r is scores[r ld + j], j < m, item id j;  candidates (cs != NULL): row q is
+    // (cs, ci)[q C + i], i < cnt[q] (a row with cnt[q] > C overflowed and is left alone)
+    const float* scores; int64_t ld; int64_t m;
+    const float* cs; const int32_t* ci; int* cnt; int C;
+    const int32_t* rowmap;                      // dense rows: the batch user of row r (NULL: r)
+    const int64_t* eptr; const int32_t* eitems; // the users' sorted exclusion rows (eptr NULL: none)
+    int k;
+    int32_t* out_items; float* out_scores;      // [users][k]
+    float* theta;                               // threshold mode: theta[q] (NaN: fewer than k eligible) and cnt[q] = 0 / C + 1
+};
+int orx_launch_topk_select(orx_ctx* ctx, const TopkSelectArgs& a, int64_t rows);      // one workgroup per row
+constexpr int TOPK_FILTER_BLOCKS = 2048;   // most workgroups of one filter launch
+constexpr int TOPK_POOL = 2048;            // pending candidates per workgroup (pool_iu / pool_s: TOPK_FILTER_BLOCKS x TOPK_POOL)
+int orx_launch_topk_filter(orx_ctx* ctx, const float* U, const float* V, const float* b, const float* w, const int32_t* uid,
+                           int64_t nq, int64_t NU, int64_t NI, int D, int kind, const float* theta, int* cnt, float* cs,
+                           int32_t* ci, int C, int2* pool_iu, float* pool_s, bool* launched);
 
 // launchers implemented in kernels_pairwise.hip
 int orx_launch_dedup(orx_ctx* ctx, const DedupArgs& a, int64_t K);

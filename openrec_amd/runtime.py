@@ -471,6 +471,85 @@ def score_all_items(kind, user, item, bias, uid, w=None, device=False):
     return out
 
 
+TOPK_MAX_K = 1024
+
+
+def _topk_k(k):
+    k = int(k)
+    if not 1 <= k <= TOPK_MAX_K:
+        raise ValueError(f"k = {k} outside [1, {TOPK_MAX_K}]")
+    return k
+
+
+def _excl_lists(excl, n, items):
+    """an exclusion mask as CSR item lists -> (ptr, items) or (None, None)"""
+    if excl is None:
+        return None, None
+    if not isinstance(excl, SparseMask):
+        excl = SparseMask.from_dense(excl)
+    if excl.shape != (n, items):
+        raise ValueError(f"exclusion mask of shape {excl.shape}, expected {(n, items)}")
+    return excl.ptr, excl.items
+
+
+def recommend_topk(kind, user, item, bias, uid, k, excl=None, w=None, device=False):
+    """The k best items of each user -> (item ids int32 [n, k], scores float32 [n, k]), without the [n, item_rows] score
+    matrix.  Scores are bit-identical to `score_all_items`; order: score descending, then item id ascending; items in
+    `excl` (a SparseMask, or a dense bool mask [n, item_rows]) and NaN scores are skipped, and a row with fewer than k such
+    items ends in item -1 / score -inf.  `device=True`: two torch tensors in HBM instead of host arrays."""
+    lib = user.ctx._lib
+    ptr, n, dev, keep = _ids_arg(uid)
+    if dev:
+        raise ValueError("recommend_topk takes host ids")
+    k = _topk_k(k)
+    kd = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    ep, ei = _excl_lists(excl, n, item.rows)
+    head = (user.ctx._h, kd, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+            ep.ctypes.data if ep is not None else None, ei.ctypes.data if ei is not None else None, k)
+    if device:
+        import torch
+        dv = torch.device("cuda", user.ctx.device)
+        items_t = torch.empty((n, k), dtype=torch.int32, device=dv)
+        scores_t = torch.empty((n, k), dtype=torch.float32, device=dv)
+        user.ctx.after_torch(items_t, scores_t)
+        check(lib.orx_recommend_topk(*head, _ffi.ORX_OUT_DEVICE, items_t.data_ptr(), scores_t.data_ptr()))
+        return items_t, scores_t
+    items_h = np.empty((n, k), np.int32)
+    scores_h = np.empty((n, k), np.float32)
+    check(lib.orx_recommend_topk(*head, 0, items_h.ctypes.data, scores_h.ctypes.data))
+    return items_h, scores_h
+
+
+def topk_rows(scores, k, excl=None, ctx=None):
+    """The same selection over scores that exist already: a DeviceScores (read in HBM) or a host array [n, m]
+    -> (item ids int32 [n, k], scores float32 [n, k]) on the host."""
+    k = _topk_k(k)
+    keep = None
+    if isinstance(scores, DeviceScores) or _is_device_tensor(scores):
+        t = scores.tensor if isinstance(scores, DeviceScores) else scores
+        c = ctx or (scores.ctx if isinstance(scores, DeviceScores) else default_context())
+        if t.dim() != 2:
+            raise ValueError(f"topk_rows takes [n, m] scores, got shape {tuple(t.shape)}")
+        keep = t.float().contiguous()
+        if keep.data_ptr() != t.data_ptr():
+            c.after_torch(keep)
+        n, m = keep.shape
+        head = (keep.data_ptr(), 1)
+    else:
+        keep = np.ascontiguousarray(scores, np.float32)
+        if keep.ndim != 2:
+            raise ValueError(f"topk_rows takes [n, m] scores, got shape {keep.shape}")
+        c = ctx or default_context()
+        n, m = keep.shape
+        head = (keep.ctypes.data, 0)
+    ep, ei = _excl_lists(excl, n, m)
+    items_h = np.empty((n, k), np.int32)
+    scores_h = np.empty((n, k), np.float32)
+    check(c._lib.orx_topk_rows(c._h, *head, n, m, ep.ctypes.data if ep is not None else None,
+                               ei.ctypes.data if ei is not None else None, k, items_h.ctypes.data, scores_h.ctypes.data))
+    return items_h, scores_h
+
+
 class _BorrowedTable(Table):
     """A table handle owned by another object (e.g. a DLRM model's parameter)."""
 

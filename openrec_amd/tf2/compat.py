@@ -9,6 +9,7 @@ tf2_examples/bpr_citeulike.py runs with only its imports changed:
 only when no real TensorFlow is importable; it never shadows one."""
 from __future__ import annotations
 
+import collections
 import sys
 import types
 import weakref
@@ -396,12 +397,41 @@ def _l2_loss(x):
     return l2_loss(x)
 
 
+TopKV2 = collections.namedtuple("TopKV2", ["values", "indices"])
+
+
+def top_k(input, k=1, sorted=True, name=None):
+    """tf.math.top_k over the last axis of a 1-D or 2-D input (a DeviceScores is read in HBM): the k largest values per
+    row, ties to the lower index.  NaN entries are never returned (a row with fewer than k others ends in index -1 /
+    -inf), and k is at most 1024.  The result is always sorted."""
+    shape = tuple(input.shape) if hasattr(input, "shape") else np.shape(input)
+    if len(shape) not in (1, 2):
+        raise NotImplementedError(f"top_k: input of rank {len(shape)}; only rank 1 and 2 are supported")
+    k = int(k)
+    if k < 0:
+        raise ValueError(f"top_k: k = {k} must be non-negative")
+    if k > shape[-1]:
+        raise ValueError(f"top_k: input must have at least k = {k} columns, has {shape[-1]}")
+    if k == 0:
+        rows = shape[:-1] + (0,)
+        return TopKV2(HostTensor(np.zeros(rows), np.float32), HostTensor(np.zeros(rows), np.int32))
+    rows = input if len(shape) == 2 else (input.reshape(1, -1) if _is_torch(input) else np.asarray(input).reshape(1, -1))
+    idx, val = rt.topk_rows(rows, k)
+    if len(shape) == 1:
+        idx, val = idx[0], val[0]
+    return TopKV2(HostTensor(val, np.float32), HostTensor(idx, np.int32))
+
+
+def _is_torch(x):
+    return hasattr(x, "data_ptr") and hasattr(x, "reshape") and getattr(x, "is_cuda", False)
+
+
 optimizers = types.SimpleNamespace(SGD=SGD, Adagrad=Adagrad, Adam=Adam)
 losses = types.SimpleNamespace(BinaryCrossentropy=_BCE, MeanSquaredError=_MSE)
 keras = types.SimpleNamespace(optimizers=optimizers, metrics=types.SimpleNamespace(Mean=Mean, AUC=AUC), Model=Model, losses=losses)
-math = types.SimpleNamespace(square=_square, reduce_sum=_reduce_sum, maximum=_maximum)
+math = types.SimpleNamespace(square=_square, reduce_sum=_reduce_sum, maximum=_maximum, top_k=top_k)
 data = types.SimpleNamespace(Dataset=TensorSliceDataset)
-nn = types.SimpleNamespace(l2_loss=_l2_loss)
+nn = types.SimpleNamespace(l2_loss=_l2_loss, top_k=top_k)
 linalg = types.SimpleNamespace(matmul=matmul)
 tf = types.SimpleNamespace(function=function, GradientTape=GradientTape, constant=constant, keras=keras, data=data, nn=nn,
                            linalg=linalg, matmul=matmul, reshape=reshape, int32=int32, float32=float32, bool=bool_,

@@ -151,6 +151,15 @@ class Recommender:
             return rt.rank_metrics_csr(pos_mask, excl_mask, list(at), **kw)
         return rt.rank_metrics(pos_mask, excl_mask, list(at), **kw)
 
+    def recommend(self, user_id, k, excl_mask=None):
+        """Beyond the reference API: the k best items of each user as (item ids [B, k], scores [B, k]) in one device call,
+        without the [B, n_items] score matrix of `inference`.  Scores equal `inference`'s bit for bit, ordered by score
+        descending and then item id ascending; items in `excl_mask` (as `Dataset.evaluation` yields it, `rt.SparseMask`, or a
+        dense bool mask) and NaN scores are never returned, and rows with fewer than k other items end in id -1 / -inf."""
+        U, V, b = self._tables()
+        w = self.mlp.layers[0].kernel if self._score_kind == "gmf" else None
+        return rt.recommend_topk(self._score_kind, U, V, b, _ids(user_id), k, excl=excl_mask, w=w)
+
     def _record(self, run_forward, run_train):
         for lf in self._factors():
             lf.snapshot_pending()               # lookups made before this step see the rows as they are now (TF gathers at call time)
