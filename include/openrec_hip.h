@@ -183,6 +183,32 @@ int orx_pairwise_step(orx_ctx* ctx, int model, orx_opt* opt,
                       int64_t K, int64_t B, int64_t id_stride, float margin, int flags,
                       float* loss_out, float* l2_out);
 
+/* The same K steps with a TRAIN MASK: only the tables the mask names receive the steps' updates (Keras updates only the variables
+ * handed to apply_gradients, tf2_examples/bpr_citeulike.py:36-38 with a shorter variable list; `layer.trainable = False`).  The
+ * use is fold-in -- new users' vectors trained against item tables that are being served --, fine-tuning of one table, and
+ * alternating optimisation.  Roles: user, item, bias (ORX_WRMF: the same three).  With T the set of trained roles:
+ *   - forward, loss and l2_loss are those of the full step; l2 runs over ALL looked-up rows, trained or not;
+ *   - gradients are taken on the pre-step tables (snapshot semantics);
+ *   - a table in T receives exactly the update the full step gives it from the same pre-step tables (SGD accumulates every
+ *     occurrence; Adagrad, momentum and Adam sum duplicates first; the item table's ids are the positive and negative lookups
+ *     concatenated; ORX_NO_L2 drops the l2 part of the gradient);
+ *   - a table outside T, and every optimizer slot of it, is bit-for-bit what it was before the call: it is read, never
+ *     written.  Slots of a table that was never trained need not exist;
+ *   - Adam: the optimizer's counter advances once per step.  A table outside T that is lazily applied under `opt` is finished
+ *     under the old counter first and takes no decay for these steps (orx_opt_advance's rule for the model's own frozen tables);
+ *   - a K-step call equals K one-step calls; K steps run on the context's stream without host synchronisation, losses are
+ *     read once at the end (loss_out = l2_out = NULL: fully asynchronous);
+ *   - a mask that names every table the call was given IS orx_pairwise_step / orx_pointwise_step: same route, same bits.
+ * ORX_ERR_ARG before any device work: an empty mask; bits outside the three; ORX_TRAIN_BIAS with bias == NULL; and with a
+ * strict subset: ORX_HOGWILD, ORX_CENSOR, ORX_GMF (its Dense(1) kernel would be a fourth role).  Ids out of range:
+ * ORX_ERR_INDEX as in the full step. */
+enum orx_train_mask { ORX_TRAIN_USER = 1, ORX_TRAIN_ITEM = 2, ORX_TRAIN_BIAS = 4 };
+int orx_pairwise_step_subset(orx_ctx* ctx, int model, orx_opt* opt,
+                             orx_table* user, orx_table* item, orx_table* bias,
+                             const int32_t* uid, const int32_t* pid, const int32_t* nid,
+                             int64_t K, int64_t B, int64_t id_stride, float margin, int flags,
+                             int train_mask, float* loss_out, float* l2_out);
+
 /* Pre-size every per-call scratch buffer for calls of up to K steps of B triplets on these tables
  * (duplicate-detection outputs, rewritten ids, loss partials, scratch tables), so that a later
  * orx_pairwise_step performs no device allocation.  Optional: buffers also grow on demand.
@@ -205,6 +231,13 @@ int orx_pointwise_step(orx_ctx* ctx, int model, orx_opt* opt,
                        const int32_t* uid, const int32_t* iid, const float* label,
                        int64_t K, int64_t B, int64_t id_stride, float a, float b, int flags,
                        float* loss_out, float* l2_out);
+
+/* orx_pointwise_step with a train mask (see orx_pairwise_step_subset): ORX_WRMF, with or without ORX_POINT_SIGMOID. */
+int orx_pointwise_step_subset(orx_ctx* ctx, int model, orx_opt* opt,
+                              orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
+                              const int32_t* uid, const int32_t* iid, const float* label,
+                              int64_t K, int64_t B, int64_t id_stride, float a, float b, int flags,
+                              int train_mask, float* loss_out, float* l2_out);
 
 /* Forward only for the pointwise models (GMF.call / WRMF.call outside a tape). */
 int orx_pointwise_loss(orx_ctx* ctx, int model,

@@ -15,6 +15,7 @@ ORX_SGD, ORX_ADAGRAD, ORX_ADAM, ORX_MOMENTUM = 0, 1, 2, 3
 ORX_BPR, ORX_UCML = 0, 1
 ORX_GMF, ORX_WRMF = 0, 1
 ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID, ORX_OUT_DEVICE = 1, 2, 4, 8, 16, 32
+ORX_TRAIN_USER, ORX_TRAIN_ITEM, ORX_TRAIN_BIAS = 1, 2, 4      # enum orx_train_mask
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
 ORX_DLRM_FP16_MLP = 32
@@ -59,10 +60,14 @@ SIGNATURES = {
     "orx_opt_slot_write": (c_int, [_p, _p, c_int, c_int64, c_int64, _fp]),
     "orx_pairwise_step": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _ip, c_int64, c_int64, c_int64,
                                   c_float, c_int, _fp, _fp]),
+    "orx_pairwise_step_subset": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _ip, c_int64, c_int64, c_int64,
+                                         c_float, c_int, c_int, _fp, _fp]),
     "orx_pairwise_reserve": (c_int, [_p, _p, _p, _p, _p, c_int64, c_int64]),
     "orx_pairwise_loss": (c_int, [_p, c_int, _p, _p, _p, _ip, _ip, _ip, c_int64, c_float, c_int, _fp, _fp]),
     "orx_pointwise_step": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _ip, _ip, _fp, c_int64, c_int64, c_int64,
                                    c_float, c_float, c_int, _fp, _fp]),
+    "orx_pointwise_step_subset": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _ip, _ip, _fp, c_int64, c_int64, c_int64,
+                                          c_float, c_float, c_int, c_int, _fp, _fp]),
     "orx_pointwise_loss": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _fp, c_int64, c_float, c_float, c_int, _fp, _fp]),
     "orx_score_all_items": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _fp]),
     "orx_score_all_items_device": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _fp]),

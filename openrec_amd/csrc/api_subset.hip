@@ -1,0 +1,230 @@
+// C-ABI entry points of the partial train step: orx_pairwise_step_subset / orx_pointwise_step_subset (include/openrec_hip.h has
+// the semantics).  A mask that names every table is the full step itself; a strict subset takes the route below.
+//
+// Per call (in chunks of up to SUBSET_CHUNK steps): the id lists of the trained tables are sorted once for all steps of the
+// chunk (kernels_rowsort.hip, one launch set with grid.y = step; the item table and the bias share one sort of the
+// concatenated positive | negative ids).  Per step: [lazy Adam: the rows the step reads from a trained table are replayed to
+// the optimizer's step], ONE gradient launch (kernels_subset.hip) that writes gradient rows for the trained roles only, then
+// the sorted row apply of every trained table -- the deterministic route of orx_apply_rows, all four optimizer kinds.  The
+// gradient launch ends before the applies begin, so every gradient is taken on the pre-step tables.  Frozen tables are
+// arguments of the gradient launch alone, as const pointers; no optimizer slot is looked up for them.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "orx_internal.h"
+
+#define CHECK(call)                                                                    \
+    do {                                                                               \
+        int _rc = (call);                                                              \
+        if (_rc != ORX_OK) return _rc;                                                 \
+    } while (0)
+#define ENSURE(ptr, cap, bytes)                                                        \
+    do {                                                                               \
+        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
+        if (_rc != ORX_OK) return _rc;                                                 \
+    } while (0)
+
+namespace {
+
+constexpr int64_t SUBSET_CHUNK = 32;          // steps whose id lists are sorted together
+constexpr int ORX_TRAIN_ALL = ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS;
+
+// the mask checks both entry points share; *full: the mask names every table the call was given
+int check_mask(const char* fn, int mask, const orx_table* bias, bool* full) {
+    ORX_ARG(mask != 0, "%s: empty train mask (no table would be trained)", fn);
+    ORX_ARG((mask & ~ORX_TRAIN_ALL) == 0, "%s: train mask 0x%x has bits outside ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS", fn, mask);
+    ORX_ARG(bias != nullptr || !(mask & ORX_TRAIN_BIAS), "%s: ORX_TRAIN_BIAS without a bias table (bias is NULL)", fn);
+    *full = mask == (bias ? ORX_TRAIN_ALL : (ORX_TRAIN_USER | ORX_TRAIN_ITEM));
+    return ORX_OK;
+}
+
+struct Carve {                                // consecutive 256-byte aligned pieces of one device buffer
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
+};
+
+// one trained table of a step
+struct Trained { orx_table* t; const uint2* sorted; int64_t n; float* grads; int64_t g_stride; };
+
+// what the two models have in common: everything but the staging of the inputs and the gradient launch's model arguments
+struct SubsetCall {
+    orx_ctx* c; orx_opt* opt; orx_table* U; orx_table* V; orx_table* b;
+    int mask; int kmodel;                     // orx_launch_subset_grads' model
+    int refs;                                 // item lookups per sample: 2 (pairwise: positive, negative) or 1 (WRMF)
+    const int32_t* du; const int32_t* di; const int32_t* dn; const float* dl; int64_t ds;      // device inputs, elements between steps
+    int64_t K, B;
+    SubsetArgs a;                             // model constants filled in by the caller
+};
+
+int apply_sorted(orx_ctx* c, orx_opt* opt, const Trained& tr) {
+    if (orx_adam_rows_lazy(opt, tr.t)) return orx_adam_rows_sorted(c, opt, tr.t, tr.sorted, tr.n, tr.grads, tr.g_stride, true);
+    if (opt->kind == ORX_ADAM) return orx_adam_dense_sorted(c, opt, tr.t, tr.sorted, tr.n, tr.grads, tr.g_stride);
+    return orx_csr_apply(c, opt, tr.t, tr.sorted, tr.n, tr.grads, tr.g_stride);
+}
+
+int run_subset(SubsetCall& q, float* loss_out, float* l2_out, bool host_ids) {
+    orx_ctx* c = q.c; orx_opt* opt = q.opt;
+    const int64_t K = q.K, B = q.B, nI = q.refs * B;
+    const int D = q.U->dim;
+    const bool tU = (q.mask & ORX_TRAIN_USER) != 0, tV = (q.mask & ORX_TRAIN_ITEM) != 0, tb = (q.mask & ORX_TRAIN_BIAS) != 0;
+    const bool adam = opt->kind == ORX_ADAM;
+    ORX_ARG(!adam || opt->t + K < 0x7fffffff, "train step: step counter overflow");
+    // frozen tables: finished under the old counter (whatever optimizer they are lazy under), then only read; the same for
+    // any other table lazy under `opt` (orx_opt_isolate).  Trained tables stay lazy under `opt` where they are.
+    orx_table* keep[3]; int n_keep = 0;
+    if (tU) keep[n_keep++] = q.U;
+    if (tV) keep[n_keep++] = q.V;
+    if (tb) keep[n_keep++] = q.b;
+    if (!tU) CHECK(orx_table_sync(q.U));
+    if (!tV) CHECK(orx_table_sync(q.V));
+    if (!tb && q.b) CHECK(orx_table_sync(q.b));
+    CHECK(orx_opt_isolate(opt, keep, n_keep));
+    for (int i = 0; i < n_keep; ++i)
+        if (!(adam && orx_adam_rows_lazy(opt, keep[i]) && keep[i]->lazy == opt)) CHECK(orx_table_sync(keep[i]));
+    if (adam) CHECK(orx_adam_lrt(opt, opt->t + K + 1));
+
+    const int nw = orx_fused_nwaves(D, B);
+    const int64_t chunk = std::min<int64_t>(K, SUBSET_CHUNK);
+    ENSURE(c->d_partial, c->d_partial_cap, (size_t)chunk * nw * 2 * sizeof(float));
+    ENSURE(c->d_loss, c->d_loss_cap, (size_t)K * 2 * sizeof(double));
+    // scratch, one buffer: sorted lists of the chunk, the concatenated item ids, one step's gradient rows
+    Carve cv;
+    const size_t o_su = cv.take(tU ? (size_t)chunk * B * sizeof(uint2) : 0);
+    const size_t o_si = cv.take((tV || tb) ? (size_t)chunk * nI * sizeof(uint2) : 0);
+    const size_t o_ci = cv.take(((tV || tb) && q.refs == 2) ? (size_t)chunk * nI * sizeof(int32_t) : 0);
+    const size_t o_gu = cv.take(tU ? (size_t)B * D * sizeof(float) : 0);
+    const size_t o_gi = cv.take(tV ? (size_t)nI * D * sizeof(float) : 0);
+    const size_t o_gb = cv.take(tb ? (size_t)nI * sizeof(float) : 0);
+    ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
+    char* base = reinterpret_cast<char*>(c->d_tmp);
+    uint2* sortU = reinterpret_cast<uint2*>(base + o_su);
+    uint2* sortI = reinterpret_cast<uint2*>(base + o_si);
+    int32_t* catI = reinterpret_cast<int32_t*>(base + o_ci);
+    SubsetArgs a = q.a;
+    a.U = q.U->w; a.V = q.V->w; a.b = q.b ? q.b->w : nullptr;
+    a.gu = tU ? reinterpret_cast<float*>(base + o_gu) : nullptr;
+    a.gi = tV ? reinterpret_cast<float*>(base + o_gi) : nullptr;
+    a.gb = tb ? reinterpret_cast<float*>(base + o_gb) : nullptr;
+    a.B = B; a.NU = q.U->rows; a.NI = q.V->rows; a.D = D; a.err = c->d_err;
+
+    for (int64_t s0 = 0; s0 < K; s0 += chunk) {
+        const int64_t kc = std::min<int64_t>(chunk, K - s0);
+        const uint2* sorted = nullptr;
+        if (tV || tb) {
+            const int32_t* ids = q.di + s0 * q.ds; int64_t stride = q.ds;
+            if (q.refs == 2) {
+                CHECK(orx_launch_subset_concat_ids(c, q.di + s0 * q.ds, q.dn + s0 * q.ds, q.ds, kc, B, catI));
+                ids = catI; stride = nI;
+            }
+            CHECK(orx_rows_sort(c, ids, kc, nI, stride, q.V->rows, &sorted));
+            ORX_HIP(hipMemcpyAsync(sortI, sorted, (size_t)kc * nI * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
+        }
+        if (tU) {
+            CHECK(orx_rows_sort(c, q.du + s0 * q.ds, kc, B, q.ds, q.U->rows, &sorted));
+            ORX_HIP(hipMemcpyAsync(sortU, sorted, (size_t)kc * B * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
+        }
+        for (int64_t i = 0; i < kc; ++i) {
+            const int64_t s = s0 + i;
+            Trained tr[3]; int nt = 0;
+            if (tU) tr[nt++] = Trained{q.U, sortU + i * B, B, a.gu, D};
+            if (tV) tr[nt++] = Trained{q.V, sortI + i * nI, nI, a.gi, D};
+            if (tb) tr[nt++] = Trained{q.b, sortI + i * nI, nI, a.gb, 1};
+            // lazy Adam: the rows of a trained table this step reads are brought to the optimizer's present step first
+            if (adam)
+                for (int k = 0; k < nt; ++k)
+                    if (tr[k].t->lazy == opt) CHECK(orx_adam_rows_sorted(c, opt, tr[k].t, tr[k].sorted, tr[k].n, nullptr, 0, false));
+            a.uid = q.du + s * q.ds; a.pid = q.di + s * q.ds; a.nid = q.dn ? q.dn + s * q.ds : nullptr;
+            a.label = q.dl ? q.dl + s * q.ds : nullptr;
+            a.partial = c->d_partial + (size_t)i * nw * 2;
+            CHECK(orx_launch_subset_grads(c, q.kmodel, a));
+            if (adam) opt->t += 1;            // once per step, whatever the mask
+            for (int k = 0; k < nt; ++k) CHECK(apply_sorted(c, opt, tr[k]));
+        }
+        ReduceArgs r;
+        r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
+        CHECK(orx_launch_loss_reduce(c, r, kc));
+    }
+    CHECK(fetch_losses(c, K, loss_out, l2_out));
+    if (host_ids) return orx_check_index_error(c);
+    return ORX_OK;
+}
+
+}  // namespace
+
+extern "C" int orx_pairwise_step_subset(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                                        const int32_t* uid, const int32_t* pid, const int32_t* nid,
+                                        int64_t K, int64_t B, int64_t id_stride, float margin, int flags,
+                                        int train_mask, float* loss_out, float* l2_out) {
+    bool full = false;
+    CHECK(check_mask("orx_pairwise_step_subset", train_mask, b, &full));
+    // the full mask, and the calls that touch no table (K = 0, an empty batch), are the full step's: its checks, its route
+    if (full || K <= 0 || B <= 0) return orx_pairwise_step(c, model, opt, U, V, b, uid, pid, nid, K, B, id_stride, margin, flags, loss_out, l2_out);
+    ORX_ARG(!(flags & ORX_HOGWILD), "orx_pairwise_step_subset: ORX_HOGWILD trains every table (a strict subset is not supported with it)");
+    ORX_ARG(!(flags & ORX_CENSOR), "orx_pairwise_step_subset: ORX_CENSOR is not folded into a step over a strict subset (call orx_table_censor after it)");
+    ORX_ARG(c && opt, "orx_pairwise_step_subset: NULL context/optimizer");
+    ORX_ARG(model == ORX_BPR || model == ORX_UCML, "orx_pairwise_step_subset: unknown model %d", model);
+    ORX_ARG(U && V, "orx_pairwise_step_subset: NULL table");
+    ORX_ARG(b || model != ORX_UCML, "orx_pairwise_step_subset: UCML needs the item bias table (bias may be NULL with ORX_BPR only)");
+    ORX_ARG(U->ctx == c && V->ctx == c && (!b || b->ctx == c) && opt->ctx == c, "orx_pairwise_step_subset: objects belong to a different context");
+    ORX_ARG(U->dim == V->dim, "orx_pairwise_step_subset: user dim %d != item dim %d", U->dim, V->dim);
+    ORX_ARG(!b || (b->dim == 1 && b->rows == V->rows), "orx_pairwise_step_subset: item_bias must be [%lld, 1]", (long long)V->rows);
+    ORX_ARG(U->dim <= 256, "orx_pairwise_step_subset: dims up to 256 (got %d)", U->dim);
+    ORX_ARG(uid && pid && nid, "orx_pairwise_step_subset: NULL id pointer");
+    ORX_HIP(hipSetDevice(c->device));
+    SubsetCall q;
+    memset(&q, 0, sizeof(q));
+    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.mask = train_mask; q.kmodel = b ? model : MODEL_BPR_NB; q.refs = 2; q.K = K; q.B = B;
+    if (flags & ORX_IDS_DEVICE) { q.du = uid; q.di = pid; q.dn = nid; q.ds = id_stride; }
+    else {
+        const int64_t n = K * B;
+        ENSURE(c->d_ids, c->d_ids_cap, (size_t)3 * n * sizeof(int32_t));
+        for (int64_t s = 0; s < K; ++s) {
+            CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
+            CHECK(stage_ids(c, pid + s * id_stride, B, n + s * B));
+            CHECK(stage_ids(c, nid + s * id_stride, B, 2 * n + s * B));
+        }
+        q.du = c->d_ids; q.di = c->d_ids + n; q.dn = c->d_ids + 2 * n; q.ds = B;
+    }
+    q.a.margin = margin; q.a.invB = 1.0f / (float)B; q.a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f;
+    return run_subset(q, loss_out, l2_out, !(flags & ORX_IDS_DEVICE));
+}
+
+extern "C" int orx_pointwise_step_subset(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
+                                         const int32_t* uid, const int32_t* iid, const float* label,
+                                         int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, int flags,
+                                         int train_mask, float* loss_out, float* l2_out) {
+    bool full = false;
+    CHECK(check_mask("orx_pointwise_step_subset", train_mask, b, &full));
+    if (full || K <= 0 || B <= 0) return orx_pointwise_step(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, flags, loss_out, l2_out);
+    ORX_ARG(model != ORX_GMF, "orx_pointwise_step_subset: ORX_GMF with a strict subset is not supported (its Dense(1) kernel is a fourth role)");
+    ORX_ARG(!(flags & ORX_HOGWILD), "orx_pointwise_step_subset: ORX_HOGWILD trains every table (a strict subset is not supported with it)");
+    ORX_ARG(c && opt, "orx_pointwise_step_subset: NULL context/optimizer");
+    ORX_ARG(model == ORX_WRMF, "orx_pointwise_step_subset: unknown model %d", model);
+    ORX_ARG(U && V && b, "orx_pointwise_step_subset: NULL table");
+    ORX_ARG(U->ctx == c && V->ctx == c && b->ctx == c && opt->ctx == c, "orx_pointwise_step_subset: objects belong to a different context");
+    ORX_ARG(U->dim == V->dim, "orx_pointwise_step_subset: user dim %d != item dim %d", U->dim, V->dim);
+    ORX_ARG(b->dim == 1 && b->rows == V->rows, "orx_pointwise_step_subset: item_bias must be [%lld, 1]", (long long)V->rows);
+    ORX_ARG(U->dim <= 256, "orx_pointwise_step_subset: dims up to 256 (got %d)", U->dim);
+    ORX_ARG(uid && iid && label, "orx_pointwise_step_subset: NULL id/label pointer");
+    ORX_HIP(hipSetDevice(c->device));
+    SubsetCall q;
+    memset(&q, 0, sizeof(q));
+    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.mask = train_mask; q.kmodel = -1; q.refs = 1; q.K = K; q.B = B;
+    if (flags & ORX_IDS_DEVICE) { q.du = uid; q.di = iid; q.dl = label; q.ds = id_stride; }
+    else {
+        const int64_t n = K * B;
+        ENSURE(c->d_ids, c->d_ids_cap, (size_t)2 * n * sizeof(int32_t));
+        ENSURE(c->d_lab, c->d_lab_cap, (size_t)n * sizeof(float));
+        for (int64_t s = 0; s < K; ++s) {
+            CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
+            CHECK(stage_ids(c, iid + s * id_stride, B, n + s * B));
+            ORX_HIP(hipMemcpyAsync(c->d_lab + s * B, label + s * id_stride, (size_t)B * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        }
+        q.du = c->d_ids; q.di = c->d_ids + n; q.dl = c->d_lab; q.ds = B;
+    }
+    q.a.invB = 1.0f / (float)B; q.a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f; q.a.a_w = a_w; q.a.b_w = b_w;
+    q.a.sigmoid = (flags & ORX_POINT_SIGMOID) ? 1 : 0;
+    return run_subset(q, loss_out, l2_out, !(flags & ORX_IDS_DEVICE));
+}

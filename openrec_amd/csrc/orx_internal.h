@@ -363,6 +363,23 @@ bool orx_launch_apply_rows_pair(orx_ctx* ctx, const RowsArgs& a, const RowsArgs&
 int orx_launch_loss_accumulate(orx_ctx* ctx, const float* partial, int64_t nwaves, double* accum);
 int orx_shard_grads_nwaves(int D, int64_t T);
 
+// partial train step (kernels_subset.hip, api_subset.hip): one gradient launch per step; an output pointer that is NULL names a
+// role the step does not train -- nothing is written for it
+struct SubsetArgs {
+    const float* U; const float* V; const float* b;               // read only (b NULL: BPR without item biases)
+    const int32_t* uid; const int32_t* pid; const int32_t* nid;   // this step's ids (WRMF: pid = item ids, nid unused)
+    const float* label;                                           // WRMF
+    float* gu; float* gi; float* gb;                              // [B][D]; [2B][D] and [2B]: positive lookups, then negative (WRMF: [B][D], [B])
+    int64_t B; int64_t NU; int64_t NI;
+    int D;
+    float invB; float margin; float l2w; float a_w; float b_w;
+    int sigmoid;
+    float* partial;                                               // [orx_fused_nwaves(D, B)][2] loss / l2 partials of this step
+    int* err;
+};
+int orx_launch_subset_grads(orx_ctx* ctx, int model /* ORX_BPR, ORX_UCML, MODEL_BPR_NB; < 0: WRMF */, const SubsetArgs& a);
+int orx_launch_subset_concat_ids(orx_ctx* ctx, const int32_t* pid, const int32_t* nid, int64_t id_stride, int64_t K, int64_t B, int32_t* out);
+
 // pointwise (GMF / WRMF) step, kernels_pointwise.hip
 struct PointArgs {
     float* U; float* V; float* b; const float* w;

@@ -263,11 +263,37 @@ def _keep_tables(opt, tables):
     opt._tables = list({id(t): t for t in (opt._tables + [t for t in tables if t is not None])}.values())
 
 
+_TRAIN_ROLES = {"user": _ffi.ORX_TRAIN_USER, "item": _ffi.ORX_TRAIN_ITEM, "bias": _ffi.ORX_TRAIN_BIAS}
+
+
+def _train_mask(train, bias):
+    """`train` of the step functions -> orx_train_mask, or None for today's full step.  An iterable of "user" / "item" /
+    "bias": the tables that receive the steps' updates; every other table is read, never written."""
+    if train is None:
+        return None
+    if isinstance(train, str):
+        train = (train,)
+    roles = list(train)
+    unknown = [r for r in roles if r not in _TRAIN_ROLES]
+    if unknown:
+        raise ValueError(f"train: unknown table name(s) {unknown!r}; expected a subset of {sorted(_TRAIN_ROLES)}")
+    if not roles:
+        raise ValueError("train: empty set (no table would be trained); pass None to train every table")
+    if "bias" in roles and bias is None:
+        raise ValueError('train: "bias" named, but the model has no item-bias table (bias=None)')
+    mask = 0
+    for r in roles:
+        mask |= _TRAIN_ROLES[r]
+    return mask
+
+
 def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None,
-                  margin=0.5, hogwild=False, no_l2=False, want_loss=True, censor=False):
+                  margin=0.5, hogwild=False, no_l2=False, want_loss=True, censor=False, train=None):
     """K fused train steps.  Returns (loss[K], l2[K]) as numpy float32 when
     want_loss, else None (fully asynchronous).  bias=None: BPR without item biases (score u.p - u.n); UCML and
-    censor need the bias (ValueError)."""
+    censor need the bias (ValueError).  train: None, or the tables to update ("user", "item", "bias"); the others stay
+    bit-for-bit as they are (orx_pairwise_step_subset)."""
+    mask = _train_mask(train, bias)
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pp, npn, dp, k1 = _ids_arg(pid)
@@ -289,8 +315,12 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
     else:
         loss = l2 = None
         lp = l2p = None
-    check(lib.orx_pairwise_step(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
-                                int(K), int(B), int(id_stride), float(margin), flags, lp, l2p))
+    if mask is None:
+        check(lib.orx_pairwise_step(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
+                                    int(K), int(B), int(id_stride), float(margin), flags, lp, l2p))
+    else:
+        check(lib.orx_pairwise_step_subset(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
+                                           int(K), int(B), int(id_stride), float(margin), flags, mask, lp, l2p))
     _keep_tables(opt, (user, item, bias))
     return (loss, l2) if want_loss else None
 
@@ -328,9 +358,10 @@ _POINT = {"gmf": _ffi.ORX_GMF, "wrmf": _ffi.ORX_WRMF}
 
 
 def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None, id_stride=None,
-                   a=1.0, b_w=1.0, hogwild=False, no_l2=False, want_loss=True, sigmoid=False):
+                   a=1.0, b_w=1.0, hogwild=False, no_l2=False, want_loss=True, sigmoid=False, train=None):
     """K fused GMF / WRMF train steps (gmf.py:22-34, wrmf.py:21-34); sigmoid: PointwiseMSELoss(sigmoid=True)
-    (pointwise_mse_loss.py:24-25; WRMF only)."""
+    (pointwise_mse_loss.py:24-25; WRMF only).  train: as in pairwise_step (WRMF; GMF takes the full set only)."""
+    mask = _train_mask(train, bias)
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pi, ni, di, k1 = _ids_arg(iid)
@@ -345,10 +376,13 @@ def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None
         | (_ffi.ORX_POINT_SIGMOID if sigmoid else 0)
     loss = np.empty(K, np.float32) if want_loss else None
     l2 = np.empty(K, np.float32) if want_loss else None
-    check(lib.orx_pointwise_step(user.ctx._h, _POINT[model], opt._h, user._h, item._h, bias._h,
-                                 w._h if w is not None else None, pu, pi, pl, int(K), int(B), int(id_stride),
-                                 float(a), float(b_w), flags,
-                                 loss.ctypes.data if want_loss else None, l2.ctypes.data if want_loss else None))
+    args = (user.ctx._h, _POINT[model], opt._h, user._h, item._h, bias._h, w._h if w is not None else None, pu, pi, pl,
+            int(K), int(B), int(id_stride), float(a), float(b_w), flags)
+    outs = (loss.ctypes.data if want_loss else None, l2.ctypes.data if want_loss else None)
+    if mask is None:
+        check(lib.orx_pointwise_step(*args, *outs))
+    else:
+        check(lib.orx_pointwise_step_subset(*args, mask, *outs))
     opt._tables = list({id(t): t for t in (opt._tables + [user, item, bias] + ([w] if w is not None else []))}.values())
     return (loss, l2) if want_loss else None
 

@@ -48,10 +48,12 @@ class PendingStep:
             self.values = self._run_forward()
         return self.values
 
-    def train(self, optimizer, no_l2):
+    def train(self, optimizer, no_l2, train=None):
+        """train: None (every variable of the model), or the roles ("user", "item", "bias") of the variables that
+        apply_gradients was handed"""
         if self.trained or self.queued:
             raise RuntimeError("this recorded step was already applied")
-        out = self._run_train(optimizer, no_l2)
+        out = self._run_train(optimizer, no_l2) if train is None else self._run_train(optimizer, no_l2, train)
         if out is None:               # queued: values arrive with the flush
             self.queued = True
             return None

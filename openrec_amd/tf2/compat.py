@@ -86,18 +86,33 @@ class _Optimizer:
 
     def apply_gradients(self, grads_and_vars):
         """Consumes the tokens of `GradientTape.gradient`: all tokens of one recorded
-        step trigger ONE fused forward+backward+update call."""
-        steps = []
+        step trigger ONE fused forward+backward+update call.  As in Keras, only the variables handed over are updated:
+        a strict subset of the step's model (`layer.trainable = False`, a shorter variable list) trains those tables and
+        leaves the others, and their optimizer slots, untouched."""
+        steps = []                              # [step, no_l2, variables]
         for g, v in grads_and_vars:
             if not isinstance(g, GradToken):
                 raise TypeError("apply_gradients expects gradients produced by openrec_amd's GradientTape")
-            if g.step not in [s for s, _ in steps]:
-                steps.append((g.step, g.no_l2))
-        for step, no_l2 in steps:
+            for entry in steps:
+                if entry[0] is g.step:
+                    entry[2].append(v)
+                    break
+            else:
+                steps.append([g.step, g.no_l2, [v]])
+        plans = [(step, no_l2, _train_subset(step.model, variables)) for step, no_l2, variables in steps]      # (raises before any step runs)
+        for step, no_l2, train in plans:
             ctx = step.model.user_latent_factor.table.ctx
             self._models.add(step.model)
-            step.train(self.native(ctx), no_l2)
+            step.train(self.native(ctx), no_l2, train)
             self._iterations += 1
+
+
+def _train_subset(model, variables):
+    """The variables handed to apply_gradients for a step of `model` -> None (all of the model's: the full step) or the roles
+    of a strict subset ("user" / "item" / "bias").  Every model maps variables to its parameters by TABLE identity
+    (`_train_roles`); a variable that is not the model's is a ValueError, a strict subset a model cannot train raises
+    NotImplementedError."""
+    return model._train_roles(variables)
 
 
 class SGD(_Optimizer):
@@ -282,19 +297,28 @@ class Model:
         kwargs.pop("training", None)
         return self.call(*args, **kwargs)
 
-    @property
-    def trainable_variables(self):
+    def _collect(self, attr):
         out, seen = [], set()
         for v in vars(self).values():
             # (Keras tracks lists of layers too: dlrm.py:30-31 keeps its latent factors in one)
             for mod in (v if isinstance(v, (list, tuple)) else [v]):
-                for var in (getattr(mod, "trainable_variables", None) or getattr(mod, "variables", None) or []):
+                found = getattr(mod, attr, None)
+                if found is None:                   # (a module that only knows one of the two names)
+                    found = getattr(mod, "variables" if attr == "trainable_variables" else "trainable_variables", None) or []
+                for var in found:
                     if id(var) not in seen:
                         seen.add(id(var))
                         out.append(var)
         return out
 
-    variables = trainable_variables
+    @property
+    def trainable_variables(self):
+        """the variables of the attributes whose `trainable` is set (a LatentFactor with `trainable = False` has none)"""
+        return self._collect("trainable_variables")
+
+    @property
+    def variables(self):
+        return self._collect("variables")
 
 
 class _AllItemScores:

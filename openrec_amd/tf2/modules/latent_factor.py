@@ -137,12 +137,19 @@ class LatentFactor:
         self._var = Variable(self.table, (name or "latent_factor") + "/embeddings")
         import weakref
         self._pending = weakref.WeakSet()              # lookups nobody has looked at yet
+        self.trainable = True
+
+    # Keras `layer.trainable` (assignable): a frozen table keeps its place in `variables` and leaves `trainable_variables`,
+    # so the reference's train_step (`tape.gradient(loss, model.trainable_variables)`) no longer updates it
+    trainable = True
 
     @property
     def variables(self):
         return [self._var]
 
-    trainable_variables = variables
+    @property
+    def trainable_variables(self):
+        return [self._var] if self.trainable else []
 
     def __call__(self, ids):
         """Embedding gather: [*] int ids -> [*, dim] fp32 -- lazily (see GatheredRows): `np.asarray(lf(ids))` is the host

@@ -19,12 +19,14 @@ class _StepQueue:
 
     def __init__(self):
         self.steps, self.key, self.bufs, self.runner, self.censor = [], None, None, None, []
+        self.subset = False
 
-    def add(self, step, key, arrays, runner):
-        """arrays: the per-step input arrays (all of one length B); runner(bufs, K) -> (loss[K], l2[K])"""
+    def add(self, step, key, arrays, runner, subset=False):
+        """arrays: the per-step input arrays (all of one length B); runner(bufs, K) -> (loss[K], l2[K]); subset: the queued
+        steps train a strict subset of the model's tables (part of `key`: such steps never share a call with others)"""
         cap = STEP_QUEUE
         if self.bufs is None:
-            self.key, self.runner = key, runner
+            self.key, self.runner, self.subset = key, runner, subset
             self.bufs = []
             for a in arrays:
                 if hasattr(a, "is_cuda") and a.is_cuda:
@@ -63,7 +65,7 @@ class _StepQueue:
     def mark_censor(self, arrays):
         """UCML.censor_vec right after a queued step with the same ids: fold it into that step (ORX_CENSOR)."""
         k = len(self.steps) - 1
-        if k < 0 or len(self.censor) > k:
+        if k < 0 or len(self.censor) > k or self.subset:      # (a subset step takes no folded censor: it runs as its own call)
             return False
         for buf, a in zip(self.bufs, arrays):
             if isinstance(buf, np.ndarray):
@@ -111,25 +113,55 @@ class Recommender:
         if getattr(self, "_queue", None) is not None:
             self._queue.run()
 
-    def _enqueue(self, step, key, arrays, runner):
+    def _enqueue(self, step, key, arrays, runner, subset=False):
         """Queue an applied step; returns False when queuing is off (the caller then runs it directly)."""
         if STEP_QUEUE <= 1:
             return False
         q = self._queue
         if q.steps and q.key != key:
             q.run()
-        q.add(step, key, arrays, runner)
+        q.add(step, key, arrays, runner, subset)
         if len(q.steps) >= STEP_QUEUE:
             q.run()
         return True
 
     @property
     def trainable_variables(self):
-        return [v for lf in self._factors() for v in lf.variables]
+        """the variables of the LatentFactors whose `trainable` is set (Keras: `layer.trainable = False` freezes a table)"""
+        return [v for lf in self._factors() for v in lf.trainable_variables]
 
     @property
-    def variables(self):           # (every variable of these models is trainable; a subclass that adds some is followed)
-        return self.trainable_variables
+    def variables(self):
+        return [v for lf in self._factors() for v in lf.variables]
+
+    def _train_roles(self, variables):
+        """The variables handed to apply_gradients for a step of this model -> None (all of them: the full step) or the
+        roles ("user" / "item" / "bias") of a strict subset, by table identity."""
+        roles = {"user": self.user_latent_factor, "item": self.item_latent_factor, "bias": self.item_bias}
+        tables = {name: lf.table for name, lf in roles.items() if lf is not None}
+        mlp = getattr(self, "mlp", None)                     # GMF: the Dense(1) kernel is a variable of the step too
+        extra = list(mlp.trainable_variables) if mlp is not None else []
+        got, got_extra = [], []
+        for v in variables:
+            t = getattr(v, "table", None)
+            name = next((n for n, tt in tables.items() if t is tt), None)
+            k = next((i for i, e in enumerate(extra) if t is e.table), None)
+            if name is not None:
+                if name not in got:
+                    got.append(name)
+            elif k is not None:
+                if k not in got_extra:
+                    got_extra.append(k)
+            else:
+                raise ValueError(f"apply_gradients: variable {getattr(v, 'name', None) or v!r} does not belong to the model of its "
+                                 f"gradient's step ({type(self).__name__})")
+        if len(got) == len(tables) and len(got_extra) == len(extra):
+            return None
+        if extra:
+            missing = [roles[n]._var.name for n in tables if n not in got] + [e.name for i, e in enumerate(extra) if i not in got_extra]
+            raise NotImplementedError(f"{type(self).__name__} (GMF): training a strict subset of the variables is not supported (the Dense "
+                                      f"kernel is a fourth role); apply_gradients was not handed {missing}")
+        return tuple(n for n in ("user", "item", "bias") if n in got)
 
     def _tables(self, flush=True):
         if flush:
@@ -186,12 +218,13 @@ class PointwiseRecommender(Recommender):
             self.flush()
             return rt.pointwise_loss(name, U, V, b, w, uid, iid, lab, **kw)
 
-        def run_train(optimizer, no_l2):
+        def run_train(optimizer, no_l2, train=None):
             def runner(bufs, K):
-                return rt.pointwise_step(name, optimizer, U, V, b, w, bufs[0], bufs[1], bufs[2], K=K, no_l2=no_l2, **kw)
+                return rt.pointwise_step(name, optimizer, U, V, b, w, bufs[0], bufs[1], bufs[2], K=K, no_l2=no_l2, train=train, **kw)
             n = uid.numel() if hasattr(uid, "numel") else np.asarray(uid).size
-            key = ("point", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)))
-            if self._enqueue(step_holder[0], key, (uid, iid, np.asarray(lab, np.float32) if not hasattr(lab, "is_cuda") else lab), runner):
+            key = ("point", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), train)
+            if self._enqueue(step_holder[0], key, (uid, iid, np.asarray(lab, np.float32) if not hasattr(lab, "is_cuda") else lab), runner,
+                             subset=train is not None):
                 return None
             loss, l2 = runner((uid, iid, lab), 1)
             return float(loss[0]), float(l2[0])
@@ -217,13 +250,13 @@ class PairwiseRecommender(Recommender):
             self.flush()
             return rt.pairwise_loss(self._model, U, V, b, uid, pid, nid, margin=self.margin)
 
-        def run_train(optimizer, no_l2):
+        def run_train(optimizer, no_l2, train=None):
             def runner(bufs, K, censor=False):
                 return rt.pairwise_step(self._model, optimizer, U, V, b, bufs[0], bufs[1], bufs[2], K=K,
-                                        margin=self.margin, no_l2=no_l2, censor=censor)
+                                        margin=self.margin, no_l2=no_l2, censor=censor, train=train)
             n = uid.numel() if hasattr(uid, "numel") else np.asarray(uid).size
-            key = ("pair", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), self.margin)
-            if self._enqueue(step_holder[0], key, (uid, pid, nid), runner):
+            key = ("pair", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), self.margin, train)
+            if self._enqueue(step_holder[0], key, (uid, pid, nid), runner, subset=train is not None):
                 return None
             loss, l2 = runner((uid, pid, nid), 1)
             return float(loss[0]), float(l2[0])
@@ -234,13 +267,14 @@ class PairwiseRecommender(Recommender):
 
     call = __call__
 
-    def train_steps(self, optimizer, user_id, p_item_id, n_item_id, K=None, want_loss=True, censor=False):
+    def train_steps(self, optimizer, user_id, p_item_id, n_item_id, K=None, want_loss=True, censor=False, train=None):
         """Beyond the reference API: K consecutive fused steps in one device call
-        (ids shaped [K, B]); the path `bench.py` measures."""
+        (ids shaped [K, B]); the path `bench.py` measures.  train: None, or the tables to update ("user", "item",
+        "bias") while the others stay as they are (rt.pairwise_step)."""
         U, V, b = self._tables()
         uid, pid, nid = _ids(user_id), _ids(p_item_id), _ids(n_item_id)
         if K is None:
             K = uid.shape[0] if getattr(uid, "ndim", 1) == 2 else 1
         opt = optimizer.native(U.ctx) if hasattr(optimizer, "native") else optimizer
         return rt.pairwise_step(self._model, opt, U, V, b, uid, pid, nid, K=K, margin=self.margin,
-                                want_loss=want_loss, censor=censor)
+                                want_loss=want_loss, censor=censor, train=train)

@@ -56,6 +56,37 @@ class DLRM:
         self._vars = out
         return out
 
+    def _train_roles(self, variables):
+        """apply_gradients' variable list for a step of this model: everything (-> None, the one step there is) or an error.
+        Variables are matched by table identity -- the model's own, or those of the modules of a hand-made composition, whose
+        embedding tables are row ranges of the combined table (modules/_compose.py _dlrm_for)."""
+        def handle(t):
+            h = getattr(t, "_h", None)
+            return getattr(h, "value", h)
+        every = self.trainable_variables
+        emb = every[0].table
+        dense = {handle(v.table): v.name for v in every[1:]}
+        got, ranges, whole = set(), set(), False
+        for v in variables:
+            t = getattr(v, "table", None)
+            base = getattr(t, "base", None)
+            if base is not None and handle(base) == handle(emb):
+                ranges.add((t.row0, t.rows))
+            elif t is not None and handle(t) is not None and handle(t) == handle(emb):
+                whole = True
+            elif t is not None and handle(t) in dense:
+                got.add(handle(t))
+            else:
+                raise ValueError(f"apply_gradients: variable {getattr(v, 'name', None) or v!r} does not belong to the model of its "
+                                 f"gradient's step (DLRM)")
+        missing = [name for h, name in dense.items() if h not in got]
+        if not whole and sum(r for _, r in ranges) != emb.rows:
+            missing.insert(0, every[0].name + (f" (rows of {len(ranges)} of its embedding tables only)" if ranges else ""))
+        if missing:
+            raise NotImplementedError(f"DLRM: training a strict subset of the variables is not supported (embeddings only, MLPs only); "
+                                      f"apply_gradients was not handed {missing}")
+        return None
+
     def __call__(self, dense_features, sparse_features, label):
         m = self._model
         d, s, y = (np.asarray(x.numpy() if hasattr(x, "numpy") else x) for x in (dense_features, sparse_features, label))

@@ -17,6 +17,10 @@ class GMF(PointwiseRecommender):
     def trainable_variables(self):
         return super().trainable_variables + self.mlp.trainable_variables
 
+    @property
+    def variables(self):
+        return super().variables + self.mlp.trainable_variables
+
     def _point_args(self):
         return "gmf", self.mlp.layers[0].kernel, {}
 
