@@ -592,6 +592,49 @@ int orx_ctx_stat(orx_ctx* ctx, int what, int64_t* out);
  * `reps` timed ones on the context's stream; *gbps_out = 2 * bytes / mean launch time, in 1e9 bytes per second. */
 int orx_copy_bandwidth(orx_ctx* ctx, int64_t bytes, int32_t reps, double* gbps_out);
 
+/* ---- the fp16 MLP products alone (diagnostics and tests; no reference equivalent: the reference's Dense layers are TensorFlow's) ----
+ * The launchers of the ORX_DLRM_FP16_MLP step on caller-owned DEVICE buffers, on the context's stream (order producers with
+ * orx_ctx_wait_stream, read results after orx_synchronize).  fp16 operands are [rows][ld] halves with ld % 8 == 0 and 16-byte aligned
+ * bases; the halves between the used columns and ld must be ZERO (the kernels multiply whole 16-byte chunks).  act / act_y: 0 none,
+ * 1 relu, 2 sigmoid.  Shapes a kernel does not carry are refused with ORX_ERR_ARG, never run.
+ *   orx_gemm16_plan     what the launchers choose on `num_cu` CUs (no device needed; the environment switches ORX_GEMM16_* of the process apply):
+ *                       nt_out[8] for C[M][N] = A[M][K] B[N][K]^T: {tile config 1 = 256x128 / 2 = 128x128 / 3 = 128x64, stages 0 = register-staged /
+ *                       2 / 3 = LDS-DMA, TAIL, wave tile, BM, BN, workgroups, mask words};  tn_out[8] for C[M][N] += A[K][M]^T B[K][N]:
+ *                       {S slices, tiles, kchunk, form 0 = register-staged / 2 / 3 = LDS-DMA / 4 = two K groups, TAIL, 0, 0, 0}
+ *   orx_gemm16_group_query  the grouped backward launch of a layer [B, out] -> [B, in]: plan_out[8] = {the DLRM step would group it, tn TAIL,
+ *                       nt TAIL, S, tiles, kchunk, tn workgroups, nt workgroups}
+ *   orx_gemm16_nt       C (fp32, optional) / C16 (fp16, optional) = epilogue(A16 B16^T): + bias[N], act; then, with actY (fp32) or actY16 (fp16)
+ *                       [M][ldy], the fused activation backward v * act_y'(Y) and, with colparts, its column sums per row block:
+ *                       colparts[P][N], *P_out = P = ceil(M / BM).  mask_out: one bit per output element "fp16 value > 0", mask words of
+ *                       orx_gemm16_plan; mask_in: such a mask of the same [M][N] in place of reading actY16 (relu; LDS-DMA forms only)
+ *   orx_gemm16_tn       C[M][N] += out_scale * A16[K][lda]^T B16[K][ldb]; slab: tiles * S * (128 * 128 + 64) floats when S > 1 (the entry then
+ *                       runs the slab reduce as well and waits for it)
+ *   orx_gemm16_group    both backward products of a layer in one launch: gW[in][out] += out_scale * X16[B][ldx]^T dZ16[B][lddz] and
+ *                       C / C16 [B][nt_cols or in] = dZ16 W16[nt_cols or in][ldw]^T with the epilogue of orx_gemm16_nt (no bias, no act)
+ *   orx_head16_fwd      pred[b] = act(bias[0] + X16[b][:K] . w16[:K])
+ *   orx_head16_bwd      dz = dy * act'(pred); partial rows per workgroup (*P_out of them, at most orx_head16_bwd_blocks(ctx, B)):
+ *                       gb_parts[P] (sum dz), gW_parts[P][K] (sum X dz16), gb_below_parts[P][K]; dZ16 (and dZ32, optional) [B][K] =
+ *                       dz16 w16 act_below'(X16)
+ *   orx_cast16          dst16[M][ld16] = fp16(src[M][lds] columns < N), round to nearest even; the columns N .. ld16 - 1 are set to zero */
+int orx_gemm16_plan(int32_t num_cu, int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int32_t* nt_out, int32_t* tn_out);
+int orx_gemm16_group_query(int32_t num_cu, int32_t B, int32_t in, int32_t out, int64_t ldx, int64_t lddz, int64_t ldw, int32_t nt_cols,
+                           int32_t* plan_out);
+int orx_gemm16_nt(orx_ctx* ctx, const void* A16, int64_t lda, const void* B16, int64_t ldb, float* C, int64_t ldc, void* C16, int64_t ldc16,
+                  const float* bias, int32_t M, int32_t N, int32_t K, int act, const float* actY, const void* actY16, int64_t ldy, int act_y,
+                  float* colparts, int32_t* P_out, void* mask_out, const void* mask_in);
+int orx_gemm16_tn(orx_ctx* ctx, const void* A16, int64_t lda, const void* B16, int64_t ldb, float* C, int64_t ldc, float* slab,
+                  int32_t M, int32_t N, int32_t K, float out_scale);
+int orx_gemm16_group(orx_ctx* ctx, const void* X16, int64_t ldx, const void* dZ16, int64_t lddz, float* gW, int64_t ldgw, float* slab,
+                     int32_t in, int32_t out, int32_t B, float out_scale, const void* W16, int64_t ldw, float* C, int64_t ldc,
+                     void* C16, int64_t ldc16, const float* actY, const void* actY16, int64_t ldy, int act_y, float* colparts,
+                     int32_t* P_out, const void* mask_in, int32_t nt_cols);
+int orx_head16_fwd(orx_ctx* ctx, const void* X16, int64_t ldx, const void* w16, const float* bias, int act, float* pred, int32_t B, int32_t K);
+int32_t orx_head16_bwd_blocks(orx_ctx* ctx, int32_t B);
+int orx_head16_bwd(orx_ctx* ctx, const void* X16, int64_t ldx, const void* w16, const float* dy, const float* pred, int act, int act_below,
+                   float* gW_parts, float* gb_parts, void* dZ16, int64_t ld16, float* dZ32, int64_t ld32, float* gb_below_parts,
+                   int32_t B, int32_t K, int32_t* P_out);
+int orx_cast16(orx_ctx* ctx, const float* src, int64_t lds, void* dst16, int64_t ld16, int32_t M, int32_t N);
+
 #ifdef __cplusplus
 }
 #endif

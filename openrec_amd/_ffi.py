@@ -131,6 +131,18 @@ SIGNATURES = {
     "orx_copy_bandwidth": (c_int, [_p, c_int64, c_int32, POINTER(c_double)]),
     "orx_mlp_forward": (c_int, [_p, c_int32, POINTER(_p), POINTER(_p), POINTER(c_int32), _p, c_int64, c_int32, c_int, _p]),
     "orx_interact_forward": (c_int, [_p, _p, c_int64, c_int32, c_int32, c_int, c_int, c_int, _p]),
+    # the fp16 MLP products alone (api_gemm16.hip): device pointers throughout
+    "orx_gemm16_plan": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, POINTER(c_int32), POINTER(c_int32)]),
+    "orx_gemm16_group_query": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int32, POINTER(c_int32)]),
+    "orx_gemm16_nt": (c_int, [_p, _p, c_int64, _p, c_int64, _fp, c_int64, _p, c_int64, _fp, c_int32, c_int32, c_int32, c_int,
+                              _fp, _p, c_int64, c_int, _fp, POINTER(c_int32), _p, _p]),
+    "orx_gemm16_tn": (c_int, [_p, _p, c_int64, _p, c_int64, _fp, c_int64, _fp, c_int32, c_int32, c_int32, c_float]),
+    "orx_gemm16_group": (c_int, [_p, _p, c_int64, _p, c_int64, _fp, c_int64, _fp, c_int32, c_int32, c_int32, c_float, _p, c_int64, _fp, c_int64,
+                                 _p, c_int64, _fp, _p, c_int64, c_int, _fp, POINTER(c_int32), _p, c_int32]),
+    "orx_head16_fwd": (c_int, [_p, _p, c_int64, _p, _fp, c_int, _fp, c_int32, c_int32]),
+    "orx_head16_bwd_blocks": (c_int32, [_p, c_int32]),
+    "orx_head16_bwd": (c_int, [_p, _p, c_int64, _p, _fp, _fp, c_int, c_int, _fp, _fp, _p, c_int64, _fp, c_int64, _fp, c_int32, c_int32, POINTER(c_int32)]),
+    "orx_cast16": (c_int, [_p, _fp, c_int64, _p, c_int64, c_int32, c_int32]),
 }
 
 _lib = None

@@ -577,11 +577,45 @@ __global__ __launch_bounds__(64 * WM * WN, MINB) void gemm16_nt_dma_kernel(Nt16A
     gemm16_nt_dma_body<WM, WN, TM, TN, NS, TAIL, DBG>(g, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// ---- what the launchers choose, as host functions of the shape and the CU count (the launchers and orx_gemm16_plan, the tests' query, call
+// the same ones).  The environment switches are read once per process.
+struct Gemm16Env { bool no_mask, no_group, tile_set; int tile, dma, wave_tile, tn_dma, tn_dma_group, tn_per_cu, tn_small_s; };
+static const Gemm16Env& gemm16_env() {
+    static const Gemm16Env e = [] {
+        auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+        Gemm16Env x;
+        x.no_mask = getenv("ORX_GEMM16_NO_MASK") != nullptr;
+        x.no_group = getenv("ORX_GEMM16_NO_GROUP") != nullptr;
+        x.tile_set = getenv("ORX_GEMM16_TILE") != nullptr;
+        x.tile = num("ORX_GEMM16_TILE", 0);
+        x.dma = num("ORX_GEMM16_DMA", 3);
+        x.wave_tile = num("ORX_GEMM16_WAVE_TILE", 64);
+        x.tn_dma = num("ORX_GEMM16_TN_DMA", 4);
+        x.tn_dma_group = num("ORX_GEMM16_TN_DMA", 3);          // (the grouped launch carries the four-wavefront DMA body: unset counts as 3)
+        x.tn_per_cu = num("ORX_GEMM16_TN_PER_CU", 1);
+        x.tn_small_s = num("ORX_GEMM16_TN_SMALL_S", 16);
+        return x;
+    }();
+    return e;
+}
+// the TAIL instantiation of the LDS-DMA nt forms: a leading dimension is not a multiple of 64 halves
+static bool nt_dma_tail(int64_t lda, int64_t ldb) { return (lda & 63) != 0 || (ldb & 63) != 0; }
+// the TAIL instantiation of the four-wavefront LDS-DMA tn form (alone with ORX_GEMM16_TN_DMA=2/3, and inside the grouped launch)
+static bool tn_dma_tail(int M, int N, int K, int kchunk, int64_t lda, int64_t ldb) {
+    return (K & 63) != 0 || kchunk % 64 != 0 || (int64_t)((M + 127) / 128) * 128 > lda || (int64_t)((N + 127) / 128) * 128 > ldb;
+}
+// ... and of the two-K-group form: also a slice whose K steps do not split evenly over the groups, or a last slice shorter than the others
+static bool tn_kg2_tail(int M, int N, int K, int kchunk, int64_t lda, int64_t ldb) {
+    const int nk_all = (std::min(K, kchunk) + 63) / 64;
+    return (K & 63) != 0 || kchunk % 64 != 0 || (nk_all & 1) != 0 || (K % kchunk) != 0 ||
+           (int64_t)((M + 127) / 128) * 128 > lda || (int64_t)((N + 127) / 128) * 128 > ldb;
+}
+
 template <int WM, int WN, int TM, int TN, int MINB, int NS>
 static int launch_nt_dma(orx_ctx* ctx, const Nt16Args& g) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
     constexpr size_t shm = (size_t)NS * (BM + BN) * 64 * 2;
-    const bool tail = (g.lda & 63) != 0 || (g.ldb & 63) != 0;
+    const bool tail = nt_dma_tail(g.lda, g.ldb);
     // How the outputs leave (ORX_GEMM16_NTS): 2 (default) = write-through stores, nothing left dirty in the XCD's L2 for the end of the
     // kernel: alone, 8192 x 1024 x 1024 goes from 24.3 to 21.0 us (scratch/exp_dma.hip), in the DLRM step the products gain 1 %;
     // 1 = nontemporal stores: 19.9 us alone, but the NEXT product then reads its operand from HBM and the step is 2 % slower;
@@ -620,20 +654,43 @@ bool orx_gemm16_nt_ok(int64_t lda, int64_t ldb, int N, int K) { return lda % 8 =
 // wavefronts, 2 = 128 x 128, 3 = 128 x 64, each in its LDS-DMA form; 0 = any other form (forced tiles, register staging, wave-tile experiment): no masks.
 // words_out: 64-bit words a mask of that product needs
 int orx_gemm16_nt_config(orx_ctx* ctx, int M, int N, int64_t* words_out) {
-    static const bool off = getenv("ORX_GEMM16_NO_MASK") != nullptr;
-    static const int force = getenv("ORX_GEMM16_TILE") ? atoi(getenv("ORX_GEMM16_TILE")) : 0;
-    static const int dma_env = getenv("ORX_GEMM16_DMA") ? atoi(getenv("ORX_GEMM16_DMA")) : 3;
-    static const int wave_tile = getenv("ORX_GEMM16_WAVE_TILE") ? atoi(getenv("ORX_GEMM16_WAVE_TILE")) : 64;
+    const Gemm16Env& e = gemm16_env();
     if (words_out) *words_out = 0;
-    if (off || force != 0 || dma_env != 3 || wave_tile != 64) return 0;
-    const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+    if (e.no_mask || e.tile != 0 || e.dma != 3 || e.wave_tile != 64) return 0;
+    const Nt16Plan p = orx_gemm16_nt_plan(ctx->num_cu, M, N, 0, 0);
+    if (words_out) *words_out = p.mask_words;
+    return p.cfg;
+}
+
+// the form of the [M, N] product: the largest tile that still gives every CU a workgroup
+// (the 4-wavefront configurations want two workgroups per CU: with one, every load and barrier latency of the short K
+// loops of the narrow layers is exposed -- a fused 8192 x 512 x 256 product took 18 us on 256 tiles of 128 x 128)
+// ORX_GEMM16_TILE=1/2/3 forces a configuration; ORX_GEMM16_DMA: 0 = the register-staged kernels, 2 / 3 = LDS-DMA staging with that many
+// stages (default 3; the 128 x 128 tile has two in every case)
+// ORX_GEMM16_WAVE_TILE=128: the 256 x 128 tile on FOUR wavefronts of 128 x 64 instead of eight of 64 x 64.  The main loop of these
+// products is bound by LDS bandwidth, not by the MFMA pipes (fragment reads 8.7 us + DMA writes 3.3 us of a 13.4 us loop at
+// 8192 x 1024 x 1024, against ~5 us of products): what a wavefront reads per K step is (rows of A + rows of B) of ITS tile, and
+// 4 x (128 + 64) rows are 25 % fewer than 8 x (64 + 64).
+Nt16Plan orx_gemm16_nt_plan(int num_cu, int M, int N, int64_t lda, int64_t ldb) {
+    const Gemm16Env& e = gemm16_env();
+    const int cus = num_cu > 0 ? num_cu : 256;
     auto blocks = [&](int bm, int bn) { return (int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    int cfg, bm, bn, nt;
-    if (blocks(256, 128) >= cus) { cfg = 1; bm = 256; bn = 128; nt = 512; }
-    else if (blocks(128, 128) >= 2 * cus) { cfg = 2; bm = 128; bn = 128; nt = 256; }
-    else { cfg = 3; bm = 128; bn = 64; nt = 256; }
-    if (words_out) *words_out = blocks(bm, bn) * nt;
-    return cfg;
+    const int dma = ((int64_t)M * lda < (1LL << 30) && (int64_t)N * ldb < (1LL << 30)) ? e.dma : 0;      // (32-bit byte offsets from A and B)
+    Nt16Plan p{};
+    if (e.tile == 1 || (e.tile == 0 && blocks(256, 128) >= cus)) {
+        p.cfg = 1; p.bm = 256; p.bn = 128; p.threads = 512;
+        p.stages = dma == 3 ? 3 : dma == 2 ? 2 : 0;
+        p.wave_tile = (dma == 3 && e.wave_tile == 128) ? 128 : 64;
+        if (p.wave_tile == 128) p.threads = 256;
+    } else if (e.tile == 2 || (e.tile == 0 && blocks(128, 128) >= 2 * cus)) {
+        p.cfg = 2; p.bm = 128; p.bn = 128; p.threads = 256; p.stages = dma ? 2 : 0; p.wave_tile = 64;
+    } else {
+        p.cfg = 3; p.bm = 128; p.bn = 64; p.threads = 256; p.stages = dma == 3 ? 3 : dma == 2 ? 2 : 0; p.wave_tile = 64;
+    }
+    p.tail = p.stages != 0 && nt_dma_tail(lda, ldb) ? 1 : 0;
+    p.blocks = blocks(p.bm, p.bn);
+    p.mask_words = p.blocks * (p.cfg == 1 ? 512 : 256);
+    return p;
 }
 
 int orx_launch_gemm16_nt(orx_ctx* ctx, const void* A16, int64_t lda, const void* B16, int64_t ldb, float* C, int64_t ldc,
@@ -648,31 +705,17 @@ int orx_launch_gemm16_nt(orx_ctx* ctx, const void* A16, int64_t lda, const void*
                actY, (const _Float16*)actY16, ldy, act_y, gb, mask_out, mask_in};
     ORX_ARG((mask_out == nullptr && mask_in == nullptr) || ((int64_t)M * lda < (1LL << 30) && (int64_t)N * ldb < (1LL << 30) && orx_gemm16_nt_config(ctx, M, N, nullptr) != 0),
             "gemm16_nt: relu masks need the LDS-DMA tile forms");
-    // the largest tile that still gives every CU a workgroup (256 CUs)
-    auto blocks = [&](int bm, int bn) { return (int64_t)((M + bm - 1) / bm) * ((N + bn - 1) / bn); };
-    static const int force = getenv("ORX_GEMM16_TILE") ? atoi(getenv("ORX_GEMM16_TILE")) : 0;
-    const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
-    // (the 4-wavefront configurations want two workgroups per CU: with one, every load and barrier latency of the short K
-    // loops of the narrow layers is exposed -- a fused 8192 x 512 x 256 product took 18 us on 256 tiles of 128 x 128)
-    // ORX_GEMM16_DMA: 0 = the register-staged kernels, 2 / 3 = LDS-DMA staging with that many stages (default 3 for the 256 x 128 tile)
-    static const int dma_env = getenv("ORX_GEMM16_DMA") ? atoi(getenv("ORX_GEMM16_DMA")) : 3;
-    const int dma = ((int64_t)M * lda < (1LL << 30) && (int64_t)N * ldb < (1LL << 30)) ? dma_env : 0;      // (32-bit byte offsets from A and B)
-    // ORX_GEMM16_WAVE_TILE=128: the 256 x 128 tile on FOUR wavefronts of 128 x 64 instead of eight of 64 x 64.  The main loop of these
-    // products is bound by LDS bandwidth, not by the MFMA pipes (fragment reads 8.7 us + DMA writes 3.3 us of a 13.4 us loop at
-    // 8192 x 1024 x 1024, against ~5 us of products): what a wavefront reads per K step is (rows of A + rows of B) of ITS tile, and
-    // 4 x (128 + 64) rows are 25 % fewer than 8 x (64 + 64).
-    static const int wave_tile = getenv("ORX_GEMM16_WAVE_TILE") ? atoi(getenv("ORX_GEMM16_WAVE_TILE")) : 64;
-    if (force == 1 || (force == 0 && blocks(256, 128) >= cus)) {
-        if (gbp) gbp->P = (M + 255) / 256;
-        if (dma == 3 && wave_tile == 128) return launch_nt_dma<2, 2, 8, 4, 1, 3>(ctx, g);
-        if (dma == 3) return launch_nt_dma<4, 2, 4, 4, 1, 3>(ctx, g);
-        if (dma == 2) return launch_nt_dma<4, 2, 4, 4, 1, 2>(ctx, g);
+    const Nt16Plan p = orx_gemm16_nt_plan(ctx->num_cu, M, N, lda, ldb);
+    if (gbp) gbp->P = (M + p.bm - 1) / p.bm;
+    if (p.cfg == 1) {
+        if (p.stages == 3 && p.wave_tile == 128) return launch_nt_dma<2, 2, 8, 4, 1, 3>(ctx, g);
+        if (p.stages == 3) return launch_nt_dma<4, 2, 4, 4, 1, 3>(ctx, g);
+        if (p.stages == 2) return launch_nt_dma<4, 2, 4, 4, 1, 2>(ctx, g);
         return launch_nt<4, 2, 4, 4, 1, 16>(ctx, g);
     }
-    if (gbp) gbp->P = (M + 127) / 128;
-    if (force == 2 || (force == 0 && blocks(128, 128) >= 2 * cus)) return dma ? launch_nt_dma<2, 2, 4, 4, 2, 2>(ctx, g) : launch_nt<2, 2, 4, 4, 2, 8>(ctx, g);
-    if (dma == 3) return launch_nt_dma<2, 2, 4, 2, 2, 3>(ctx, g);
-    if (dma == 2) return launch_nt_dma<2, 2, 4, 2, 2, 2>(ctx, g);
+    if (p.cfg == 2) return p.stages ? launch_nt_dma<2, 2, 4, 4, 2, 2>(ctx, g) : launch_nt<2, 2, 4, 4, 2, 8>(ctx, g);
+    if (p.stages == 3) return launch_nt_dma<2, 2, 4, 2, 2, 3>(ctx, g);
+    if (p.stages == 2) return launch_nt_dma<2, 2, 4, 2, 2, 2>(ctx, g);
     return launch_nt<2, 2, 4, 2, 2, 16>(ctx, g);
 }
 
@@ -1046,27 +1089,40 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const SlabReduce* jobs
 }
 
 // the split the launcher will use for a [M x N] gradient over K samples (slab floats needed = tiles * S * 128 * 128)
-void orx_gemm16_tn_plan(orx_ctx* ctx, int M, int N, int K, int* S_out, int* tiles_out, int* kchunk_out) {
+Tn16Plan orx_gemm16_tn_form(int num_cu, int M, int N, int K, int64_t lda, int64_t ldb) {
     const int tiles = ((M + 127) / 128) * ((N + 127) / 128);
-    const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+    const int cus = num_cu > 0 ? num_cu : 256;
+    const Gemm16Env& e = gemm16_env();
     // S depends on the SHAPE of the gradient only, never on the number of samples: the workspace and the reduce descriptors
     // are made once per model, and a later call with fewer samples (the last batch of an epoch) must write -- and the
     // reduce must add -- the same S slices; slices beyond the samples write zeros
     // ONE workgroup per CU (three LDS stages): half the slices of two per CU -- the slabs are written here and read again by the
     // optimizer launch, 146 -> 73 MB each way at the C5 shapes; the products take the same time (0.290 ms), the step 0.558 -> 0.543 ms.
     // ORX_GEMM16_TN_PER_CU=2 with ORX_GEMM16_TN_DMA=2: the two-per-CU form
-    static const int per_cu = getenv("ORX_GEMM16_TN_PER_CU") ? atoi(getenv("ORX_GEMM16_TN_PER_CU")) : 1;
+    const int per_cu = e.tn_per_cu;
     // (round 6) gradients of <= 16 tiles used to take 32 slices to fill the chip: a 512 x 256 gradient (0.5 MB) left 16.8 MB of slabs for the
     // optimizer launch to read back.  Their weight-gradient workgroups now share a launch with the layer's input gradient
     // (gemm16_group_kernel), which fills the chip: fewer slices are enough (ORX_GEMM16_TN_SMALL_S; 32: the round-5 plan).
     // Measured at the C5 shapes on one box (profiles/r6_tn_slices.txt): 8 slices 499 us per step (the optimizer launch 33 -> 20 us, but the
     // grouped launches +3-4 us each and the 13 x 512 gradient, which has no input gradient to share a launch with, 8 -> 19 us), 16: 487,
     // 32: 493.  So: 16 for gradients of 5 .. 16 tiles; smaller ones keep 32 (their slabs are small, and rows beyond M are not stored).
-    static const int small_s = getenv("ORX_GEMM16_TN_SMALL_S") ? atoi(getenv("ORX_GEMM16_TN_SMALL_S")) : 16;
+    const int small_s = e.tn_small_s;
     int S = std::max(1, std::min(32, (per_cu * cus) / tiles));
     if (tiles > 4 && tiles <= 16 && small_s >= 1) S = std::min(S, small_s);
     const int kchunk = std::max(64, (((K + S - 1) / S + 63) / 64) * 64);
-    *S_out = S; *tiles_out = tiles; *kchunk_out = kchunk;
+    // ORX_GEMM16_TN_DMA: 0 = the register-staged kernel, 2 = LDS-DMA staging with two stages and two workgroups per CU, 3 = three stages, one
+    // workgroup per CU; 4 (default, round 6) = eight wavefronts in two K groups, one workgroup per CU (gemm16_tn_dma_kg2_kernel); a slice whose K
+    // steps do not split evenly, or whose tiles reach beyond a leading dimension, takes the tail form
+    Tn16Plan p{};
+    p.S = S; p.tiles = tiles; p.kchunk = kchunk;
+    p.form = e.tn_dma == 4 ? 4 : (e.tn_dma == 2 || e.tn_dma == 3) ? e.tn_dma : 0;
+    p.tail = p.form == 4 ? tn_kg2_tail(M, N, K, kchunk, lda, ldb) : p.form != 0 ? tn_dma_tail(M, N, K, kchunk, lda, ldb) : 0;
+    return p;
+}
+
+void orx_gemm16_tn_plan(orx_ctx* ctx, int M, int N, int K, int* S_out, int* tiles_out, int* kchunk_out) {
+    const Tn16Plan p = orx_gemm16_tn_form(ctx->num_cu, M, N, K, 0, 0);
+    *S_out = p.S; *tiles_out = p.tiles; *kchunk_out = p.kchunk;
 }
 
 bool orx_gemm16_tn_ok(int64_t lda, int64_t ldb, int N) { return lda % 8 == 0 && ldb % 8 == 0 && N % 8 == 0; }
@@ -1076,19 +1132,13 @@ int orx_launch_gemm16_tn(orx_ctx* ctx, const void* A16, int64_t lda, const void*
     if (M == 0 || N == 0 || K == 0) return ORX_OK;
     ORX_ARG(lda % 8 == 0 && ldb % 8 == 0 && (((uintptr_t)A16 | (uintptr_t)B16) & 15) == 0, "gemm16_tn: operands need 16-byte rows");
     ProfScope ps(ctx, ORX_K_GEMM);
-    int S, tiles, kchunk;
-    orx_gemm16_tn_plan(ctx, M, N, K, &S, &tiles, &kchunk);
+    const Tn16Plan p = orx_gemm16_tn_form(ctx->num_cu, M, N, K, lda, ldb);
+    const int S = p.S, tiles = p.tiles, kchunk = p.kchunk;
+    const bool tail = p.tail != 0;
     ORX_ARG(S == 1 || slab != nullptr, "gemm16_tn: split-K needs a slab workspace");
     Tn16Args g{(const _Float16*)A16, lda, (const _Float16*)B16, ldb, C, ldc, slab, M, N, K, kchunk, out_scale};
-    // ORX_GEMM16_TN_DMA: 0 = the register-staged kernel, 2 = LDS-DMA staging with two stages and two workgroups per CU,
-    // 3 (default) = three stages, one workgroup per CU
-    static const int dma = getenv("ORX_GEMM16_TN_DMA") ? atoi(getenv("ORX_GEMM16_TN_DMA")) : 4;
+    const int dma = p.form;
     if (dma == 4) {
-        // 4 (default, round 6) = eight wavefronts in two K groups, one workgroup per CU (gemm16_tn_dma_kg2_kernel); a slice whose K steps do not
-        // split evenly, or whose tiles reach beyond a leading dimension, takes the tail form
-        const int nk_all = (std::min(K, kchunk) + 63) / 64;
-        const bool tail = (K & 63) != 0 || kchunk % 64 != 0 || (nk_all & 1) != 0 || (K % kchunk) != 0 ||
-                          (int64_t)((M + 127) / 128) * 128 > lda || (int64_t)((N + 127) / 128) * 128 > ldb;
         constexpr size_t shm = (size_t)2 * 2 * 64 * 256 * 2;
         static_assert(shm >= (size_t)128 * 132 * 4, "LDS of the accumulator exchange");
         auto kern = tail ? gemm16_tn_dma_kg2_kernel<true> : gemm16_tn_dma_kg2_kernel<false>;
@@ -1101,7 +1151,6 @@ int orx_launch_gemm16_tn(orx_ctx* ctx, const void* A16, int64_t lda, const void*
         return ORX_OK;
     }
     if (dma == 2 || dma == 3) {
-        const bool tail = (K & 63) != 0 || kchunk % 64 != 0 || (int64_t)((M + 127) / 128) * 128 > lda || (int64_t)((N + 127) / 128) * 128 > ldb;
         const size_t shm = (size_t)dma * 64 * 256 * 2;
         auto kern = dma == 2 ? (tail ? gemm16_tn_dma_kernel<2, 2, true> : gemm16_tn_dma_kernel<2, 2, false>)
                              : (tail ? gemm16_tn_dma_kernel<1, 3, true> : gemm16_tn_dma_kernel<1, 3, false>);
@@ -1126,18 +1175,30 @@ int orx_launch_gemm16_tn(orx_ctx* ctx, const void* A16, int64_t lda, const void*
 // Can the two backward products of a layer [B, out] -> [B, in] share a launch (gemm16_group_kernel)?  Only where the input gradient takes
 // the 128 x 64 tile with three DMA stages and the weight gradient the DMA kernel -- the forms the grouped kernel carries -- i.e. where
 // neither product fills the chip alone.  ORX_GEMM16_NO_GROUP=1: separate launches (A/B measurements, the bit-identity test).
-bool orx_gemm16_group_ok(orx_ctx* ctx, int B, int in, int out, int64_t ldx16, int64_t ldw16) {
-    static const bool off = getenv("ORX_GEMM16_NO_GROUP") != nullptr;
-    static const int dma_nt = getenv("ORX_GEMM16_DMA") ? atoi(getenv("ORX_GEMM16_DMA")) : 3;
-    static const int dma_tn = getenv("ORX_GEMM16_TN_DMA") ? atoi(getenv("ORX_GEMM16_TN_DMA")) : 3;
-    static const bool forced = getenv("ORX_GEMM16_TILE") != nullptr;
-    if (off || forced || dma_nt != 3 || (dma_tn != 2 && dma_tn != 3)) return false;
-    const int cus = ctx->num_cu > 0 ? ctx->num_cu : 256;
+static bool group_ok(int num_cu, int B, int in, int out, int64_t ldx16, int64_t ldw16) {
+    const Gemm16Env& e = gemm16_env();
+    if (e.no_group || e.tile_set || e.dma != 3 || (e.tn_dma_group != 2 && e.tn_dma_group != 3)) return false;
+    const int cus = num_cu > 0 ? num_cu : 256;
     auto blocks = [&](int bm, int bn) { return (int64_t)((B + bm - 1) / bm) * ((in + bn - 1) / bn); };
     if (blocks(256, 128) >= cus || blocks(128, 128) >= 2 * cus) return false;                   // (the larger tiles: the product fills the chip)
     // 32-bit byte offsets of the DMA requests: dZ16 [B][out], W16 [in][ldw16], X16 [B][ldx16]
     if ((int64_t)B * out >= (1LL << 29) || (int64_t)in * ldw16 >= (1LL << 29) || (int64_t)B * ldx16 >= (1LL << 29)) return false;
     return orx_gemm16_nt_ok(out, ldw16, in, out) && orx_gemm16_tn_ok(ldx16, out, out);
+}
+bool orx_gemm16_group_ok(orx_ctx* ctx, int B, int in, int out, int64_t ldx16, int64_t ldw16) { return group_ok(ctx->num_cu, B, in, out, ldx16, ldw16); }
+
+// the grouped launch of a layer [B, out] -> [B, in]: whether the DLRM step takes it, its grid and its two TAIL flags
+Group16Plan orx_gemm16_group_plan(int num_cu, int B, int in, int out, int64_t ldx, int64_t lddz, int64_t ldw, int nt_cols) {
+    const int in_nt = nt_cols > 0 ? nt_cols : in;          // columns of the input-gradient product (>= in: the operand's zero padding rows)
+    const Tn16Plan t = orx_gemm16_tn_form(num_cu, in, out, B, ldx, lddz);
+    Group16Plan p{};
+    p.grouped = group_ok(num_cu, B, in, out, ldx, ldw) ? 1 : 0;
+    p.S = t.S; p.tiles = t.tiles; p.kchunk = t.kchunk;
+    p.n_tn = t.tiles * t.S;
+    p.n_nt = ((B + 127) / 128) * ((in_nt + 63) / 64);
+    p.tn_tail = tn_dma_tail(in, out, B, t.kchunk, ldx, lddz) ? 1 : 0;
+    p.nt_tail = nt_dma_tail(lddz, ldw) ? 1 : 0;
+    return p;
 }
 
 // dW [in][out] (+)= X16^T dZ16 (slabs when the plan splits K) and dX = dZ16 W16^T with the fused activation backward of the layer below,
@@ -1150,18 +1211,17 @@ int orx_launch_gemm16_group(orx_ctx* ctx, const void* X16, int64_t ldx, const vo
     const int in_nt = nt_cols > 0 ? nt_cols : in;          // columns of the input-gradient product (>= in: the operand's zero padding rows)
     ORX_ARG(ldx % 8 == 0 && lddz % 8 == 0 && ldw % 8 == 0 && (((uintptr_t)X16 | (uintptr_t)dZ16 | (uintptr_t)W16) & 15) == 0, "gemm16_group: operands need 16-byte rows");
     ProfScope ps(ctx, ORX_K_GEMM);
-    int S, tiles, kchunk;
-    orx_gemm16_tn_plan(ctx, in, out, B, &S, &tiles, &kchunk);
+    const Group16Plan p = orx_gemm16_group_plan(ctx->num_cu, B, in, out, ldx, lddz, ldw, nt_cols);
+    const int S = p.S, kchunk = p.kchunk;
     ORX_ARG(S == 1 || slab != nullptr, "gemm16_group: split-K needs a slab workspace");
     Group16Args g;
     g.tn = Tn16Args{(const _Float16*)X16, ldx, (const _Float16*)dZ16, lddz, gW, ldgw, slab, in, out, B, kchunk, out_scale};
     g.nt = Nt16Args{(const _Float16*)dZ16, lddz, (const _Float16*)W16, ldw, C, ldc, (_Float16*)C16, ldc16, nullptr, B, in_nt, out, 0,
                     actY, (const _Float16*)actY16, ldy, act_y, gbp ? gbp->parts : nullptr, nullptr, mask_in};
     if (gbp) gbp->P = (B + 127) / 128;
-    g.n_tn = tiles * S;
-    g.n_nt = ((B + 127) / 128) * ((in_nt + 63) / 64);
-    const bool tn_tail = (B & 63) != 0 || kchunk % 64 != 0 || (int64_t)((in + 127) / 128) * 128 > ldx || (int64_t)((out + 127) / 128) * 128 > lddz;
-    const bool nt_tail = (lddz & 63) != 0 || (ldw & 63) != 0;
+    g.n_tn = p.n_tn;
+    g.n_nt = p.n_nt;
+    const bool tn_tail = p.tn_tail != 0, nt_tail = p.nt_tail != 0;
     static const int nts_env = getenv("ORX_GEMM16_NTS") != nullptr ? atoi(getenv("ORX_GEMM16_NTS")) : 2;
     const int nts = nts_env >= 0 && nts_env <= 2 ? nts_env : 0;
     using K = void (*)(Group16Args);

@@ -572,6 +572,16 @@ int orx_launch_gemm16_nt(orx_ctx* ctx, const void* A16, int64_t lda, const void*
                          // relu masks (kernels_gemm16.hip Nt16Args): written by a relu layer's forward launch, read by the input-gradient launch above it
                          unsigned long long* mask_out = nullptr, const unsigned long long* mask_in = nullptr);
 int orx_gemm16_nt_config(orx_ctx* ctx, int M, int N, int64_t* words_out);
+// What the launchers choose for a shape on `num_cu` CUs (host code; the launchers and the query orx_gemm16_plan call these):
+//   nt: cfg 1 = 256 x 128, 2 = 128 x 128, 3 = 128 x 64; stages 0 = register-staged, 2 / 3 = LDS-DMA; wave_tile 64 / 128; tail = the TAIL form
+struct Nt16Plan { int cfg, stages, wave_tile, tail, bm, bn, threads; int64_t blocks, mask_words; };
+Nt16Plan orx_gemm16_nt_plan(int num_cu, int M, int N, int64_t lda, int64_t ldb);
+//   tn: the split (S slices of kchunk samples over `tiles` tiles); form 0 = register-staged, 2 / 3 = LDS-DMA, 4 = two K groups; tail
+struct Tn16Plan { int S, tiles, kchunk, form, tail; };
+Tn16Plan orx_gemm16_tn_form(int num_cu, int M, int N, int K, int64_t lda, int64_t ldb);
+//   grouped launch of a layer [B, out] -> [B, in]: would the DLRM step group it, the grid's two parts, the two TAIL flags
+struct Group16Plan { int grouped, tn_tail, nt_tail, S, tiles, kchunk, n_tn, n_nt; };
+Group16Plan orx_gemm16_group_plan(int num_cu, int B, int in, int out, int64_t ldx, int64_t lddz, int64_t ldw, int nt_cols);
 #define ORX_SLAB_STRIDE (128 * 128 + 64)          // floats per (tile, slice) of a split-K workspace (kernels_gemm16.hip)
 struct SlabReduce { const float* slab; float* C; int64_t ldc; int M, N, S, ntn, tiles; };
 bool orx_gemm16_tn_ok(int64_t lda, int64_t ldb, int N);
