@@ -635,6 +635,26 @@ int orx_head16_bwd(orx_ctx* ctx, const void* X16, int64_t ldx, const void* w16, 
                    int32_t B, int32_t K, int32_t* P_out);
 int orx_cast16(orx_ctx* ctx, const float* src, int64_t lds, void* dst16, int64_t ld16, int32_t M, int32_t N);
 
+/* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
+ *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,
+ *                       PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads per range workgroup, threads of a big plan, references per
+ *                       partition workgroup, rows per range of the first plan (dedup_kernel), its user ranges} for tables of NU / NI rows
+ *                       and nU / nP / nN references per step
+ *   orx_plan_dump       the plan of K steps of B triplets (nid NULL: samples, `label` optional) for tables of NU / NI rows and dim D, made
+ *                       on the route the train steps take; ids and labels are HOST arrays [K][B].
+ *                       opts[8] = {plan version (1: dedup_kernel + urgent_kernel, 2: bucketed; must be the one the process runs, ORX_PLAN_V1),
+ *                                  staging, urgent marks, pairing tpw (0: off, else orx_fused_tpw(D)), min_late (-1: heuristic),
+ *                                  force 1024-thread workgroups, step0 (> 0: planned as [0, step0) then [step0, K)), 0}
+ *                       out[10] = host buffers (each may be NULL), per step, padding removed: rewritten ids int32 [K][3][B]; pairing words
+ *                                  int32 [K][B] (origin << 10 | ORX_PAIR bits); dlist uint32 [K][2B]; dcount [K]; alloc [K][8];
+ *                                  refinfo [K][3][B][2]; segstart [K][B]; dseg [K][2B]; dcnt [K][2B]; tree items [K][item_stride][4]
+ *                       info[8] = {item_stride, tree_off[3], index-error flag of the context (read only: it stays for orx_check_index_error),
+ *                                  1024-thread workgroups chosen for the NEXT plan, Bp, steps per chunk}
+ *                       out == NULL: sizes the buffers and fills info only.  Synchronizes the stream. */
+int orx_plan_geometry(int64_t NU, int64_t NI, int64_t nU, int64_t nP, int64_t nN, int32_t* out);
+int orx_plan_dump(orx_ctx* ctx, const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* label, int64_t K, int64_t B,
+                  int64_t NU, int64_t NI, int32_t D, const int32_t* opts, void* const* out, int64_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -143,6 +143,10 @@ SIGNATURES = {
     "orx_head16_bwd_blocks": (c_int32, [_p, c_int32]),
     "orx_head16_bwd": (c_int, [_p, _p, c_int64, _p, _fp, _fp, c_int, c_int, _fp, _fp, _p, c_int64, _fp, c_int64, _fp, c_int32, c_int32, POINTER(c_int32)]),
     "orx_cast16": (c_int, [_p, _fp, c_int64, _p, c_int64, c_int32, c_int32]),
+    # the duplicate plan of the exact steps alone (api_plan.hip): host arrays in and out
+    "orx_plan_geometry": (c_int, [c_int64, c_int64, c_int64, c_int64, c_int64, POINTER(c_int32)]),
+    "orx_plan_dump": (c_int, [_p, _ip, _ip, _ip, _fp, c_int64, c_int64, c_int64, c_int64, c_int32, POINTER(c_int32), POINTER(c_void_p),
+                              POINTER(c_int64)]),
 }
 
 _lib = None

@@ -735,9 +735,9 @@ int orx_exact_buffers(orx_ctx* c, orx_table* U, orx_table* V, int64_t K, int64_t
 }
 
 // DedupArgs of steps i0 .. of the chunk's plan arrays
-static void plan_dedup_args(orx_ctx* c, orx_table* U, orx_table* V, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t ds,
-                            int64_t nU, int64_t nP, int64_t nN, int64_t B, bool role_bits, bool inline_apply, bool staging,
-                            const PairPlan& plan, int64_t i0, DedupArgs* out) {
+void orx_plan_dedup_args(orx_ctx* c, orx_table* U, orx_table* V, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t ds,
+                         int64_t nU, int64_t nP, int64_t nN, int64_t B, bool role_bits, bool inline_apply, bool staging,
+                         const PairPlan& plan, int64_t i0, DedupArgs* out) {
     DedupArgs& d = *out;
     memset(&d, 0, sizeof(d));
     d.uid = uid; d.pid = pid; d.nid = nid; d.id_stride = ds;
@@ -804,7 +804,7 @@ int orx_exact_plan_issue(orx_ctx* c, orx_table* U, orx_table* V, const int32_t* 
         }
     }
     DedupArgs d;
-    plan_dedup_args(c, U, V, uid, pid, nid, ds, nU, nP, nN, B, true, inline_apply, staging, plan, i0, &d);
+    orx_plan_dedup_args(c, U, V, uid, pid, nid, ds, nU, nP, nN, B, true, inline_apply, staging, plan, i0, &d);
     // bucketed plan; ONE read-back of the per-step counters into pinned memory, and the urgent marks are made while
     // the host waits for it (the fused kernel ignores them in a launch without apply blocks)
     d.roles = nullptr; d.dupbits = nullptr;
@@ -926,7 +926,7 @@ int orx_exact_plan_chunk(orx_ctx* c, orx_table* U, orx_table* V, const int32_t* 
     }
     // duplicate detection for every step of the chunk, on the id arrays alone
     DedupArgs d;
-    plan_dedup_args(c, U, V, uid, pid, nid, ds, nU, nP, nN, B, role_bits, inline_apply, staging, plan, 0, &d);
+    orx_plan_dedup_args(c, U, V, uid, pid, nid, ds, nU, nP, nN, B, role_bits, inline_apply, staging, plan, 0, &d);
     ORX_HIP(hipMemsetAsync(c->d_dcount, 0, (size_t)kc * sizeof(int), c->stream));     // (the bucketed plan zeroes its counters itself)
     if (staging) {
         ORX_HIP(hipMemsetAsync(c->d_tricnt, 0, (size_t)kc * B * sizeof(int), c->stream));

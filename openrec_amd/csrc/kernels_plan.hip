@@ -672,6 +672,15 @@ static void plan_geometry(const DedupArgs& d, PlanArgs* a) {
     a->shift = std::max(5, ilog2(std::max(per_u, per_i)));          // bitmaps of 1 << shift bits
 }
 
+// the geometry and the constants of the plan for whoever has to know them without making one (api_plan.hip: orx_plan_geometry)
+void orx_plan_geometry_query(const DedupArgs& d, int32_t out[14]) {
+    PlanArgs a;
+    plan_geometry(d, &a);
+    out[0] = a.nru; out[1] = a.nri; out[2] = a.lgu; out[3] = a.lgi; out[4] = a.shift; out[5] = (1 << a.shift) >> 5;
+    out[6] = PL_UN; out[7] = PL_LCNT; out[8] = PL_PAIR_CAP; out[9] = ORX_SEG_DIRECT; out[10] = ORX_PIECE;
+    out[11] = PL_THREADS; out[12] = 1024; out[13] = PL_CHUNK;
+}
+
 // scratch of the bucketed plan of `chunk` steps with this geometry (grow-only)
 static int plan_ensure(orx_ctx* c, int64_t chunk, const PlanArgs& a, bool want_dupbits) {
     const int nb = a.nru + a.nri;

@@ -474,6 +474,13 @@ int orx_exact_plan_issue(orx_ctx* c, orx_table* U, orx_table* V, const int32_t* 
                          int64_t nU, int64_t nP, int64_t nN, int64_t kc, int64_t B, bool inline_apply, bool staging,
                          const PairPlan& plan, int64_t i0, hipEvent_t counters, const std::function<int()>* after_readback = nullptr);
 int orx_exact_plan_finish(orx_ctx* c, int64_t kc, int64_t B, bool inline_apply, bool staging, int64_t i0, hipEvent_t counters, ExactChunk* out, bool pairing_on = false);
+// the DedupArgs of steps i0 .. of the chunk's plan arrays, as every exact step fills them (api.hip)
+void orx_plan_dedup_args(orx_ctx* c, orx_table* U, orx_table* V, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t ds,
+                         int64_t nU, int64_t nP, int64_t nN, int64_t B, bool role_bits, bool inline_apply, bool staging,
+                         const PairPlan& plan, int64_t i0, DedupArgs* out);
+// geometry of the bucketed plan for d.{nU, nP, nN, NU, NI} and the constants of kernels_plan.hip (host only):
+// {nru, nri, lgu, lgi, shift, W, PL_UN, PL_LCNT, PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads, threads of a big plan, PL_CHUNK}
+void orx_plan_geometry_query(const DedupArgs& d, int32_t out[14]);
 void orx_exact_step_views(orx_ctx* c, const PairPlan& plan, int64_t i, int64_t B, int D, bool use_stage, PairArgs* a);
 int orx_launch_rows_planned(orx_ctx* ctx, int optkind, const RowsArgs& a);
 // K id lists of n local rows each (ids [K][n], < 0 = padding) against ONE table: plan once (duplicate roles, staging
