@@ -277,6 +277,36 @@ int orx_rank_metrics_csr(orx_ctx* ctx, int kind, orx_table* user, orx_table* ite
                          const int64_t* pos_ptr, const int32_t* pos_items, const int64_t* excl_ptr, const int32_t* excl_items,
                          const float* at, int32_t nat, float* auc, float* ndcg, float* recall);
 
+/* orx_rank_metrics_csr with pred == NULL, without the [n, item_rows] score matrix or any other buffer of that size: kinds,
+ * bias == NULL, w, at / nat, outputs and error codes as there, results equal to it bit for bit.
+ *   lists      each user's pos_items and excl_items rows must be STRICTLY ASCENDING (what SparseMask.from_lists / from_dense
+ *              produce); anything else is ORX_ERR_ARG naming the user.  An id outside [0, item rows) or a uid outside
+ *              [0, user rows) is ORX_ERR_INDEX.  All of this is checked on the host before any launch.
+ *   scratch    users are processed in batches so that the device scratch made for the call stays within scratch_bytes
+ *              (0: 512 MB).  dot / GMF with dim <= 128: per user the two lists with their scores and 3 x 64 words of
+ *              thresholds and counters.  L2, dim > 128 and ORX_SCORE_SIMPLE: the scorer itself into a bounded piece of score
+ *              rows plus the sweeps of orx_rank_metrics_csr.  When not even the smallest batch fits (one user; its score rows
+ *              are 65 when n > 64 on the dense route, the scorer's 128-user tile) the call exceeds the budget for that one
+ *              batch; orx_rank_metrics_matrixfree_scratch tells beforehand.
+ * Lazy tables are synced first.  A repeated call gives the same bits. */
+int orx_rank_metrics_matrixfree(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
+                                const int32_t* uid, int64_t n,
+                                const int64_t* pos_ptr, const int32_t* pos_items,
+                                const int64_t* excl_ptr, const int32_t* excl_items,
+                                const float* at, int32_t nat, size_t scratch_bytes,
+                                float* auc, float* ndcg, float* recall);
+
+/* Host only: the device scratch (*bytes) and the users per batch orx_rank_metrics_matrixfree would use for n users, `items`
+ * item rows of dimension dim, lists of at most max_pos / max_excl items per user and the given budget (0: the default).  The
+ * entry point sizes its buffers with this function. */
+int orx_rank_metrics_matrixfree_scratch(int64_t n, int64_t items, int32_t dim, int32_t kind, int64_t max_pos, int64_t max_excl,
+                                        size_t scratch_bytes, int64_t* bytes, int64_t* users_per_batch);
+
+/* Host only: the list checks orx_rank_metrics_matrixfree makes before any launch (offsets from 0 that never decrease, ids
+ * inside [0, items) else ORX_ERR_INDEX, every row strictly ascending else ORX_ERR_ARG naming the user); the longest lists out. */
+int orx_rank_metrics_matrixfree_check(int64_t n, int64_t items, const int64_t* pos_ptr, const int32_t* pos_items,
+                                      const int64_t* excl_ptr, const int32_t* excl_items, int64_t* max_pos, int64_t* max_excl);
+
 /* ---- top-K recommendation (beyond the reference API: what `Recommender.inference` is used for after training).
  * For each user q of uid[n] (host int32) the k items with the largest orx_score_all_items score s(q, j) -- the same kinds,
  * bias may be NULL, w for GMF -- without materialising the [n, item_rows] score matrix.

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ORX_LIB_PATH") or os.path.join(HERE, "_lib", "libopenrec_hip.so")      # (ORX_LIB_PATH: A/B runs of two builds on one box)
@@ -73,6 +73,9 @@ SIGNATURES = {
     "orx_score_all_items_device": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _fp]),
     "orx_rank_metrics": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _fp, _p, _p, c_int64, c_int64, _fp, c_int32, _fp, _fp, _fp]),
     "orx_rank_metrics_csr": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _fp, c_int32, c_int64, c_int64, _p, _p, _p, _p, _fp, c_int32, _fp, _fp, _fp]),
+    "orx_rank_metrics_matrixfree": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _p, _p, _p, _p, _fp, c_int32, c_size_t, _fp, _fp, _fp]),
+    "orx_rank_metrics_matrixfree_scratch": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int64, c_int64, c_size_t, _p, _p]),
+    "orx_rank_metrics_matrixfree_check": (c_int, [c_int64, c_int64, _p, _p, _p, _p, _p, _p]),
     "orx_recommend_topk": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _p, _ip, c_int32, c_int, _ip, _fp]),
     "orx_topk_rows": (c_int, [_p, _fp, c_int32, c_int64, c_int64, _p, _ip, c_int32, _ip, _fp]),
     "orx_sampler_create": (c_int, [_p, _ip, _ip, c_int64, _p, _ip, c_int64, c_int64, _pp]),

@@ -758,6 +758,24 @@ int orx_rank_csr_segments(int64_t n, int64_t NI);
 int orx_launch_mask_bits(orx_ctx* ctx, const EvalCsrArgs& a, int64_t n, int clear);
 int orx_launch_rank_sweeps(orx_ctx* ctx, const EvalCsrArgs& a, int64_t q0, int64_t nq, int64_t max_pos);
 
+// the same metrics without the score matrix (kernels_evalmf.hip): one batch of nq users
+struct EvalMfArgs {
+    const float* U; const float* V; const float* b; const float* w;
+    const int32_t* uid; int64_t nq; int64_t NU; int64_t NI;
+    int D; int Dp; int TI; int64_t chunk;
+    const int64_t* pos_ptr; const int32_t* pos_items;     // CSR over the batch's users, offsets from 0, rows strictly ascending
+    const int64_t* excl_ptr; const int32_t* excl_items;
+    float* pos_s; float* excl_s;                          // the listed items' scores, entry for entry
+    float* ts; int* tex; int NB;                          // [nq][NB] the chunk's sorted thresholds (ts[0] = -inf) and their "excluded" flags
+    unsigned* hist; unsigned* corr; unsigned* nzdrop;     // [nq][NB] | [nq][NB] (one piece) and [nq]: the chunk's counts over ALL items
+    const float* at; int nat;
+    float* auc; float* ndcg; float* recall; int* neval;
+    int* err;
+};
+bool orx_evalmf_has_tile(int D);
+int orx_launch_evalmf_gather(orx_ctx* ctx, const EvalMfArgs& a, int kind, int64_t max_list);
+int orx_launch_evalmf_chunk(orx_ctx* ctx, const EvalMfArgs& a, int kind, int c0, int last);
+
 // kernels_sampler.hip (on-device triplet sampler)
 struct SamplerArgs {
     const int32_t* rec_user; const int32_t* rec_item; int64_t R;      // interaction records

@@ -734,6 +734,51 @@ def rank_metrics_csr(pos, excl, at, pred=None, kind=None, user=None, item=None, 
     return dict(auc=auc, ndcg=ndcg, recall=rec)
 
 
+def rank_metrics_matrixfree_scratch(n, items, dim, kind, max_pos, max_excl, scratch_bytes=0, ctx=None):
+    """(bytes, users_per_batch): the device scratch `rank_metrics_matrixfree` would make for such a call, and the users it
+    would take per batch.  Host only."""
+    lib = ctx._lib if ctx is not None else _ffi.load()
+    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    b, u = ctypes.c_int64(), ctypes.c_int64()
+    check(lib.orx_rank_metrics_matrixfree_scratch(int(n), int(items), int(dim), k, int(max_pos), int(max_excl), int(scratch_bytes),
+                                                  byref(b), byref(u)))
+    return int(b.value), int(u.value)
+
+
+def rank_metrics_matrixfree_check(pos, excl):
+    """The list checks `rank_metrics_matrixfree` makes before any device work -> (longest positive list, longest exclusion
+    list).  ValueError for a row that is not strictly ascending, IndexError for an id outside the table.  Host only."""
+    assert isinstance(pos, SparseMask) and isinstance(excl, SparseMask) and pos.shape == excl.shape
+    mp, me = ctypes.c_int64(), ctypes.c_int64()
+    check(_ffi.load().orx_rank_metrics_matrixfree_check(pos.shape[0], pos.shape[1], pos.ptr.ctypes.data, pos.items.ctypes.data,
+                                                        excl.ptr.ctypes.data, excl.items.ctypes.data, byref(mp), byref(me)))
+    return int(mp.value), int(me.value)
+
+
+def rank_metrics_matrixfree(pos, excl, at, kind, user, item, bias, uid, w=None, scratch_bytes=0):
+    """`rank_metrics_csr(pos, excl, at, kind=..., ...)` without the [n, item_rows] score matrix or the two bitmaps: the same
+    numbers bit for bit, from device scratch that stays within `scratch_bytes` (0: 512 MB) however many users and items there
+    are.  `pos` / `excl`: SparseMask whose rows are strictly ascending (what from_lists / from_dense make)."""
+    assert isinstance(pos, SparseMask) and isinstance(excl, SparseMask) and pos.shape == excl.shape
+    n, items = pos.shape
+    if items != item.rows:
+        raise ValueError(f"masks over {items} items, the item table has {item.rows} rows")
+    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
+    ptr, nn, dev, keep = _ids_arg(uid)
+    if dev:
+        raise ValueError("rank_metrics_matrixfree takes host ids")
+    if nn != n:
+        raise ValueError(f"{nn} user ids for masks of {n} rows")
+    c = user.ctx
+    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
+    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    check(c._lib.orx_rank_metrics_matrixfree(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+                                             pos.ptr.ctypes.data, pos.items.ctypes.data, excl.ptr.ctypes.data, excl.items.ctypes.data,
+                                             atv.ctypes.data, atv.size, int(scratch_bytes), auc.ctypes.data, ndcg.ctypes.data,
+                                             rec.ctypes.data))
+    return dict(auc=auc, ndcg=ndcg, recall=rec)
+
+
 CKPT_PIECE_BYTES = 256 << 20          # tables and slots move through the host in pieces of at most this many bytes
 
 

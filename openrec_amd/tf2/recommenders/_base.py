@@ -171,14 +171,19 @@ class Recommender:
 
     _score_kind = "dot"
 
-    def evaluate(self, user_id, pos_mask, excl_mask, at=(100,)):
+    def evaluate(self, user_id, pos_mask, excl_mask, at=(100,), score_matrix=True):
         """Beyond the reference API: `eval_step` of tf2_examples/bpr_citeulike.py:41-46 as one device call
         (all-item scores + AUC / NDCG / Recall; the [B, n_items] score matrix never reaches the host).  The masks as
         `Dataset.evaluation` yields them (item lists, `rt.SparseMask`) go over as lists; dense masks are accepted too
-        (both as lists when they are sparse enough to be worth the host-side nonzero)."""
+        (both as lists when they are sparse enough to be worth the host-side nonzero).  `score_matrix=False`: the same numbers
+        bit for bit from `rt.rank_metrics_matrixfree`, whose device scratch does not grow with users x items (dense masks
+        go through `SparseMask.from_dense`)."""
         U, V, b = self._tables()
         w = self.mlp.layers[0].kernel if self._score_kind == "gmf" else None
         kw = dict(kind=self._score_kind, user=U, item=V, bias=b, w=w, uid=_ids(user_id))
+        if not score_matrix:
+            pos, excl = (m if isinstance(m, rt.SparseMask) else rt.SparseMask.from_dense(m) for m in (pos_mask, excl_mask))
+            return rt.rank_metrics_matrixfree(pos, excl, list(at), **kw)
         if isinstance(pos_mask, rt.SparseMask) and isinstance(excl_mask, rt.SparseMask):
             return rt.rank_metrics_csr(pos_mask, excl_mask, list(at), **kw)
         return rt.rank_metrics(pos_mask, excl_mask, list(at), **kw)
