@@ -79,7 +79,7 @@ enum orx_flags {
     ORX_POINT_SIGMOID = 16, /* orx_pointwise_step / _loss with ORX_WRMF: PointwiseMSELoss(sigmoid=True),
                              the prediction goes through a sigmoid before the weighted squared
                              error (modules/pointwise_mse_loss.py:24-25)        */
-    ORX_OUT_DEVICE = 32   /* orx_recommend_topk: the outputs are device pointers */
+    ORX_OUT_DEVICE = 32   /* orx_recommend_topk, orx_score_candidates: the outputs are device pointers */
 };
 
 /* kernels whose device time can be sampled with orx_prof_* */
@@ -306,6 +306,42 @@ int orx_rank_metrics_matrixfree_scratch(int64_t n, int64_t items, int32_t dim, i
  * inside [0, items) else ORX_ERR_INDEX, every row strictly ascending else ORX_ERR_ARG naming the user); the longest lists out. */
 int orx_rank_metrics_matrixfree_check(int64_t n, int64_t items, const int64_t* pos_ptr, const int32_t* pos_items,
                                       const int64_t* excl_ptr, const int32_t* excl_items, int64_t* max_pos, int64_t* max_excl);
+
+/* ---- candidate lists (beyond the reference API: the re-ranking stage after orx_recommend_topk or any external retrieval, and
+ * the evaluation against sampled or explicit negatives of openrec/tf2/data/dataset.py:70-74 without masks over all items).
+ * Kinds, bias == NULL and w as in orx_score_all_items; uid host int32[n]; cand_ptr host int64[n + 1] from 0, cand_items host
+ * int32: the items listed for each user.  The work and the device scratch grow with the listed entries, not with
+ * n x item rows.  An item id outside [0, item rows) or a uid outside [0, user rows) is ORX_ERR_INDEX, found on the host before
+ * any launch (the context stays usable).  Lazy tables are synced first.  A repeated call gives the same bits; the result does
+ * not depend on launch shapes or atomics.
+ *   dot / GMF with dim <= 128: the listed item rows are gathered through the matrix cores with the scorer's operand layout and
+ *   k order.  L2, dim > 128 and ORX_SCORE_SIMPLE: the scorer itself writes the score rows of a bounded batch of users and the
+ *   listed entries are picked out of them (no faster in compute; the masks over all items are still gone).
+ *
+ * orx_score_candidates: out[e] = the score of entry e, bit for bit the element [q, cand_items[e]] that orx_score_all_items
+ * writes for that user.  A list may be in any order and may repeat items.  out: float[cand_ptr[n]], host memory, device memory
+ * with flags = ORX_OUT_DEVICE. */
+int orx_score_candidates(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
+                         const int32_t* uid, int64_t n, const int64_t* cand_ptr, const int32_t* cand_items, int flags, float* out);
+
+/* The ranking metrics of each user over the universe cand[q]: bit for bit (NaN-aware) what orx_rank_metrics_csr returns for the
+ * same pos lists and the exclusion lists [0, item rows) \ cand[q] -- AUC over cand \ pos against every positive, a positive
+ * outside cand ranked as an excluded positive, 0 / 0 -> NaN.  Every row of both lists must be STRICTLY ASCENDING, anything else
+ * is ORX_ERR_ARG naming the user and the list.  at / nat (<= 16) and the outputs (any may be NULL) as in orx_rank_metrics_csr.
+ * Users are processed in batches so that the device scratch of a call (the lists, their scores, on the dense route the piece
+ * of score rows) stays within scratch_bytes (0: 512 MB); a single user whose own lists exceed it runs as a batch of one. */
+int orx_rank_metrics_candidates(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
+                                const int32_t* uid, int64_t n,
+                                const int64_t* pos_ptr, const int32_t* pos_items,
+                                const int64_t* cand_ptr, const int32_t* cand_items,
+                                const float* at, int32_t nat, size_t scratch_bytes,
+                                float* auc, float* ndcg, float* recall);
+
+/* Host only: the list checks orx_rank_metrics_candidates makes before any launch (offsets from 0 that never decrease, ids
+ * inside [0, items) else ORX_ERR_INDEX, every row strictly ascending else ORX_ERR_ARG naming the user and the list); the
+ * longest lists out. */
+int orx_rank_metrics_candidates_check(int64_t n, int64_t items, const int64_t* pos_ptr, const int32_t* pos_items,
+                                      const int64_t* cand_ptr, const int32_t* cand_items, int64_t* max_pos, int64_t* max_cand);
 
 /* ---- top-K recommendation (beyond the reference API: what `Recommender.inference` is used for after training).
  * For each user q of uid[n] (host int32) the k items with the largest orx_score_all_items score s(q, j) -- the same kinds,

@@ -776,6 +776,26 @@ bool orx_evalmf_has_tile(int D);
 int orx_launch_evalmf_gather(orx_ctx* ctx, const EvalMfArgs& a, int kind, int64_t max_list);
 int orx_launch_evalmf_chunk(orx_ctx* ctx, const EvalMfArgs& a, int kind, int c0, int last);
 
+// scores and metrics of candidate lists (kernels_cand.hip): one batch of nq users, flat lists with offsets from 0
+struct CandScoreArgs {
+    const float* U; const float* V; const float* b; const float* w;
+    const int32_t* uid; int64_t nq; int D;
+    const int64_t* ptr; const int32_t* items; int64_t E;  // E = ptr[nq] entries, ids checked on the host
+    float* out;                                           // [E] entry for entry
+};
+struct CandRankArgs {
+    const int64_t* pos_ptr; const int32_t* pos_items; const float* pos_s;       // rows strictly ascending
+    const int64_t* cand_ptr; const int32_t* cand_items; const float* cand_s;
+    int NB;                                               // 2^STEPS from the call's longest positive list, as rank_sweep_kernel picks it
+    const float* at; int nat;
+    float* auc; float* ndcg; float* recall;
+};
+bool orx_cand_has_tile(int D);
+int orx_launch_cand_score(orx_ctx* ctx, const CandScoreArgs& a, int kind);
+int orx_launch_cand_pick(orx_ctx* ctx, const float* rows, int64_t NI, const int64_t* ptr, const int32_t* items, int64_t nq,
+                         int64_t E, float* out);
+int orx_launch_cand_rank(orx_ctx* ctx, const CandRankArgs& a, int64_t nq);
+
 // kernels_sampler.hip (on-device triplet sampler)
 struct SamplerArgs {
     const int32_t* rec_user; const int32_t* rec_item; int64_t R;      // interaction records

@@ -779,6 +779,97 @@ def rank_metrics_matrixfree(pos, excl, at, kind, user, item, bias, uid, w=None, 
     return dict(auc=auc, ndcg=ndcg, recall=rec)
 
 
+class CandidateLists:
+    """One list of item ids per user, kept in the GIVEN order and with its repeats (a re-ranker's input is ordered by the
+    retrieval stage): `ptr` int64 [n + 1] from 0, `items` int32.  `SparseMask` is the sorted, distinct form."""
+
+    def __init__(self, ptr, items, n_items):
+        self.ptr = np.ascontiguousarray(ptr, np.int64); self.items = np.ascontiguousarray(items, np.int32)
+        self.shape = (self.ptr.size - 1, int(n_items))
+
+    @classmethod
+    def from_lists(cls, lists, n_items):
+        rows = [np.asarray(r, np.int64).reshape(-1) for r in lists]
+        ptr = np.zeros(len(rows) + 1, np.int64); np.cumsum([r.size for r in rows], out=ptr[1:])
+        items = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        if items.size and (items.min() < 0 or items.max() >= n_items):
+            raise IndexError(f"item id outside [0, {n_items})")
+        return cls(ptr, items.astype(np.int32), n_items)
+
+    def row(self, q):
+        return self.items[self.ptr[q]:self.ptr[q + 1]]
+
+
+def as_candidate_lists(cand, n_items):
+    """a SparseMask, a CandidateLists or a list of per-user id arrays (order kept) -> an object with ptr / items / shape"""
+    if isinstance(cand, (SparseMask, CandidateLists)):
+        return cand
+    return CandidateLists.from_lists(cand, n_items)
+
+
+def score_candidates(kind, user, item, bias, uid, cand, w=None, device=False):
+    """The scores of each user's own candidates -> flat float32 [len(cand.items)] aligned with `cand.items` (with
+    `device=True` a torch tensor in HBM).  `cand`: a SparseMask, a CandidateLists, or a list of per-user id arrays kept in the
+    given order (repeats allowed).  Every score equals `score_all_items(...)[q, item]` bit for bit; only the listed items are
+    scored, so neither work nor memory grows with users x items."""
+    lib = user.ctx._lib
+    ptr, n, dev, keep = _ids_arg(uid)
+    if dev:
+        raise ValueError("score_candidates takes host ids")
+    cand = as_candidate_lists(cand, item.rows)
+    if cand.shape != (n, item.rows):
+        raise ValueError(f"candidate lists of shape {cand.shape}, expected {(n, item.rows)}")
+    kd = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    total = int(cand.ptr[-1])
+    head = (user.ctx._h, kd, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+            cand.ptr.ctypes.data, cand.items.ctypes.data)
+    if device:
+        import torch
+        out_t = torch.empty((total,), dtype=torch.float32, device=torch.device("cuda", user.ctx.device))
+        user.ctx.after_torch(out_t)
+        check(lib.orx_score_candidates(*head, _ffi.ORX_OUT_DEVICE, out_t.data_ptr()))
+        return out_t
+    out = np.empty(total, np.float32)
+    check(lib.orx_score_candidates(*head, 0, out.ctypes.data))
+    return out
+
+
+def rank_metrics_candidates_check(pos, cand):
+    """The list checks `rank_metrics_candidates` makes before any device work -> (longest positive list, longest candidate
+    list).  ValueError naming user and list for a row that is not strictly ascending, IndexError for an id outside the table.
+    Host only."""
+    assert pos.shape == cand.shape
+    mp, mc = ctypes.c_int64(), ctypes.c_int64()
+    check(_ffi.load().orx_rank_metrics_candidates_check(pos.shape[0], pos.shape[1], pos.ptr.ctypes.data, pos.items.ctypes.data,
+                                                        cand.ptr.ctypes.data, cand.items.ctypes.data, byref(mp), byref(mc)))
+    return int(mp.value), int(mc.value)
+
+
+def rank_metrics_candidates(pos, cand, at, kind, user, item, bias, uid, w=None, scratch_bytes=0):
+    """AUC / NDCG / Recall of each user over the universe `cand[q]` (sampled or explicit negatives plus the positives):
+    bit for bit `rank_metrics_csr(pos, ~cand, at, kind=..., ...)`, but only the listed items are scored and nothing of size
+    users x items exists anywhere.  `pos` / `cand`: SparseMask whose rows are strictly ascending; device scratch stays within
+    `scratch_bytes` (0: 512 MB)."""
+    assert isinstance(pos, SparseMask) and isinstance(cand, (SparseMask, CandidateLists)) and pos.shape == cand.shape
+    n, items = pos.shape
+    if items != item.rows:
+        raise ValueError(f"masks over {items} items, the item table has {item.rows} rows")
+    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
+    ptr, nn, dev, keep = _ids_arg(uid)
+    if dev:
+        raise ValueError("rank_metrics_candidates takes host ids")
+    if nn != n:
+        raise ValueError(f"{nn} user ids for masks of {n} rows")
+    c = user.ctx
+    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
+    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    check(c._lib.orx_rank_metrics_candidates(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+                                             pos.ptr.ctypes.data, pos.items.ctypes.data, cand.ptr.ctypes.data, cand.items.ctypes.data,
+                                             atv.ctypes.data, atv.size, int(scratch_bytes), auc.ctypes.data, ndcg.ctypes.data,
+                                             rec.ctypes.data))
+    return dict(auc=auc, ndcg=ndcg, recall=rec)
+
+
 CKPT_PIECE_BYTES = 256 << 20          # tables and slots move through the host in pieces of at most this many bytes
 
 

@@ -247,17 +247,29 @@ class Dataset:
         return _BatchIterator(self._streams(lambda s: s.per_pos_stratified_pointwise(pos_ratio), num_parallel_calls),
                               ("user_id", "item_id", "label"), (np.int32, np.int32, np.float32), batch_size, take)
 
-    def evaluation(self, batch_size, excl_datasets=[]):
+    def evaluation(self, batch_size, excl_datasets=[], candidates=False):
         """dataset.py:60-82 / :161-176.  The masks of a batch are `SparseMask` objects (one sorted item list per user -- what
         the index holds; the metrics take them as lists and `np.asarray(mask)` gives the reference's dense bool rows).  With
-        explicit negatives the exclusion mask is "everything but the labelled items" and stays a dense array."""
+        explicit negatives the exclusion mask is "everything but the labelled items" and stays a dense array.
+        `candidates=True` (an index with explicit or sampled negatives only): the batches carry `cand_mask` instead of
+        `excl_mask`, the labelled items (positives and negatives) minus the positives of `excl_datasets` as a `SparseMask` --
+        exactly the complement of that dense exclusion mask, for `Recommender.evaluate(cand_mask=...)`."""
         from ...runtime import SparseMask
         ix = self.datastore
         dense_excl = ix.contain_negatives()
+        if candidates and not dense_excl:
+            raise ValueError("evaluation(candidates=True) needs explicit or sampled negatives (num_negatives / implicit_negative=False): "
+                             "with implicit negatives the candidates would be all items")
 
         def gen():
             for u in ix.warm_users():
                 pos = np.unique(np.asarray(ix.positive_items(u), np.int64))
+                if candidates:
+                    cand = np.union1d(pos, np.asarray(ix.negative_items(u), np.int64))
+                    for d in excl_datasets:
+                        cand = np.setdiff1d(cand, np.asarray(d.datastore.positive_items(u), np.int64))
+                    yield u, pos, cand
+                    continue
                 if dense_excl:
                     excl = np.ones(ix.total_items, bool)
                     excl[pos] = False
@@ -270,5 +282,7 @@ class Dataset:
 
         def lists(rows):
             return SparseMask.from_lists(rows, ix.total_items)
+        if candidates:
+            return _BatchIterator([gen()], ("user_id", "pos_mask", "cand_mask"), (np.int32, lists, lists), batch_size, None)
         return _BatchIterator([gen()], ("user_id", "pos_mask", "excl_mask"),
                               (np.int32, lists, bool if dense_excl else lists), batch_size, None)

@@ -171,16 +171,25 @@ class Recommender:
 
     _score_kind = "dot"
 
-    def evaluate(self, user_id, pos_mask, excl_mask, at=(100,), score_matrix=True):
+    def evaluate(self, user_id, pos_mask, excl_mask=None, at=(100,), score_matrix=True, cand_mask=None):
         """Beyond the reference API: `eval_step` of tf2_examples/bpr_citeulike.py:41-46 as one device call
         (all-item scores + AUC / NDCG / Recall; the [B, n_items] score matrix never reaches the host).  The masks as
         `Dataset.evaluation` yields them (item lists, `rt.SparseMask`) go over as lists; dense masks are accepted too
         (both as lists when they are sparse enough to be worth the host-side nonzero).  `score_matrix=False`: the same numbers
         bit for bit from `rt.rank_metrics_matrixfree`, whose device scratch does not grow with users x items (dense masks
-        go through `SparseMask.from_dense`)."""
+        go through `SparseMask.from_dense`).  `cand_mask` instead of `excl_mask` (what `Dataset.evaluation(candidates=True)`
+        yields): the universe of each user is its candidate list, the numbers are those of `excl_mask = ~cand_mask` bit for
+        bit, and only the listed items are scored (`rt.rank_metrics_candidates`)."""
+        if cand_mask is not None and excl_mask is not None:
+            raise ValueError("evaluate takes excl_mask or cand_mask, not both")
+        if cand_mask is None and excl_mask is None:
+            raise ValueError("evaluate needs excl_mask or cand_mask")
         U, V, b = self._tables()
         w = self.mlp.layers[0].kernel if self._score_kind == "gmf" else None
         kw = dict(kind=self._score_kind, user=U, item=V, bias=b, w=w, uid=_ids(user_id))
+        if cand_mask is not None:
+            pos, cand = (m if isinstance(m, rt.SparseMask) else rt.SparseMask.from_dense(m) for m in (pos_mask, cand_mask))
+            return rt.rank_metrics_candidates(pos, cand, list(at), **kw)
         if not score_matrix:
             pos, excl = (m if isinstance(m, rt.SparseMask) else rt.SparseMask.from_dense(m) for m in (pos_mask, excl_mask))
             return rt.rank_metrics_matrixfree(pos, excl, list(at), **kw)
@@ -196,6 +205,17 @@ class Recommender:
         U, V, b = self._tables()
         w = self.mlp.layers[0].kernel if self._score_kind == "gmf" else None
         return rt.recommend_topk(self._score_kind, U, V, b, _ids(user_id), k, excl=excl_mask, w=w)
+
+    def score(self, user_id, candidates):
+        """Beyond the reference API: the scores of each user's own candidate list (the re-ranking stage after `recommend` or
+        any other retrieval) -> a list of float32 arrays, one per user, aligned with its candidates.  `candidates`: one id
+        array per user, in any order and with repeats (or an `rt.SparseMask` / `rt.CandidateLists`).  Scores equal
+        `inference`'s at the same places bit for bit; only the listed items are scored."""
+        U, V, b = self._tables()
+        w = self.mlp.layers[0].kernel if self._score_kind == "gmf" else None
+        cand = rt.as_candidate_lists(candidates, V.rows)
+        flat = rt.score_candidates(self._score_kind, U, V, b, _ids(user_id), cand, w=w)
+        return [flat[cand.ptr[q]:cand.ptr[q + 1]] for q in range(cand.shape[0])]
 
     def _record(self, run_forward, run_train):
         for lf in self._factors():
