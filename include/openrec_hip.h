@@ -380,6 +380,23 @@ int orx_sampler_create(orx_ctx* ctx, const int32_t* rec_user, const int32_t* rec
 int orx_sampler_destroy(orx_sampler* s);
 int orx_sampler_pairwise(orx_sampler* s, uint64_t seed, int64_t first, int64_t n,
                          int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev);
+/* Dynamic negative sampling: (user, positive) of samples [first, first + n) exactly as orx_sampler_pairwise gives them, and as
+ * the negative the HARDEST of n_cand uniform candidates: the one the current model scores highest.  Candidate c of sample g is a
+ * uniform item that is not a positive of the user; it depends on (seed, g, c) only (never on n_cand, n, first or the launch
+ * shape), and candidate 0 is the negative of orx_sampler_pairwise, so n_cand = 1 is that call bit for bit.  Candidates of a
+ * sample are independent and may repeat.  Scores are fp32 of the kinds of orx_score_all_items: ORX_BPR U[u].V[c] + b[c],
+ * ORX_UCML -||U[u] - V[c]||^2 + b[c]; bias may be NULL (no "+ b").  nid is the candidate with the largest score; equal scores:
+ * the smallest c; a NaN score never wins against a number; all NaN: candidate 0.  No atomics: a repeated call gives the same bits.
+ * cand_dev / cand_score_dev (DEVICE, [n * n_cand] row-major, or NULL): every candidate and the score the selection saw.
+ * ORX_ERR_ARG before any launch: n_cand outside [1, 64], a model other than BPR / UCML, tables on another context than the
+ * sampler's, user rows != total_users, item rows != total_items, user dim != item dim, a bias that is not [total_items, 1].
+ * n = 0: ORX_OK, nothing is launched.  Lazily-applied Adam: the rows read are drawn on the device, so the WHOLE of user, item and
+ * bias is brought up to date first (as orx_score_all_items does), not only the exposed rows; the next Adam step makes the tables
+ * lazy again.  Runs on the context's stream, no host synchronisation. */
+int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* user, orx_table* item, orx_table* bias,
+                              uint64_t seed, int64_t first, int64_t n, int32_t n_cand,
+                              int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev,
+                              int32_t* cand_dev /* [n*n_cand] or NULL */, float* cand_score_dev /* [n*n_cand] or NULL */);
 /* The pointwise producers of GMF / WRMF (dataset.py:18-36 _stratified_pointwise_generator, :38-58
  * _per_pos_stratified_pointwise_generator): samples [first, first + n) as (user, item, label) DEVICE arrays.
  *   stratified         : with probability pos_ratio the next record of the shuffled epoch (label 1), otherwise a uniform

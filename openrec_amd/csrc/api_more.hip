@@ -991,17 +991,6 @@ extern "C" int orx_rank_metrics_csr(orx_ctx* c, int kind, orx_table* U, orx_tabl
 }
 
 // ------------------------------------------------------------- device sampler ---
-struct orx_sampler {
-    orx_ctx* ctx = nullptr;
-    int32_t *rec_user = nullptr, *rec_item = nullptr, *items = nullptr;
-    int64_t* ptr = nullptr;
-    int64_t R = 0, total_users = 0, total_items = 0;
-    int h = 1;
-    // stratified pointwise stream: positives consumed so far (device), next sample index and seed the counter belongs to
-    int64_t* d_counter = nullptr; int64_t strat_next = -1; uint64_t strat_seed = 0;
-    int* d_blockcnt = nullptr; int64_t* d_blockbase = nullptr; size_t block_cap = 0;
-};
-
 extern "C" int orx_sampler_create(orx_ctx* ctx, const int32_t* rec_user, const int32_t* rec_item, int64_t n_records,
                                   const int64_t* csr_ptr, const int32_t* csr_items, int64_t total_users, int64_t total_items,
                                   orx_sampler** out) {

@@ -1,0 +1,192 @@
+// Dynamic negative sampling on the device (orx_sampler_pairwise_hard): every triplet's negative is the hardest of M uniform
+// candidates under the current model.
+//
+// Stream.  Sample g = first + i takes (u, p) exactly as sample_pairwise_kernel does for (seed, g) (kernels_sampler.hip; mix64 and
+// feistel_perm are restated here unchanged).  Candidate c in [0, M) is a uniform item, re-drawn while it is a positive of u (the same
+// binary search in the CSR row, at most 256 attempts):
+//     seed_c  = c == 0 ? seed : mix64(seed + c * 0xD1B54A32D192ED03)
+//     cand(c) = mix64(seed_c ^ (g * 0x9E3779B97F4A7C15) ^ (attempt << 56) ^ 0xA5A5A5A5) % total_items
+// so candidate c depends on (seed, g, c) only -- never on M, n, first or the launch shape -- and candidate 0 is bit for bit the
+// negative orx_sampler_pairwise writes for (seed, g).  Candidates of one sample are independent draws and may repeat.
+//
+// Score, fp32, the kinds of orx_score_all_items: BPR U[u].V[c] + b[c], UCML -||U[u] - V[c]||^2 + b[c] (no "+ b" without a bias
+// table).  Summation order: a lane adds its four products as (x0 + x1) + (x2 + x3), the lanes of a row are added by a butterfly
+// (xor 1, 2, 4, ...), the bias comes last.  nid[i] is the candidate with the largest score; equal scores: the smallest c; a NaN never
+// wins against a number; all NaN: candidate 0.  The selection reads the kernel's own fp32 scores, there are no atomics: a repeated
+// call gives the same bits.
+//
+// Shape.  The work is a random gather of M item rows (and one user row) of 4 D bytes per sample.  A wavefront owns a chunk of S
+// consecutive samples, S * M <= 128 slots (sample, candidate), and walks it in four phases over wavefront-private LDS:
+//   A  lane j draws (u, p) of sample j
+//   B  lane f draws candidate f % M of sample f / M (rejection loop and binary search per lane), into LDS and, coalesced, cand_out
+//   C  LPR = D / 4 lanes (rounded up to a power of two) cover a row with one 16-byte load each, so 64 / LPR groups score as many
+//      slots at once (four at D = 64); a group takes a run of consecutive slots, two per round, and loads the rows of the next
+//      round before it reduces this one: four rows per group in flight.  A slot's user row stays in registers while the sample stays
+//      the same.  The reduction is DPP inside 16 lanes, shuffles beyond
+//   D  lane j takes the arg-max of sample j's M scores; the scores go out coalesced
+// D % 4 != 0 or D > 256: the plain path, the whole wavefront on one slot with scalar loads.
+#include "orx_device.h"
+
+__device__ __forceinline__ uint64_t hn_mix64(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+
+// keyed permutation of [0, n): 4-round Feistel on 2*h bits (2^(2h) >= n) + cycle walking
+__device__ __forceinline__ uint64_t hn_feistel_perm(uint64_t x, uint64_t n, int h, uint64_t key) {
+    const uint64_t mask = (1ull << h) - 1;
+    do {
+        uint64_t l = x >> h, r = x & mask;
+#pragma unroll
+        for (int round = 0; round < 4; ++round) {
+            const uint64_t f = hn_mix64(r ^ (key + 0x632BE59BD9B4E019ull * (round + 1))) & mask;
+            const uint64_t t = l ^ f;
+            l = r; r = t;
+        }
+        x = (l << h) | r;
+    } while (x >= n);
+    return x;
+}
+
+__device__ __forceinline__ int hn_draw(const SamplerArgs& a, uint64_t g, int c, int u) {
+    const uint64_t seed_c = c == 0 ? a.seed : hn_mix64(a.seed + (uint64_t)c * 0xD1B54A32D192ED03ull);
+    const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
+    int ng = 0;
+    for (int attempt = 0; attempt < 256; ++attempt) {
+        ng = (int)(hn_mix64(seed_c ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull) % (uint64_t)a.total_items);
+        int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
+        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
+        if (!(lo < hi0 && a.items[lo] == ng)) break;
+    }
+    return ng;
+}
+
+constexpr int HN_SLOTS = 128;       // slots (sample, candidate) of one wavefront's chunk; a chunk holds at most 64 samples
+
+__device__ __forceinline__ float hn_partial(int ucml, f4 u, f4 v) {
+    if (ucml) { const f4 d = u - v; return (d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w); }
+    return (u.x * v.x + u.y * v.y) + (u.z * v.z + u.w * v.w);
+}
+
+template <int LPR, bool VEC>
+__global__ __launch_bounds__(256) void hardneg_kernel(HardNegArgs h, int S) {
+    __shared__ int s_user[4][64];
+    __shared__ int s_cand[4][HN_SLOTS];
+    __shared__ float s_score[4][HN_SLOTS];
+    const SamplerArgs& a = h.s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int M = h.M, D = h.D, ucml = h.model == ORX_UCML;
+    int* su = s_user[wave]; int* sc = s_cand[wave]; float* ss = s_score[wave];
+    const int64_t nchunks = (a.n + S - 1) / S;
+    // (every wavefront of a workgroup takes the same number of trips: the barriers below are workgroup barriers)
+    for (int64_t chunk0 = (int64_t)blockIdx.x * 4; chunk0 < nchunks; chunk0 += (int64_t)gridDim.x * 4) {
+        const int64_t i0 = (chunk0 + wave) * S;
+        const int ns = i0 >= a.n ? 0 : (int)(a.n - i0 < S ? a.n - i0 : S);      // samples of this wavefront's chunk
+        const int nslots = ns * M;
+        // ---- A: (u, p) of sample i0 + lane
+        if (lane < ns) {
+            const uint64_t g = (uint64_t)(a.first + i0 + lane);
+            const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
+            const uint64_t rec = hn_feistel_perm(pos, (uint64_t)a.R, a.h, hn_mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+            const int u = a.rec_user[rec];
+            su[lane] = u; a.uid[i0 + lane] = u; a.pid[i0 + lane] = a.rec_item[rec];
+        }
+        __syncthreads();
+        // ---- B: the candidates
+        for (int f = lane; f < nslots; f += 64) {
+            const int smp = f / M, c = f - smp * M;
+            const int ng = hn_draw(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
+            sc[f] = ng;
+            if (h.cand) h.cand[i0 * M + f] = ng;
+        }
+        __syncthreads();
+        // ---- C: the scores
+        if (VEC) {
+            constexpr int G = 64 / LPR;
+            const int grp = lane / LPR, sub = lane % LPR, col = 4 * sub;
+            const bool act = col < D;
+            const int per = ((nslots + 2 * G - 1) / (2 * G)) * 2;       // slots of a group: an even run of consecutive ones
+            const int f0 = grp * per, f1 = f0 + per < nslots ? f0 + per : nslots;
+            f4 uc[2], vc[2], un[2], vn[2]; float bc[2], bn[2]; int smp_c[2], smp_n[2];
+            const f4 zero = {0.f, 0.f, 0.f, 0.f};
+            // the rows of slots f, f + 1; `prev` / `uprev`: the sample and user row this lane loaded last
+            auto load2 = [&](int f, int prev, f4 uprev, f4 (&uu)[2], f4 (&vv)[2], float (&bb)[2], int (&sm)[2]) {
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    uu[k] = uprev; vv[k] = zero; bb[k] = 0.f; sm[k] = prev;
+                    if (f + k < f1) {
+                        const int item = sc[f + k], smp = (f + k) / M;
+                        if (act) vv[k] = *reinterpret_cast<const f4*>(h.V + (size_t)item * D + col);
+                        if (h.b && sub == 0) bb[k] = h.b[item];
+                        if (smp != prev) uu[k] = act ? *reinterpret_cast<const f4*>(h.U + (size_t)su[smp] * D + col) : zero;
+                        sm[k] = smp; prev = smp; uprev = uu[k];
+                    }
+                }
+            };
+            load2(f0, -1, zero, uc, vc, bc, smp_c);
+            for (int f = f0; f < f1; f += 2) {
+                load2(f + 2, smp_c[1], uc[1], un, vn, bn, smp_n);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const float tot = group_allreduce<LPR>(hn_partial(ucml, uc[k], vc[k]));
+                    if (sub == 0 && f + k < f1) {
+                        const float sv = ucml ? -tot : tot;
+                        ss[f + k] = h.b ? sv + bc[k] : sv;
+                    }
+                }
+#pragma unroll
+                for (int k = 0; k < 2; ++k) { uc[k] = un[k]; vc[k] = vn[k]; bc[k] = bn[k]; smp_c[k] = smp_n[k]; }
+            }
+        } else {
+            for (int f = 0; f < nslots; ++f) {
+                const float* ur = h.U + (size_t)su[f / M] * D;
+                const int item = sc[f];
+                const float* vr = h.V + (size_t)item * D;
+                float acc = 0.f;
+                for (int d = lane; d < D; d += 64) {
+                    const float x = ur[d], y = vr[d];
+                    acc += ucml ? (x - y) * (x - y) : x * y;
+                }
+                const float tot = group_allreduce<64>(acc);
+                if (lane == 0) {
+                    const float sv = ucml ? -tot : tot;
+                    ss[f] = h.b ? sv + h.b[item] : sv;
+                }
+            }
+        }
+        __syncthreads();
+        // ---- D: the hardest candidate of sample i0 + lane
+        if (lane < ns) {
+            int best = 0; float sb = ss[lane * M];
+            for (int c = 1; c < M; ++c) {
+                const float x = ss[lane * M + c];
+                if (x > sb || (sb != sb && x == x)) { sb = x; best = c; }
+            }
+            a.nid[i0 + lane] = sc[lane * M + best];
+        }
+        if (h.cand_score)
+            for (int f = lane; f < nslots; f += 64) h.cand_score[i0 * M + f] = ss[f];
+        __syncthreads();
+    }
+}
+
+int orx_launch_hardneg(orx_ctx* ctx, const HardNegArgs& h) {
+    if (h.s.n == 0) return ORX_OK;
+    int S = HN_SLOTS / h.M; if (S < 1) S = 1; if (S > 64) S = 64;
+    const int64_t nchunks = (h.s.n + S - 1) / S;
+    int64_t g = (nchunks + 3) / 4; if (g > (int64_t)ctx->num_cu * 16) g = (int64_t)ctx->num_cu * 16;
+    const dim3 grid((unsigned)g), block(256);
+    const int D = h.D;
+    if (D % 4 != 0 || D > 256) ORX_LAUNCH(ctx, (hardneg_kernel<64, false>), grid, block, 0, h, S);
+    else if (D <= 4) ORX_LAUNCH(ctx, (hardneg_kernel<1, true>), grid, block, 0, h, S);
+    else if (D <= 8) ORX_LAUNCH(ctx, (hardneg_kernel<2, true>), grid, block, 0, h, S);
+    else if (D <= 16) ORX_LAUNCH(ctx, (hardneg_kernel<4, true>), grid, block, 0, h, S);
+    else if (D <= 32) ORX_LAUNCH(ctx, (hardneg_kernel<8, true>), grid, block, 0, h, S);
+    else if (D <= 64) ORX_LAUNCH(ctx, (hardneg_kernel<16, true>), grid, block, 0, h, S);
+    else if (D <= 128) ORX_LAUNCH(ctx, (hardneg_kernel<32, true>), grid, block, 0, h, S);
+    else ORX_LAUNCH(ctx, (hardneg_kernel<64, true>), grid, block, 0, h, S);
+    ORX_HIP(hipGetLastError());
+    return ORX_OK;
+}

@@ -808,3 +808,24 @@ int orx_launch_sample_pairwise(orx_ctx* ctx, const SamplerArgs& a);
 int orx_launch_sample_stratified(orx_ctx* ctx, const SamplerArgs& a, float pos_ratio, float* label, int* blockcnt, int64_t* blockbase,
                                  int64_t* counter);
 int orx_launch_sample_perpos(orx_ctx* ctx, const SamplerArgs& a, int nneg, float* label);
+
+// the sampler object (api_more.hip creates it)
+struct orx_sampler {
+    orx_ctx* ctx = nullptr;
+    int32_t *rec_user = nullptr, *rec_item = nullptr, *items = nullptr;
+    int64_t* ptr = nullptr;
+    int64_t R = 0, total_users = 0, total_items = 0;
+    int h = 1;
+    // stratified pointwise stream: positives consumed so far (device), next sample index and seed the counter belongs to
+    int64_t* d_counter = nullptr; int64_t strat_next = -1; uint64_t strat_seed = 0;
+    int* d_blockcnt = nullptr; int64_t* d_blockbase = nullptr; size_t block_cap = 0;
+};
+
+// kernels_hardneg.hip (orx_sampler_pairwise_hard): the pairwise draw of `s` plus M candidates per sample, scored against the tables
+struct HardNegArgs {
+    SamplerArgs s;
+    const float* U; const float* V; const float* b;       // b NULL: no item bias
+    int model; int D; int M;
+    int32_t* cand; float* cand_score;                     // [n * M] or NULL
+};
+int orx_launch_hardneg(orx_ctx* ctx, const HardNegArgs& a);

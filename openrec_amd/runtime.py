@@ -1019,6 +1019,31 @@ class DeviceSampler:
         assert du and dp and dn and nu >= n, "the sampler writes device buffers"
         check(self._lib.orx_sampler_pairwise(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), pu, pp, pn))
 
+    def pairwise_hard(self, seed, first, n, uid, pid, nid, model, U, V, b=None, candidates=8,
+                      cand_out=None, cand_score_out=None):
+        """Dynamic negative sampling: uid / pid as `pairwise(seed, first, n)` writes them, nid the hardest of `candidates`
+        uniform non-positive items of the user -- the one `model` ("bpr": U[u].V[c] + b[c], "ucml": -|U[u] - V[c]|^2 + b[c];
+        b=None: no bias) scores highest on the tables as they stand.  Candidate c depends on (seed, sample, c) only and
+        candidate 0 is `pairwise`'s negative, so candidates=1 is `pairwise` bit for bit.  Equal scores: the smallest c; NaN
+        never wins.  cand_out (int32) / cand_score_out (float32): optional DEVICE buffers [n * candidates] that receive every
+        candidate and its score.  All buffers are device buffers; the call runs on the context's stream without a host
+        synchronisation, so its output can feed `pairwise_step` directly.  1 <= candidates <= 64."""
+        pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
+        assert du and dp and dn and min(nu, np_, nn) >= n, "the sampler writes device buffers"
+        pc = ps = None
+        if cand_out is not None:
+            pc, nc, dc, _ = _ids_arg(cand_out)
+            assert dc and nc >= n * int(candidates), "cand_out: a device int32 buffer of n * candidates"
+        if cand_score_out is not None:
+            ps, nsc, ds, _ = _label_arg(cand_score_out)
+            assert ds and nsc >= n * int(candidates), "cand_score_out: a device float32 buffer of n * candidates"
+        mid = model if isinstance(model, int) else {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
+        for t in (U, V, b):
+            if t is not None:
+                t._sync_pending()
+        check(self._lib.orx_sampler_pairwise_hard(self._h, int(mid), U._h, V._h, _bias_h(b), int(seed) & (2 ** 64 - 1), int(first),
+                                                  int(n), int(candidates), pu, pp, pn, pc, ps))
+
     def _pointwise(self, fn, seed, first, n, pos_ratio, uid, iid, label):
         pu, nu, du, _ = _ids_arg(uid); pi, _, di, _ = _ids_arg(iid); pl, nl, dl, _ = _label_arg(label)
         assert du and di and dl and nu >= n and nl >= n, "the sampler writes device buffers"
