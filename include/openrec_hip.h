@@ -397,6 +397,33 @@ int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* user, orx_ta
                               uint64_t seed, int64_t first, int64_t n, int32_t n_cand,
                               int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev,
                               int32_t* cand_dev /* [n*n_cand] or NULL */, float* cand_score_dev /* [n*n_cand] or NULL */);
+/* ---- negatives from a weighted item proposal (popularity^alpha, in-stock items, ...).
+ * orx_alias_build: host only, no context or device: the Walker / Vose alias table of n weights, computed in double.  Column j
+ * holds a 32-bit threshold thr[j] and an alias alias[j]: with a uniform 32-bit t, column j yields j if t < thr[j] and alias[j]
+ * otherwise, so a uniform column and a uniform t draw item i with probability w[i] / sum(w) up to the 32-bit quantisation.
+ * A column that keeps all of its mass has alias[j] == j (its threshold is then irrelevant).  An item of weight 0 is never an
+ * outcome: its own column has thr == 0 and no column aliases to it, the columns rounding leaves over at the end of Vose's
+ * loop included.  ORX_ERR_ARG, nothing written: n < 1, n > INT32_MAX, a NaN, infinite or negative weight, all weights 0.
+ *
+ * orx_sampler_set_proposal: weights is a HOST array [total_items], or NULL for uniform negatives again.  The table of
+ * orx_alias_build is kept on the device, one 8-byte record (thr, alias) per item.  The call may synchronise the context's
+ * stream: draws enqueued before it see the old table, draws after it the new one.  Bad weights: ORX_ERR_ARG, and the proposal
+ * that was in force stays in force.  orx_sampler_proposal_read copies the device table back into host arrays [total_items];
+ * ORX_ERR_ARG when no proposal is set.
+ *
+ * With a proposal set, attempt a of candidate c of sample g of orx_sampler_pairwise (c = 0) / orx_sampler_pairwise_hard is
+ *     r    = mix64(seed_c ^ (g * 0x9E3779B97F4A7C15) ^ (a << 56) ^ 0xA5A5A5A5)      the word the uniform draw forms
+ *     j    = r % total_items
+ *     t    = (uint32)(mix64(r ^ 0x5851F42D4C957F2D) >> 32)
+ *     item = t < thr[j] ? j : alias[j]
+ * re-drawn while item is a positive of the user (at most 256 attempts, then the last draw is kept, as without a proposal).
+ * Everything else of the two streams is unchanged: (u, p), candidate 0 = the pairwise negative, dependence on (seed, g, c)
+ * only, no atomics.  Without a proposal both calls give the bits they always gave; with all weights equal to 1.0 every column
+ * keeps its mass and the stream is the uniform one bit for bit.  The pointwise producers below draw uniform negatives only:
+ * they return ORX_ERR_ARG before any launch while a proposal is set. */
+int orx_alias_build(const double* weights, int64_t n, uint32_t* thr_out, int32_t* alias_out);
+int orx_sampler_set_proposal(orx_sampler* s, const double* weights /* host [total_items], or NULL = uniform again */);
+int orx_sampler_proposal_read(orx_sampler* s, uint32_t* thr_out, int32_t* alias_out);
 /* The pointwise producers of GMF / WRMF (dataset.py:18-36 _stratified_pointwise_generator, :38-58
  * _per_pos_stratified_pointwise_generator): samples [first, first + n) as (user, item, label) DEVICE arrays.
  *   stratified         : with probability pos_ratio the next record of the shuffled epoch (label 1), otherwise a uniform

@@ -85,6 +85,9 @@ SIGNATURES = {
     "orx_sampler_destroy": (c_int, [_p]),
     "orx_sampler_pairwise": (c_int, [_p, c_uint64, c_int64, c_int64, _ip, _ip, _ip]),
     "orx_sampler_pairwise_hard": (c_int, [_p, c_int, _p, _p, _p, c_uint64, c_int64, c_int64, c_int32, _ip, _ip, _ip, _ip, _fp]),
+    "orx_alias_build": (c_int, [_p, c_int64, _p, _ip]),
+    "orx_sampler_set_proposal": (c_int, [_p, _p]),
+    "orx_sampler_proposal_read": (c_int, [_p, _p, _ip]),
     "orx_sampler_stratified": (c_int, [_p, c_uint64, c_int64, c_int64, c_float, _ip, _ip, _p]),
     "orx_sampler_per_pos_stratified": (c_int, [_p, c_uint64, c_int64, c_int64, c_double, _ip, _ip, _p]),
     "orx_dlrm_create": (c_int, [_p, c_int32, c_int32, _p, c_int32, _p, c_int32, _p, c_int32, c_int, c_float, c_uint64, _pp]),

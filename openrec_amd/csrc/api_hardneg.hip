@@ -33,6 +33,7 @@ extern "C" int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* u
     a.s.rec_user = s->rec_user; a.s.rec_item = s->rec_item; a.s.R = s->R; a.s.ptr = s->ptr; a.s.items = s->items;
     a.s.total_items = s->total_items; a.s.total_users = s->total_users; a.s.seed = seed; a.s.first = first; a.s.n = n; a.s.h = s->h;
     a.s.uid = uid_dev; a.s.pid = pid_dev; a.s.nid = nid_dev;
+    a.s.prop = s->prop_on ? s->d_prop : nullptr;
     a.U = user->w; a.V = item->w; a.b = bias ? bias->w : nullptr;
     a.model = model; a.D = user->dim; a.M = n_cand; a.cand = cand_dev; a.cand_score = cand_score_dev;
     return orx_launch_hardneg(s->ctx, a);

@@ -1018,7 +1018,7 @@ extern "C" int orx_sampler_destroy(orx_sampler* s) {
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
     hipFree(s->rec_user); hipFree(s->rec_item); hipFree(s->ptr); hipFree(s->items);
-    hipFree(s->d_counter); hipFree(s->d_blockcnt); hipFree(s->d_blockbase);
+    hipFree(s->d_counter); hipFree(s->d_blockcnt); hipFree(s->d_blockbase); hipFree(s->d_prop);
     delete s;
     return ORX_OK;
 }
@@ -1031,6 +1031,7 @@ extern "C" int orx_sampler_pairwise(orx_sampler* s, uint64_t seed, int64_t first
     a.rec_user = s->rec_user; a.rec_item = s->rec_item; a.R = s->R; a.ptr = s->ptr; a.items = s->items;
     a.total_items = s->total_items; a.total_users = s->total_users; a.seed = seed; a.first = first; a.n = n; a.h = s->h;
     a.uid = uid_dev; a.pid = pid_dev; a.nid = nid_dev;
+    a.prop = s->prop_on ? s->d_prop : nullptr;
     return orx_launch_sample_pairwise(s->ctx, a);
 }
 
@@ -1044,6 +1045,8 @@ extern "C" int orx_sampler_stratified(orx_sampler* s, uint64_t seed, int64_t fir
                                       int32_t* uid_dev, int32_t* iid_dev, float* label_dev) {
     ORX_ARG(s && uid_dev && iid_dev && label_dev && first >= 0 && n >= 0, "orx_sampler_stratified: bad argument");
     ORX_ARG(pos_ratio >= 0.f && pos_ratio <= 1.f, "orx_sampler_stratified: pos_ratio must lie in [0, 1]");
+    ORX_ARG(!s->prop_on, "orx_sampler_stratified: a proposal is set (orx_sampler_set_proposal) and the pointwise producers draw "
+            "uniform negatives only; set it to NULL first");
     ORX_ARG(first == 0 || (first == s->strat_next && seed == s->strat_seed),
             "orx_sampler_stratified: the stream is sequential (a positive's place in the epoch counts the positives before it): "
             "continue at sample %lld of the same seed, or restart at 0", (long long)s->strat_next);
@@ -1068,6 +1071,8 @@ extern "C" int orx_sampler_per_pos_stratified(orx_sampler* s, uint64_t seed, int
                                               int32_t* uid_dev, int32_t* iid_dev, float* label_dev) {
     ORX_ARG(s && uid_dev && iid_dev && label_dev && first >= 0 && n >= 0, "orx_sampler_per_pos_stratified: bad argument");
     ORX_ARG(pos_ratio > 0.0 && pos_ratio <= 1.0, "orx_sampler_per_pos_stratified: pos_ratio must lie in (0, 1]");
+    ORX_ARG(!s->prop_on, "orx_sampler_per_pos_stratified: a proposal is set (orx_sampler_set_proposal) and the pointwise producers "
+            "draw uniform negatives only; set it to NULL first");
     // dataset.py:40 computes int((1 - pos_ratio) / pos_ratio) in Python doubles; in fp32 the quotient lands on the other side of
     // an integer for common ratios (0.05: 19 instead of 18; 1/3: 1 instead of 2), i.e. another group size than the reference's
     const int nneg = (int)((1.0 - pos_ratio) / pos_ratio);

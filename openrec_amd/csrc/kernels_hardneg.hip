@@ -8,6 +8,9 @@
 //     cand(c) = mix64(seed_c ^ (g * 0x9E3779B97F4A7C15) ^ (attempt << 56) ^ 0xA5A5A5A5) % total_items
 // so candidate c depends on (seed, g, c) only -- never on M, n, first or the launch shape -- and candidate 0 is bit for bit the
 // negative orx_sampler_pairwise writes for (seed, g).  Candidates of one sample are independent draws and may repeat.
+// With a proposal (SamplerArgs::prop, the PROP = true instantiations) the word r under the modulus picks the column j = r %
+// total_items of the alias table and t = (uint32)(mix64(r ^ 0x5851F42D4C957F2D) >> 32) takes j if t < thr[j], else alias[j]: one
+// more dependent 8-byte load per attempt of phase B, in front of the CSR search; phases A, C and D do not know about it.
 //
 // Score, fp32, the kinds of orx_score_all_items: BPR U[u].V[c] + b[c], UCML -||U[u] - V[c]||^2 + b[c] (no "+ b" without a bias
 // table).  Summation order: a lane adds its four products as (x0 + x1) + (x2 + x3), the lanes of a row are added by a butterfly
@@ -50,12 +53,18 @@ __device__ __forceinline__ uint64_t hn_feistel_perm(uint64_t x, uint64_t n, int 
     return x;
 }
 
+template <bool PROP>
 __device__ __forceinline__ int hn_draw(const SamplerArgs& a, uint64_t g, int c, int u) {
     const uint64_t seed_c = c == 0 ? a.seed : hn_mix64(a.seed + (uint64_t)c * 0xD1B54A32D192ED03ull);
     const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
     int ng = 0;
     for (int attempt = 0; attempt < 256; ++attempt) {
-        ng = (int)(hn_mix64(seed_c ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull) % (uint64_t)a.total_items);
+        const uint64_t r = hn_mix64(seed_c ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull);
+        ng = (int)(r % (uint64_t)a.total_items);
+        if (PROP) {
+            const uint2 rec = a.prop[ng];
+            if (!((uint32_t)(hn_mix64(r ^ 0x5851F42D4C957F2Dull) >> 32) < rec.x)) ng = (int)rec.y;
+        }
         int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
         while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
         if (!(lo < hi0 && a.items[lo] == ng)) break;
@@ -70,7 +79,7 @@ __device__ __forceinline__ float hn_partial(int ucml, f4 u, f4 v) {
     return (u.x * v.x + u.y * v.y) + (u.z * v.z + u.w * v.w);
 }
 
-template <int LPR, bool VEC>
+template <int LPR, bool VEC, bool PROP>
 __global__ __launch_bounds__(256) void hardneg_kernel(HardNegArgs h, int S) {
     __shared__ int s_user[4][64];
     __shared__ int s_cand[4][HN_SLOTS];
@@ -97,7 +106,7 @@ __global__ __launch_bounds__(256) void hardneg_kernel(HardNegArgs h, int S) {
         // ---- B: the candidates
         for (int f = lane; f < nslots; f += 64) {
             const int smp = f / M, c = f - smp * M;
-            const int ng = hn_draw(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
+            const int ng = hn_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
             sc[f] = ng;
             if (h.cand) h.cand[i0 * M + f] = ng;
         }
@@ -179,14 +188,20 @@ int orx_launch_hardneg(orx_ctx* ctx, const HardNegArgs& h) {
     int64_t g = (nchunks + 3) / 4; if (g > (int64_t)ctx->num_cu * 16) g = (int64_t)ctx->num_cu * 16;
     const dim3 grid((unsigned)g), block(256);
     const int D = h.D;
-    if (D % 4 != 0 || D > 256) ORX_LAUNCH(ctx, (hardneg_kernel<64, false>), grid, block, 0, h, S);
-    else if (D <= 4) ORX_LAUNCH(ctx, (hardneg_kernel<1, true>), grid, block, 0, h, S);
-    else if (D <= 8) ORX_LAUNCH(ctx, (hardneg_kernel<2, true>), grid, block, 0, h, S);
-    else if (D <= 16) ORX_LAUNCH(ctx, (hardneg_kernel<4, true>), grid, block, 0, h, S);
-    else if (D <= 32) ORX_LAUNCH(ctx, (hardneg_kernel<8, true>), grid, block, 0, h, S);
-    else if (D <= 64) ORX_LAUNCH(ctx, (hardneg_kernel<16, true>), grid, block, 0, h, S);
-    else if (D <= 128) ORX_LAUNCH(ctx, (hardneg_kernel<32, true>), grid, block, 0, h, S);
-    else ORX_LAUNCH(ctx, (hardneg_kernel<64, true>), grid, block, 0, h, S);
+#define HN_LAUNCH(LPR, VEC)                                                                       \
+    do {                                                                                          \
+        if (h.s.prop) ORX_LAUNCH(ctx, (hardneg_kernel<LPR, VEC, true>), grid, block, 0, h, S);    \
+        else ORX_LAUNCH(ctx, (hardneg_kernel<LPR, VEC, false>), grid, block, 0, h, S);            \
+    } while (0)
+    if (D % 4 != 0 || D > 256) HN_LAUNCH(64, false);
+    else if (D <= 4) HN_LAUNCH(1, true);
+    else if (D <= 8) HN_LAUNCH(2, true);
+    else if (D <= 16) HN_LAUNCH(4, true);
+    else if (D <= 32) HN_LAUNCH(8, true);
+    else if (D <= 64) HN_LAUNCH(16, true);
+    else if (D <= 128) HN_LAUNCH(32, true);
+    else HN_LAUNCH(64, true);
+#undef HN_LAUNCH
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }

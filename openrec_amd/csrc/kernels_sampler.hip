@@ -8,6 +8,10 @@
 //               like the reference's shuffle-and-pop
 //   negatives : uniform items re-drawn while they are positives of the user (membership by binary
 //               search in the user's sorted CSR row), like the reference's rejection loop
+//   proposal  : with an alias table (orx_sampler_set_proposal; SamplerArgs::prop) the uniform draw r picks the COLUMN
+//               j = r % total_items and a second word t = (uint32)(mix64(r ^ 0x5851F42D4C957F2D) >> 32) decides between the
+//               column's own item (t < thr[j]) and its alias: one 8-byte load per attempt in front of the CSR search.  The
+//               uniform kernel is the PROP = false instantiation and does not see the table
 #include "orx_device.h"
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
@@ -34,6 +38,7 @@ __device__ __forceinline__ uint64_t feistel_perm(uint64_t x, uint64_t n, int h, 
 }
 
 
+template <bool PROP>
 __global__ __launch_bounds__(256) void sample_pairwise_kernel(SamplerArgs a) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
@@ -44,7 +49,12 @@ __global__ __launch_bounds__(256) void sample_pairwise_kernel(SamplerArgs a) {
         const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
         int ng = 0;
         for (int attempt = 0; attempt < 256; ++attempt) {
-            ng = (int)(mix64(a.seed ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull) % (uint64_t)a.total_items);
+            const uint64_t r = mix64(a.seed ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull);
+            ng = (int)(r % (uint64_t)a.total_items);
+            if (PROP) {
+                const uint2 rec = a.prop[ng];
+                if (!((uint32_t)(mix64(r ^ 0x5851F42D4C957F2Dull) >> 32) < rec.x)) ng = (int)rec.y;
+            }
             int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
             while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
             if (!(lo < hi0 && a.items[lo] == ng)) break;
@@ -56,7 +66,8 @@ __global__ __launch_bounds__(256) void sample_pairwise_kernel(SamplerArgs a) {
 int orx_launch_sample_pairwise(orx_ctx* ctx, const SamplerArgs& a) {
     if (a.n == 0) return ORX_OK;
     int64_t g = (a.n + 255) / 256; if (g > 8192) g = 8192;
-    ORX_LAUNCH(ctx, sample_pairwise_kernel, dim3((unsigned)g), dim3(256), 0, a);
+    if (a.prop) ORX_LAUNCH(ctx, sample_pairwise_kernel<true>, dim3((unsigned)g), dim3(256), 0, a);
+    else ORX_LAUNCH(ctx, sample_pairwise_kernel<false>, dim3((unsigned)g), dim3(256), 0, a);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }

@@ -803,6 +803,7 @@ struct SamplerArgs {
     int64_t total_items; int64_t total_users;
     uint64_t seed; int64_t first; int64_t n; int h;
     int32_t* uid; int32_t* pid; int32_t* nid;
+    const uint2* prop = nullptr;                                       // alias table of the negatives' proposal, (thr, alias) per item; NULL: uniform
 };
 int orx_launch_sample_pairwise(orx_ctx* ctx, const SamplerArgs& a);
 int orx_launch_sample_stratified(orx_ctx* ctx, const SamplerArgs& a, float pos_ratio, float* label, int* blockcnt, int64_t* blockbase,
@@ -819,6 +820,8 @@ struct orx_sampler {
     // stratified pointwise stream: positives consumed so far (device), next sample index and seed the counter belongs to
     int64_t* d_counter = nullptr; int64_t strat_next = -1; uint64_t strat_seed = 0;
     int* d_blockcnt = nullptr; int64_t* d_blockbase = nullptr; size_t block_cap = 0;
+    // proposal of the negatives (api_proposal.hip): [total_items] records (thr, alias), allocated by the first orx_sampler_set_proposal
+    uint2* d_prop = nullptr; bool prop_on = false;
 };
 
 // kernels_hardneg.hip (orx_sampler_pairwise_hard): the pairwise draw of `s` plus M candidates per sample, scored against the tables

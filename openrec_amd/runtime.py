@@ -991,6 +991,17 @@ def load_checkpoint(path, tables, opt=None, shard=None):
         opt.step = int(man["opt"]["step"])
 
 
+def alias_build(weights):
+    """The Walker / Vose alias table of `weights` (floats >= 0, not all 0) -> (thr uint32[n], alias int32[n]): with a uniform
+    32-bit t, column j yields j if t < thr[j] and alias[j] otherwise; a uniform column then draws item i in proportion to
+    weights[i].  An item of weight 0 is never an outcome.  ValueError for an empty array, a NaN, infinite or negative weight or
+    weights that are all 0.  Host only: no context, no device."""
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    thr, alias = np.empty(w.size, np.uint32), np.empty(w.size, np.int32)
+    check(_ffi.load().orx_alias_build(w.ctypes.data, w.size, thr.ctypes.data, alias.ctypes.data))
+    return thr, alias
+
+
 class DeviceSampler:
     """On-device pairwise sampler over an interaction set (see kernels_sampler.hip).  `raw_data`: the
     structured array the reference's Dataset takes ('user_id', 'item_id')."""
@@ -1011,10 +1022,49 @@ class DeviceSampler:
                                      int(total_users), int(total_items), byref(h)))
         self._h, self.n_records = h, int(u.size)
         self._fin = weakref.finalize(self, lib.orx_sampler_destroy, h)
+        self.total_items = int(total_items)
+        self._item_users = np.bincount(ci, minlength=int(total_items)).astype(np.float64)     # distinct users per item
+        self._has_proposal = False
+
+    def set_proposal(self, weights=None, *, popularity=None):
+        """Draw the negatives of `pairwise` and the candidates of `pairwise_hard` from a weighted proposal over the items
+        instead of uniformly: an item comes up in proportion to its weight (then, as always, re-drawn while it is a positive of
+        the user), an item of weight 0 never.  `weights`: a float array of total_items, >= 0 and not all 0.  `popularity=alpha`
+        builds the weights from the sampler's own interactions: (the number of distinct users of the item) ** alpha, 0.75 being
+        the word2vec value.  An item nobody interacted with has weight 0 if alpha > 0 and weight 1 (= 0 ** 0, like every other
+        item) if alpha == 0, so popularity=0 is the uniform proposal over the whole catalogue.  Neither argument (or
+        weights=None): uniform negatives again, bit for bit the stream of a sampler that never had a proposal.  Giving both is
+        a ValueError, and so are bad weights -- the proposal in force then stays in force.  The call may synchronise the
+        context's stream: draws enqueued before it use the old proposal.  The pointwise producers raise while one is set."""
+        if weights is not None and popularity is not None:
+            raise ValueError("set_proposal: give weights or popularity=alpha, not both")
+        if popularity is not None:
+            alpha = float(popularity)
+            if not np.isfinite(alpha) or alpha < 0:
+                raise ValueError("set_proposal: popularity=alpha needs a finite alpha >= 0, got %r" % (popularity,))
+            weights = np.ones(self.total_items) if alpha == 0 else self._item_users ** alpha
+        if weights is None:
+            check(self._lib.orx_sampler_set_proposal(self._h, None))
+            self._has_proposal = False
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != self.total_items:
+            raise ValueError("set_proposal: %d weights for %d items" % (w.size, self.total_items))
+        check(self._lib.orx_sampler_set_proposal(self._h, w.ctypes.data))
+        self._has_proposal = True
+
+    def proposal(self):
+        """(thr uint32[total_items], alias int32[total_items]) read back from the device -- `alias_build` of the weights in
+        force -- or None when no proposal is set"""
+        if not self._has_proposal:
+            return None
+        thr, alias = np.empty(self.total_items, np.uint32), np.empty(self.total_items, np.int32)
+        check(self._lib.orx_sampler_proposal_read(self._h, thr.ctypes.data, alias.ctypes.data))
+        return thr, alias
 
     def pairwise(self, seed, first, n, uid, pid, nid):
         """Fill the DEVICE int32 buffers uid / pid / nid (torch tensors or DevicePtr) with samples
-        [first, first + n) of stream `seed`."""
+        [first, first + n) of stream `seed`.  Negatives: uniform over the user's non-positives, or from `set_proposal`'s."""
         pu, nu, du, _ = _ids_arg(uid); pp, _, dp, _ = _ids_arg(pid); pn, _, dn, _ = _ids_arg(nid)
         assert du and dp and dn and nu >= n, "the sampler writes device buffers"
         check(self._lib.orx_sampler_pairwise(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), pu, pp, pn))
@@ -1027,7 +1077,8 @@ class DeviceSampler:
         candidate 0 is `pairwise`'s negative, so candidates=1 is `pairwise` bit for bit.  Equal scores: the smallest c; NaN
         never wins.  cand_out (int32) / cand_score_out (float32): optional DEVICE buffers [n * candidates] that receive every
         candidate and its score.  All buffers are device buffers; the call runs on the context's stream without a host
-        synchronisation, so its output can feed `pairwise_step` directly.  1 <= candidates <= 64."""
+        synchronisation, so its output can feed `pairwise_step` directly.  1 <= candidates <= 64.  With `set_proposal` the
+        candidates come from the proposal instead of uniformly; everything else stays as described."""
         pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
         assert du and dp and dn and min(nu, np_, nn) >= n, "the sampler writes device buffers"
         pc = ps = None

@@ -1,0 +1,290 @@
+"""Negatives from a weighted item proposal on the device (DeviceSampler.set_proposal, kernels_sampler.hip, kernels_hardneg.hip):
+the table on the device is alias_build's, `pairwise` and the candidates of `pairwise_hard` equal tests/proposal_ref.py bit for
+bit with the table read back, the selection is exact on the kernel's own scores, the uniform stream keeps its bits, and the
+plumbing (replacing, resetting, errors, the pointwise producers' refusal, feeding the fused step)."""
+import numpy as np
+import pytest
+
+import hardneg_ref as hr
+import proposal_ref as pr
+
+pytestmark = pytest.mark.gpu
+
+NU, NI, NR = 500, 300, 7001
+N, FIRST, SEED = 2001, 6000, 7        # the window crosses the epoch boundary at 7001 and is no multiple of a block size
+
+
+@pytest.fixture(scope="module")
+def raw():
+    return hr.make_data(0, NU, NI, NR)
+
+
+def _popularity(raw, alpha):
+    return np.bincount(hr.positive_keys(raw, NI) % NI, minlength=NI).astype(np.float64) ** alpha
+
+
+@pytest.fixture(scope="module")
+def w_pop(raw):
+    return _popularity(raw, 0.75)
+
+
+@pytest.fixture(scope="module")
+def w_zero():
+    """250 of the 300 items have weight 0"""
+    rng = np.random.default_rng(5)
+    w = np.zeros(NI); w[rng.permutation(NI)[:50]] = rng.random(50) + 0.01
+    return w
+
+
+@pytest.fixture(scope="module")
+def ref_pop(raw, w_pop):
+    """(u, p, cand[N, 64]) of the window under popularity^0.75, from the NumPy restatement on alias_build's table"""
+    from openrec_amd import runtime as rt
+    return pr.candidates(raw, NI, SEED, np.arange(FIRST, FIRST + N), 64, *rt.alias_build(w_pop))
+
+
+@pytest.fixture(scope="module")
+def ref_uniform(raw):
+    return hr.candidates(raw, NI, SEED, np.arange(FIRST, FIRST + N), 8)
+
+
+@pytest.fixture(scope="module")
+def _sampler(raw):
+    from openrec_amd import runtime as rt
+    return rt.DeviceSampler(raw, NU, NI)
+
+
+@pytest.fixture
+def sampler(_sampler):
+    """every test starts and ends without a proposal"""
+    _sampler.set_proposal(None)
+    yield _sampler
+    _sampler.set_proposal(None)
+
+
+def _tables(D, bias=True, seed=1):
+    from openrec_amd import runtime as rt
+    U = rt.Table(NU, D).init_uniform(-0.5, 0.5, seed=seed)
+    V = rt.Table(NI, D).init_uniform(-0.5, 0.5, seed=seed + 1)
+    b = rt.Table(NI, 1).init_uniform(-0.5, 0.5, seed=seed + 2) if bias else None
+    return U, V, b
+
+
+def _bufs(n, k=3):
+    import torch
+    return [torch.empty(n, dtype=torch.int32, device=torch.device("cuda", 0)) for _ in range(k)]
+
+
+def _pair(sm, first=FIRST, n=N, seed=SEED, sync=True):
+    """-> uid, pid, nid of `pairwise` as numpy (sync=False: the device tensors, nothing waited for)"""
+    u, p, ng = _bufs(n)
+    sm.pairwise(seed, first, n, u, p, ng)
+    if not sync:
+        return u, p, ng
+    sm.ctx.synchronize()
+    return u.cpu().numpy(), p.cpu().numpy(), ng.cpu().numpy()
+
+
+def _hard(sm, model, U, V, b, M, first=FIRST, n=N, seed=SEED):
+    """-> uid, pid, nid, cand[n, M], score[n, M] as numpy"""
+    import torch
+    u, p, ng = _bufs(n)
+    c = torch.empty(n * M, dtype=torch.int32, device=u.device)
+    s = torch.empty(n * M, dtype=torch.float32, device=u.device)
+    sm.pairwise_hard(seed, first, n, u, p, ng, model, U, V, b, candidates=M, cand_out=c, cand_score_out=s)
+    sm.ctx.synchronize()
+    return u.cpu().numpy(), p.cpu().numpy(), ng.cpu().numpy(), c.cpu().numpy().reshape(n, M), s.cpu().numpy().reshape(n, M)
+
+
+def _same_bits(a, b):
+    return all(np.array_equal(x.view(np.int32), y.view(np.int32)) for x, y in zip(a, b))
+
+
+def test_the_device_table_is_alias_builds(sampler, raw, w_pop, w_zero):
+    from openrec_amd import runtime as rt
+    assert sampler.proposal() is None
+    for w in (w_pop, w_zero, np.ones(NI), np.arange(NI, dtype=np.float32)):
+        sampler.set_proposal(w)
+        thr, alias = sampler.proposal()
+        want = rt.alias_build(w)
+        assert thr.dtype == np.uint32 and alias.dtype == np.int32
+        assert np.array_equal(thr, want[0]) and np.array_equal(alias, want[1])
+    sampler.set_proposal(None)
+    assert sampler.proposal() is None
+    with pytest.raises(ValueError):               # the C call refuses too when no proposal is set
+        rt.check(sampler._lib.orx_sampler_proposal_read(sampler._h, thr.ctypes.data, alias.ctypes.data))
+    # popularity=alpha: the distinct users of an item to the power alpha; an item without interactions has weight 0 if alpha > 0
+    sampler.set_proposal(popularity=0.75)
+    assert _same_bits(sampler.proposal(), rt.alias_build(w_pop))
+    sampler.set_proposal(popularity=0)
+    assert np.array_equal(sampler.proposal()[1], np.arange(NI))
+    lonely = raw[raw["item_id"] != 200]
+    sm2 = rt.DeviceSampler(lonely, NU, NI)
+    sm2.set_proposal(popularity=1.0)
+    thr, alias = sm2.proposal()
+    assert pr.implied_probabilities(thr, alias)[200] == 0 and thr[200] == 0
+    sm2.set_proposal(popularity=0.0)
+    assert np.array_equal(sm2.proposal()[1], np.arange(NI))
+    with pytest.raises(ValueError):
+        sampler.set_proposal(w_pop, popularity=0.75)
+    with pytest.raises(ValueError):
+        sampler.set_proposal(w_pop[:-1])
+
+
+@pytest.mark.parametrize("first,n", [(0, 1), (0, 257), (3, NR + 13), (3 * NR + 4567, 1000)])
+def test_pairwise_windows_equal_the_reference(sampler, raw, first, n):
+    """one sample, more than one block, a window across an epoch boundary, a window deep in epoch 3"""
+    sampler.set_proposal(popularity=0.75)
+    thr, alias = sampler.proposal()
+    ru, rp, rc = pr.candidates(raw, NI, SEED, np.arange(first, first + n), 1, thr, alias)
+    u, p, ng = _pair(sampler, first, n)
+    assert np.array_equal(u, ru) and np.array_equal(p, rp) and np.array_equal(ng, rc[:, 0])
+    if n > 200:
+        _, _, unif = hr.candidates(raw, NI, SEED, np.arange(first, first + n), 1)
+        assert not np.array_equal(unif[:, 0], ng)
+
+
+@pytest.mark.parametrize("model", ["bpr", "ucml"])
+@pytest.mark.parametrize("D", [4, 64])
+def test_hard_candidates_equal_the_reference_and_the_selection_is_exact(sampler, ref_pop, D, model):
+    sampler.set_proposal(popularity=0.75)
+    U, V, b = _tables(D, seed=D)
+    ru, rp, rc = ref_pop
+    u0, p0, n0 = _pair(sampler)
+    out = {}
+    for M in (1, 3, 8, 64):
+        u, p, ng, c, s = out[M] = _hard(sampler, model, U, V, b, M)
+        assert np.array_equal(u, ru) and np.array_equal(p, rp)
+        assert np.array_equal(c, rc[:, :M]), M
+        assert np.isfinite(s).all()
+        assert np.array_equal(ng, c[np.arange(N), hr.select(s)]), M
+    assert np.array_equal(out[1][2], n0) and np.array_equal(out[1][0], u0) and np.array_equal(out[1][1], p0)      # M = 1 is `pairwise`
+    assert (out[8][2] != out[1][2]).any()
+    assert np.array_equal(out[64][4][:, :8].view(np.int32), out[8][4].view(np.int32))       # a candidate's score does not depend on M
+
+
+def test_selection_rules_hold_under_a_proposal(sampler, ref_pop):
+    """NaN and -inf rows: the existing tie and NaN rules"""
+    sampler.set_proposal(popularity=0.75)
+    U, V, b = _tables(64)
+    Vh = V.read(); Vh[5] = np.nan; Vh[8] = -np.inf
+    V.write(Vh)
+    bh = b.read(); bh[6] = -np.inf; bh[7] = np.nan
+    b.write(bh)
+    for model in ("bpr", "ucml"):
+        u, p, ng, c, s = _hard(sampler, model, U, V, b, 8)
+        assert np.array_equal(c, ref_pop[2][:, :8])
+        assert np.isnan(s[c == 5]).all() and np.isnan(s[c == 7]).all() and np.isneginf(s[c == 6]).all() and (c == 5).any()
+        assert np.array_equal(ng, c[np.arange(N), hr.select(s)])
+    V.fill(0.0)
+    u, p, ng, c, s = _hard(sampler, "bpr", U, V, None, 8)
+    assert (s == 0).all() and np.array_equal(ng, c[:, 0])
+
+
+def test_the_plain_path(sampler, ref_pop):
+    sampler.set_proposal(popularity=0.75)
+    U, V, b = _tables(7, seed=70)
+    u, p, ng, c, s = _hard(sampler, "bpr", U, V, b, 3)
+    assert np.array_equal(u, ref_pop[0]) and np.array_equal(p, ref_pop[1]) and np.array_equal(c, ref_pop[2][:, :3])
+    assert np.isfinite(s).all() and np.array_equal(ng, c[np.arange(N), hr.select(s)])
+
+
+def test_all_ones_and_no_proposal_give_the_uniform_bits(sampler, ref_uniform):
+    U, V, b = _tables(64)
+    plain = _pair(sampler), _hard(sampler, "bpr", U, V, b, 8)
+    assert np.array_equal(plain[0][2], ref_uniform[2][:, 0]) and np.array_equal(plain[1][3], ref_uniform[2])
+    sampler.set_proposal(np.ones(NI))
+    assert sampler.proposal() is not None
+    ones = _pair(sampler), _hard(sampler, "bpr", U, V, b, 8)
+    assert _same_bits(ones[0], plain[0]) and _same_bits(ones[1], plain[1])
+    sampler.set_proposal(popularity=0.75)
+    assert not np.array_equal(_pair(sampler)[2], plain[0][2])
+    sampler.set_proposal(None)                    # resetting restores the uniform bits
+    again = _pair(sampler), _hard(sampler, "bpr", U, V, b, 8)
+    assert _same_bits(again[0], plain[0]) and _same_bits(again[1], plain[1])
+
+
+def test_items_of_weight_zero_never_come_up(sampler, raw, w_zero):
+    sampler.set_proposal(w_zero)
+    thr, alias = sampler.proposal()
+    U, V, b = _tables(64)
+    ru, rp, rc = pr.candidates(raw, NI, SEED, np.arange(FIRST, FIRST + N), 8, thr, alias)
+    u, p, ng = _pair(sampler)
+    _, _, nh, c, _ = _hard(sampler, "ucml", U, V, b, 8)
+    assert np.array_equal(ng, rc[:, 0]) and np.array_equal(c, rc)
+    # (a user whose every item of positive weight is a positive would keep its last draw, which has positive weight too)
+    assert (w_zero[ng] > 0).all() and (w_zero[c] > 0).all() and (w_zero[nh] > 0).all()
+    assert len(np.unique(c)) > 40
+
+
+def test_a_new_proposal_governs_the_calls_after_it(sampler, raw, w_pop, w_zero):
+    """two calls on one stream with a set_proposal between them and no synchronise of the test's own"""
+    from openrec_amd import runtime as rt
+    g = np.arange(FIRST, FIRST + N)
+    sampler.set_proposal(w_pop)
+    first = _pair(sampler, sync=False)
+    sampler.set_proposal(w_zero)
+    second = _pair(sampler, sync=False)
+    sampler.ctx.synchronize()
+    _, _, r1 = pr.candidates(raw, NI, SEED, g, 1, *rt.alias_build(w_pop))
+    _, _, r2 = pr.candidates(raw, NI, SEED, g, 1, *rt.alias_build(w_zero))
+    assert np.array_equal(first[2].cpu().numpy(), r1[:, 0])
+    assert np.array_equal(second[2].cpu().numpy(), r2[:, 0])
+    assert not np.array_equal(r1, r2)
+
+
+def test_errors_leave_the_proposal_and_the_context_as_they_were(sampler, w_pop):
+    import torch
+    sampler.set_proposal(w_pop)
+    before = _pair(sampler)
+    bad = w_pop.copy()
+    for i, v in ((0, np.nan), (NI - 1, np.inf), (7, -1.0)):
+        x = bad.copy(); x[i] = v
+        with pytest.raises(ValueError):
+            sampler.set_proposal(x)
+    with pytest.raises(ValueError):
+        sampler.set_proposal(np.zeros(NI))
+    with pytest.raises(ValueError):
+        sampler.set_proposal(np.ones(NI + 1))
+    assert sampler.proposal() is not None
+    assert _same_bits(_pair(sampler), before)                    # the earlier proposal still governs the next draw
+    # the pointwise producers refuse while a proposal is set ...
+    n = 512
+    u, i = _bufs(n, 2)
+    lab = torch.empty(n, dtype=torch.float32, device=u.device)
+    with pytest.raises(ValueError):
+        sampler.stratified_pointwise(3, 0, n, 0.5, u, i, lab)
+    with pytest.raises(ValueError):
+        sampler.per_pos_stratified_pointwise(3, 0, n, 0.25, u, i, lab)
+    assert _same_bits(_pair(sampler), before)                    # ... and the context stays usable
+    # ... and work again without one
+    sampler.set_proposal(None)
+    sampler.stratified_pointwise(3, 0, n, 0.5, u, i, lab)
+    sampler.per_pos_stratified_pointwise(3, 0, n, 0.25, u, i, lab)
+    sampler.ctx.synchronize()
+    assert set(lab.cpu().numpy().tolist()) == {0.0, 1.0}
+    assert int(i.min()) >= 0 and int(i.max()) < NI and int(u.max()) < NU
+
+
+def test_a_repeated_call_gives_the_same_bits(sampler):
+    sampler.set_proposal(popularity=0.75)
+    U, V, b = _tables(64)
+    assert _same_bits(_pair(sampler), _pair(sampler))
+    for model, M in (("bpr", 8), ("ucml", 64)):
+        assert _same_bits(_hard(sampler, model, U, V, b, M), _hard(sampler, model, U, V, b, M))
+
+
+def test_weighted_negatives_feed_the_fused_step(sampler):
+    import torch
+    from openrec_amd import runtime as rt
+    sampler.set_proposal(popularity=0.75)
+    U, V, b = _tables(64)
+    K, B = 4, 512
+    easy, hard = _bufs(K * B), _bufs(K * B)
+    sampler.pairwise(SEED, 0, K * B, *easy)
+    loss, l2 = rt.pairwise_step("bpr", rt.Optimizer.sgd(0.05), U, V, b, *easy, K=K, B=B)      # same stream: no sync in between
+    assert np.isfinite(loss).all() and np.isfinite(l2).all()
+    sampler.pairwise_hard(SEED, 0, K * B, *hard, "bpr", U, V, b, candidates=8)
+    loss, l2 = rt.pairwise_step("bpr", rt.Optimizer.sgd(0.05), U, V, b, *hard, K=K, B=B)
+    assert np.isfinite(loss).all() and np.isfinite(l2).all()
+    assert torch.equal(hard[0], easy[0]) and torch.equal(hard[1], easy[1]) and not torch.equal(hard[2], easy[2])
