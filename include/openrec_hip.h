@@ -223,6 +223,30 @@ int orx_pairwise_loss(orx_ctx* ctx, int model,
                       const int32_t* uid, const int32_t* pid, const int32_t* nid,
                       int64_t B, float margin, int flags, float* loss_out, float* l2_out);
 
+/* The pairwise step with PER-TRIPLET WEIGHTS and an L2 COEFFICIENT: the objective real training runs use.  For step s of the call,
+ * with w_i = weight[s*id_stride + i] (1 when weight == NULL):
+ *   BPR : loss = (1/B) sum_i w_i * (-log_sigmoid(max(x_i, -30)))     (the weight inside the mean of pairwise_log_loss.py:32)
+ *   UCML: loss = sum_i w_i * max(margin - diff_i, 0)                 (inside the sum of ucml.py:39)
+ *   J    = loss + l2_reg * l2_loss, l2_loss the model's own term (bpr.py:35, ucml.py:40), never weighted.
+ * loss_out[s] is the weighted loss, l2_out[s] the UNSCALED l2_loss (the caller forms J).  A weight of 0 leaves a triplet its l2 part
+ * only; weights are not validated (NaN and inf propagate).  weight lives where the ids live (a device pointer under ORX_IDS_DEVICE)
+ * and has their stride.  train_mask: as in orx_pairwise_step_subset; 0 = every table the call was given.  Everything else is
+ * orx_pairwise_step's contract (snapshot gradients, duplicates per optimizer, lazy Adam, ORX_CENSOR; a K-step call equals K one-step
+ * calls; loss_out = l2_out = NULL: fully asynchronous), and weight == NULL with l2_reg == 1 gives its bits.
+ * ORX_ERR_ARG before any device work: ORX_HOGWILD (a speed-comparison mode only); l2_reg negative or not finite; ORX_NO_L2 together
+ * with l2_reg != 0; and everything orx_pairwise_step / orx_pairwise_step_subset refuse. */
+int orx_pairwise_step_weighted(orx_ctx* ctx, int model, orx_opt* opt,
+                               orx_table* user, orx_table* item, orx_table* bias,
+                               const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                               int64_t K, int64_t B, int64_t id_stride, float margin, float l2_reg, int flags,
+                               int train_mask, float* loss_out, float* l2_out);
+
+/* Forward only: the weighted loss of orx_pairwise_step_weighted and the unscaled l2_loss of one batch. */
+int orx_pairwise_loss_weighted(orx_ctx* ctx, int model,
+                               orx_table* user, orx_table* item, orx_table* bias,
+                               const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                               int64_t B, float margin, int flags, float* loss_out, float* l2_out);
+
 /* K train steps of GMF.call / WRMF.call (gmf.py:22-34, wrmf.py:21-34,
  * pointwise_mse_loss.py:18-31).  w: GMF's Dense(1, use_bias=False) kernel as a
  * [D,1] table (NULL for WRMF).  a, b: WRMF confidence weights (wrmf.py:7). */
@@ -238,6 +262,16 @@ int orx_pointwise_step_subset(orx_ctx* ctx, int model, orx_opt* opt,
                               const int32_t* uid, const int32_t* iid, const float* label,
                               int64_t K, int64_t B, int64_t id_stride, float a, float b, int flags,
                               int train_mask, float* loss_out, float* l2_out);
+
+/* orx_pointwise_step / orx_pointwise_step_subset with the objective J = loss + l2_reg * l2_loss (gmf.py:32 -- the Dense kernel
+ * included --, wrmf.py:32); l2_out stays the unscaled l2_loss.  No sample weights here: WRMF has a and b.  train_mask 0: every
+ * table.  ORX_ERR_ARG before any device work: ORX_HOGWILD, l2_reg negative or not finite, ORX_NO_L2 with l2_reg != 0, and what the
+ * two plain entry points refuse.  l2_reg == 1 gives orx_pointwise_step's bits. */
+int orx_pointwise_step_l2reg(orx_ctx* ctx, int model, orx_opt* opt,
+                             orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
+                             const int32_t* uid, const int32_t* iid, const float* label,
+                             int64_t K, int64_t B, int64_t id_stride, float a, float b, float l2_reg, int flags,
+                             int train_mask, float* loss_out, float* l2_out);
 
 /* Forward only for the pointwise models (GMF.call / WRMF.call outside a tape). */
 int orx_pointwise_loss(orx_ctx* ctx, int model,
@@ -424,6 +458,14 @@ int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* user, orx_ta
 int orx_alias_build(const double* weights, int64_t n, uint32_t* thr_out, int32_t* alias_out);
 int orx_sampler_set_proposal(orx_sampler* s, const double* weights /* host [total_items], or NULL = uniform again */);
 int orx_sampler_proposal_read(orx_sampler* s, uint32_t* thr_out, int32_t* alias_out);
+
+/* Per-record weights for orx_pairwise_step_weighted, delivered on the device.  orx_sampler_set_record_weights: host_w is a HOST
+ * array [n_records] in the order of the records given to orx_sampler_create (copied to the device; not validated), or NULL to drop
+ * them.  orx_sampler_pairwise_weights: w_dev[i] (a DEVICE array [n]) = the weight of the record that sample first + i of stream
+ * `seed` draws as its positive -- the keyed permutation of orx_sampler_pairwise / orx_sampler_pairwise_hard, with or without a
+ * proposal; it depends on (seed, first + i) only.  ORX_ERR_STATE while no record weights are set; n = 0: ORX_OK, no launch. */
+int orx_sampler_set_record_weights(orx_sampler* s, const float* host_w /* [n_records] or NULL */);
+int orx_sampler_pairwise_weights(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, float* w_dev);
 /* The pointwise producers of GMF / WRMF (dataset.py:18-36 _stratified_pointwise_generator, :38-58
  * _per_pos_stratified_pointwise_generator): samples [first, first + n) as (user, item, label) DEVICE arrays.
  *   stratified         : with probability pos_ratio the next record of the shuffled epoch (label 1), otherwise a uniform

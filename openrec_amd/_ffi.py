@@ -62,6 +62,13 @@ SIGNATURES = {
                                   c_float, c_int, _fp, _fp]),
     "orx_pairwise_step_subset": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _ip, c_int64, c_int64, c_int64,
                                          c_float, c_int, c_int, _fp, _fp]),
+    "orx_pairwise_step_weighted": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _ip, _fp, c_int64, c_int64, c_int64,
+                                           c_float, c_float, c_int, c_int, _fp, _fp]),
+    "orx_pairwise_loss_weighted": (c_int, [_p, c_int, _p, _p, _p, _ip, _ip, _ip, _fp, c_int64, c_float, c_int, _fp, _fp]),
+    "orx_pointwise_step_l2reg": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _ip, _ip, _fp, c_int64, c_int64, c_int64,
+                                         c_float, c_float, c_float, c_int, c_int, _fp, _fp]),
+    "orx_sampler_set_record_weights": (c_int, [_p, _fp]),
+    "orx_sampler_pairwise_weights": (c_int, [_p, c_uint64, c_int64, c_int64, _fp]),
     "orx_pairwise_reserve": (c_int, [_p, _p, _p, _p, _p, c_int64, c_int64]),
     "orx_pairwise_loss": (c_int, [_p, c_int, _p, _p, _p, _ip, _ip, _ip, c_int64, c_float, c_int, _fp, _fp]),
     "orx_pointwise_step": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _ip, _ip, _fp, c_int64, c_int64, c_int64,

@@ -995,11 +995,34 @@ static bool lazy_adam_ok(const orx_opt* opt, const orx_table* U, const orx_table
            getenv("ORX_ADAM_DENSE") == nullptr;
 }
 
+// per-triplet weights of K steps next to the ids: a device array as it is, a host array into d_lab (stride B, as stage_triplets
+// packs the ids); NULL stays NULL
+int stage_weights(orx_ctx* c, const float* weight, int64_t K, int64_t B, int64_t id_stride, int flags, const float** dw) {
+    *dw = weight;
+    if (!weight || (flags & ORX_IDS_DEVICE)) return ORX_OK;
+    ENSURE(c->d_lab, c->d_lab_cap, (size_t)K * B * sizeof(float));
+    for (int64_t s = 0; s < K; ++s)
+        ORX_HIP(hipMemcpyAsync(c->d_lab + s * B, weight + s * id_stride, (size_t)B * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    *dw = c->d_lab;
+    return ORX_OK;
+}
+
 extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
                                  orx_table* U, orx_table* V, orx_table* b,
                                  const int32_t* uid, const int32_t* pid, const int32_t* nid,
                                  int64_t K, int64_t B, int64_t id_stride, float margin, int flags,
                                  float* loss_out, float* l2_out) {
+    return orx_pairwise_step_impl(c, model, opt, U, V, b, uid, pid, nid, nullptr, K, B, id_stride, margin, (flags & ORX_NO_L2) ? 0.f : 1.f, flags,
+                                  loss_out, l2_out);
+}
+
+// The full pairwise step behind orx_pairwise_step (weight NULL, l2w 0 or 1) and orx_pairwise_step_weighted: `weight` lives where the
+// ids live and has their stride; l2w is the coefficient of l2_loss in the objective.  A weighted call runs the WT instantiations of the fused
+// kernels (kernels_pairwise_weighted.hip) and keeps plan statistics of its own.
+int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                           const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                           int64_t K, int64_t B, int64_t id_stride, float margin, float l2w, int flags,
+                           float* loss_out, float* l2_out) {
     ORX_ARG(c && opt, "orx_pairwise_step: NULL context/optimizer");
     ORX_ARG(model == ORX_BPR || model == ORX_UCML, "orx_pairwise_step: unknown model %d", model);
     CHECK(check_pair_tables(U, V, b, model, flags));
@@ -1015,6 +1038,8 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     }
     const int32_t *du, *dp, *dn; int64_t ds;
     CHECK(stage_triplets(c, uid, pid, nid, K, B, id_stride, flags, &du, &dp, &dn, &ds));
+    const float* dw;
+    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &dw));
 
     const bool hogwild = (flags & ORX_HOGWILD) != 0;
     ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pairwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
@@ -1049,8 +1074,8 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     // rows referenced >= 3 times in a step: private staging slots instead of atomics (fb bit 3: atomics)
     bool staging = role_bits && orx_fused_can_inline_apply(U->dim) && !(fb & 8);
     // no read-back (see plan_stats_poll): the previous call of this shape was quiet
-    // (kmodel: a biased and a bias-free call of one shape run different kernels and keep apart)
-    const int64_t stats_key[5] = {B, U->rows, V->rows, (int64_t)kmodel * 16 + opt->kind, (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (inline_apply ? 2 : 0)};
+    // (kmodel: a biased and a bias-free call of one shape run different kernels and keep apart; so do a weighted and an unweighted call)
+    const int64_t stats_key[5] = {B, U->rows, V->rows, (int64_t)kmodel * 16 + opt->kind + (dw ? 1024 : 0), (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (inline_apply ? 2 : 0)};
     CHECK(plan_stats_poll(c));
     const bool plan_wait = getenv("ORX_PLAN_WAIT") != nullptr || getenv("ORX_PLAN_PIPE") != nullptr;      // (experiments / tests: always read back)
     bool nowait = mode == MODE_EXACT && orx_plan_v2(role_bits) && staging && !censor && opt->kind != ORX_ADAM && !plan_wait &&
@@ -1094,7 +1119,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
     a.eps = orx_rule_eps(opt);
     a.margin = margin;
     a.invB = 1.0f / (float)B;
-    a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f;
+    a.l2w = l2w;
     a.err = c->d_err;
     if (lazy_adam) {
         a.a2U = sU.s1; a.a2V = sV.s1; a.a2b = sb.s1;
@@ -1134,6 +1159,7 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
             } else {
                 a.uid = du + s * ds; a.pid = dp + s * ds; a.nid = dn + s * ds;
             }
+            a.wt = dw ? dw + s * ds : nullptr;      // (the caller's order: the kernel reads it at the triplet's original position)
             orx_exact_step_views(c, plan, i, B, U->dim, stage_views, &a);
             if (!b) { a.stageb = nullptr; a.partb = nullptr; a.prev_stageb = nullptr; }      // (no bias: nothing is staged for it)
             a.ids4 = plan.pair_tpw > 1 ? c->d_ids4 + (size_t)i * B : nullptr;
@@ -1320,6 +1346,12 @@ extern "C" int orx_pairwise_reserve(orx_ctx* c, orx_opt* opt, orx_table* U, orx_
 extern "C" int orx_pairwise_loss(orx_ctx* c, int model, orx_table* U, orx_table* V, orx_table* b,
                                  const int32_t* uid, const int32_t* pid, const int32_t* nid,
                                  int64_t B, float margin, int flags, float* loss_out, float* l2_out) {
+    return orx_pairwise_loss_impl(c, model, U, V, b, uid, pid, nid, nullptr, B, margin, flags, loss_out, l2_out);
+}
+
+int orx_pairwise_loss_impl(orx_ctx* c, int model, orx_table* U, orx_table* V, orx_table* b,
+                           const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                           int64_t B, float margin, int flags, float* loss_out, float* l2_out) {
     if (U) CHECK(orx_table_sync(U));
     if (V) CHECK(orx_table_sync(V));
     if (b) CHECK(orx_table_sync(b));
@@ -1330,6 +1362,8 @@ extern "C" int orx_pairwise_loss(orx_ctx* c, int model, orx_table* U, orx_table*
     ORX_HIP(hipSetDevice(c->device));
     const int32_t *du, *dp, *dn; int64_t ds;
     CHECK(stage_triplets(c, uid, pid, nid, 1, B, B, flags, &du, &dp, &dn, &ds));
+    const float* dw;
+    CHECK(stage_weights(c, weight, 1, B, B, flags, &dw));
     const int nw = orx_fused_nwaves(U->dim, B);
     ENSURE(c->d_partial, c->d_partial_cap, (size_t)nw * 2 * sizeof(float));
     ENSURE(c->d_loss, c->d_loss_cap, 2 * sizeof(double));
@@ -1339,7 +1373,7 @@ extern "C" int orx_pairwise_loss(orx_ctx* c, int model, orx_table* U, orx_table*
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
     a.margin = margin; a.invB = 1.0f / (float)B; a.l2w = 1.f;
     a.partial = c->d_partial; a.err = c->d_err;
-    a.uid = du; a.pid = dp; a.nid = dn;
+    a.uid = du; a.pid = dp; a.nid = dn; a.wt = dw;
     CHECK(orx_launch_fused(c, b ? model : MODEL_BPR_NB, ORX_SGD, MODE_LOSS, a));
     ReduceArgs r;
     r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nw;

@@ -49,6 +49,15 @@ extern "C" int orx_pointwise_step(orx_ctx* c, int model, orx_opt* opt,
                                   const int32_t* uid, const int32_t* iid, const float* label,
                                   int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, int flags,
                                   float* loss_out, float* l2_out) {
+    return orx_pointwise_step_impl(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, (flags & ORX_NO_L2) ? 0.f : 1.f, flags,
+                                   loss_out, l2_out);
+}
+
+// (l2w: the coefficient of l2_loss in the objective -- orx_pointwise_step_l2reg; the plain entry point passes 0 or 1)
+int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
+                            const int32_t* uid, const int32_t* iid, const float* label,
+                            int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags,
+                            float* loss_out, float* l2_out) {
     ORX_ARG(c && opt, "orx_pointwise_step: NULL context/optimizer");
     CHECK(check_point_tables(model, U, V, b, w));
     ORX_ARG(K >= 0 && B > 0, "orx_pointwise_step: K must be >= 0 and B > 0");
@@ -128,7 +137,7 @@ extern "C" int orx_pointwise_step(orx_ctx* c, int model, orx_opt* opt,
     a.aU = sU.s0; a.aV = sV.s0; a.ab = sb.s0;
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = D;
     a.lr = opt->lr; a.eps = orx_rule_eps(opt);
-    a.invB = 1.0f / (float)B; a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f; a.a_w = a_w; a.b_w = b_w;
+    a.invB = 1.0f / (float)B; a.l2w = l2w; a.a_w = a_w; a.b_w = b_w;
     a.sigmoid = (model == ORX_WRMF && (flags & ORX_POINT_SIGMOID)) ? 1 : 0;
     a.wpartial = c->d_wpart; a.err = c->d_err;
     // GMF on the float4 kernels: the Dense(1) gradient is reduced and applied by the last workgroups of the step's own launch
@@ -1018,7 +1027,7 @@ extern "C" int orx_sampler_destroy(orx_sampler* s) {
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
     hipFree(s->rec_user); hipFree(s->rec_item); hipFree(s->ptr); hipFree(s->items);
-    hipFree(s->d_counter); hipFree(s->d_blockcnt); hipFree(s->d_blockbase); hipFree(s->d_prop);
+    hipFree(s->d_counter); hipFree(s->d_blockcnt); hipFree(s->d_blockbase); hipFree(s->d_prop); hipFree(s->d_recw);
     delete s;
     return ORX_OK;
 }

@@ -54,6 +54,7 @@ struct SubsetCall {
     int mask; int kmodel;                     // orx_launch_subset_grads' model
     int refs;                                 // item lookups per sample: 2 (pairwise: positive, negative) or 1 (WRMF)
     const int32_t* du; const int32_t* di; const int32_t* dn; const float* dl; int64_t ds;      // device inputs, elements between steps
+    const float* dw;                          // pairwise: per-triplet weights at the ids' stride, NULL: all ones
     int64_t K, B;
     SubsetArgs a;                             // model constants filled in by the caller
 };
@@ -137,6 +138,7 @@ int run_subset(SubsetCall& q, float* loss_out, float* l2_out, bool host_ids) {
                     if (tr[k].t->lazy == opt) CHECK(orx_adam_rows_sorted(c, opt, tr[k].t, tr[k].sorted, tr[k].n, nullptr, 0, false));
             a.uid = q.du + s * q.ds; a.pid = q.di + s * q.ds; a.nid = q.dn ? q.dn + s * q.ds : nullptr;
             a.label = q.dl ? q.dl + s * q.ds : nullptr;
+            a.wt = q.dw ? q.dw + s * q.ds : nullptr;
             a.partial = c->d_partial + (size_t)i * nw * 2;
             CHECK(orx_launch_subset_grads(c, q.kmodel, a));
             if (adam) opt->t += 1;            // once per step, whatever the mask
@@ -157,10 +159,19 @@ extern "C" int orx_pairwise_step_subset(orx_ctx* c, int model, orx_opt* opt, orx
                                         const int32_t* uid, const int32_t* pid, const int32_t* nid,
                                         int64_t K, int64_t B, int64_t id_stride, float margin, int flags,
                                         int train_mask, float* loss_out, float* l2_out) {
+    return orx_pairwise_subset_impl(c, model, opt, U, V, b, uid, pid, nid, nullptr, K, B, id_stride, margin, (flags & ORX_NO_L2) ? 0.f : 1.f, flags,
+                                    train_mask, loss_out, l2_out);
+}
+
+// (weight, l2w: as orx_pairwise_step_impl)
+int orx_pairwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                             const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                             int64_t K, int64_t B, int64_t id_stride, float margin, float l2w, int flags,
+                             int train_mask, float* loss_out, float* l2_out) {
     bool full = false;
     CHECK(check_mask("orx_pairwise_step_subset", train_mask, b, &full));
     // the full mask, and the calls that touch no table (K = 0, an empty batch), are the full step's: its checks, its route
-    if (full || K <= 0 || B <= 0) return orx_pairwise_step(c, model, opt, U, V, b, uid, pid, nid, K, B, id_stride, margin, flags, loss_out, l2_out);
+    if (full || K <= 0 || B <= 0) return orx_pairwise_step_impl(c, model, opt, U, V, b, uid, pid, nid, weight, K, B, id_stride, margin, l2w, flags, loss_out, l2_out);
     ORX_ARG(!(flags & ORX_HOGWILD), "orx_pairwise_step_subset: ORX_HOGWILD trains every table (a strict subset is not supported with it)");
     ORX_ARG(!(flags & ORX_CENSOR), "orx_pairwise_step_subset: ORX_CENSOR is not folded into a step over a strict subset (call orx_table_censor after it)");
     ORX_ARG(c && opt, "orx_pairwise_step_subset: NULL context/optimizer");
@@ -187,7 +198,8 @@ extern "C" int orx_pairwise_step_subset(orx_ctx* c, int model, orx_opt* opt, orx
         }
         q.du = c->d_ids; q.di = c->d_ids + n; q.dn = c->d_ids + 2 * n; q.ds = B;
     }
-    q.a.margin = margin; q.a.invB = 1.0f / (float)B; q.a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f;
+    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &q.dw));      // (host weights travel like the ids: d_lab is free in a pairwise call)
+    q.a.margin = margin; q.a.invB = 1.0f / (float)B; q.a.l2w = l2w;
     return run_subset(q, loss_out, l2_out, !(flags & ORX_IDS_DEVICE));
 }
 
@@ -195,9 +207,17 @@ extern "C" int orx_pointwise_step_subset(orx_ctx* c, int model, orx_opt* opt, or
                                          const int32_t* uid, const int32_t* iid, const float* label,
                                          int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, int flags,
                                          int train_mask, float* loss_out, float* l2_out) {
+    return orx_pointwise_subset_impl(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, (flags & ORX_NO_L2) ? 0.f : 1.f, flags,
+                                     train_mask, loss_out, l2_out);
+}
+
+int orx_pointwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
+                              const int32_t* uid, const int32_t* iid, const float* label,
+                              int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags,
+                              int train_mask, float* loss_out, float* l2_out) {
     bool full = false;
     CHECK(check_mask("orx_pointwise_step_subset", train_mask, b, &full));
-    if (full || K <= 0 || B <= 0) return orx_pointwise_step(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, flags, loss_out, l2_out);
+    if (full || K <= 0 || B <= 0) return orx_pointwise_step_impl(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, l2w, flags, loss_out, l2_out);
     ORX_ARG(model != ORX_GMF, "orx_pointwise_step_subset: ORX_GMF with a strict subset is not supported (its Dense(1) kernel is a fourth role)");
     ORX_ARG(!(flags & ORX_HOGWILD), "orx_pointwise_step_subset: ORX_HOGWILD trains every table (a strict subset is not supported with it)");
     ORX_ARG(c && opt, "orx_pointwise_step_subset: NULL context/optimizer");
@@ -224,7 +244,7 @@ extern "C" int orx_pointwise_step_subset(orx_ctx* c, int model, orx_opt* opt, or
         }
         q.du = c->d_ids; q.di = c->d_ids + n; q.dl = c->d_lab; q.ds = B;
     }
-    q.a.invB = 1.0f / (float)B; q.a.l2w = (flags & ORX_NO_L2) ? 0.f : 1.f; q.a.a_w = a_w; q.a.b_w = b_w;
+    q.a.invB = 1.0f / (float)B; q.a.l2w = l2w; q.a.a_w = a_w; q.a.b_w = b_w;
     q.a.sigmoid = (flags & ORX_POINT_SIGMOID) ? 1 : 0;
     return run_subset(q, loss_out, l2_out, !(flags & ORX_IDS_DEVICE));
 }

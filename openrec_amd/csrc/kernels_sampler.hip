@@ -72,6 +72,26 @@ int orx_launch_sample_pairwise(orx_ctx* ctx, const SamplerArgs& a) {
     return ORX_OK;
 }
 
+// The weight of the record each pairwise sample draws as its positive (orx_sampler_pairwise_weights): the same keyed permutation as
+// sample_pairwise_kernel, one 4-byte gather per sample; nothing of the negatives' draw is repeated.
+__global__ __launch_bounds__(256) void sample_weights_kernel(SamplerArgs a, const float* rec_w, float* out) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
+        const uint64_t g = (uint64_t)(a.first + i);
+        const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
+        const uint64_t rec = feistel_perm(pos, (uint64_t)a.R, a.h, mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+        out[i] = rec_w[rec];
+    }
+}
+
+int orx_launch_sample_weights(orx_ctx* ctx, const SamplerArgs& a, const float* rec_w, float* out) {
+    if (a.n == 0) return ORX_OK;
+    int64_t g = (a.n + 255) / 256; if (g > 8192) g = 8192;
+    ORX_LAUNCH(ctx, sample_weights_kernel, dim3((unsigned)g), dim3(256), 0, a, rec_w, out);
+    ORX_HIP(hipGetLastError());
+    return ORX_OK;
+}
+
 
 // ------------------------------------------------------------------------------------------- pointwise samplers ---
 // openrec/tf2/data/dataset.py:18-36 `_stratified_pointwise_generator` and :38-58 `_per_pos_stratified_pointwise_generator`,

@@ -33,7 +33,8 @@ __device__ __forceinline__ void wrmf_score(float s, float y, float a_w, float b_
 }
 
 // LPR lanes own one row (D = 4 LPR), 64 / LPR triplets per wavefront per pass
-template <int LPR, int MODEL>
+// (WT: per-triplet weights SubsetArgs::wt, a compile-time variant as in fused_kernel)
+template <int LPR, int MODEL, bool WT>
 __global__ __launch_bounds__(256) void subset_pair_grads_kernel(SubsetArgs a) {
     constexpr int TPW = 64 / LPR;
     constexpr int D = 4 * LPR;
@@ -57,7 +58,8 @@ __global__ __launch_bounds__(256) void subset_pair_grads_kernel(SubsetArgs a) {
             const float bp = NB ? 0.0f : a.b[p], bn = NB ? 0.0f : a.b[n];
             const float red = group_allreduce<LPR>(score_partial<SM>(ru, rp, rn));
             float term, g;
-            score<SM>(red, bp, bn, a.invB, a.margin, term, g);
+            if (WT) score_weighted<SM>(red, bp, bn, a.invB, a.wt[t], a.margin, term, g);
+            else score<SM>(red, bp, bn, a.invB, a.margin, term, g);
             sq_acc += dot4(ru, ru) + dot4(rp, rp) + dot4(rn, rn);
             if (sub == 0) loss_acc += term;
             row_grads<SM>(ru, rp, rn, g, a.l2w, gu, gp, gn, gbp, gbn);
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256) void subset_pair_grads_kernel(SubsetArgs a) {
 }
 
 // any dim: one wavefront per triplet
-template <int MODEL>
+template <int MODEL, bool WT>
 __global__ __launch_bounds__(256) void subset_pair_grads_generic_kernel(SubsetArgs a) {
     constexpr bool NB = MODEL == MODEL_BPR_NB;
     constexpr int SM = NB ? (int)ORX_BPR : MODEL;
@@ -106,7 +108,8 @@ __global__ __launch_bounds__(256) void subset_pair_grads_generic_kernel(SubsetAr
             }
             const float red = wave_sum(part);
             float term;
-            score<SM>(red, NB ? 0.0f : a.b[p], NB ? 0.0f : a.b[n], a.invB, a.margin, term, g);
+            if (WT) score_weighted<SM>(red, NB ? 0.0f : a.b[p], NB ? 0.0f : a.b[n], a.invB, a.wt[t], a.margin, term, g);
+            else score<SM>(red, NB ? 0.0f : a.b[p], NB ? 0.0f : a.b[n], a.invB, a.margin, term, g);
             if (lane == 0) loss_acc += term;
         } else if (lane == 0) {
             *a.err = 1;
@@ -233,15 +236,15 @@ inline int lpr_of(int D) {
     switch (D) { case 16: return 4; case 32: return 8; case 64: return 16; case 128: return 32; case 256: return 64; default: return 0; }
 }
 
-template <int MODEL>
+template <int MODEL, bool WT>
 void launch_pair(orx_ctx* ctx, int lpr, dim3 g, const SubsetArgs& a) {
     switch (lpr) {
-        case 4: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<4, MODEL>), g, dim3(256), 0, a); break;
-        case 8: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<8, MODEL>), g, dim3(256), 0, a); break;
-        case 16: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<16, MODEL>), g, dim3(256), 0, a); break;
-        case 32: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<32, MODEL>), g, dim3(256), 0, a); break;
-        case 64: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<64, MODEL>), g, dim3(256), 0, a); break;
-        default: ORX_LAUNCH(ctx, (subset_pair_grads_generic_kernel<MODEL>), g, dim3(256), 0, a); break;
+        case 4: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<4, MODEL, WT>), g, dim3(256), 0, a); break;
+        case 8: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<8, MODEL, WT>), g, dim3(256), 0, a); break;
+        case 16: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<16, MODEL, WT>), g, dim3(256), 0, a); break;
+        case 32: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<32, MODEL, WT>), g, dim3(256), 0, a); break;
+        case 64: ORX_LAUNCH(ctx, (subset_pair_grads_kernel<64, MODEL, WT>), g, dim3(256), 0, a); break;
+        default: ORX_LAUNCH(ctx, (subset_pair_grads_generic_kernel<MODEL, WT>), g, dim3(256), 0, a); break;
     }
 }
 
@@ -252,9 +255,13 @@ int orx_launch_subset_grads(orx_ctx* ctx, int model, const SubsetArgs& a) {
     ProfScope ps(ctx, model < 0 ? ORX_K_POINT : ORX_K_FUSED);
     const int lpr = lpr_of(a.D);
     const dim3 g((unsigned)(orx_fused_nwaves(a.D, a.B) / 4));
-    if (model == ORX_BPR) launch_pair<ORX_BPR>(ctx, lpr, g, a);
-    else if (model == ORX_UCML) launch_pair<ORX_UCML>(ctx, lpr, g, a);
-    else if (model == MODEL_BPR_NB) launch_pair<MODEL_BPR_NB>(ctx, lpr, g, a);
+    if (model >= 0 && a.wt != nullptr) {
+        if (model == ORX_BPR) launch_pair<ORX_BPR, true>(ctx, lpr, g, a);
+        else if (model == ORX_UCML) launch_pair<ORX_UCML, true>(ctx, lpr, g, a);
+        else launch_pair<MODEL_BPR_NB, true>(ctx, lpr, g, a);
+    } else if (model == ORX_BPR) launch_pair<ORX_BPR, false>(ctx, lpr, g, a);
+    else if (model == ORX_UCML) launch_pair<ORX_UCML, false>(ctx, lpr, g, a);
+    else if (model == MODEL_BPR_NB) launch_pair<MODEL_BPR_NB, false>(ctx, lpr, g, a);
     else {
         switch (lpr) {
             case 4: ORX_LAUNCH(ctx, subset_point_grads_kernel<4>, g, dim3(256), 0, a); break;

@@ -91,6 +91,15 @@ __device__ __forceinline__ void score(float red, float bp, float bn, float invB,
     }
 }
 
+// score with a per-triplet weight w (orx_pairwise_step_weighted): the weight multiplies the triplet's term inside BPR's mean
+// (it joins 1/B) and inside UCML's sum (term and hinge indicator), so the loss term and g scale together; w = 1 gives score's bits
+template <int MODEL>
+__device__ __forceinline__ void score_weighted(float red, float bp, float bn, float invB, float w, float margin,
+                                               float& term, float& g) {
+    score<MODEL>(red, bp, bn, MODEL == ORX_BPR ? invB * w : invB, margin, term, g);
+    if (MODEL != ORX_BPR) { term *= w; g *= w; }
+}
+
 template <int MODEL>
 __device__ __forceinline__ float score_partial(f4 u, f4 p, f4 n) {
     if (MODEL == ORX_BPR) {

@@ -182,6 +182,27 @@ int orx_table_side(orx_table* t);                               // allocate the 
 int orx_opt_slots(orx_opt* opt, orx_table* t, OptSlots* out);   // allocate optimizer slots
 int stage_ids(orx_ctx* c, const int32_t* host, int64_t n, int64_t off);   // H2D into ctx->d_ids
 int fetch_losses(orx_ctx* c, int64_t K, float* loss_out, float* l2_out);
+// per-triplet weights of K steps: a device array as it is, a host array into ctx->d_lab packed at stride B; NULL stays NULL
+int stage_weights(orx_ctx* c, const float* weight, int64_t K, int64_t B, int64_t id_stride, int flags, const float** dw);
+// the bodies of the train steps with the objective's two knobs exposed (api_weighted.hip): per-triplet weights (NULL: all ones) and
+// the coefficient l2w of l2_loss; the plain entry points pass NULL and 0 / 1
+int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                           const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                           int64_t K, int64_t B, int64_t id_stride, float margin, float l2w, int flags, float* loss_out, float* l2_out);
+int orx_pairwise_loss_impl(orx_ctx* c, int model, orx_table* U, orx_table* V, orx_table* b,
+                           const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                           int64_t B, float margin, int flags, float* loss_out, float* l2_out);
+int orx_pairwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                             const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
+                             int64_t K, int64_t B, int64_t id_stride, float margin, float l2w, int flags, int train_mask,
+                             float* loss_out, float* l2_out);
+int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
+                            const int32_t* uid, const int32_t* iid, const float* label,
+                            int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags, float* loss_out, float* l2_out);
+int orx_pointwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
+                              const int32_t* uid, const int32_t* iid, const float* label,
+                              int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags, int train_mask,
+                              float* loss_out, float* l2_out);
 void orx_prof_begin(orx_ctx* ctx, int kid);
 void orx_prof_end(orx_ctx* ctx, int kid);
 
@@ -250,6 +271,7 @@ struct PairArgs {
     float lr; float eps; float margin; float invB; float l2w;
     float* partial;                           // [nwaves][2] loss / l2 partials of this step
     int* err;
+    const float* wt;                          // [B] this step's per-triplet weights in the CALLER's order (orx_pairwise_step_weighted), NULL: all ones
 };
 
 struct DedupArgs {
@@ -376,6 +398,7 @@ struct SubsetArgs {
     int sigmoid;
     float* partial;                                               // [orx_fused_nwaves(D, B)][2] loss / l2 partials of this step
     int* err;
+    const float* wt;                                              // [B] per-triplet weights of this step (pairwise), NULL: all ones
 };
 int orx_launch_subset_grads(orx_ctx* ctx, int model /* ORX_BPR, ORX_UCML, MODEL_BPR_NB; < 0: WRMF */, const SubsetArgs& a);
 int orx_launch_subset_concat_ids(orx_ctx* ctx, const int32_t* pid, const int32_t* nid, int64_t id_stride, int64_t K, int64_t B, int32_t* out);
@@ -451,6 +474,7 @@ int orx_launch_topk_filter(orx_ctx* ctx, const float* U, const float* V, const f
 // launchers implemented in kernels_pairwise.hip
 int orx_launch_dedup(orx_ctx* ctx, const DedupArgs& a, int64_t K);
 int orx_launch_fused(orx_ctx* ctx, int model, int optkind, int mode, const PairArgs& a);
+int orx_launch_fused_weighted(orx_ctx* ctx, int model, int optkind, int mode, const PairArgs& a);     // a.wt != NULL (kernels_pairwise_weighted.hip)
 int orx_launch_hot_reduce(orx_ctx* ctx, const PairArgs& a, int level);
 
 // host-side plan of the exact steps (api.hip), shared by the pairwise and the pointwise step
@@ -809,6 +833,8 @@ int orx_launch_sample_pairwise(orx_ctx* ctx, const SamplerArgs& a);
 int orx_launch_sample_stratified(orx_ctx* ctx, const SamplerArgs& a, float pos_ratio, float* label, int* blockcnt, int64_t* blockbase,
                                  int64_t* counter);
 int orx_launch_sample_perpos(orx_ctx* ctx, const SamplerArgs& a, int nneg, float* label);
+// out[i] = rec_w[record of sample a.first + i] (the positives' permutation of sample_pairwise_kernel); reads a.R, a.h, a.seed, a.first, a.n
+int orx_launch_sample_weights(orx_ctx* ctx, const SamplerArgs& a, const float* rec_w, float* out);
 
 // the sampler object (api_more.hip creates it)
 struct orx_sampler {
@@ -822,6 +848,8 @@ struct orx_sampler {
     int* d_blockcnt = nullptr; int64_t* d_blockbase = nullptr; size_t block_cap = 0;
     // proposal of the negatives (api_proposal.hip): [total_items] records (thr, alias), allocated by the first orx_sampler_set_proposal
     uint2* d_prop = nullptr; bool prop_on = false;
+    // per-record weights (api_weighted.hip): [R] in the records' order, allocated by the first orx_sampler_set_record_weights
+    float* d_recw = nullptr; bool recw_on = false;
 };
 
 // kernels_hardneg.hip (orx_sampler_pairwise_hard): the pairwise draw of `s` plus M candidates per sample, scored against the tables

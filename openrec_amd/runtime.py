@@ -287,13 +287,39 @@ def _train_mask(train, bias):
     return mask
 
 
+def _weights_arg(weights, ids_on_device, n_ids, what):
+    """per-triplet weights -> (pointer, keepalive); they live where the ids live and are shaped like them"""
+    pw, nw, dw, kw = _label_arg(weights)
+    if dw != ids_on_device:
+        raise ValueError(f"{what}: weights on the {'device' if dw else 'host'} with ids on the {'device' if ids_on_device else 'host'} "
+                         "(the weights live where the ids live)")
+    if nw != n_ids:
+        raise ValueError(f"{what}: {nw} weights for {n_ids} ids (weights are shaped like the ids)")
+    return pw, kw
+
+
+def _l2_reg_arg(l2_reg, no_l2, what):
+    if l2_reg is None:
+        return 0.0 if no_l2 else 1.0
+    if no_l2:
+        raise ValueError(f"{what}: no_l2=True together with l2_reg (drop no_l2, or pass l2_reg=0.0)")
+    return float(l2_reg)
+
+
 def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None,
-                  margin=0.5, hogwild=False, no_l2=False, want_loss=True, censor=False, train=None):
+                  margin=0.5, hogwild=False, no_l2=False, want_loss=True, censor=False, train=None,
+                  weights=None, l2_reg=None):
     """K fused train steps.  Returns (loss[K], l2[K]) as numpy float32 when
     want_loss, else None (fully asynchronous).  bias=None: BPR without item biases (score u.p - u.n); UCML and
     censor need the bias (ValueError).  train: None, or the tables to update ("user", "item", "bias"); the others stay
-    bit-for-bit as they are (orx_pairwise_step_subset)."""
+    bit-for-bit as they are (orx_pairwise_step_subset).
+    weights / l2_reg (orx_pairwise_step_weighted): the objective loss_w + l2_reg * l2_loss, where weights[i] multiplies triplet
+    i's term inside BPR's mean / UCML's sum.  weights: a float32 numpy array or device tensor shaped like the ids and living where
+    they live; the returned loss is the weighted one, l2 the unscaled l2_loss.  Both None: the plain step, as ever."""
     mask = _train_mask(train, bias)
+    weighted = weights is not None or l2_reg is not None
+    if weighted:
+        l2c = _l2_reg_arg(l2_reg, no_l2, "pairwise_step")
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pp, npn, dp, k1 = _ids_arg(pid)
@@ -315,7 +341,15 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
     else:
         loss = l2 = None
         lp = l2p = None
-    if mask is None:
+    if weighted:
+        pw = kw = None
+        if weights is not None:
+            pw, kw = _weights_arg(weights, du, nu, "pairwise_step")
+            user.ctx.after_torch(weights)
+        check(lib.orx_pairwise_step_weighted(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn, pw,
+                                             int(K), int(B), int(id_stride), float(margin), l2c, flags & ~_ffi.ORX_NO_L2,
+                                             mask or 0, lp, l2p))
+    elif mask is None:
         check(lib.orx_pairwise_step(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
                                     int(K), int(B), int(id_stride), float(margin), flags, lp, l2p))
     else:
@@ -331,7 +365,8 @@ def pairwise_reserve(opt, user, item, bias, K, B):
     _keep_tables(opt, (user, item, bias))
 
 
-def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5):
+def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5, weights=None):
+    """forward only: (loss, l2_loss) of one batch; weights: per-triplet weights as in pairwise_step"""
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pp, _, dp, k1 = _ids_arg(pid)
@@ -339,6 +374,12 @@ def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5):
     mid = {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
     loss = np.empty(1, np.float32)
     l2 = np.empty(1, np.float32)
+    if weights is not None:
+        pw, kw = _weights_arg(weights, du, nu, "pairwise_loss")
+        user.ctx.after_torch(weights)
+        check(lib.orx_pairwise_loss_weighted(user.ctx._h, mid, user._h, item._h, _bias_h(bias), pu, pp, pn, pw, nu, float(margin),
+                                             _ffi.ORX_IDS_DEVICE if du else 0, loss.ctypes.data, l2.ctypes.data))
+        return float(loss[0]), float(l2[0])
     check(lib.orx_pairwise_loss(user.ctx._h, mid, user._h, item._h, _bias_h(bias), pu, pp, pn, nu, float(margin),
                                 _ffi.ORX_IDS_DEVICE if du else 0, loss.ctypes.data, l2.ctypes.data))
     return float(loss[0]), float(l2[0])
@@ -358,10 +399,13 @@ _POINT = {"gmf": _ffi.ORX_GMF, "wrmf": _ffi.ORX_WRMF}
 
 
 def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None, id_stride=None,
-                   a=1.0, b_w=1.0, hogwild=False, no_l2=False, want_loss=True, sigmoid=False, train=None):
+                   a=1.0, b_w=1.0, hogwild=False, no_l2=False, want_loss=True, sigmoid=False, train=None, l2_reg=None):
     """K fused GMF / WRMF train steps (gmf.py:22-34, wrmf.py:21-34); sigmoid: PointwiseMSELoss(sigmoid=True)
-    (pointwise_mse_loss.py:24-25; WRMF only).  train: as in pairwise_step (WRMF; GMF takes the full set only)."""
+    (pointwise_mse_loss.py:24-25; WRMF only).  train: as in pairwise_step (WRMF; GMF takes the full set only).
+    l2_reg: the objective loss + l2_reg * l2_loss (orx_pointwise_step_l2reg); the returned l2 stays the unscaled l2_loss."""
     mask = _train_mask(train, bias)
+    if l2_reg is not None:
+        l2c = _l2_reg_arg(l2_reg, no_l2, "pointwise_step")
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pi, ni, di, k1 = _ids_arg(iid)
@@ -379,7 +423,9 @@ def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None
     args = (user.ctx._h, _POINT[model], opt._h, user._h, item._h, bias._h, w._h if w is not None else None, pu, pi, pl,
             int(K), int(B), int(id_stride), float(a), float(b_w), flags)
     outs = (loss.ctypes.data if want_loss else None, l2.ctypes.data if want_loss else None)
-    if mask is None:
+    if l2_reg is not None:
+        check(lib.orx_pointwise_step_l2reg(*args[:-1], l2c, flags & ~_ffi.ORX_NO_L2, mask or 0, *outs))
+    elif mask is None:
         check(lib.orx_pointwise_step(*args, *outs))
     else:
         check(lib.orx_pointwise_step_subset(*args, mask, *outs))
@@ -1069,6 +1115,26 @@ class DeviceSampler:
         assert du and dp and dn and nu >= n, "the sampler writes device buffers"
         check(self._lib.orx_sampler_pairwise(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), pu, pp, pn))
 
+    def set_record_weights(self, weights=None):
+        """One weight per interaction record, in the order of `raw_data` (float32; not validated), kept on the device for
+        `pairwise_weights`; None drops them.  The call may synchronise the context's stream."""
+        if weights is None:
+            check(self._lib.orx_sampler_set_record_weights(self._h, None))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        if w.size != self.n_records:
+            raise ValueError("set_record_weights: %d weights for %d records" % (w.size, self.n_records))
+        check(self._lib.orx_sampler_set_record_weights(self._h, w.ctypes.data))
+
+    def pairwise_weights(self, seed, first, n, out):
+        """Fill the DEVICE float32 buffer `out` with the record weights of samples [first, first + n) of stream `seed`: out[i]
+        is the weight of the (user, positive) record that `pairwise` / `pairwise_hard` write at i for the same (seed, first),
+        with or without a proposal -- ready to be `pairwise_step`'s weights.  Raises OrxError (ORX_ERR_STATE) while no record
+        weights are set."""
+        po, no, do, _ = _label_arg(out)
+        assert do and no >= n, "the sampler writes device buffers"
+        check(self._lib.orx_sampler_pairwise_weights(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), po))
+
     def pairwise_hard(self, seed, first, n, uid, pid, nid, model, U, V, b=None, candidates=8,
                       cand_out=None, cand_score_out=None):
         """Dynamic negative sampling: uid / pid as `pairwise(seed, first, n)` writes them, nid the hardest of `candidates`
@@ -1108,3 +1174,6 @@ class DeviceSampler:
     def per_pos_stratified_pointwise(self, seed, first, n, pos_ratio, uid, iid, label):
         """(user, item, label) samples [first, first + n) of `Dataset.per_pos_stratified_pointwise` into DEVICE buffers"""
         self._pointwise(self._lib.orx_sampler_per_pos_stratified, seed, first, n, pos_ratio, uid, iid, label)
+
+
+Sampler = DeviceSampler

@@ -65,11 +65,13 @@ class PendingStep:
 class LazyScalar:
     """A scalar that materializes on demand (`.numpy()`, float(), arithmetic)."""
 
-    def __init__(self, step, index):
-        self._step, self._index = step, index
+    def __init__(self, step, index, scale=1.0):
+        """scale: the model's l2_reg on the second output (the call returns l2_reg * l2_loss); 1.0 leaves the value as it is"""
+        self._step, self._index, self._scale = step, index, float(scale)
 
     def numpy(self):
-        return np.float32(self._step.forward()[self._index])
+        v = np.float32(self._step.forward()[self._index])
+        return v if self._scale == 1.0 else np.float32(v * np.float32(self._scale))
 
     def __float__(self):
         return float(self.numpy())

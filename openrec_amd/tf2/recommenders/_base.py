@@ -226,7 +226,20 @@ class Recommender:
             tape.record(step)
         else:
             step.forward()                      # eager semantics outside a tape
-        return LazyScalar(step, 0), LazyScalar(step, 1)
+        # the call returns (loss, l2_reg * l2_loss): a tape over the tuple trains loss + l2_reg * l2_loss (TF sums a nested target)
+        return LazyScalar(step, 0), LazyScalar(step, 1, scale=self.l2_reg)
+
+    l2_reg = 1.0                                # the reference's objective (bpr_citeulike.py:36-37)
+
+    def _set_l2_reg(self, l2_reg):
+        l2_reg = float(l2_reg)
+        if not (np.isfinite(l2_reg) and l2_reg >= 0):
+            raise ValueError(f"l2_reg must be finite and >= 0, got {l2_reg!r}")
+        self.l2_reg = l2_reg
+
+    def _l2_arg(self, no_l2):
+        """rt.*_step's l2_reg for a step of this model: None (today's entry points) for the reference's weight 1 and for no_l2"""
+        return None if (no_l2 or self.l2_reg == 1.0) else self.l2_reg
 
 
 class PointwiseRecommender(Recommender):
@@ -245,9 +258,11 @@ class PointwiseRecommender(Recommender):
 
         def run_train(optimizer, no_l2, train=None):
             def runner(bufs, K):
-                return rt.pointwise_step(name, optimizer, U, V, b, w, bufs[0], bufs[1], bufs[2], K=K, no_l2=no_l2, train=train, **kw)
+                return rt.pointwise_step(name, optimizer, U, V, b, w, bufs[0], bufs[1], bufs[2], K=K, no_l2=no_l2, train=train,
+                                         l2_reg=l2_reg, **kw)
+            l2_reg = self._l2_arg(no_l2)
             n = uid.numel() if hasattr(uid, "numel") else np.asarray(uid).size
-            key = ("point", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), train)
+            key = ("point", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), train, l2_reg)
             if self._enqueue(step_holder[0], key, (uid, iid, np.asarray(lab, np.float32) if not hasattr(lab, "is_cuda") else lab), runner,
                              subset=train is not None):
                 return None
@@ -265,25 +280,38 @@ class PairwiseRecommender(Recommender):
     _model = None
     margin = 0.5
 
-    def __call__(self, user_id, p_item_id, n_item_id):
+    def __call__(self, user_id, p_item_id, n_item_id, sample_weight=None):
+        """sample_weight: one weight per triplet (a float array or device tensor living where the ids live); it multiplies the
+        triplet's term inside BPR's mean / UCML's sum (rt.pairwise_step's weights)"""
         tape = active_tape()
         U, V, b = self._tables(flush=tape is None)        # under a tape nothing is observed yet: keep the queue
         uid, pid, nid = _ids(user_id), _ids(p_item_id), _ids(n_item_id)
+        wts = None
+        if sample_weight is not None:
+            wts = _ids(sample_weight)
+            if not hasattr(wts, "is_cuda"):
+                wts = np.ascontiguousarray(wts, np.float32)
         step_holder = []
 
         def run_forward():
             self.flush()
-            return rt.pairwise_loss(self._model, U, V, b, uid, pid, nid, margin=self.margin)
+            return rt.pairwise_loss(self._model, U, V, b, uid, pid, nid, margin=self.margin, weights=wts)
 
         def run_train(optimizer, no_l2, train=None):
             def runner(bufs, K, censor=False):
+                # (both None: today's entry points; the weights are the queue's fourth buffer)
                 return rt.pairwise_step(self._model, optimizer, U, V, b, bufs[0], bufs[1], bufs[2], K=K,
-                                        margin=self.margin, no_l2=no_l2, censor=censor, train=train)
+                                        margin=self.margin, no_l2=no_l2, censor=censor, train=train,
+                                        weights=bufs[3] if wts is not None else None, l2_reg=l2_reg)
+            l2_reg = self._l2_arg(no_l2)
             n = uid.numel() if hasattr(uid, "numel") else np.asarray(uid).size
-            key = ("pair", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), self.margin, train)
-            if self._enqueue(step_holder[0], key, (uid, pid, nid), runner, subset=train is not None):
+            # a weighted and an unweighted step, or steps of two coefficients, never share a device call
+            key = ("pair", id(optimizer), bool(no_l2), int(n), bool(getattr(uid, "is_cuda", False)), self.margin, train,
+                   l2_reg, wts is not None)
+            arrays = (uid, pid, nid) if wts is None else (uid, pid, nid, wts)
+            if self._enqueue(step_holder[0], key, arrays, runner, subset=train is not None):
                 return None
-            loss, l2 = runner((uid, pid, nid), 1)
+            loss, l2 = runner(arrays, 1)
             return float(loss[0]), float(l2[0])
 
         out = self._record(run_forward, run_train)
@@ -292,14 +320,17 @@ class PairwiseRecommender(Recommender):
 
     call = __call__
 
-    def train_steps(self, optimizer, user_id, p_item_id, n_item_id, K=None, want_loss=True, censor=False, train=None):
+    def train_steps(self, optimizer, user_id, p_item_id, n_item_id, K=None, want_loss=True, censor=False, train=None,
+                    sample_weight=None):
         """Beyond the reference API: K consecutive fused steps in one device call
         (ids shaped [K, B]); the path `bench.py` measures.  train: None, or the tables to update ("user", "item",
-        "bias") while the others stay as they are (rt.pairwise_step)."""
+        "bias") while the others stay as they are (rt.pairwise_step).  sample_weight: per-triplet weights shaped like the
+        ids.  The objective is loss + l2_reg * l2_loss with the model's l2_reg; the returned l2 is the unscaled l2_loss."""
         U, V, b = self._tables()
         uid, pid, nid = _ids(user_id), _ids(p_item_id), _ids(n_item_id)
         if K is None:
             K = uid.shape[0] if getattr(uid, "ndim", 1) == 2 else 1
         opt = optimizer.native(U.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
         return rt.pairwise_step(self._model, opt, U, V, b, uid, pid, nid, K=K, margin=self.margin,
-                                want_loss=want_loss, censor=censor, train=train)
+                                want_loss=want_loss, censor=censor, train=train, weights=wts, l2_reg=self._l2_arg(False))

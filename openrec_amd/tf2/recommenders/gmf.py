@@ -8,10 +8,12 @@ from ... import runtime as rt
 class GMF(PointwiseRecommender):
     _score_kind = "gmf"
 
-    def __init__(self, dim_user_embed, dim_item_embed, total_users, total_items, ctx=None):
+    def __init__(self, dim_user_embed, dim_item_embed, total_users, total_items, ctx=None, l2_reg=1.0):
+        """l2_reg: the call returns (loss, l2_reg * l2_loss); 1.0 is the reference"""
         self._build_tables(dim_user_embed, dim_item_embed, total_users, total_items, ctx)
         self.mlp = MLP(units_list=[1], use_bias=False).build(dim_user_embed, ctx)
         self.mlp.layers[0].kernel.pre_access = self.flush
+        self._set_l2_reg(l2_reg)
 
     @property
     def trainable_variables(self):

@@ -8,9 +8,11 @@ class UCML(PairwiseRecommender):
     _model = "ucml"
     _score_kind = "l2"
 
-    def __init__(self, dim_user_embed, dim_item_embed, total_users, total_items, margin=0.5, ctx=None):
+    def __init__(self, dim_user_embed, dim_item_embed, total_users, total_items, margin=0.5, ctx=None, l2_reg=1.0):
+        """l2_reg: the call returns (loss, l2_reg * l2_loss); 1.0 is the reference"""
         self._build_tables(dim_user_embed, dim_item_embed, total_users, total_items, ctx)
         self.margin = margin
+        self._set_l2_reg(l2_reg)
 
     def censor_vec(self, user_id, p_item_id, n_item_id):
         """ucml.py:44-48: users, then positive items, then negative items (sequential).  Right after a queued

@@ -8,10 +8,12 @@ from ... import runtime as rt
 
 class WRMF(PointwiseRecommender):
 
-    def __init__(self, dim_user_embed, dim_item_embed, total_users, total_items, a=1.0, b=1.0, ctx=None):
+    def __init__(self, dim_user_embed, dim_item_embed, total_users, total_items, a=1.0, b=1.0, ctx=None, l2_reg=1.0):
+        """l2_reg: the call returns (loss, l2_reg * l2_loss); 1.0 is the reference"""
         self._build_tables(dim_user_embed, dim_item_embed, total_users, total_items, ctx)
         self.pointwise_mse_loss = PointwiseMSELoss(a=a, b=b)
         self._a, self._b = a, b
+        self._set_l2_reg(l2_reg)
 
     def _point_args(self):
         return "wrmf", None, dict(a=self._a, b_w=self._b)
