@@ -431,6 +431,44 @@ int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* user, orx_ta
                               uint64_t seed, int64_t first, int64_t n, int32_t n_cand,
                               int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev,
                               int32_t* cand_dev /* [n*n_cand] or NULL */, float* cand_score_dev /* [n*n_cand] or NULL */);
+/* WARP negatives: (user, positive) of samples [first, first + n) exactly as orx_sampler_pairwise gives them, and as the negative
+ * the FIRST of up to T = max_trials candidates that violates the margin against the positive under the current model; the
+ * triplet's weight is trial_weight[number of candidates it took - 1], a function of WARP's rank estimate
+ * floor((items - 1) / trials) that the caller tabulates (host array [T]: any rank loss, exact bits, no transcendental on the device).
+ * Stream: candidate c of sample g is candidate c of orx_sampler_pairwise_hard -- the same seed_c, rejection loop and 256-attempt
+ * limit, from the proposal when one is set (orx_sampler_set_proposal) -- so candidate 0 is the pairwise negative.
+ * Scores: fp32, the kinds of orx_sampler_pairwise_hard (ORX_BPR U[u].V[j] + b[j], ORX_UCML -||U[u] - V[j]||^2 + b[j]; bias may be
+ * NULL: no "+ b"), s_p for the positive and s_c for candidate c, by one scorer.  Summation order: the products of four adjacent
+ * columns as (x0 + x1) + (x2 + x3), those partial sums by a butterfly over the columns' lanes (xor 1, 2, 4, ...), the bias last; a
+ * dim that is no multiple of 4 or above 256: columns l, l + 64, .. in order per lane l, the butterfly over 64 lanes, the bias.  The
+ * scores are this kernel's own: bit equality with cand_score of orx_sampler_pairwise_hard is NOT promised (two kernels).
+ * Violation: candidate c violates iff (s_c + margin) > s_p -- one rounded fp32 add, then a compare; a NaN on either side never
+ * violates; margin may be +inf or -inf.  For ORX_UCML this is "the hinge max(margin - (s_p - s_c), 0) of the
+ * reference's UCML (recommenders/ucml.py:39) is active for (u, p, c)".
+ * Result: t = 1 + the smallest violating c < T, or 0 when none of the T candidates violates.
+ *   nid[i]        = candidate t - 1, or candidate 0 when t = 0
+ *   weight[i]     = trial_weight[t - 1], or exactly +0.0f when t = 0 (orx_pairwise_step_weighted: such a triplet keeps only its l2 part)
+ *   trials[i]     = t                                                            (trials_dev [n] or NULL)
+ *   pos_score[i]  = s_p                                                          (pos_score_dev [n] or NULL)
+ *   cand_score[i * T + c] = s_c for every c < t, or every c < T when t = 0       (cand_score_dev [n * T] or NULL)
+ * and cand_score entries beyond that are unspecified (the kernel may or may not have scored them, and writes none it did not scan).
+ * Independence: a sample's outputs depend on (seed, g), the tables, margin and trial_weight only -- never on n, first, the launch
+ * shape or how candidates are grouped into rounds.  No atomics: a repeated call gives the same bits.
+ * Prefix rule: for T1 < T2 a sample with t(T1) > 0 has t(T2) = t(T1) and the same nid; one with t(T1) = 0 has t(T2) = 0 or
+ * T1 < t(T2) <= T2.
+ * Weight table: kept on the device inside the sampler and uploaded only when its T floats differ (as bits) from the copy already
+ * there, so a loop that passes the same table enqueues the call without a host synchronisation; a CHANGED table may synchronise
+ * the context's stream, as orx_sampler_set_proposal does.
+ * ORX_ERR_ARG before any launch: everything orx_sampler_pairwise_hard refuses, max_trials outside [1, 256], a NaN margin,
+ * trial_weight == NULL, weight_dev == NULL with n > 0.  n = 0: ORX_OK, nothing is launched.  Lazily-applied Adam: the WHOLE of
+ * user, item and bias is brought up to date first, as in orx_sampler_pairwise_hard.  Runs on the context's stream. */
+int orx_sampler_pairwise_warp(orx_sampler* s, int model, orx_table* user, orx_table* item, orx_table* bias,
+                              uint64_t seed, int64_t first, int64_t n, int32_t max_trials, float margin,
+                              const float* trial_weight /* HOST [max_trials] */,
+                              int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev, float* weight_dev,
+                              int32_t* trials_dev      /* [n] or NULL */,
+                              float* pos_score_dev     /* [n] or NULL */,
+                              float* cand_score_dev    /* [n * max_trials] or NULL */);
 /* ---- negatives from a weighted item proposal (popularity^alpha, in-stock items, ...).
  * orx_alias_build: host only, no context or device: the Walker / Vose alias table of n weights, computed in double.  Column j
  * holds a 32-bit threshold thr[j] and an alias alias[j]: with a uniform 32-bit t, column j yields j if t < thr[j] and alias[j]

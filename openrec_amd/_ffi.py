@@ -92,6 +92,8 @@ SIGNATURES = {
     "orx_sampler_destroy": (c_int, [_p]),
     "orx_sampler_pairwise": (c_int, [_p, c_uint64, c_int64, c_int64, _ip, _ip, _ip]),
     "orx_sampler_pairwise_hard": (c_int, [_p, c_int, _p, _p, _p, c_uint64, c_int64, c_int64, c_int32, _ip, _ip, _ip, _ip, _fp]),
+    "orx_sampler_pairwise_warp": (c_int, [_p, c_int, _p, _p, _p, c_uint64, c_int64, c_int64, c_int32, c_float, _fp,
+                                          _ip, _ip, _ip, _fp, _ip, _fp, _fp]),
     "orx_alias_build": (c_int, [_p, c_int64, _p, _ip]),
     "orx_sampler_set_proposal": (c_int, [_p, _p]),
     "orx_sampler_proposal_read": (c_int, [_p, _p, _ip]),

@@ -1028,6 +1028,7 @@ extern "C" int orx_sampler_destroy(orx_sampler* s) {
     hipStreamSynchronize(s->ctx->stream);
     hipFree(s->rec_user); hipFree(s->rec_item); hipFree(s->ptr); hipFree(s->items);
     hipFree(s->d_counter); hipFree(s->d_blockcnt); hipFree(s->d_blockbase); hipFree(s->d_prop); hipFree(s->d_recw);
+    hipFree(s->d_warpw);
     delete s;
     return ORX_OK;
 }

@@ -850,6 +850,8 @@ struct orx_sampler {
     uint2* d_prop = nullptr; bool prop_on = false;
     // per-record weights (api_weighted.hip): [R] in the records' order, allocated by the first orx_sampler_set_record_weights
     float* d_recw = nullptr; bool recw_on = false;
+    // WARP's trial-weight table (api_warp.hip): the device copy and the host floats it holds, uploaded only when they change
+    float* d_warpw = nullptr; float h_warpw[256]; int warpw_n = 0;
 };
 
 // kernels_hardneg.hip (orx_sampler_pairwise_hard): the pairwise draw of `s` plus M candidates per sample, scored against the tables
@@ -860,3 +862,14 @@ struct HardNegArgs {
     int32_t* cand; float* cand_score;                     // [n * M] or NULL
 };
 int orx_launch_hardneg(orx_ctx* ctx, const HardNegArgs& a);
+
+// kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
+struct WarpNegArgs {
+    SamplerArgs s;
+    const float* U; const float* V; const float* b;       // b NULL: no item bias
+    int model; int D; int T; float margin;
+    const float* tw;                                      // DEVICE [T]: the weight of a triplet whose violator is candidate t - 1
+    float* weight; int32_t* trials; float* pos_score;     // [n]; trials / pos_score may be NULL
+    float* cand_score;                                    // [n * T] or NULL
+};
+int orx_launch_warpneg(orx_ctx* ctx, const WarpNegArgs& a);

@@ -1048,6 +1048,35 @@ def alias_build(weights):
     return thr, alias
 
 
+WARP_KINDS = ("log", "log1p", "harmonic")
+
+
+def warp_weights(total_items, max_trials, kind="log", normalize=False):
+    """The weight table of `DeviceSampler.pairwise_warp` -> float32[max_trials]: entry t - 1 is the rank loss of a triplet whose
+    first violating candidate was the t-th drawn, a function of WARP's rank estimate r_t = floor((total_items - 1) / t):
+    "log": log(max(1, r_t)) (LightFM), "log1p": log(r_t + 1) (CML), "harmonic": sum_{i <= r_t} 1 / i (WSABIE).  Computed in
+    float64 and cast once; normalize=True divides by the entry of t = 1 first.  ValueError for total_items < 2, max_trials outside
+    [1, 256] or an unknown kind.  Host only: no context, no device."""
+    total_items, max_trials = int(total_items), int(max_trials)
+    if total_items < 2:
+        raise ValueError("warp_weights: total_items must be at least 2, got %d" % total_items)
+    if not 1 <= max_trials <= 256:
+        raise ValueError("warp_weights: max_trials must be in [1, 256], got %d" % max_trials)
+    if kind not in WARP_KINDS:
+        raise ValueError("warp_weights: kind must be one of %s, got %r" % (", ".join(WARP_KINDS), kind))
+    r = (total_items - 1) // np.arange(1, max_trials + 1, dtype=np.int64)
+    if kind == "log":
+        w = np.log(np.maximum(1, r).astype(np.float64))
+    elif kind == "log1p":
+        w = np.log((r + 1).astype(np.float64))
+    else:
+        h = np.concatenate([[0.0], np.cumsum(1.0 / np.arange(1, int(r[0]) + 1, dtype=np.float64))])
+        w = h[r]
+    if normalize:
+        w = w / w[0]
+    return w.astype(np.float32)
+
+
 class DeviceSampler:
     """On-device pairwise sampler over an interaction set (see kernels_sampler.hip).  `raw_data`: the
     structured array the reference's Dataset takes ('user_id', 'item_id')."""
@@ -1071,6 +1100,7 @@ class DeviceSampler:
         self.total_items = int(total_items)
         self._item_users = np.bincount(ci, minlength=int(total_items)).astype(np.float64)     # distinct users per item
         self._has_proposal = False
+        self._warp_tables = {}
 
     def set_proposal(self, weights=None, *, popularity=None):
         """Draw the negatives of `pairwise` and the candidates of `pairwise_hard` from a weighted proposal over the items
@@ -1160,6 +1190,56 @@ class DeviceSampler:
                 t._sync_pending()
         check(self._lib.orx_sampler_pairwise_hard(self._h, int(mid), U._h, V._h, _bias_h(b), int(seed) & (2 ** 64 - 1), int(first),
                                                   int(n), int(candidates), pu, pp, pn, pc, ps))
+
+    def pairwise_warp(self, seed, first, n, uid, pid, nid, weight, model, U, V, b=None, max_trials=10, margin=1.0,
+                      rank_weight="log", trials_out=None, pos_score_out=None, cand_score_out=None):
+        """WARP negative sampling: uid / pid as `pairwise(seed, first, n)` writes them; the candidates of `pairwise_hard`
+        (candidate 0 is `pairwise`'s negative; from the proposal when `set_proposal` is in force) are taken one after another
+        until one violates the margin against the positive under `model` on the tables as they stand ("bpr": U[u].V[j] + b[j],
+        "ucml": -|U[u] - V[j]|^2 + b[j]; b=None: no bias).  Candidate c violates iff (s_c + margin) > s_p in fp32 -- one rounded
+        add, then a compare; a NaN score never violates; margin may be +-inf, a NaN margin is a ValueError.  With t = 1 + the
+        first violating candidate, or 0 when none of the `max_trials` (1 .. 256) violates:
+            nid[i] = candidate t - 1 (candidate 0 when t = 0)        weight[i] = table[t - 1] (exactly +0.0 when t = 0)
+        where `rank_weight` gives the table: a kind of `warp_weights(total_items, max_trials, kind)` or an array of max_trials
+        floats.  `weight` is ready to be `pairwise_step(..., weights=weight)`: a weight of 0 leaves a triplet only its l2 part.
+        trials_out (int32 [n]): t.  pos_score_out (float32 [n]): s_p.  cand_score_out (float32 [n * max_trials]): s_c for every
+        c < t (every c < max_trials when t = 0); the entries beyond are unspecified.  A sample's outputs depend on (seed, first +
+        i), the tables, the margin and the table only, never on n, first or the launch; a repeated call gives the same bits; for
+        T1 < T2 a sample that found its violator within T1 keeps t and nid at T2.  The rank estimate floor((items - 1) / t) is
+        WARP's for UNIFORM candidates; with a proposal set it estimates the rank under the proposal, not the uniform one.
+        All buffers are device buffers; the call runs on the context's stream without a host synchronisation while the table
+        stays the same (a changed table is uploaded and may synchronise the stream), so its output feeds `pairwise_step`."""
+        T = int(max_trials)
+        if not 1 <= T <= 256:
+            raise ValueError("pairwise_warp: max_trials must be in [1, 256], got %d" % T)
+        if isinstance(rank_weight, str):
+            key = (rank_weight, T)
+            if self._warp_tables.get("key") != key:
+                self._warp_tables = {"key": key, "table": warp_weights(self.total_items, T, rank_weight)}
+            table = self._warp_tables["table"]
+        else:
+            table = np.ascontiguousarray(rank_weight, dtype=np.float32).reshape(-1)
+            if table.size != T:
+                raise ValueError("pairwise_warp: rank_weight has %d entries, max_trials is %d" % (table.size, T))
+        pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
+        pw, nw, dw, _ = _label_arg(weight)
+        assert du and dp and dn and dw and min(nu, np_, nn, nw) >= n, "the sampler writes device buffers"
+        pt = pps = pcs = None
+        if trials_out is not None:
+            pt, nt, dt, _ = _ids_arg(trials_out)
+            assert dt and nt >= n, "trials_out: a device int32 buffer of n"
+        if pos_score_out is not None:
+            pps, nps, dps, _ = _label_arg(pos_score_out)
+            assert dps and nps >= n, "pos_score_out: a device float32 buffer of n"
+        if cand_score_out is not None:
+            pcs, ncs, dcs, _ = _label_arg(cand_score_out)
+            assert dcs and ncs >= n * T, "cand_score_out: a device float32 buffer of n * max_trials"
+        mid = model if isinstance(model, int) else {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
+        for t in (U, V, b):
+            if t is not None:
+                t._sync_pending()
+        check(self._lib.orx_sampler_pairwise_warp(self._h, int(mid), U._h, V._h, _bias_h(b), int(seed) & (2 ** 64 - 1), int(first),
+                                                  int(n), T, float(margin), table.ctypes.data, pu, pp, pn, pw, pt, pps, pcs))
 
     def _pointwise(self, fn, seed, first, n, pos_ratio, uid, iid, label):
         pu, nu, du, _ = _ids_arg(uid); pi, _, di, _ = _ids_arg(iid); pl, nl, dl, _ = _label_arg(label)
