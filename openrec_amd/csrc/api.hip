@@ -1121,6 +1121,11 @@ int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, or
     a.invB = 1.0f / (float)B;
     a.l2w = l2w;
     a.err = c->d_err;
+    // Neither the loss nor the l2 sum is asked for (a training loop between two observations of the loss): the kernels that have a
+    // loss-free form (fused_kernel LOSS = false: exact SGD on the float4 dims, unweighted) skip their partials, and for every kernel
+    // the sums over the partials are not launched -- d_partial and d_loss are read by nothing but the fetch_losses of the call itself
+    const bool want_loss = loss_out != nullptr || l2_out != nullptr;
+    a.no_loss = want_loss ? 0 : 1;
     if (lazy_adam) {
         a.a2U = sU.s1; a.a2V = sV.s1; a.a2b = sb.s1;
         CHECK(orx_opt_last(opt, U, !lazy_resume, &a.lastU)); CHECK(orx_opt_last(opt, V, !lazy_resume, &a.lastV));
@@ -1273,7 +1278,7 @@ int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, or
                 for (int l = 0; l < tree_levels; ++l) CHECK(orx_launch_hot_reduce(c, a, l));
                 if (mode == MODE_EXACT && !defer) {
                     // the chunk's last step: its duplicated rows and the chunk's loss sums leave in ONE launch where that is possible
-                    if (i == kc - 1 && !censor && !lazy_adam) {
+                    if (i == kc - 1 && !censor && !lazy_adam && want_loss) {
                         ReduceArgs r;
                         r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
                         int rc = ORX_OK;
@@ -1298,7 +1303,7 @@ int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, or
                 }
             }
         }
-        if (!tail_done) {
+        if (!tail_done && want_loss) {
             ReduceArgs r;
             r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
             CHECK(orx_launch_loss_reduce(c, r, kc));

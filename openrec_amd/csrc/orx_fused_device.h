@@ -12,7 +12,10 @@
 // LONGGAP (lazy Adam): 0 = the merged replay loop, 1 = + the bounded per-row replay of rows far behind, 2 = the closed-form replay (orx_device.h AdamCF)
 // WT: per-triplet weights (PairArgs::wt, orx_pairwise_step_weighted) -- a compile-time variant, so the kernels of the plain entry
 // points are the code they were
-template <int LPR, int MODEL, int OPT, int MODE, bool CENSOR = false, bool STAGED = false, int LONGGAP = 0, bool WT = false>
+// LOSS = false: the call asked for neither the loss nor the l2 sum (PairArgs::no_loss) -- g is computed as ever (the same score<>, its
+// loss term unused), the l2 dot products, the two wavefront reductions and the store of the partial are gone.  Instantiated for the
+// exact SGD step without weights only (launch_fused_mode); every other kernel computes its partials whether or not they are read
+template <int LPR, int MODEL, int OPT, int MODE, bool CENSOR = false, bool STAGED = false, int LONGGAP = 0, bool WT = false, bool LOSS = true>
 __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
     constexpr int TPW = 64 / LPR;
     constexpr int D = 4 * LPR;
@@ -146,8 +149,10 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
         // the caller's array knows nothing of the plan's reordering.  !WT: the plain 1/B of every other entry point
         if (WT) score_weighted<SM>(red, NB ? 0.f : bp, NB ? 0.f : bn, a.invB, a.wt[t0], a.margin, term, g);
         else score<SM>(red, NB ? 0.f : bp, NB ? 0.f : bn, a.invB, a.margin, term, g);
-        sq_acc += dot4(ru, ru) + dot4(rp, rp) + dot4(rn, rn);
-        if (sub == 0) loss_acc += term;
+        if (LOSS) {
+            sq_acc += dot4(ru, ru) + dot4(rp, rp) + dot4(rn, rn);
+            if (sub == 0) loss_acc += term;
+        }
         if (MODE == MODE_LOSS) continue;
 
         f4 gu, gp, gn; float gbp, gbn;
@@ -294,6 +299,7 @@ __global__ __launch_bounds__(256) void fused_kernel(PairArgs a) {
 #undef kn
 #undef FLAG_DUP
 #undef FLAG_ROLE
+    if (!LOSS) return;
     const float ls = wave_sum(loss_acc);
     const float sq = wave_sum(sq_acc);
     if (lane == 0) {
@@ -410,6 +416,15 @@ static void launch_fused_mode(int mode, dim3 g, orx_ctx* s, const PairArgs& a) {
     constexpr bool CEN = MODEL != MODEL_BPR_NB;      // censor instantiations (UCML's censor_vec; bias-free BPR has none)
     switch (mode) {
         case MODE_EXACT:
+            if constexpr (!WT && OPT == ORX_SGD) {      // the loss-free forms (fused_kernel LOSS = false): the headline and the UCML + censor workload take them
+                if (a.no_loss) {
+                    if (CEN && a.censor && a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, CEN, true, 0, false, false>), g, dim3(256), 0, a);
+                    else if (CEN && a.censor) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, CEN, false, 0, false, false>), g, dim3(256), 0, a);
+                    else if (a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, false, true, 0, false, false>), g, dim3(256), 0, a);
+                    else ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, false, false, 0, false, false>), g, dim3(256), 0, a);
+                    break;
+                }
+            }
             if (CEN && a.censor && a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, CEN, true, 0, WT>), g, dim3(256), 0, a);
             else if (CEN && a.censor) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, CEN, false, 0, WT>), g, dim3(256), 0, a);
             else if (a.stage) ORX_LAUNCH(s, (fused_kernel<LPR, MODEL, OPT, MODE_EXACT, false, true, 0, WT>), g, dim3(256), 0, a);

@@ -270,6 +270,7 @@ struct PairArgs {
     int D;
     float lr; float eps; float margin; float invB; float l2w;
     float* partial;                           // [nwaves][2] loss / l2 partials of this step
+    int no_loss;                              // the caller takes neither the loss nor the l2 sum: kernels with a loss-free form skip the partials (fused_kernel LOSS)
     int* err;
     const float* wt;                          // [B] this step's per-triplet weights in the CALLER's order (orx_pairwise_step_weighted), NULL: all ones
 };
