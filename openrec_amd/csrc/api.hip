@@ -49,18 +49,6 @@ int orx_ensure(void** p, size_t* cap, size_t bytes) {
     return ORX_OK;
 }
 
-#define ENSURE(ptr, cap, bytes)                                                        \
-    do {                                                                               \
-        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 void orx_prof_begin(orx_ctx* ctx, int kid) {
     hipEvent_t e0, e1;
     ctx->cur_e0 = ctx->cur_e1 = nullptr;
@@ -146,8 +134,6 @@ extern "C" int orx_ctx_destroy(orx_ctx* c) {
     if (c->h_plan) hipHostFree(c->h_plan);
     if (c->plan_ev) hipEventDestroy(c->plan_ev);
     if (c->stats_ev) hipEventDestroy(c->stats_ev);
-    for (int k = 0; k < 2; ++k) { if (c->pipe_cnt[k]) hipEventDestroy(c->pipe_cnt[k]); if (c->pipe_done[k]) hipEventDestroy(c->pipe_done[k]); }
-    if (c->plan_stream) hipStreamDestroy(c->plan_stream);
     if (c->wait_ev) hipEventDestroy(c->wait_ev);
     if (c->own_stream) hipStreamDestroy(c->stream);
     delete c;
@@ -475,8 +461,7 @@ int orx_opt_slots(orx_opt* o, orx_table* t, OptSlots* out) {
 }
 
 bool orx_adam_cf_ok(const orx_opt* o) {
-    static const bool off = getenv("ORX_ADAM_NO_CF") != nullptr;
-    return !off && o->kind == ORX_ADAM && o->p0 > 0.f && o->p0 <= 0.95f && o->p1 < 1.0f && (1.0f - sqrtf(o->p1)) <= 1e-3f;
+    return o->kind == ORX_ADAM && o->p0 > 0.f && o->p0 <= 0.95f && o->p1 < 1.0f && (1.0f - sqrtf(o->p1)) <= 1e-3f;
 }
 
 AdamCFParams orx_adam_cf_params(const orx_opt* o) {
@@ -692,15 +677,6 @@ int orx_exact_buffers(orx_ctx* c, orx_table* U, orx_table* V, int64_t K, int64_t
                 c->h_plan_cap = (size_t)chunk * 9 * sizeof(int);
             }
             if (!c->plan_ev) ORX_HIP(hipEventCreateWithFlags(&c->plan_ev, hipEventDisableTiming));
-            if (!c->plan_stream) {                          // the plan pipeline's stream and events (orx_pairwise_step)
-                int lo_p = 0, hi_p = 0;
-                ORX_HIP(hipDeviceGetStreamPriorityRange(&lo_p, &hi_p));
-                ORX_HIP(hipStreamCreateWithPriority(&c->plan_stream, hipStreamNonBlocking, hi_p));
-                for (int k = 0; k < 2; ++k) {
-                    ORX_HIP(hipEventCreateWithFlags(&c->pipe_cnt[k], hipEventDisableTiming));
-                    ORX_HIP(hipEventCreateWithFlags(&c->pipe_done[k], hipEventDisableTiming));
-                }
-            }
         } else {
             if (role_bits) ENSURE(c->d_roles, c->d_roles_cap, (size_t)chunk * 3 * Bp);
             if (inline_apply) ENSURE(c->d_dupbits, c->d_dupbits_cap, (size_t)chunk * nb_total * orx_dedup_words() * sizeof(unsigned int));
@@ -772,8 +748,7 @@ static void plan_decide(int64_t kc, int64_t B, bool inline_apply, bool staging, 
         // B/5 duplicated rows on the apply is its own launch.
         int max_dup = 0;
         for (int64_t i = 0; i < kc; ++i) max_dup = std::max(max_dup, dc[i]);
-        const char* thr = getenv("ORX_INLINE_DUP_DIV");        // debug: threshold = B / value
-        out->dense_dups = (int64_t)max_dup * (thr ? atoi(thr) : 5) > B;
+        out->dense_dups = (int64_t)max_dup * 5 > B;
     }
     if (staging) {
         // long segments (a row referenced > 16 times in one step) need the hot_reduce_kernel levels between the
@@ -971,13 +946,11 @@ void orx_exact_step_views(orx_ctx* c, const PairPlan& plan, int64_t i, int64_t B
 
 // pairing (kernels_plan.hip): SGD on the float4 dims with >= 2 triplets per wavefront, bucketed plan
 // (ORX_FORCE_FALLBACK bit 4 / ORX_NO_PAIR=1: off)
-bool orx_pairing_wanted(int mode, bool role_bits, int optkind, int dim, int64_t B, int fb);
-int orx_pairing_buffers(orx_ctx* c, int64_t B, int dim, PairPlan* plan);
-static bool pairing_wanted(int mode, bool role_bits, int optkind, int dim, int64_t B, int fb) {
+bool orx_pairing_wanted(int mode, bool role_bits, int optkind, int dim, int64_t B, int fb) {
     return mode == MODE_EXACT && orx_plan_v2(role_bits) && optkind == ORX_SGD && orx_fused_tpw(dim) > 1 && B >= 2 && B <= (1 << 22) && !(fb & 16) &&
            getenv("ORX_NO_PAIR") == nullptr;
 }
-static int pairing_buffers(orx_ctx* c, int64_t B, int dim, PairPlan* plan) {
+int orx_pairing_buffers(orx_ctx* c, int64_t B, int dim, PairPlan* plan) {
     ENSURE(c->d_partner, c->d_partner_cap, (size_t)plan->cap * B * sizeof(int4));
     ENSURE(c->d_pslot, c->d_pslot_cap, (size_t)plan->cap * 2 * plan->list_stride * sizeof(int));
     ENSURE(c->d_ids4, c->d_ids4_cap, (size_t)plan->cap * B * sizeof(int4));
@@ -985,14 +958,45 @@ static int pairing_buffers(orx_ctx* c, int64_t B, int dim, PairPlan* plan) {
     return ORX_OK;
 }
 
-bool orx_pairing_wanted(int mode, bool role_bits, int optkind, int dim, int64_t B, int fb) { return pairing_wanted(mode, role_bits, optkind, dim, B, fb); }
-int orx_pairing_buffers(orx_ctx* c, int64_t B, int dim, PairPlan* plan) { return pairing_buffers(c, B, dim, plan); }
+// ---- host setup that the pairwise and the pointwise step call (api_more.hip) share
+// ORX_FORCE_FALLBACK (debug / tests; read per call): bit 0 = behave as if the tables had >= 2^28 rows (no role bits: every
+// duplicate uses atomics, separate dup_apply launches), bit 1 = no in-launch apply, bit 2 = the censor in separate passes,
+// bit 3 = atomics instead of staging slots, bit 4 = no pairing
+int orx_fallback_bits() {
+    const char* e = getenv("ORX_FORCE_FALLBACK");
+    return e ? atoi(e) : 0;
+}
 
-// TF-2.0 Adam applied lazily (see orx_pairwise_step): float4 dims, role bits available, not hogwild
-static bool lazy_adam_ok(const orx_opt* opt, const orx_table* U, const orx_table* V, int flags) {
-    return opt->kind == ORX_ADAM && !(flags & ORX_HOGWILD) && orx_fused_can_inline_apply(U->dim) &&
-           U->rows < (1LL << 28) && V->rows < (1LL << 28) && U->owned && V->owned &&      // (wrapped memory is read behind our back)
-           getenv("ORX_ADAM_DENSE") == nullptr;
+// epochs are consumed one per step; on wrap-around every table clears its epoch-tagged arrays
+int orx_epochs_reserve(orx_ctx* c, int64_t K, std::initializer_list<orx_table*> tables) {
+    if ((int64_t)c->epoch + K + 16 > 0x7fffffff) { c->epoch = 0; c->epoch_gen += 1; }
+    for (orx_table* t : tables) {
+        if (t->tag_gen != c->epoch_gen) {
+            if (t->ready) ORX_HIP(hipMemsetAsync(t->ready, 0, (size_t)t->rows * sizeof(int), c->stream));
+            if (t->side) ORX_HIP(hipMemsetAsync(t->side, 0, (size_t)t->rows * 2 * sizeof(int), c->stream));
+            t->tag_gen = c->epoch_gen;
+        }
+    }
+    return ORX_OK;
+}
+
+// blocks of a step's launch that apply the duplicated rows of the step before it: one lane group per duplicated row in a single
+// pass for the usual ~0.15*B duplicated rows (the count lives in device memory; surplus blocks exit, a larger count grid-strides)
+int orx_apply_blocks(int64_t B, int D) {
+    return (int)std::min<int64_t>(2048, std::max<int64_t>(16, (B / 4) / (1024 / D) + 1));
+}
+
+// one step of the dense TF-2.0 Adam (MODE_ACCUM): the counter advances, then the decay sweep over every table whole (NULL: skipped)
+int orx_adam_dense_step(orx_ctx* c, orx_opt* opt, std::initializer_list<std::pair<orx_table*, OptSlots>> tables, float* lr_t_out) {
+    opt->t += 1;
+    const double b1 = opt->p0, b2 = opt->p1;
+    const float lr_t = (float)(opt->lr * std::sqrt(1.0 - std::pow(b2, (double)opt->t)) / (1.0 - std::pow(b1, (double)opt->t)));
+    for (const auto& ts : tables) {
+        orx_table* t = ts.first;
+        if (t) CHECK(orx_launch_adam_sweep(c, t->w, ts.second.s0, ts.second.s1, t->gsum, t->rows * t->dim, lr_t, opt->p0, opt->p1, opt->p2));
+    }
+    if (lr_t_out) *lr_t_out = lr_t;
+    return ORX_OK;
 }
 
 // per-triplet weights of K steps next to the ids: a device array as it is, a host array into d_lab (stride B, as stage_triplets
@@ -1016,6 +1020,231 @@ extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
                                   loss_out, l2_out);
 }
 
+// The form a pairwise call takes, from the optimizer, the tables, the call's flags and the fallback bits alone: the step runs it,
+// orx_pairwise_reserve (flags 0, no fallback bits) sizes the buffers for it.
+struct PairForm {
+    bool lazy_adam;
+    int mode;
+    bool role_bits, fused_censor, censor, inline_apply, staging;
+};
+static PairForm pair_form(const orx_opt* opt, const orx_table* U, const orx_table* V, const orx_table* b, int64_t K, int flags, int fb) {
+    PairForm f;
+    const bool hogwild = (flags & ORX_HOGWILD) != 0, want_censor = (flags & ORX_CENSOR) != 0;
+    const bool fast_dim = orx_fused_can_inline_apply(U->dim) != 0, small_tables = U->rows < (1LL << 28) && V->rows < (1LL << 28);
+    // TF-2.0 Adam decays m, v and moves var on EVERY row every step.  On the float4 dims that is applied lazily and
+    // exactly: a row's gradient-free steps are replayed when the row is next touched (or observed: orx_table_sync);
+    // the dense form (every reference accumulates, then three whole-table sweeps per step) remains for the other
+    // cases and behind ORX_ADAM_DENSE=1.  (Wrapped memory is read behind our back: never lazy.)
+    f.lazy_adam = opt->kind == ORX_ADAM && !hogwild && fast_dim && small_tables && U->owned && V->owned && (!b || b->owned) &&
+                  getenv("ORX_ADAM_DENSE") == nullptr;
+    f.mode = (opt->kind == ORX_ADAM && !f.lazy_adam) ? MODE_ACCUM : (hogwild ? MODE_HOGWILD : MODE_EXACT);
+    // rows referenced exactly twice get plain stores into two scratch rows; the role of a reference
+    // travels in bits 30:29 of its id, which needs tables below 2^29 rows
+    f.role_bits = f.mode == MODE_EXACT && small_tables && !(fb & 1);
+    // censor_vec after every step (ucml.py:44-48): fused into the row write-back for the float4 dims in
+    // exact mode; separate passes otherwise
+    f.fused_censor = want_censor && f.mode == MODE_EXACT && fast_dim && !(fb & 4);
+    f.censor = want_censor && !f.fused_censor;
+    // the previous step's duplicated rows are applied by extra blocks of the next step's launch
+    // (no dup_apply launch, no kernel boundary) -- not with a separate censor pass between the steps
+    f.inline_apply = f.role_bits && !f.censor && K > 1 && fast_dim && !(fb & 2);
+    // rows referenced >= 3 times in a step: private staging slots instead of atomics
+    f.staging = f.role_bits && fast_dim && !(fb & 8);
+    return f;
+}
+
+// one pairwise call on its way from orx_pairwise_step_impl through pair_prepare and pair_args to pair_run_chunk
+struct PairCall {
+    orx_ctx* c; orx_opt* opt; orx_table* U; orx_table* V; orx_table* b;      // b NULL: BPR without item biases
+    int kmodel; int64_t K, B;
+    const int32_t* du; const int32_t* dp; const int32_t* dn; const float* dw; int64_t ds;      // the inputs on the device, elements between steps
+    bool want_loss;
+    PairForm f;
+    bool lazy_resume;           // lazy Adam: the tables were lazy under this optimizer already (their step stamps hold)
+    bool nowait;                // no read-back (see plan_stats_poll): the previous call of this shape was quiet
+    int64_t stats_key[5];
+    OptSlots sU, sV, sb;
+    PairPlan plan;
+    PairArgs a;
+};
+
+// tables and optimizer brought to the call's form, the read-back decision, every buffer of the call
+static int pair_prepare(PairCall& q, int fb) {
+    orx_ctx* c = q.c; orx_opt* opt = q.opt; orx_table *U = q.U, *V = q.V, *b = q.b;
+    PairForm& f = q.f;
+    const int64_t K = q.K, B = q.B;
+    // the three tables are lazy together under one optimizer (the item rows and their biases then share step stamps),
+    // or not at all: anything else first brings every row up to date
+    q.lazy_resume = f.lazy_adam && U->lazy == opt && V->lazy == opt && (!b || b->lazy == opt);
+    if (!q.lazy_resume) for (orx_table* t : {U, V, b}) CHECK(orx_table_sync(t));      // (NULL: nothing to do)
+    { orx_table* mine[3] = {U, V, b}; CHECK(orx_opt_isolate(opt, mine, b ? 3 : 2)); }      // (a shared optimizer: see orx_opt_isolate)
+    // (kmodel: a biased and a bias-free call of one shape run different kernels and keep apart; so do a weighted and an unweighted call)
+    const bool want_censor = f.censor || f.fused_censor;
+    const int64_t key[5] = {B, U->rows, V->rows, (int64_t)q.kmodel * 16 + opt->kind + (q.dw ? 1024 : 0), (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (f.inline_apply ? 2 : 0)};
+    CHECK(plan_stats_poll(c));
+    const bool plan_wait = getenv("ORX_PLAN_WAIT") != nullptr;      // (experiments / tests: always read back)
+    q.nowait = f.mode == MODE_EXACT && orx_plan_v2(f.role_bits) && f.staging && !f.censor && opt->kind != ORX_ADAM && !plan_wait &&
+               c->plan_stats.valid && c->plan_stats.quiet;
+    for (int k = 0; k < 5; ++k) { q.stats_key[k] = key[k]; q.nowait = q.nowait && c->plan_stats.key[k] == key[k]; }
+    if (q.nowait) f.staging = false;
+    const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
+    if (f.mode != MODE_HOGWILD) {
+        CHECK(orx_table_scratch(U, f.role_bits)); CHECK(orx_table_scratch(V, f.role_bits));
+        if (b) CHECK(orx_table_scratch(b, f.role_bits));
+    }
+    CHECK(orx_opt_slots(opt, U, &q.sU)); CHECK(orx_opt_slots(opt, V, &q.sV));
+    if (b) CHECK(orx_opt_slots(opt, b, &q.sb));
+
+    PairPlan& plan = q.plan;
+    CHECK(orx_exact_buffers(c, U, V, K, B, f.mode, f.role_bits, f.inline_apply, f.staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
+    // Adam's normalised update amplifies summation-order noise where an element's summed gradient nearly cancels: its
+    // rows referenced >= 3 times always take staging slots (fixed summation order), never fp32 atomics
+    if (opt->kind == ORX_ADAM) plan.min_late = 1;
+    // pairing (kernels_plan.hip): the two triplets of a row referenced exactly twice share a wavefront and exchange gradients there
+    // (SGD only -- Adagrad with pairing measured slower, profiles/r5_adagrad_pairing_ab.txt -- on the float4 dims with >= 2 triplets per wavefront; fb bit 4 / ORX_NO_PAIR=1: off)
+    // The pairing plan costs ~1.5 us per step (records, decisions, the swaps); it pays where a good share of the batch pairs
+    // (uniform ids over tables ~ 10 x the batch: 11 %).  Tables so small that most duplicated rows have three or more references, or
+    // ids so skewed that the hot rows take them, pair little: the plan of a call tells (accepted pairs per step), and pairing then
+    // pauses for 32 calls before it is tried again.  ORX_PAIR_ALWAYS=1: no pause.
+    const bool pair_ok = orx_pairing_wanted(f.mode, f.role_bits, opt->kind, U->dim, B, fb);
+    if (pair_ok && c->pair_pause > 0) c->pair_pause -= 1;
+    else if (pair_ok) CHECK(orx_pairing_buffers(c, B, U->dim, &plan));
+    return ORX_OK;
+}
+
+// the kernels' arguments that hold for every step of the call
+static int pair_args(PairCall& q, float margin, float l2w) {
+    orx_ctx* c = q.c; orx_opt* opt = q.opt; orx_table *U = q.U, *V = q.V, *b = q.b;
+    const PairForm& f = q.f;
+    const int64_t K = q.K, B = q.B;
+    PairArgs& a = q.a;
+    memset(&a, 0, sizeof(a));
+    a.U = U->w; a.V = V->w; a.b = b ? b->w : nullptr;
+    a.gU = U->gsum; a.gV = V->gsum; a.gb = b ? b->gsum : nullptr;
+    if (f.role_bits) { a.gU2 = U->gsum2; a.gV2 = V->gsum2; a.gb2 = b ? b->gsum2 : nullptr; a.role_bits = 1; a.readyU = U->ready; a.readyV = V->ready; }
+    a.aU = q.sU.s0; a.aV = q.sV.s0; a.ab = q.sb.s0;
+    a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
+    a.lr = opt->lr;
+    a.eps = orx_rule_eps(opt);
+    a.margin = margin;
+    a.invB = 1.0f / (float)B;
+    a.l2w = l2w;
+    a.err = c->d_err;
+    // Neither the loss nor the l2 sum is asked for (a training loop between two observations of the loss): the kernels that have a
+    // loss-free form (fused_kernel LOSS = false: exact SGD on the float4 dims, unweighted) skip their partials, and for every kernel
+    // the sums over the partials are not launched -- d_partial and d_loss are read by nothing but the fetch_losses of the call itself
+    a.no_loss = q.want_loss ? 0 : 1;
+    if (f.lazy_adam) {
+        CHECK(orx_lazy_adam_fill(opt, U, V, b, q.sU, q.sV, q.sb, !q.lazy_resume, K, &a));
+        // expected steps between two references of a row = rows / references per step
+        a.long_gap = (U->rows / B > 64 || V->rows / (2 * B) > 64) && getenv("ORX_ADAM_NO_LONGGAP") == nullptr;
+    }
+    CHECK(orx_epochs_reserve(c, K, {U, V}));
+    if (f.fused_censor) { CHECK(orx_table_side(V)); a.censor = 1; a.min_norm = 0.1f; a.sideV = V->side; }
+    return ORX_OK;
+}
+
+// arguments of step i of the chunk that starts at step s0, and its fused launch (with_apply: the launch also applies the duplicated
+// rows of step i - 1)
+static int pair_launch_step(PairCall& q, int64_t s0, int64_t i, bool stage_views, bool with_apply) {
+    orx_ctx* c = q.c;
+    PairArgs& a = q.a;
+    const PairPlan& plan = q.plan;
+    const int64_t s = s0 + i, B = q.B;
+    if (q.f.mode == MODE_EXACT) {       // ids rewritten by the plan (duplicate flag in bit 31)
+        a.uid = c->d_ids2 + (size_t)i * 3 * plan.Bp; a.pid = a.uid + plan.Bp; a.nid = a.uid + 2 * plan.Bp;
+    } else {
+        a.uid = q.du + s * q.ds; a.pid = q.dp + s * q.ds; a.nid = q.dn + s * q.ds;
+    }
+    a.wt = q.dw ? q.dw + s * q.ds : nullptr;      // (the caller's order: the kernel reads it at the triplet's original position)
+    orx_exact_step_views(c, plan, i, B, a.D, stage_views, &a);
+    if (!q.b) { a.stageb = nullptr; a.partb = nullptr; a.prev_stageb = nullptr; }      // (no bias: nothing is staged for it)
+    a.ids4 = plan.pair_tpw > 1 ? c->d_ids4 + (size_t)i * B : nullptr;
+    a.partial = c->d_partial + (size_t)i * plan.nw * 2;
+    a.epoch = ++c->epoch;           // one epoch per step: ready flags and censor side marks are tagged with it
+    if (q.f.lazy_adam) { q.opt->t += 1; a.step_t = (int)q.opt->t; }
+    if (with_apply && i > 0) {
+        a.n_apply_blocks = orx_apply_blocks(B, a.D);
+        a.prev_dlist = c->d_dlist + (size_t)(i - 1) * plan.list_stride; a.prev_dcount = c->d_dcount + (i - 1);
+    } else {
+        a.n_apply_blocks = 0; a.prev_dlist = nullptr; a.prev_dcount = nullptr;
+    }
+    return orx_launch_fused(c, q.kmodel, q.opt->kind, q.f.mode, a);
+}
+
+// steps s0 .. s0 + kc - 1: their plan, their launches, their loss sums
+static int pair_run_chunk(PairCall& q, int64_t s0, int64_t kc) {
+    orx_ctx* c = q.c; orx_opt* opt = q.opt; orx_table *U = q.U, *V = q.V, *b = q.b;
+    const PairForm& f = q.f;
+    PairArgs& a = q.a;
+    const int64_t B = q.B, ds = q.ds;
+    const int32_t *du = q.du + s0 * ds, *dp = q.dp + s0 * ds, *dn = q.dn + s0 * ds;      // step 0 of the chunk
+    const bool exact = f.mode == MODE_EXACT, v2 = exact && orx_plan_v2(f.role_bits);
+    bool first_launched = false;
+    bool tail_done = false;             // the chunk's loss sums left with the last step's duplicate apply
+    ExactChunk ck;                      // (no read-back: in-launch apply where the call allows it, no staging, no tree)
+    if (q.nowait) {
+        CHECK(orx_exact_plan_issue(c, U, V, du, dp, dn, ds, B, B, B, kc, B, f.inline_apply, f.staging, q.plan, 0, nullptr, nullptr));
+        ht_mark("plan_issued");
+    } else if (exact) {
+        // With the bucketed plan the chunk's FIRST fused launch goes out before the host waits for the plan's counters:
+        // step 0 never carries apply blocks, and the kernel built with the staging bookkeeping is right whether or not
+        // any range made a staging plan (references without one carry (-1, 0) and use atomics).
+        const std::function<int()> early = [&]() -> int { first_launched = true; return pair_launch_step(q, s0, 0, f.staging, false); };
+        CHECK(orx_exact_plan_chunk(c, U, V, du, dp, dn, ds, B, B, B, kc, B, f.role_bits, f.inline_apply, f.staging, q.plan, &ck,
+                                   v2 && !f.censor ? &early : nullptr));
+    }
+    if (f.censor) {
+        // one elected reference per distinct row of each of the three id lists, for every step of the chunk
+        ENSURE(c->d_cflag, c->d_cflag_cap, (size_t)3 * kc * B);
+        const int32_t* lists[3] = {du, dp, dn};
+        const int64_t rows[3] = {U->rows, V->rows, V->rows};
+        for (int l = 0; l < 3; ++l) {
+            DedupArgs d;
+            memset(&d, 0, sizeof(d));
+            d.uid = lists[l]; d.pid = lists[l]; d.nid = lists[l]; d.id_stride = ds;
+            d.dflag = c->d_cflag + (size_t)l * kc * B; d.flag_stride = B;
+            d.nU = B; d.NU = rows[l]; d.nbu = orx_dedup_buckets(rows[l]); d.first_only = 1;
+            CHECK(orx_launch_dedup(c, d, kc));
+        }
+    }
+    const ReduceArgs r = {c->d_partial, c->d_loss + 2 * s0, q.plan.nw};
+    // may the duplicated rows of a step be applied by the NEXT step's launch?
+    const bool inl = f.inline_apply && !ck.hot && !ck.dense_dups;
+    for (int64_t i = 0; i < kc; ++i) {
+        const bool defer = exact && inl && i < kc - 1;      // step i's duplicated rows wait for launch i + 1
+        if (!(i == 0 && first_launched)) CHECK(pair_launch_step(q, s0, i, ck.use_stage, i > 0 && inl));
+        for (int l = 0; l < ck.tree_levels; ++l) CHECK(orx_launch_hot_reduce(c, a, l));
+        if (exact && !defer) {
+            // the chunk's last step: its duplicated rows and the chunk's loss sums leave in ONE launch where that is possible
+            if (i == kc - 1 && !f.censor && !f.lazy_adam && q.want_loss) {
+                int rc = ORX_OK;
+                if (orx_launch_tail(c, opt->kind, a, r, kc, &rc)) { CHECK(rc); tail_done = true; }
+            }
+            if (!tail_done) CHECK(orx_launch_dup_apply(c, opt->kind, a));
+        }
+        // Adam, dense form: the decay sweep of TF 2.0 over the whole tables
+        if (f.mode == MODE_ACCUM) CHECK(orx_adam_dense_step(c, opt, {{U, q.sU}, {V, q.sV}, {b, q.sb}}, nullptr));
+        if (f.censor) {                   // ucml.py:44-48: users and pos items (two tables), then neg items
+            const unsigned char* fu = c->d_cflag + (size_t)i * B;
+            const unsigned char* fp = c->d_cflag + (size_t)(kc + i) * B;
+            const unsigned char* fn = c->d_cflag + (size_t)(2 * kc + i) * B;
+            CHECK(orx_launch_censor2(c, U->w, fu, U->rows, du + i * ds, B, V->w, fp, V->rows, dp + i * ds, B, U->dim, 0.1f));
+            CHECK(orx_launch_censor2(c, V->w, fn, V->rows, dn + i * ds, B, nullptr, nullptr, 0, nullptr, 0, U->dim, 0.1f));
+        }
+    }
+    if (!tail_done && q.want_loss) CHECK(orx_launch_loss_reduce(c, r, kc));
+    if (v2) {
+        // what this chunk's plan counted: left behind the last launch for the next call (no read-back), or seen already
+        if (q.nowait) CHECK(plan_stats_leave(c, kc, B, q.plan.pair_tpw > 1, q.stats_key));
+        else {
+            c->plan_stats.valid = true; c->plan_stats.quiet = ck.quiet; c->stats_pending = false;
+            for (int k = 0; k < 5; ++k) c->plan_stats.key[k] = q.stats_key[k];
+        }
+    }
+    return ORX_OK;
+}
+
 // The full pairwise step behind orx_pairwise_step (weight NULL, l2w 0 or 1) and orx_pairwise_step_weighted: `weight` lives where the
 // ids live and has their stride; l2w is the coefficient of l2_loss in the objective.  A weighted call runs the WT instantiations of the fused
 // kernels (kernels_pairwise_weighted.hip) and keeps plan statistics of its own.
@@ -1036,289 +1265,19 @@ int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, or
         for (int64_t s = 0; s < K; ++s) { if (loss_out) loss_out[s] = model == ORX_BPR ? NAN : 0.f; if (l2_out) l2_out[s] = 0.f; }
         return ORX_OK;
     }
-    const int32_t *du, *dp, *dn; int64_t ds;
-    CHECK(stage_triplets(c, uid, pid, nid, K, B, id_stride, flags, &du, &dp, &dn, &ds));
-    const float* dw;
-    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &dw));
-
-    const bool hogwild = (flags & ORX_HOGWILD) != 0;
-    ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pairwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
-    // TF-2.0 Adam decays m, v and moves var on EVERY row every step.  On the float4 dims that is applied lazily and
-    // exactly: a row's gradient-free steps are replayed when the row is next touched (or observed: orx_table_sync);
-    // the dense form (every reference accumulates, then three whole-table sweeps per step) remains for the other
-    // cases and behind ORX_ADAM_DENSE=1.
-    // b == NULL: BPR without item biases -- the kernels of MODEL_BPR_NB, every use of the bias table below is skipped
-    const int kmodel = b ? model : MODEL_BPR_NB;
-    const bool lazy_adam = lazy_adam_ok(opt, U, V, flags) && (!b || b->owned);
-    const int mode = (opt->kind == ORX_ADAM && !lazy_adam) ? MODE_ACCUM : (hogwild ? MODE_HOGWILD : MODE_EXACT);
-    // the three tables are lazy together under one optimizer (the item rows and their biases then share step stamps),
-    // or not at all: anything else first brings every row up to date
-    const bool lazy_resume = lazy_adam && U->lazy == opt && V->lazy == opt && (!b || b->lazy == opt);
-    if (!lazy_resume) for (orx_table* t : {U, V, b}) CHECK(orx_table_sync(t));      // (NULL: nothing to do)
-    { orx_table* mine[3] = {U, V, b}; CHECK(orx_opt_isolate(opt, mine, b ? 3 : 2)); }      // (a shared optimizer: see orx_opt_isolate)
-    // rows referenced exactly twice get plain stores into two scratch rows; the role of a reference
-    // travels in bits 30:29 of its id, which needs tables below 2^29 rows
-    // ORX_FORCE_FALLBACK (debug / tests): bit 0 = behave as if the tables had >= 2^28 rows (no role bits: every
-    // duplicate uses atomics, separate dup_apply launches), bit 1 = no in-launch apply
-    const char* fb_env = getenv("ORX_FORCE_FALLBACK");
-    const int fb = fb_env ? atoi(fb_env) : 0;
-    const bool role_bits = mode == MODE_EXACT && U->rows < (1LL << 28) && V->rows < (1LL << 28) && !(fb & 1);
-    // censor_vec after every step (ucml.py:44-48): fused into the row write-back for the float4 dims in
-    // exact mode (fb bit 2 forces the separate passes); separate passes otherwise
-    const bool want_censor = (flags & ORX_CENSOR) != 0;
-    const bool fused_censor = want_censor && mode == MODE_EXACT && orx_fused_can_inline_apply(U->dim) && !(fb & 4);
-    const bool censor = want_censor && !fused_censor;
-    // the previous step's duplicated rows are applied by extra blocks of the next step's launch
-    // (no dup_apply launch, no kernel boundary) -- not with a separate censor pass between the steps
-    const bool inline_apply = role_bits && !censor && K > 1 && orx_fused_can_inline_apply(U->dim) && !(fb & 2);
-    // rows referenced >= 3 times in a step: private staging slots instead of atomics (fb bit 3: atomics)
-    bool staging = role_bits && orx_fused_can_inline_apply(U->dim) && !(fb & 8);
-    // no read-back (see plan_stats_poll): the previous call of this shape was quiet
-    // (kmodel: a biased and a bias-free call of one shape run different kernels and keep apart; so do a weighted and an unweighted call)
-    const int64_t stats_key[5] = {B, U->rows, V->rows, (int64_t)kmodel * 16 + opt->kind + (dw ? 1024 : 0), (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (inline_apply ? 2 : 0)};
-    CHECK(plan_stats_poll(c));
-    const bool plan_wait = getenv("ORX_PLAN_WAIT") != nullptr || getenv("ORX_PLAN_PIPE") != nullptr;      // (experiments / tests: always read back)
-    bool nowait = mode == MODE_EXACT && orx_plan_v2(role_bits) && staging && !censor && opt->kind != ORX_ADAM && !plan_wait &&
-                  c->plan_stats.valid && c->plan_stats.quiet;
-    for (int k = 0; k < 5 && nowait; ++k) nowait = c->plan_stats.key[k] == stats_key[k];
-    if (nowait) staging = false;
-    const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-    if (mode != MODE_HOGWILD) {
-        CHECK(orx_table_scratch(U, role_bits)); CHECK(orx_table_scratch(V, role_bits));
-        if (b) CHECK(orx_table_scratch(b, role_bits));
-    }
-    OptSlots sU, sV, sb;
-    CHECK(orx_opt_slots(opt, U, &sU)); CHECK(orx_opt_slots(opt, V, &sV));
-    if (b) CHECK(orx_opt_slots(opt, b, &sb));
-
-    PairPlan plan;
-    CHECK(orx_exact_buffers(c, U, V, K, B, mode, role_bits, inline_apply, staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
-    const int nw = plan.nw;
-    const int64_t chunk = plan.chunk, list_stride = plan.list_stride, Bp = plan.Bp;
-    // Adam's normalised update amplifies summation-order noise where an element's summed gradient nearly cancels: its
-    // rows referenced >= 3 times always take staging slots (fixed summation order), never fp32 atomics
-    if (opt->kind == ORX_ADAM) plan.min_late = 1;
-    // pairing (kernels_plan.hip): the two triplets of a row referenced exactly twice share a wavefront and exchange gradients there
-    // (SGD only -- Adagrad with pairing measured slower, profiles/r5_adagrad_pairing_ab.txt -- on the float4 dims with >= 2 triplets per wavefront; fb bit 4 / ORX_NO_PAIR=1: off)
-    // The pairing plan costs ~1.5 us per step (records, decisions, the swaps); it pays where a good share of the batch pairs
-    // (uniform ids over tables ~ 10 x the batch: 11 %).  Tables so small that most duplicated rows have three or more references, or
-    // ids so skewed that the hot rows take them, pair little: the plan of a call tells (accepted pairs per step), and pairing then
-    // pauses for 32 calls before it is tried again.  ORX_PAIR_ALWAYS=1: no pause.
-    const bool pair_ok = pairing_wanted(mode, role_bits, opt->kind, U->dim, B, fb);
-    if (pair_ok && c->pair_pause > 0) c->pair_pause -= 1;
-    else if (pair_ok) CHECK(pairing_buffers(c, B, U->dim, &plan));
-
-    PairArgs a;
-    memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b ? b->w : nullptr;
-    a.gU = U->gsum; a.gV = V->gsum; a.gb = b ? b->gsum : nullptr;
-    if (role_bits) { a.gU2 = U->gsum2; a.gV2 = V->gsum2; a.gb2 = b ? b->gsum2 : nullptr; a.role_bits = 1; a.readyU = U->ready; a.readyV = V->ready; }
-    a.aU = sU.s0; a.aV = sV.s0; a.ab = sb.s0;
-    a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
-    a.lr = opt->lr;
-    a.eps = orx_rule_eps(opt);
-    a.margin = margin;
-    a.invB = 1.0f / (float)B;
-    a.l2w = l2w;
-    a.err = c->d_err;
-    // Neither the loss nor the l2 sum is asked for (a training loop between two observations of the loss): the kernels that have a
-    // loss-free form (fused_kernel LOSS = false: exact SGD on the float4 dims, unweighted) skip their partials, and for every kernel
-    // the sums over the partials are not launched -- d_partial and d_loss are read by nothing but the fetch_losses of the call itself
-    const bool want_loss = loss_out != nullptr || l2_out != nullptr;
-    a.no_loss = want_loss ? 0 : 1;
-    if (lazy_adam) {
-        a.a2U = sU.s1; a.a2V = sV.s1; a.a2b = sb.s1;
-        CHECK(orx_opt_last(opt, U, !lazy_resume, &a.lastU)); CHECK(orx_opt_last(opt, V, !lazy_resume, &a.lastV));
-        if (b) CHECK(orx_opt_last(opt, b, !lazy_resume, &a.lastb));
-        CHECK(orx_adam_lrt(opt, opt->t + K));
-        a.lrt = opt->d_lrt; a.b1 = opt->p0; a.b2 = opt->p1; a.eps = opt->p2;
-        if (orx_adam_cf_ok(opt) && opt->d_lrv != nullptr) {      // closed-form replay (fused_kernel LONGGAP = 2)
-            a.lrv = reinterpret_cast<const float4*>(opt->d_lrv);
-            a.cf_delta = (float)(-0.5 * std::log((double)opt->p1)); a.cf_lb1 = (float)std::log2((double)opt->p0); a.cf_lb2 = (float)std::log2((double)opt->p1);
-        }
-        a.newton = (1.0f - sqrtf(opt->p1)) <= 1e-3f && getenv("ORX_ADAM_NO_NEWTON") == nullptr;
-        // expected steps between two references of a row = rows / references per step
-        a.long_gap = (U->rows / B > 64 || V->rows / (2 * B) > 64) && getenv("ORX_ADAM_NO_LONGGAP") == nullptr;
-        U->lazy = opt; V->lazy = opt;
-        if (b) b->lazy = opt;
-    }
-    // epochs are consumed one per step; on wrap-around every table clears its epoch-tagged arrays
-    if ((int64_t)c->epoch + K + 16 > 0x7fffffff) { c->epoch = 0; c->epoch_gen += 1; }
-    for (orx_table* t : {U, V}) {
-        if (t->tag_gen != c->epoch_gen) {
-            if (t->ready) ORX_HIP(hipMemsetAsync(t->ready, 0, (size_t)t->rows * sizeof(int), c->stream));
-            if (t->side) ORX_HIP(hipMemsetAsync(t->side, 0, (size_t)t->rows * 2 * sizeof(int), c->stream));
-            t->tag_gen = c->epoch_gen;
-        }
-    }
-    if (fused_censor) { CHECK(orx_table_side(V)); a.censor = 1; a.min_norm = 0.1f; a.sideV = V->side; }
-
+    PairCall q;
+    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.K = K; q.B = B;
+    q.kmodel = b ? model : MODEL_BPR_NB;        // b == NULL: the kernels of MODEL_BPR_NB, every use of the bias table is skipped
+    q.want_loss = loss_out != nullptr || l2_out != nullptr;
+    CHECK(stage_triplets(c, uid, pid, nid, K, B, id_stride, flags, &q.du, &q.dp, &q.dn, &q.ds));
+    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &q.dw));
+    ORX_ARG(!(flags & ORX_HOGWILD) || opt->kind != ORX_MOMENTUM, "orx_pairwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
+    const int fb = orx_fallback_bits();
+    q.f = pair_form(opt, U, V, b, K, flags, fb);
+    CHECK(pair_prepare(q, fb));
+    CHECK(pair_args(q, margin, l2w));
     ht_mark("setup");
-    for (int64_t s0 = 0; s0 < K; s0 += chunk) {
-        const int64_t kc = (K - s0 < chunk) ? (K - s0) : chunk;
-        // arguments of step i of the chunk, and its fused launch
-        auto launch_step = [&](int64_t i, bool stage_views, bool with_apply) -> int {
-            const int64_t s = s0 + i;
-            if (mode == MODE_EXACT) {       // ids rewritten by the plan (duplicate flag in bit 31)
-                a.uid = c->d_ids2 + (size_t)i * 3 * Bp; a.pid = a.uid + Bp; a.nid = a.uid + 2 * Bp;
-            } else {
-                a.uid = du + s * ds; a.pid = dp + s * ds; a.nid = dn + s * ds;
-            }
-            a.wt = dw ? dw + s * ds : nullptr;      // (the caller's order: the kernel reads it at the triplet's original position)
-            orx_exact_step_views(c, plan, i, B, U->dim, stage_views, &a);
-            if (!b) { a.stageb = nullptr; a.partb = nullptr; a.prev_stageb = nullptr; }      // (no bias: nothing is staged for it)
-            a.ids4 = plan.pair_tpw > 1 ? c->d_ids4 + (size_t)i * B : nullptr;
-            a.partial = c->d_partial + (size_t)i * nw * 2;
-            a.epoch = ++c->epoch;           // one epoch per step: ready flags and censor side marks are tagged with it
-            if (lazy_adam) { opt->t += 1; a.step_t = (int)opt->t; }
-            if (with_apply && i > 0) {    // this launch also applies the duplicated rows of step i-1
-                // one lane group per duplicated row in a single pass for the usual ~0.15*B duplicated rows
-                // (the count lives in device memory; surplus blocks exit, a larger count grid-strides)
-                a.n_apply_blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(16, (B / 4) / (1024 / U->dim) + 1));
-                a.prev_dlist = c->d_dlist + (size_t)(i - 1) * list_stride; a.prev_dcount = c->d_dcount + (i - 1);
-            } else {
-                a.n_apply_blocks = 0; a.prev_dlist = nullptr; a.prev_dcount = nullptr;
-            }
-            return orx_launch_fused(c, kmodel, opt->kind, mode, a);
-        };
-        bool first_launched = false;
-        bool tail_done = false;             // the chunk's loss sums left with the last step's duplicate apply
-        // ---- the plan of the chunk, optionally in PIECES (bucketed plan, in-launch apply): piece 0 (6 steps) is planned on the step
-        // stream, every later piece (4x the previous one) on a second stream while the steps of the piece before it run -- the fused
-        // launches of a K-step call then start ~45 us after the call instead of after the plan of all K steps (110 us at K = 20,
-        // 620 us at K = 200).  The pieces share the chunk's plan arrays, so the in-launch apply runs across their boundaries.
-        std::vector<int64_t> pc_lo, pc_hi;                   // piece j = steps [pc_lo[j], pc_hi[j]) of the chunk
-        std::vector<ExactChunk> pck;
-        const bool v2 = mode == MODE_EXACT && orx_plan_v2(role_bits);
-        // MEASURED AND LEFT OFF (profiles/r3_plan_pipeline.txt; ORX_PLAN_PIPE=1 turns it on): what runs beside the fused kernels takes
-        // from them what it gets.  K = 20: 41.5 / 40.5 us per step with the pipeline against 39.2 without (fused launch 32.5 against
-        // 30.8 us); K = 40: 37.9 / 36.9; K = 64: 37.2 / 36.3; K = 200: 34.3 / 33.7 -- the same verdict as round 2's chunk-level overlap.
-        const bool pipe = v2 && inline_apply && !censor && kc > 8 && getenv("ORX_PLAN_PIPE") != nullptr;
-        if (mode == MODE_EXACT) {
-            if (pipe) {
-                for (int64_t lo = 0, sz = 6; lo < kc; lo += sz, sz *= 4) {
-                    int64_t hi = std::min<int64_t>(kc, lo + sz);
-                    if (kc - hi < 3) hi = kc;                // (no 1-2 step tail piece)
-                    pc_lo.push_back(lo); pc_hi.push_back(hi);
-                    if (hi == kc) break;
-                }
-            } else {
-                pc_lo.push_back(0); pc_hi.push_back(kc);
-            }
-            pck.resize(pc_lo.size());
-            // With the bucketed plan the chunk's FIRST fused launch goes out before the host waits for the plan's counters:
-            // step 0 never carries apply blocks, and the kernel built with the staging bookkeeping is right whether or not
-            // any range made a staging plan (references without one carry (-1, 0) and use atomics).
-            const std::function<int()> early = [&]() -> int { first_launched = true; return launch_step(0, staging, false); };
-            const bool can_early = v2 && !censor && getenv("ORX_PLAN_NO_EARLY") == nullptr;
-            if (nowait) {
-                CHECK(orx_exact_plan_issue(c, U, V, du + s0 * ds, dp + s0 * ds, dn + s0 * ds, ds, B, B, B, kc, B, inline_apply, staging, plan, 0, nullptr, nullptr));
-                pck[0] = ExactChunk();                       // (in-launch apply where the call allows it, no staging, no tree)
-                ht_mark("plan_issued");
-            } else if (pipe) {
-                CHECK(orx_exact_plan_issue(c, U, V, du + s0 * ds, dp + s0 * ds, dn + s0 * ds, ds, B, B, B, pc_hi[0], B, inline_apply, staging, plan, 0,
-                                           c->plan_ev, can_early ? &early : nullptr));
-                CHECK(orx_exact_plan_finish(c, pc_hi[0], B, inline_apply, staging, 0, c->plan_ev, &pck[0], plan.pair_tpw > 1));
-            } else {
-                CHECK(orx_exact_plan_chunk(c, U, V, du + s0 * ds, dp + s0 * ds, dn + s0 * ds, ds, B, B, B, kc, B, role_bits, inline_apply, staging,
-                                           plan, &pck[0], can_early ? &early : nullptr));
-            }
-        }
-        // enqueue the plan of piece j (>= 1) on the plan stream; it starts once the device has passed `after`
-        auto issue_piece = [&](size_t j, hipEvent_t after) -> int {
-            hipStream_t main_stream = c->stream;
-            ORX_HIP(hipStreamWaitEvent(c->plan_stream, after, 0));
-            c->stream = c->plan_stream;
-            const int64_t lo = pc_lo[j], n = pc_hi[j] - lo;
-            const int rc = orx_exact_plan_issue(c, U, V, du + (s0 + lo) * ds, dp + (s0 + lo) * ds, dn + (s0 + lo) * ds, ds, B, B, B, n, B,
-                                                inline_apply, staging, plan, lo, c->pipe_cnt[j & 1], nullptr);
-            if (rc == ORX_OK) { const hipError_t e = hipEventRecord(c->pipe_done[j & 1], c->plan_stream); if (e != hipSuccess) { c->stream = main_stream; ORX_HIP(e); } }
-            c->stream = main_stream;
-            return rc;
-        };
-        if (censor) {
-            // one elected reference per distinct row of each of the three id lists, for every step of the chunk
-            ENSURE(c->d_cflag, c->d_cflag_cap, (size_t)3 * kc * B);
-            const int32_t* lists[3] = {du + s0 * ds, dp + s0 * ds, dn + s0 * ds};
-            const int64_t rows[3] = {U->rows, V->rows, V->rows};
-            for (int l = 0; l < 3; ++l) {
-                DedupArgs d;
-                memset(&d, 0, sizeof(d));
-                d.uid = lists[l]; d.pid = lists[l]; d.nid = lists[l]; d.id_stride = ds;
-                d.dflag = c->d_cflag + (size_t)l * kc * B; d.flag_stride = B;
-                d.nU = B; d.NU = rows[l]; d.nbu = orx_dedup_buckets(rows[l]); d.first_only = 1;
-                CHECK(orx_launch_dedup(c, d, kc));
-            }
-        }
-        // per piece: may the duplicated rows of its steps be applied by the NEXT step's launch?
-        auto piece_inl = [&](size_t j) { return inline_apply && !pck[j].hot && !pck[j].dense_dups; };
-        const size_t npc = mode == MODE_EXACT ? pc_lo.size() : 1;
-        for (size_t j = 0; j < npc; ++j) {
-            const int64_t lo = mode == MODE_EXACT ? pc_lo[j] : 0, hi = mode == MODE_EXACT ? pc_hi[j] : kc;
-            // (piece 1 may start behind piece 0's counters: plan_ev sits behind its plan kernels, ahead of step 0 and the urgent marks)
-            if (j + 1 < npc) CHECK(issue_piece(j + 1, j == 0 ? c->plan_ev : c->pipe_done[j & 1]));
-            if (j > 0) ORX_HIP(hipStreamWaitEvent(c->stream, c->pipe_done[j & 1], 0));      // the step stream takes up this piece's steps behind its plan
-            const bool inl_j = mode == MODE_EXACT && piece_inl(j);
-            const int tree_levels = mode == MODE_EXACT ? pck[j].tree_levels : 0;
-            for (int64_t i = lo; i < hi; ++i) {
-                const int64_t s = s0 + i;
-                bool inl_next = inl_j;                         // is step i + 1 launched with apply blocks for step i's rows?
-                if (i == hi - 1 && j + 1 < npc) {
-                    // the last step of a piece: the next piece's counters decide (its plan has had the whole piece to finish)
-                    CHECK(orx_exact_plan_finish(c, pc_hi[j + 1] - pc_lo[j + 1], B, inline_apply, staging, pc_lo[j + 1], c->pipe_cnt[(j + 1) & 1], &pck[j + 1], plan.pair_tpw > 1));
-                    inl_next = inl_j && piece_inl(j + 1);
-                }
-                const bool defer = mode == MODE_EXACT && inl_next && i < kc - 1;      // step i's duplicated rows wait for launch i + 1
-                if (!(i == 0 && first_launched)) {
-                    const bool prev_deferred = i > 0 && (i > lo ? inl_j : (j > 0 && piece_inl(j - 1) && inl_j));
-                    // (a step reads the staging segments of the step before it: the views cover both pieces' plans)
-                    const bool sv = mode == MODE_EXACT && (pck[j].use_stage || (i == lo && j > 0 && pck[j - 1].use_stage));
-                    CHECK(launch_step(i, sv, prev_deferred));
-                }
-                for (int l = 0; l < tree_levels; ++l) CHECK(orx_launch_hot_reduce(c, a, l));
-                if (mode == MODE_EXACT && !defer) {
-                    // the chunk's last step: its duplicated rows and the chunk's loss sums leave in ONE launch where that is possible
-                    if (i == kc - 1 && !censor && !lazy_adam && want_loss) {
-                        ReduceArgs r;
-                        r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
-                        int rc = ORX_OK;
-                        if (orx_launch_tail(c, opt->kind, a, r, kc, &rc)) { CHECK(rc); tail_done = true; }
-                    }
-                    if (!tail_done) CHECK(orx_launch_dup_apply(c, opt->kind, a));
-                }
-                if (mode == MODE_ACCUM) {   // Adam: dense-decay sweep of TF 2.0 over the whole tables
-                    opt->t += 1;
-                    const double b1 = opt->p0, b2 = opt->p1;
-                    const float lr_t = (float)(opt->lr * std::sqrt(1.0 - std::pow(b2, (double)opt->t)) / (1.0 - std::pow(b1, (double)opt->t)));
-                    CHECK(orx_launch_adam_sweep(c, U->w, sU.s0, sU.s1, U->gsum, U->rows * U->dim, lr_t, opt->p0, opt->p1, opt->p2));
-                    CHECK(orx_launch_adam_sweep(c, V->w, sV.s0, sV.s1, V->gsum, V->rows * V->dim, lr_t, opt->p0, opt->p1, opt->p2));
-                    if (b) CHECK(orx_launch_adam_sweep(c, b->w, sb.s0, sb.s1, b->gsum, b->rows, lr_t, opt->p0, opt->p1, opt->p2));
-                }
-                if (censor) {                   // ucml.py:44-48: users and pos items (two tables), then neg items
-                    const unsigned char* fu = c->d_cflag + (size_t)i * B;
-                    const unsigned char* fp = c->d_cflag + (size_t)(kc + i) * B;
-                    const unsigned char* fn = c->d_cflag + (size_t)(2 * kc + i) * B;
-                    CHECK(orx_launch_censor2(c, U->w, fu, U->rows, du + s * ds, B, V->w, fp, V->rows, dp + s * ds, B, U->dim, 0.1f));
-                    CHECK(orx_launch_censor2(c, V->w, fn, V->rows, dn + s * ds, B, nullptr, nullptr, 0, nullptr, 0, U->dim, 0.1f));
-                }
-            }
-        }
-        if (!tail_done && want_loss) {
-            ReduceArgs r;
-            r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
-            CHECK(orx_launch_loss_reduce(c, r, kc));
-        }
-        if (mode == MODE_EXACT && orx_plan_v2(role_bits)) {
-            // what this chunk's plan counted: left behind the last launch for the next call (no read-back), or seen already
-            if (nowait) CHECK(plan_stats_leave(c, kc, B, plan.pair_tpw > 1, stats_key));
-            else {
-                bool quiet = true;
-                for (const ExactChunk& ck : pck) quiet = quiet && ck.quiet;
-                c->plan_stats.valid = true; c->plan_stats.quiet = quiet; c->stats_pending = false;
-                for (int k = 0; k < 5; ++k) c->plan_stats.key[k] = stats_key[k];
-            }
-        }
-    }
+    for (int64_t s0 = 0; s0 < K; s0 += q.plan.chunk) CHECK(pair_run_chunk(q, s0, std::min<int64_t>(K - s0, q.plan.chunk)));
     ht_mark("launched");
     CHECK(fetch_losses(c, K, loss_out, l2_out));
     ht_mark("losses"); ht_dump();
@@ -1331,19 +1290,16 @@ extern "C" int orx_pairwise_reserve(orx_ctx* c, orx_opt* opt, orx_table* U, orx_
     CHECK(check_pair_tables(U, V, b));
     ORX_ARG(K > 0 && B > 0, "orx_pairwise_reserve: K and B must be positive");
     ORX_HIP(hipSetDevice(c->device));
-    const int mode = (opt->kind == ORX_ADAM && !lazy_adam_ok(opt, U, V, 0)) ? MODE_ACCUM : MODE_EXACT;
-    const bool role_bits = mode == MODE_EXACT && U->rows < (1LL << 28) && V->rows < (1LL << 28);
-    const bool inline_apply = role_bits && K > 1 && orx_fused_can_inline_apply(U->dim);
-    const bool staging = role_bits && orx_fused_can_inline_apply(U->dim);
+    const PairForm f = pair_form(opt, U, V, b, K, 0, 0);
     const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-    CHECK(orx_table_scratch(U, role_bits)); CHECK(orx_table_scratch(V, role_bits));
-    if (b) CHECK(orx_table_scratch(b, role_bits));
+    CHECK(orx_table_scratch(U, f.role_bits)); CHECK(orx_table_scratch(V, f.role_bits));
+    if (b) CHECK(orx_table_scratch(b, f.role_bits));
     OptSlots s;
     CHECK(orx_opt_slots(opt, U, &s)); CHECK(orx_opt_slots(opt, V, &s));
     if (b) CHECK(orx_opt_slots(opt, b, &s));
     PairPlan plan;
-    CHECK(orx_exact_buffers(c, U, V, K, B, mode, role_bits, inline_apply, staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
-    if (pairing_wanted(mode, role_bits, opt->kind, U->dim, B, 0)) CHECK(pairing_buffers(c, B, U->dim, &plan));
+    CHECK(orx_exact_buffers(c, U, V, K, B, f.mode, f.role_bits, f.inline_apply, f.staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
+    if (orx_pairing_wanted(f.mode, f.role_bits, opt->kind, U->dim, B, 0)) CHECK(orx_pairing_buffers(c, B, U->dim, &plan));
     ORX_HIP(hipStreamSynchronize(c->stream));
     return ORX_OK;
 }

@@ -7,17 +7,6 @@
 
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-#define ENSURE(ptr, cap, bytes)                                                        \
-    do {                                                                               \
-        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 static constexpr size_t ORX_CAND_SCRATCH = (size_t)512 << 20;       // default budget of one batch of users
 static constexpr int64_t ORX_CAND_MAX_DENSE_BATCH = 32768;          // (users are a grid dimension of the scorer)
 static constexpr int ORX_CAND_NAT = 16;

@@ -1,12 +1,6 @@
 // C-ABI entry point of dynamic negative sampling: orx_sampler_pairwise_hard (kernels_hardneg.hip has the semantics and the design).
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 extern "C" int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* user, orx_table* item, orx_table* bias,
                                          uint64_t seed, int64_t first, int64_t n, int32_t n_cand,
                                          int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev,

@@ -6,17 +6,6 @@
 
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-#define ENSURE(ptr, cap, bytes)                                                        \
-    do {                                                                               \
-        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 // ------------------------------------------------------------ pointwise step ---
 static int check_point_tables(int model, orx_table* U, orx_table* V, orx_table* b, orx_table* w) {
     ORX_ARG(model == ORX_GMF || model == ORX_WRMF, "pointwise: unknown model %d", model);
@@ -68,8 +57,7 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
     CHECK(stage_point(c, uid, iid, label, K, B, id_stride, flags, &du, &di, &dl, &ds));
     const bool hogwild = (flags & ORX_HOGWILD) != 0;
     ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pointwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
-    const char* fb_env = getenv("ORX_FORCE_FALLBACK");
-    const int fb = fb_env ? atoi(fb_env) : 0;
+    const int fb = orx_fallback_bits();
     // TF-2.0 Adam applied lazily, as in orx_pairwise_step: float4 dims with the exact-step plan; the
     // Dense(1) kernel of GMF is a dense parameter and takes the plain rule.  Otherwise every reference accumulates
     // and the tables are swept whole.
@@ -105,7 +93,6 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
     if (role_bits) {
         CHECK(orx_table_scratch(U, true)); CHECK(orx_table_scratch(V, true)); CHECK(orx_table_scratch(b, true));
         const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-        const size_t part_cap = c->d_partial_cap;       // orx_exact_buffers sizes d_partial for its own use: keep ours
         CHECK(orx_exact_buffers(c, U, V, K, B, mode, true, inline_apply, staging, nb_total, nslot, &plan));
         if (opt->kind == ORX_ADAM) plan.min_late = 1;      // Adam: fixed summation order for every row referenced >= 3 times (api.hip)
         // pairing (round 6): as in orx_pairwise_step -- SGD, float4 dims with >= 2 samples per wavefront, paused for 32 calls when a plan
@@ -114,8 +101,7 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
             if (c->pair_pause > 0) c->pair_pause -= 1;
             else CHECK(orx_pairing_buffers(c, B, D, &plan));
         }
-        (void)part_cap;
-        ENSURE(c->d_partial, c->d_partial_cap, (size_t)K * nslot * 2 * sizeof(float));
+        ENSURE(c->d_partial, c->d_partial_cap, (size_t)K * nslot * 2 * sizeof(float));      // (orx_exact_buffers sized it for its own shape: a chunk)
     } else if (mode == MODE_EXACT) {
         ENSURE(c->d_dflag, c->d_dflag_cap, (size_t)K * 2 * B);
         ENSURE(c->d_dlist, c->d_dlist_cap, (size_t)K * list_stride * sizeof(uint32_t));
@@ -155,29 +141,13 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
     memset(&pa, 0, sizeof(pa));
     pa.U = U->w; pa.V = V->w; pa.b = b->w; pa.gU = U->gsum; pa.gV = V->gsum; pa.gb = b->gsum;
     if (role_bits) { pa.gU2 = U->gsum2; pa.gV2 = V->gsum2; pa.gb2 = b->gsum2; pa.role_bits = 1; pa.readyU = U->ready; pa.readyV = V->ready; }
-    // epochs tag the ready flags: one per step; on wrap-around the tables clear theirs (as orx_pairwise_step does)
-    if ((int64_t)c->epoch + K + 16 > 0x7fffffff) { c->epoch = 0; c->epoch_gen += 1; }
-    for (orx_table* t : {U, V}) {
-        if (t->tag_gen != c->epoch_gen) {
-            if (t->ready) ORX_HIP(hipMemsetAsync(t->ready, 0, (size_t)t->rows * sizeof(int), c->stream));
-            if (t->side) ORX_HIP(hipMemsetAsync(t->side, 0, (size_t)t->rows * 2 * sizeof(int), c->stream));
-            t->tag_gen = c->epoch_gen;
-        }
-    }
+    CHECK(orx_epochs_reserve(c, K, {U, V}));      // epochs tag the ready flags: one per step
     pa.aU = sU.s0; pa.aV = sV.s0; pa.ab = sb.s0; pa.B = B; pa.D = D; pa.lr = a.lr; pa.eps = a.eps;
     if (lazy_adam) {
-        a.a2U = pa.a2U = sU.s1; a.a2V = pa.a2V = sV.s1; a.a2b = pa.a2b = sb.s1;
-        CHECK(orx_opt_last(opt, U, !lazy_resume, &a.lastU)); CHECK(orx_opt_last(opt, V, !lazy_resume, &a.lastV));
-        CHECK(orx_opt_last(opt, b, !lazy_resume, &a.lastb));
-        pa.lastU = a.lastU; pa.lastV = a.lastV; pa.lastb = a.lastb;
-        CHECK(orx_adam_lrt(opt, opt->t + K));
-        a.lrt = pa.lrt = opt->d_lrt; a.b1 = pa.b1 = opt->p0; a.b2 = pa.b2 = opt->p1; a.eps = pa.eps = opt->p2;
-        if (orx_adam_cf_ok(opt) && opt->d_lrv != nullptr) {
-            a.lrv = reinterpret_cast<const float4*>(opt->d_lrv);
-            a.cf_delta = (float)(-0.5 * std::log((double)opt->p1)); a.cf_lb1 = (float)std::log2((double)opt->p0); a.cf_lb2 = (float)std::log2((double)opt->p1);
-        }
-        a.newton = pa.newton = (1.0f - sqrtf(opt->p1)) <= 1e-3f && getenv("ORX_ADAM_NO_NEWTON") == nullptr;
-        U->lazy = opt; V->lazy = opt; b->lazy = opt;
+        CHECK(orx_lazy_adam_fill(opt, U, V, b, sU, sV, sb, !lazy_resume, K, &a));
+        // (the view for dup_apply_kernel / the in-launch apply: the same, but its replay loops)
+        pa.a2U = a.a2U; pa.a2V = a.a2V; pa.a2b = a.a2b; pa.lastU = a.lastU; pa.lastV = a.lastV; pa.lastb = a.lastb;
+        pa.lrt = a.lrt; pa.b1 = a.b1; pa.b2 = a.b2; pa.eps = a.eps; pa.newton = a.newton;
     }
     const int64_t chunk = role_bits ? plan.chunk : K;
     for (int64_t s0 = 0; s0 < K; s0 += chunk) {
@@ -210,7 +180,7 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
         if (role_bits) {
             a.epoch = pa.epoch = ++c->epoch;
             if (inl && i > 0) {                  // this launch also applies the duplicated rows of step i-1
-                pa.n_apply_blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(16, (B / 4) / (1024 / D) + 1));
+                pa.n_apply_blocks = orx_apply_blocks(B, D);
                 pa.prev_dlist = c->d_dlist + (size_t)(i - 1) * plan.list_stride; pa.prev_dcount = c->d_dcount + (i - 1);
                 a.n_apply_blocks = pa.n_apply_blocks;
                 a.ap = pa;
@@ -222,14 +192,7 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
             if (!inl || i == kc - 1) CHECK(orx_launch_dup_apply(c, opt->kind, pa));
         }
         float lr_t = lazy_adam ? opt->h_lrt[(size_t)opt->t] : 0.f;
-        if (mode == MODE_ACCUM) {
-            opt->t += 1;
-            const double b1 = opt->p0, b2 = opt->p1;
-            lr_t = (float)(opt->lr * std::sqrt(1.0 - std::pow(b2, (double)opt->t)) / (1.0 - std::pow(b1, (double)opt->t)));
-            CHECK(orx_launch_adam_sweep(c, U->w, sU.s0, sU.s1, U->gsum, U->rows * D, lr_t, opt->p0, opt->p1, opt->p2));
-            CHECK(orx_launch_adam_sweep(c, V->w, sV.s0, sV.s1, V->gsum, V->rows * D, lr_t, opt->p0, opt->p1, opt->p2));
-            CHECK(orx_launch_adam_sweep(c, b->w, sb.s0, sb.s1, b->gsum, b->rows, lr_t, opt->p0, opt->p1, opt->p2));
-        }
+        if (mode == MODE_ACCUM) CHECK(orx_adam_dense_step(c, opt, {{U, sU}, {V, sV}, {b, sb}}, &lr_t));
         if (model == ORX_GMF) {                  // dense Dense(1) kernel: reduce partials, apply the dense rule
             if (mode == MODE_ACCUM || lazy_adam) {
                 if (!dense_tail) CHECK(orx_launch_dense_reduce(c, c->d_wpart, orx_point_wparts(D, B), D, w->w, a.l2w, w->gsum, a.partial + 2 * nw, nullptr, -1, 0.f, 0.f));

@@ -8,12 +8,6 @@
 #include <cstring>
 #include <vector>
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 extern "C" int orx_plan_geometry(int64_t NU, int64_t NI, int64_t nU, int64_t nP, int64_t nN, int32_t* out) {
     ORX_ARG(out && NU > 0 && NI > 0 && nU >= 0 && nP >= 0 && nN >= 0, "orx_plan_geometry: bad argument");
     DedupArgs d;

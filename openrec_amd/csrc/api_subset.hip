@@ -15,17 +15,6 @@
 
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-#define ENSURE(ptr, cap, bytes)                                                        \
-    do {                                                                               \
-        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 namespace {
 
 constexpr int64_t SUBSET_CHUNK = 32;          // steps whose id lists are sorted together

@@ -7,17 +7,6 @@
 
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-#define ENSURE(ptr, cap, bytes)                                                        \
-    do {                                                                               \
-        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 static constexpr size_t ORX_TOPK_DENSE_BYTES = (size_t)256 << 20;   // dense score rows (direct route, fallback, host rows)
 static constexpr size_t ORX_TOPK_BATCH_BYTES = (size_t)512 << 20;   // sample rows + candidate lists of one batch of users
 static constexpr int ORX_TOPK_MAX_K = 1024;

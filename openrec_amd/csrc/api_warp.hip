@@ -5,12 +5,6 @@
 
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 extern "C" int orx_sampler_pairwise_warp(orx_sampler* s, int model, orx_table* user, orx_table* item, orx_table* bias,
                                          uint64_t seed, int64_t first, int64_t n, int32_t max_trials, float margin,
                                          const float* trial_weight,

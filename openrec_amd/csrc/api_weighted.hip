@@ -9,12 +9,6 @@
 
 #include "orx_internal.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 namespace {
 
 // what the three step entry points refuse on top of the plain steps

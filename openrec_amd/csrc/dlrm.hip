@@ -10,12 +10,6 @@
 #include "orx_internal.h"
 #include "orx_csr_device.h"
 
-#define CHECK(call)                                                                    \
-    do {                                                                               \
-        int _rc = (call);                                                              \
-        if (_rc != ORX_OK) return _rc;                                                 \
-    } while (0)
-
 struct DenseLayer {
     int in = 0, out = 0, act = 0;       // act: 1 relu, 2 sigmoid
     orx_table* W = nullptr;             // [in, out]

@@ -3,12 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <functional>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/openrec_hip.h"
@@ -32,6 +35,19 @@ void orx_set_error(const char* fmt, ...);
             orx_set_error(__VA_ARGS__);                                                \
             return ORX_ERR_ARG;                                                        \
         }                                                                              \
+    } while (0)
+
+// inside a function that returns an orx status: pass a failed call's status on / grow a device buffer (orx_ensure)
+#define CHECK(call)                                                                    \
+    do {                                                                               \
+        int _rc = (call);                                                              \
+        if (_rc != ORX_OK) return _rc;                                                 \
+    } while (0)
+
+#define ENSURE(ptr, cap, bytes)                                                        \
+    do {                                                                               \
+        int _rc = orx_ensure((void**)&(ptr), &(cap), (bytes));                         \
+        if (_rc != ORX_OK) return _rc;                                                 \
     } while (0)
 
 // --------------------------------------------------------------- objects ---
@@ -78,10 +94,6 @@ struct orx_ctx {
     int64_t stat_pairs = 0, stat_max_dup = 0, stat_nowait_calls = 0;      // orx_ctx_stat
     hipEvent_t stats_ev = nullptr;
     bool stats_pending = false; int64_t stats_kc = 0, stats_B = 0; bool stats_pairing = false; int stats_age = 0; int64_t stats_key[5] = {0, 0, 0, 0, 0};
-    // plan pipeline (api.hip): the pieces of a chunk after the first are planned on a second stream while the previous piece's
-    // steps run; per piece parity: counters on the host / plan complete on the device
-    hipStream_t plan_stream = nullptr;
-    hipEvent_t pipe_cnt[2] = {nullptr, nullptr}, pipe_done[2] = {nullptr, nullptr};
     hipEvent_t wait_ev = nullptr;                                // orx_ctx_wait_stream
     int epoch = 0;                                               // step epoch: tags ready flags and censor side marks
     int epoch_gen = 0;                                           // bumped when `epoch` wraps (tables then clear their tags)
@@ -163,7 +175,7 @@ constexpr int ORX_ADAM_CF_TERMS = 512;        // J: b1^J is negligible for b1 <=
 // what a kernel needs for the closed-form replay: the moments table and the constants (lrv NULL: the replay loops)
 struct AdamCFParams { const float4* lrv; float delta, lb1, lb2; };
 AdamCFParams orx_adam_cf_params(const orx_opt* o);
-bool orx_adam_cf_ok(const orx_opt* o);        // closed-form replay applicable (b1 <= 0.95, 1 - sqrt(b2) <= 1e-3, ORX_ADAM_NO_CF unset)
+bool orx_adam_cf_ok(const orx_opt* o);        // closed-form replay applicable (b1 <= 0.95, 1 - sqrt(b2) <= 1e-3)
 // Lazily-applied TF-2.0 Adam: the dense decay of a row that no triplet touches (m *= b1, v *= b2, w -= lr_t m /
 // (sqrt(v)+eps), every step) is replayed exactly when the row is next needed.  orx_table_sync brings every row of a
 // table up to the optimizer's current step; every entry point that reads or writes a table calls it first.
@@ -203,6 +215,28 @@ int orx_pointwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U,
                               const int32_t* uid, const int32_t* iid, const float* label,
                               int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags, int train_mask,
                               float* loss_out, float* l2_out);
+// host setup the pairwise and the pointwise step call share (api.hip)
+int orx_fallback_bits();                                          // ORX_FORCE_FALLBACK, read per call
+int orx_epochs_reserve(orx_ctx* c, int64_t K, std::initializer_list<orx_table*> tables);     // K step epochs; on wrap-around the tables clear their tags
+int orx_apply_blocks(int64_t B, int D);                           // blocks of a step's launch that apply the previous step's duplicated rows
+int orx_adam_dense_step(orx_ctx* c, orx_opt* opt, std::initializer_list<std::pair<orx_table*, OptSlots>> tables, float* lr_t_out);
+// lazy Adam, what PairArgs and PointArgs share: second slots, per-row step stamps (restamp: the tables were not lazy under
+// `opt` so far), lr_t of the K steps to come, the constants of the replay; the tables become lazy under `opt`.  b may be NULL.
+template <class Args>
+int orx_lazy_adam_fill(orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, const OptSlots& sU, const OptSlots& sV, const OptSlots& sb,
+                       bool restamp, int64_t K, Args* a) {
+    a->a2U = sU.s1; a->a2V = sV.s1; a->a2b = sb.s1;
+    CHECK(orx_opt_last(opt, U, restamp, &a->lastU)); CHECK(orx_opt_last(opt, V, restamp, &a->lastV));
+    if (b) CHECK(orx_opt_last(opt, b, restamp, &a->lastb));
+    CHECK(orx_adam_lrt(opt, opt->t + K));
+    a->lrt = opt->d_lrt; a->b1 = opt->p0; a->b2 = opt->p1; a->eps = opt->p2;
+    const AdamCFParams cf = orx_adam_cf_params(opt);              // (lrv NULL: the replay loops)
+    a->lrv = cf.lrv; a->cf_delta = cf.delta; a->cf_lb1 = cf.lb1; a->cf_lb2 = cf.lb2;
+    a->newton = (1.0f - sqrtf(opt->p1)) <= 1e-3f;
+    U->lazy = opt; V->lazy = opt;
+    if (b) b->lazy = opt;
+    return ORX_OK;
+}
 void orx_prof_begin(orx_ctx* ctx, int kid);
 void orx_prof_end(orx_ctx* ctx, int kid);
 

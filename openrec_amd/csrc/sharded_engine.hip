@@ -16,8 +16,6 @@
 #include <vector>
 #include <utility>
 
-#define CHECK(call) do { const int rc_ = (call); if (rc_ != ORX_OK) return rc_; } while (0)
-
 namespace {
 
 struct RcclApi {

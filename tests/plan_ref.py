@@ -24,10 +24,10 @@ What the consumers read (file:line of openrec_amd/csrc at the time of writing):
       one reference per scratch row.  Role 2: atomics, or the staging slot segstart[dense] + rank (kernels_pairwise.hip:539-543).
   R4  the apply walks dcount list entries, skips ORX_DLIST_DEAD, bit 31 = item table (kernels_pairwise.hip:762-779,
       orx_apply_device.h:87-96): dcnt > 0 sums [dseg, dseg + dcnt) of the staging buffer, dcnt < 0 sums -dcnt partial sums from dseg on,
-      dcnt = 0 reads the scratch rows.  hot_reduce_kernel runs alloc[2 + l] items of level l from tree_off[l] (api.hip:784).
+      dcnt = 0 reads the scratch rows.  hot_reduce_kernel runs alloc[2 + l] items of level l from tree_off[l] (api.hip:759).
   R5  urgent (bit 28): the reference waits for the ready flag that the in-launch apply of step s-1 sets for every LIVE list entry
       (kernels_pairwise.hip:544-549).  A missing mark is a race, a mark on a row nobody applies never gets its flag.
-  R6  host: alloc[5] - alloc[7] = rows the apply really has, alloc[1..4] > 0 = not quiet (api.hip:842-845).
+  R6  host: alloc[5] - alloc[7] = rows the apply really has, alloc[1..4] > 0 = not quiet (api.hip:817-820).
 """
 import numpy as np
 

@@ -49,8 +49,8 @@ class env:
 
 
 # every knob that changes the path of the step, pinned (None: unset) unless a case sets it
-CLEAN = dict(ORX_PAIR_ALWAYS=1, ORX_NO_PAIR=None, ORX_PLAN_WAIT=None, ORX_PLAN_PIPE=None, ORX_PLAN_MIN_LATE=None,
-             ORX_INLINE_DUP_DIV=None, ORX_FORCE_FALLBACK=None, ORX_PLAN_V1=None)
+CLEAN = dict(ORX_PAIR_ALWAYS=1, ORX_NO_PAIR=None, ORX_PLAN_WAIT=None, ORX_PLAN_MIN_LATE=None,
+             ORX_FORCE_FALLBACK=None, ORX_PLAN_V1=None)
 
 
 def _env(**kw):

@@ -307,7 +307,7 @@ def _branches(case):
                 bk = R._bucket_of(rows, t, geo, 2)
                 nb = geo["nru"] if t == 0 else geo["nri"]
                 per = np.bincount(bk, minlength=nb)
-                out["next_plan_big"] |= bool(per.max() > 16384)            # api.hip:847
+                out["next_plan_big"] |= bool(per.max() > 16384)            # api.hip:822
                 out["non_register"] |= bool(per.max() > geo["PL_UN"] * geo["T"])
                 ur, cnt = np.unique(rows, return_counts=True)
                 ubk = R._bucket_of(ur, t, geo, 2)
@@ -361,7 +361,7 @@ def test_sequences_reach_what_the_previous_call_selects():
                 split |= s0 > 0
                 whole |= s0 == 0
                 if opt["tpw"] > 1:
-                    for _piece in range(2 if s0 else 1):      # (every issue of a pairing plan takes the next generation, api.hip:800)
+                    for _piece in range(2 if s0 else 1):      # (every issue of a pairing plan takes the next generation, api.hip:775)
                         gens += 1
                         wrapped |= gens > 63                  # this plan's generation has been used before in this buffer
                         unwrapped |= gens <= 63
