@@ -221,8 +221,8 @@ __global__ __launch_bounds__(256) void evalmf_sweep_kernel(EvalMfArgs a, int c0)
     put(Bsel(0), jbeg, 0);
     __syncthreads();
     if (K3 == 1) {
-        for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s += x * x; } un2[r] = s; }
-        if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s += x * x; } vn2[r] = s; }
+        for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s = __builtin_fmaf(x, x, s); } un2[r] = s; }
+        if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s = __builtin_fmaf(x, x, s); } vn2[r] = s; }
         __syncthreads();
     }
     const float* urow = As + (16 * UW * wave + (lane & 15)) * pitch + 4 * (lane >> 4);
@@ -286,7 +286,7 @@ __global__ __launch_bounds__(256) void evalmf_sweep_kernel(EvalMfArgs a, int c0)
             put(Bsel((t + 1) & 1), j0 + TI, (t + 1) & 1);
             if (K3 == 1) {
                 __syncthreads();
-                if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s += x * x; } vn2[((t + 1) & 1) * TI + tid] = s; }
+                if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s = __builtin_fmaf(x, x, s); } vn2[((t + 1) & 1) * TI + tid] = s; }
             }
         }
         __syncthreads();

@@ -14,8 +14,12 @@
 // 16 columns lane group q = lane / 16 takes columns 4q .. 4q+3 for four consecutive MFMA steps, for the item and the user
 // operand alike: ONE ds_read_b128 per operand and four steps instead of four ds_read_b32.  The ITEMS are the M side of the
 // product, so a lane ends up with four CONSECUTIVE items of one user: one 16-byte store per lane and 16 x 16 tile.
-// UCML uses |u - v|^2 = |u|^2 + |v|^2 - 2 u.v with the norms taken from the same LDS tiles.  The output, nq x NI floats, is
-// the traffic that bounds the kernel (4 GB for 1000 users x 1 M items against 256 MB of item rows).
+// UCML uses |u - v|^2 = |u|^2 + |v|^2 - 2 u.v with the norms taken from the same LDS tiles.  The norms are chains of explicit
+// fmaf: written as `s += x * x` the compiler fused some products and rounded others (packed multiplies for part of a row), and
+// chose differently per instantiation and between the first tile's loop and the later tiles' -- the L2 score of one (user,
+// item) then differed in its last bit between a call of <= 64 and of > 64 users, and between an item of a run's first tile
+// and of a later one, which the callers that score in batches or prefixes rely on never happening.
+// The output, nq x NI floats, is the traffic that bounds the kernel (4 GB for 1000 users x 1 M items against 256 MB of item rows).
 #include "orx_device.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -105,8 +109,8 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
     put(Bsel(0), jbeg, 0);
     __syncthreads();
     if (K3 == 1) {
-        for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s += x * x; } un2[r] = s; }
-        if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s += x * x; } vn2[r] = s; }
+        for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s = __builtin_fmaf(x, x, s); } un2[r] = s; }
+        if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s = __builtin_fmaf(x, x, s); } vn2[r] = s; }
         __syncthreads();
     }
     const float* urow = As + (16 * UW * wave + (lane & 15)) * pitch + 4 * (lane >> 4);   // this lane's first user row, its 4 columns of a block
@@ -168,7 +172,7 @@ __global__ __launch_bounds__(256) void score_mfma_kernel(ScoreArgs a) {
             put(Bsel((t + 1) & 1), j0 + TI, (t + 1) & 1);
             if (K3 == 1) {
                 __syncthreads();
-                if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s += x * x; } vn2[((t + 1) & 1) * TI + tid] = s; }
+                if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s = __builtin_fmaf(x, x, s); } vn2[((t + 1) & 1) * TI + tid] = s; }
             }
         }
         __syncthreads();

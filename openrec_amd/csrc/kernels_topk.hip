@@ -23,10 +23,10 @@
 //   4. fallback   a user whose candidates overflowed C is scored row by row into bounded scratch with the normal scorer
 //                 and selected by the same kernel over the dense row (what orx_topk_rows does).  Many equal scores (a
 //                 constant table, identical item rows) land here and stay exact.
-// UCML (L2) scores take step 4's route for every user: their |u|^2 and |v|^2 sums are fp32 chains in which the compiler fuses
-// some products into FMAs and rounds others (a choice made per kernel body, kernels_score.hip's included), so a restated
-// kernel does not reproduce the scorer's bits from the same source; only the scorer itself does.  The L2 branches of the
-// restated kernel below are kept so that it stays statement for statement the scorer's, but they are not instantiated.
+// UCML (L2) scores take step 4's route for every user: their |u|^2 and |v|^2 sums were fp32 chains in which the compiler fused
+// some products into FMAs and rounded others (a choice made per kernel body), so a restated kernel did not reproduce the
+// scorer's bits from the same source.  The sums are explicit fmaf chains now (kernels_score.hip says why), here as there; the
+// L2 branches of the restated kernel below stay statement for statement the scorer's, but they are still not instantiated.
 // D > 256 (no MFMA tile), ORX_SCORE_SIMPLE, and item counts no larger than the sample take step 4's route directly, in
 // bounded user batches.  Device scratch: nb x (P + 2 C + 2 k) words per batch of nb users, the pools (TOPK_FILTER_BLOCKS x
 // TOPK_POOL x 12 bytes: a longer item table gets longer chunks, not more workgroups) and at most ORX_TOPK_DENSE_BYTES of dense
@@ -179,8 +179,8 @@ __global__ __launch_bounds__(256) void topk_filter_kernel(TopkFilterArgs a) {
     put(Bsel(0), jbeg, 0);
     __syncthreads();
     if (K3 == 1) {
-        for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s += x * x; } un2[r] = s; }
-        if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s += x * x; } vn2[r] = s; }
+        for (int r = tid; r < UB; r += 256) { float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = As[r * pitch + c]; s = __builtin_fmaf(x, x, s); } un2[r] = s; }
+        if (tid < TI) { const int r = tid; float s = 0.f; for (int c = 0; c < Dp; ++c) { const float x = Bsel(0)[r * pitch + c]; s = __builtin_fmaf(x, x, s); } vn2[r] = s; }
         __syncthreads();
     }
     const float* urow = As + (16 * UW * wave + (lane & 15)) * pitch + 4 * (lane >> 4);
@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256) void topk_filter_kernel(TopkFilterArgs a) {
             put(Bsel((t + 1) & 1), j0 + TI, (t + 1) & 1);
             if (K3 == 1) {
                 __syncthreads();
-                if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s += x * x; } vn2[((t + 1) & 1) * TI + tid] = s; }
+                if (tid < TI) { float s = 0.f; const float* Bn = Bsel((t + 1) & 1); for (int c = 0; c < Dp; ++c) { const float x = Bn[tid * pitch + c]; s = __builtin_fmaf(x, x, s); } vn2[((t + 1) & 1) * TI + tid] = s; }
             }
         }
         __syncthreads();
