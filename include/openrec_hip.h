@@ -247,6 +247,51 @@ int orx_pairwise_loss_weighted(orx_ctx* ctx, int model,
                                const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
                                int64_t B, float margin, int flags, float* loss_out, float* l2_out);
 
+/* ONE POSITIVE AGAINST N NEGATIVES: K train steps of a dot-product model (BPR's tables) under a sampled-softmax or an N-pair
+ * log-sigmoid loss.  Sample i of step s has user u = U[uid[s*id_stride + i]], positive p = V[pid[s*id_stride + i]] and negatives
+ * n_j = V[nid[(s*id_stride + i)*N + j]], j < N.  Scores are fp32 and of the dot kind only:
+ *   s_p = u.p + b[pid],   s_j = u.n_j + b[nid_j] + off_j          (no "+ b" with bias == NULL)
+ * off = neg_offset[(s*id_stride + i)*N + j], 0 when neg_offset == NULL: a constant added to a negative's logit -- -log Q(item) when
+ * the negatives come from a weighted proposal; -inf removes the negative from the loss.  It is not validated.
+ *   ORX_MN_SOFTMAX: l_i = logsumexp(s_p, s_0 .. s_{N-1}) - s_p, evaluated with the maximum subtracted (scores of magnitude 200 give
+ *                   finite results); pi_j = exp(s_j - lse)
+ *   ORX_MN_LOGSIG : l_i = (1/N) sum_j -log_sigmoid(max(s_p - s_j, -30))      (the clamp of pairwise_log_loss.py:32: N = 1 is BPR's term)
+ *   loss    = (1/B) sum_i w_i l_i                  w_i = weight[s*id_stride + i], 1 when weight == NULL
+ *   l2_loss = 1/2 (sum |u|^2 + sum |p|^2 + sum over all B*N negatives |n|^2)          no biases (bpr.py:35), never weighted
+ *   J       = loss + l2_reg * l2_loss
+ * loss_out[s] is the loss, l2_out[s] the UNSCALED l2_loss, as in orx_pairwise_step_weighted.  Gradients, per occurrence and on the
+ * pre-step tables, with c_i = w_i / B:
+ *   a_ij = c_i pi_j (softmax),   a_ij = c_i sigmoid(s_j - s_p) [s_p - s_j >= -30] / N (logsig),   A_i = sum_j a_ij
+ *   g_u = sum_j a_ij n_j - A_i p + l2_reg u,   g_p = -A_i u + l2_reg p,   g_nj = a_ij u + l2_reg n_j,   g_bp = -A_i,   g_bnj = a_ij
+ * A_i is the sum of the pi_j themselves (never 1 - pi_p).  Every occurrence is its own term: a negative may repeat inside a sample,
+ * may equal the positive, and a row may appear in many samples.  The apply is orx_apply_rows': the user table with the id list
+ * uid[B], the item table and the bias with ONE list, pid[B] followed by nid[B*N]; SGD accumulates every occurrence, Adagrad,
+ * momentum and Adam sum a row's occurrences over that whole list first, Adam's counter advances once per step.  Lazily-applied
+ * Adam: exactly the rows a step reads are brought up to date before it.  A K-step call is K one-step calls; everything runs on the
+ * context's stream without a host synchronisation between steps, and loss_out == l2_out == NULL makes the call fully asynchronous.
+ * weight and neg_offset live where the ids live (device pointers under ORX_IDS_DEVICE).  No float atomics in the gradient launch
+ * or the loss sums: loss_out / l2_out are bit-repeatable, and so are the tables when bias == NULL (the sorted apply).
+ * ORX_ERR_ARG before any device work: N outside [1, 64]; an unknown loss kind; ORX_HOGWILD or ORX_CENSOR; l2_reg negative or not
+ * finite; ORX_NO_L2 with l2_reg != 0; user dim != item dim; a bias that is not [item rows, 1]; tables or optimizer on another
+ * context; what orx_apply_rows refuses for the optimizer and the tables (ORX_ADAM_DENSE with a bias).  Not offered: train masks,
+ * UCML / L2 scoring, the sharded engines.  An id outside its table: ORX_ERR_INDEX as orx_pairwise_step reports it (the gradient
+ * launch checks every id and never uses a bad one as an address: such a user or positive zeroes its sample, such a negative
+ * itself); the context stays usable.  K == 0 or B == 0: ORX_OK, nothing is launched. */
+enum orx_multineg_kind { ORX_MN_SOFTMAX = 0, ORX_MN_LOGSIG = 1 };
+int orx_multineg_step(orx_ctx* ctx, int loss_kind, orx_opt* opt,
+                      orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                      const int32_t* uid, const int32_t* pid, const int32_t* nid,
+                      const float* weight /* NULL ok */, const float* neg_offset /* NULL ok */,
+                      int64_t K, int64_t B, int32_t N, int64_t id_stride, float l2_reg, int flags,
+                      float* loss_out, float* l2_out);
+/* Forward only: (loss, l2_loss) of one batch of orx_multineg_step, by the loss-only form of its kernel: no gradient is written, no
+ * table changes.  On the same tables it gives the step's loss_out / l2_out bit for bit.  flags: ORX_IDS_DEVICE. */
+int orx_multineg_loss(orx_ctx* ctx, int loss_kind,
+                      orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                      const int32_t* uid, const int32_t* pid, const int32_t* nid,
+                      const float* weight /* NULL ok */, const float* neg_offset /* NULL ok */,
+                      int64_t B, int32_t N, int flags, float* loss_out, float* l2_out);
+
 /* K train steps of GMF.call / WRMF.call (gmf.py:22-34, wrmf.py:21-34,
  * pointwise_mse_loss.py:18-31).  w: GMF's Dense(1, use_bias=False) kernel as a
  * [D,1] table (NULL for WRMF).  a, b: WRMF confidence weights (wrmf.py:7). */
@@ -431,6 +476,13 @@ int orx_sampler_pairwise_hard(orx_sampler* s, int model, orx_table* user, orx_ta
                               uint64_t seed, int64_t first, int64_t n, int32_t n_cand,
                               int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev,
                               int32_t* cand_dev /* [n*n_cand] or NULL */, float* cand_score_dev /* [n*n_cand] or NULL */);
+/* The negatives of orx_multineg_step: (user, positive) of samples [first, first + n) exactly as orx_sampler_pairwise gives them,
+ * and nid_dev[i * n_neg + j] = candidate j of sample first + i of orx_sampler_pairwise_hard, bit for bit, with or without a
+ * proposal -- the draws alone, no table is read and nothing is scored.  n_neg = 1 is orx_sampler_pairwise.  A window does not
+ * depend on how it is split into calls.  ORX_ERR_ARG before any launch: n_neg outside [1, 64], a NULL output with n > 0.
+ * n = 0: ORX_OK, nothing is launched.  Runs on the context's stream, no host synchronisation. */
+int orx_sampler_pairwise_multi(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, int32_t n_neg,
+                               int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev /* [n * n_neg] */);
 /* WARP negatives: (user, positive) of samples [first, first + n) exactly as orx_sampler_pairwise gives them, and as the negative
  * the FIRST of up to T = max_trials candidates that violates the margin against the positive under the current model; the
  * triplet's weight is trial_weight[number of candidates it took - 1], a function of WARP's rank estimate

@@ -898,6 +898,22 @@ struct HardNegArgs {
 };
 int orx_launch_hardneg(orx_ctx* ctx, const HardNegArgs& a);
 
+// kernels_multineg.hip (orx_multineg_step / orx_multineg_loss): one step's gradient launch of a positive against N negatives
+struct MultiNegArgs {
+    const float* U; const float* V; const float* b;       // read only; b NULL: no item bias
+    const int32_t* uid; const int32_t* pid; const int32_t* nid;   // this step's ids: [B], [B], [B][N]
+    const float* wt; const float* off;                    // [B] weights (NULL: all ones), [B][N] offsets of the negative logits (NULL: 0)
+    float* gu; float* gi; int32_t* list;                  // [B][gs]; [(1 + N) B][gs], bias gradient in column D; [(1 + N) B] item ids
+    int64_t B; int64_t NU; int64_t NI;
+    int N; int D; int gs;
+    float invB; float l2w;
+    float* partial;                                       // [orx_multineg_nwaves(ctx, D, B)][2] loss / l2 partials of this step
+    int* err;
+};
+int orx_multineg_nwaves(orx_ctx* ctx, int D, int64_t B);
+int orx_launch_multineg(orx_ctx* ctx, int kind /* orx_multineg_kind */, bool grads, const MultiNegArgs& a);
+int orx_launch_sample_multi(orx_ctx* ctx, const SamplerArgs& a, int M);      // a.nid [n * M]
+
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {
     SamplerArgs s;

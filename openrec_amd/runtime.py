@@ -385,6 +385,104 @@ def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5, weights=No
     return float(loss[0]), float(l2[0])
 
 
+_MN_KIND = {"softmax": _ffi.ORX_MN_SOFTMAX, "logsig": _ffi.ORX_MN_LOGSIG}
+
+
+def _multineg_args(what, loss, user, item, bias, uid, pid, nid, K, B, id_stride, weights, neg_offset):
+    """the checks and the pointers multineg_step and multineg_loss share; every bad argument is a ValueError raised here,
+    before the library is called"""
+    if loss not in _MN_KIND:
+        raise ValueError(f"{what}: unknown loss {loss!r}; expected one of {sorted(_MN_KIND)}")
+    shape = tuple(getattr(nid, "shape", ()))
+    if isinstance(nid, DevicePtr) or len(shape) < 2:
+        raise ValueError(f"{what}: nid must be an array shaped [..., B, N] (N is taken from its last axis)")
+    N = int(shape[-1])
+    if not 1 <= N <= 64:
+        raise ValueError(f"{what}: N = {N} negatives per positive; N must be in [1, 64]")
+    if user.shape[1] != item.shape[1]:
+        raise ValueError(f"{what}: user dim {user.shape[1]} != item dim {item.shape[1]} (dot scores only)")
+    if bias is not None and tuple(bias.shape) != (item.shape[0], 1):
+        raise ValueError(f"{what}: bias must be [{item.shape[0]}, 1], got {list(bias.shape)}")
+    pu, nu, du, k0 = _ids_arg(uid)
+    pp, npn, dp, k1 = _ids_arg(pid)
+    pn, nn, dn, k2 = _ids_arg(nid)
+    if not (du == dp == dn):
+        raise ValueError(f"{what}: ids must be all on the host or all on the device")
+    K = int(K)
+    if K < 0:
+        raise ValueError(f"{what}: K = {K}")
+    if B is None:
+        B = nu // K if K else 0
+    B = int(B)
+    if id_stride is None:
+        id_stride = B
+    id_stride = int(id_stride)
+    if B < 0 or id_stride < B:
+        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
+    need = (K - 1) * id_stride + B if K and B else 0
+    if nu != npn or nu < need or nn != nu * N:
+        raise ValueError(f"{what}: {nu} user ids, {npn} positive ids and {nn} negative ids for K = {K}, B = {B}, "
+                         f"id_stride = {id_stride}, N = {N} (uid and pid alike, nid N times as long)")
+    pw = po = None
+    keep = [k0, k1, k2]
+    if weights is not None:
+        pw, kw = _weights_arg(weights, du, nu, what)
+        keep.append(kw)
+    if neg_offset is not None:
+        po, no, do, ko = _label_arg(neg_offset)
+        if do != du:
+            raise ValueError(f"{what}: neg_offset on the {'device' if do else 'host'} with ids on the {'device' if du else 'host'} "
+                             "(the offsets live where the ids live)")
+        if no != nn:
+            raise ValueError(f"{what}: {no} offsets for {nn} negative ids (neg_offset is shaped like nid)")
+        keep.append(ko)
+    user.ctx.after_torch(uid, pid, nid, weights, neg_offset)
+    return _MN_KIND[loss], N, K, B, id_stride, du, (pu, pp, pn, pw, po), keep
+
+
+def multineg_step(loss, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None, weights=None, neg_offset=None,
+                  l2_reg=1.0, no_l2=False, want_loss=True):
+    """K train steps of one positive against N negatives per sample (orx_multineg_step).  loss: "softmax" -- sampled softmax,
+    -log softmax of the positive among the 1 + N logits -- or "logsig" -- the mean of N BPR log-sigmoid pair terms.  Scores are
+    dot products plus the item bias (bias=None: none).  nid is shaped [..., B, N] and N (1 .. 64) is taken from it; uid / pid as
+    in pairwise_step.  weights: per-sample weights shaped like uid; neg_offset: a constant added to every negative's logit,
+    shaped like nid (-log Q(item) for negatives from a weighted proposal; -inf drops a negative); both live where the ids live.
+    The objective is loss + l2_reg * l2_loss (no_l2=True: l2_reg = 0).  Returns (loss[K], l2[K]) as numpy float32 -- l2 the
+    unscaled l2_loss -- when want_loss, else None (fully asynchronous).  Bad arguments raise ValueError before the library is
+    called; an id outside its table raises IndexError."""
+    what = "multineg_step"
+    if no_l2:
+        if l2_reg not in (None, 0, 0.0, 1.0):
+            raise ValueError(f"{what}: no_l2=True together with l2_reg = {l2_reg} (drop no_l2, or pass l2_reg=0.0)")
+        l2_reg = 0.0
+    l2c = float(1.0 if l2_reg is None else l2_reg)
+    if not (np.isfinite(l2c) and l2c >= 0.0):
+        raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+    kind, N, K, B, id_stride, dev, ptrs, keep = _multineg_args(what, loss, user, item, bias, uid, pid, nid, K, B, id_stride,
+                                                                weights, neg_offset)
+    if want_loss:
+        out = np.empty(K, np.float32), np.empty(K, np.float32)
+        lp, l2p = out[0].ctypes.data, out[1].ctypes.data
+    else:
+        out = None
+        lp = l2p = None
+    check(user.ctx._lib.orx_multineg_step(user.ctx._h, kind, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, N, id_stride,
+                                          l2c, _ffi.ORX_IDS_DEVICE if dev else 0, lp, l2p))
+    _keep_tables(opt, (user, item, bias))
+    return out
+
+
+def multineg_loss(loss, user, item, bias, uid, pid, nid, weights=None, neg_offset=None):
+    """forward only: (loss, l2_loss) of one batch of multineg_step -- the step's own numbers bit for bit on the same tables; no
+    table changes"""
+    kind, N, _, B, _, dev, ptrs, keep = _multineg_args("multineg_loss", loss, user, item, bias, uid, pid, nid, 1, None, None,
+                                                       weights, neg_offset)
+    out = np.empty(1, np.float32), np.empty(1, np.float32)
+    check(user.ctx._lib.orx_multineg_loss(user.ctx._h, kind, user._h, item._h, _bias_h(bias), *ptrs, B, N,
+                                          _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
+    return float(out[0][0]), float(out[1][0])
+
+
 def _label_arg(x):
     if _is_device_tensor(x):
         assert str(x.dtype).endswith("float32") and x.is_contiguous()
@@ -1190,6 +1288,18 @@ class DeviceSampler:
                 t._sync_pending()
         check(self._lib.orx_sampler_pairwise_hard(self._h, int(mid), U._h, V._h, _bias_h(b), int(seed) & (2 ** 64 - 1), int(first),
                                                   int(n), int(candidates), pu, pp, pn, pc, ps))
+
+    def pairwise_multi(self, seed, first, n, uid, pid, nid, negatives=16):
+        """The negatives of `multineg_step`: uid / pid as `pairwise(seed, first, n)` writes them, and nid -- a DEVICE int32
+        buffer [n, negatives] -- the first `negatives` candidates of `pairwise_hard` for every sample, bit for bit (candidate 0
+        is `pairwise`'s negative; from the proposal when `set_proposal` is in force).  Only the draws: no table is read.
+        1 <= negatives <= 64.  Runs on the context's stream without a host synchronisation."""
+        N = int(negatives)
+        if not 1 <= N <= 64:
+            raise ValueError(f"pairwise_multi: negatives = {N}; must be in [1, 64]")
+        pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
+        assert du and dp and dn and min(nu, np_) >= n and nn >= n * N, "the sampler writes device buffers (nid: n * negatives)"
+        check(self._lib.orx_sampler_pairwise_multi(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), N, pu, pp, pn))
 
     def pairwise_warp(self, seed, first, n, uid, pid, nid, weight, model, U, V, b=None, max_trials=10, margin=1.0,
                       rank_weight="log", trials_out=None, pos_score_out=None, cand_score_out=None):

@@ -334,3 +334,24 @@ class PairwiseRecommender(Recommender):
         wts = _ids(sample_weight) if sample_weight is not None else None
         return rt.pairwise_step(self._model, opt, U, V, b, uid, pid, nid, K=K, margin=self.margin,
                                 want_loss=want_loss, censor=censor, train=train, weights=wts, l2_reg=self._l2_arg(False))
+
+    def train_steps_multi(self, optimizer, user_id, p_item_id, n_item_ids, loss="softmax", K=None, want_loss=True,
+                          sample_weight=None, neg_offset=None):
+        """Beyond the reference API: K consecutive steps of ONE positive against N negatives per sample in one device call
+        (rt.multineg_step).  user_id / p_item_id shaped [K, B] (or [B]: one step), n_item_ids [K, B, N] (or [B, N]).
+        loss: "softmax" (sampled softmax over the 1 + N logits) or "logsig" (the mean of N BPR pair terms).  sample_weight:
+        per-sample weights shaped like user_id; neg_offset: added to the negatives' logits, shaped like n_item_ids.  The
+        objective is loss + l2_reg * l2_loss with the model's l2_reg; the returned l2 is the unscaled l2_loss.  Dot-product
+        models only: it goes through no tape, takes no train mask, and UCML raises NotImplementedError."""
+        if self._model != "bpr":
+            raise NotImplementedError(f"{type(self).__name__}.train_steps_multi: the N-negative step scores by dot products "
+                                      "(u.v + b); UCML's squared-distance scores are not supported by it")
+        U, V, b = self._tables()
+        uid, pid, nid = _ids(user_id), _ids(p_item_id), _ids(n_item_ids)
+        if K is None:
+            K = uid.shape[0] if getattr(uid, "ndim", 1) == 2 else 1
+        opt = optimizer.native(U.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(neg_offset) if neg_offset is not None else None
+        return rt.multineg_step(loss, opt, U, V, b, uid, pid, nid, K=K, weights=wts, neg_offset=off, l2_reg=self.l2_reg,
+                                want_loss=want_loss)
