@@ -877,6 +877,39 @@ int orx_head16_bwd(orx_ctx* ctx, const void* X16, int64_t ldx, const void* w16, 
                    int32_t B, int32_t K, int32_t* P_out);
 int orx_cast16(orx_ctx* ctx, const float* src, int64_t lds, void* dst16, int64_t ld16, int32_t M, int32_t N);
 
+/* ---- alternating least squares for WRMF (beyond the reference API, whose wrmf.py trains by SGD over sampled points: the closed
+ * form of Hu / Koren / Volinsky over ALL row x column cells).  One half-step holds `fixed` (F, rows f_j, [M, D]) and overwrites rows
+ * [row0, row0 + nrows) of `solved` (X, [R, D]).  Row r has the observed columns O_r = cols[row_ptr[r] .. row_ptr[r + 1]) of a CSR
+ * over ALL R rows of `solved` (row_ptr int64 [R + 1], cols int32, ascending and distinct inside a row); observation (r, j) has
+ * preference 1 and confidence c_rj = conf[e] (a float array aligned with cols) or `a` for all of them when conf == NULL; every other
+ * cell has preference 0 and confidence b.  There is no bias term.
+ *     G   = F^T F                                              once per call
+ *     A_r = b G + sum_{j in O_r} (c_rj - b) f_j f_j^T + reg I
+ *     y_r = sum_{j in O_r} c_rj f_j
+ *     x_r = A_r^-1 y_r                                         Cholesky in fp32; A_r is SPD for reg > 0, b >= 0, c_rj >= b
+ * A row without observations becomes exact +0.0 without a solve.  The user half-step passes the user -> items CSR with fixed = the
+ * item table, the item half-step the item -> users CSR with fixed = the user table; the two descend
+ *     sum over all cells c (p - u.v)^2 + reg (|U|_F^2 + |V|_F^2).
+ * Rows of more than orx_als_segment_len() entries are cut into segments of that many entries; each segment's partial (A, y) is formed
+ * from zero and the row adds them in segment order.  No float atomics anywhere: x_r is a function of (F, the row's entries, a, b,
+ * reg) alone -- bit for bit the same whatever the row range of the call, the other rows in it, the scratch available, or where the
+ * CSR lives.
+ *   flags          ORX_IDS_DEVICE: row_ptr, cols and conf are device pointers and the call runs on the context's stream without a
+ *                  host synchronisation; else they are host arrays, the rows' part of them is copied over, and the call returns after
+ *                  orx_check_index_error.
+ *   conf values    are not validated (c_rj < b can make A_r indefinite); a non-finite value in F, conf or the scalars' products gives a
+ *                  non-finite x_r and never a hang: no loop's trip count depends on a floating-point value.
+ *   lazy Adam      both tables are brought up to date before they are read, as orx_score_all_items does; the optimizer slots of the
+ *                  solved table are left as they are (an optimizer that trained it keeps its moments).
+ * ORX_ERR_ARG before any launch, the tables untouched: fixed dim != solved dim or dim > 128; reg <= 0 or not finite; b < 0 or not
+ * finite; conf == NULL and a < b or a not finite; fixed == solved; a table on another context than `ctx`; a row range outside
+ * `solved`; unknown flags; a host row_ptr that decreases.  A column id outside [0, M) is dropped from its row and reported by
+ * orx_check_index_error (at once with a host CSR).  nrows == 0: ORX_OK, nothing is launched. */
+int32_t orx_als_segment_len(void);
+int orx_als_half_step(orx_ctx* ctx, orx_table* fixed, orx_table* solved,
+                      const int64_t* row_ptr, const int32_t* cols, const float* conf /* or NULL */,
+                      int64_t row0, int64_t nrows, float a, float b, float reg, int flags);
+
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,
  *                       PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads per range workgroup, threads of a big plan, references per

@@ -1367,3 +1367,150 @@ class DeviceSampler:
 
 
 Sampler = DeviceSampler
+
+
+# ---- alternating least squares for WRMF (orx_als_half_step) ------------------------------------------------------------------
+def als_segment_len():
+    """orx_als_segment_len: rows of more entries than this are cut into segments whose partial sums are added in segment order"""
+    return int(_ffi.load().orx_als_segment_len())
+
+
+class ALSCsr:
+    """One direction of an interaction set for `als_half_step`: row r observes the columns cols[ptr[r]:ptr[r + 1]] (ascending,
+    distinct), with the confidences conf[...] aligned with cols, or None for one confidence `a` everywhere.  The host arrays are
+    always there; `to_device(ctx)` adds copies in HBM (torch tensors) that the half-steps then read without any upload."""
+
+    def __init__(self, ptr, cols, conf, n_cols):
+        self.ptr = np.ascontiguousarray(ptr, np.int64)
+        self.cols = np.ascontiguousarray(cols, np.int32)
+        self.conf = None if conf is None else np.ascontiguousarray(conf, np.float32)
+        if self.ptr.ndim != 1 or self.ptr.size < 1 or self.ptr[0] != 0 or np.any(np.diff(self.ptr) < 0) or self.ptr[-1] != self.cols.size:
+            raise ValueError("ALSCsr: ptr must start at 0, never decrease and end at len(cols)")
+        if self.conf is not None and self.conf.shape != self.cols.shape:
+            raise ValueError("ALSCsr: conf must be aligned with cols")
+        self.shape = (self.ptr.size - 1, int(n_cols))
+        self._dev = None           # (ctx, ptr, cols, conf) device tensors
+
+    @classmethod
+    def from_pairs(cls, rows, cols, conf, n_rows, n_cols):
+        """(row, col[, confidence]) records -> CSR; a repeated pair is one entry (as DeviceSampler merges them) whose confidence
+        is the sum of its records'"""
+        rows = np.asarray(rows, np.int64).reshape(-1); cols = np.asarray(cols, np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= n_rows or cols.min() < 0 or cols.max() >= n_cols):
+            raise IndexError(f"ALS data: an id outside [0, {n_rows}) x [0, {n_cols})")
+        key, inv = np.unique(rows * int(n_cols) + cols, return_inverse=True)       # sorted by (row, col), distinct
+        ptr = np.zeros(int(n_rows) + 1, np.int64)
+        np.cumsum(np.bincount(key // int(n_cols), minlength=int(n_rows)), out=ptr[1:])
+        c = None
+        if conf is not None:
+            c = np.bincount(inv.reshape(-1), weights=np.asarray(conf, np.float64).reshape(-1), minlength=key.size).astype(np.float32)
+        return cls(ptr, (key % int(n_cols)).astype(np.int32), c, n_cols)
+
+    @property
+    def on_device(self):
+        return self._dev is not None
+
+    def to_device(self, ctx=None):
+        """a view of the same lists that als_half_step reads from HBM (needs torch)"""
+        import torch
+        ctx = ctx or default_context()
+        dv = torch.device("cuda", ctx.device)
+        out = ALSCsr.__new__(ALSCsr)
+        out.ptr, out.cols, out.conf, out.shape = self.ptr, self.cols, self.conf, self.shape
+        t = [torch.from_numpy(self.ptr).to(dv), torch.from_numpy(self.cols).to(dv),
+             torch.from_numpy(self.conf).to(dv) if self.conf is not None else None]
+        torch.cuda.current_stream(dv).synchronize()        # the copies are complete before the library's stream reads them
+        out._dev = (ctx, *t)
+        return out
+
+    def to_host(self):
+        """a view of the same lists that als_half_step uploads from the host arrays at every call"""
+        out = ALSCsr.__new__(ALSCsr)
+        out.ptr, out.cols, out.conf, out.shape, out._dev = self.ptr, self.cols, self.conf, self.shape, None
+        return out
+
+
+class ALSData:
+    """An interaction set prepared for ALS: `by_user` (user -> items) and `by_item` (item -> users), each an ALSCsr, built once.
+    `raw_data`: the structured array the reference's Dataset takes ('user_id', 'item_id'); repeated records are one observation.
+    `confidence`: one float per record (the c_ui of Hu / Koren / Volinsky; records of one pair add up), or None for the model's
+    `a` everywhere.  The lists are kept on the device when torch is there (device=False: host arrays only)."""
+
+    def __init__(self, raw_data, total_users, total_items, confidence=None, ctx=None, device=True):
+        self.ctx = ctx or default_context()
+        u = np.asarray(raw_data["user_id"]); i = np.asarray(raw_data["item_id"])
+        if confidence is not None:
+            confidence = np.asarray(confidence, np.float64).reshape(-1)
+            if confidence.size != u.size:
+                raise ValueError(f"ALSData: {confidence.size} confidences for {u.size} records")
+        self.total_users, self.total_items = int(total_users), int(total_items)
+        self.by_user = ALSCsr.from_pairs(u, i, confidence, self.total_users, self.total_items)
+        self.by_item = ALSCsr.from_pairs(i, u, confidence, self.total_items, self.total_users)
+        self.nnz = int(self.by_user.cols.size)
+        if device:
+            try:
+                import torch  # noqa: F401
+            except ImportError:
+                device = False
+        if device:
+            self.by_user, self.by_item = self.by_user.to_device(self.ctx), self.by_item.to_device(self.ctx)
+
+
+def _als_rows(rows, n):
+    if rows is None:
+        return 0, n
+    if isinstance(rows, range):
+        if rows.step != 1:
+            raise ValueError("als_half_step: rows must be a contiguous range")
+        row0, nrows = (rows.start, len(rows)) if len(rows) else (0, 0)
+    else:
+        row0, nrows = (int(x) for x in rows)
+    if row0 < 0 or nrows < 0 or row0 + nrows > n:
+        raise ValueError(f"als_half_step: rows [{row0}, {row0 + nrows}) outside the solved table's {n} rows")
+    return row0, nrows
+
+
+def als_half_step(fixed, solved, csr, a=1.0, b=1.0, reg=0.1, rows=None):
+    """One ALS half-step of WRMF: `fixed` stays, rows `rows` (None: all; a range or (row0, nrows)) of `solved` are overwritten
+    with the exact minimisers of  sum_cells c (p - x.f)^2 + reg |x|^2  given `fixed` -- observed cells (csr: an ALSCsr over the
+    rows of `solved` and the rows of `fixed` as columns) have preference 1 and confidence csr.conf, or `a` when it is None;
+    all others preference 0 and confidence `b`.  No bias term.  x is a function of the row's own data alone: the same bits for
+    any split into calls.  Bad arguments raise ValueError before the library is called; a column outside `fixed` IndexError."""
+    if not isinstance(csr, ALSCsr):
+        raise ValueError("als_half_step: csr must be an ALSCsr (ALSData.by_user / .by_item)")
+    if fixed is solved or fixed._h.value == solved._h.value:
+        raise ValueError("als_half_step: fixed and solved are the same table")
+    if fixed.ctx is not solved.ctx:
+        raise ValueError("als_half_step: the tables live on different contexts")
+    if fixed.dim != solved.dim:
+        raise ValueError(f"als_half_step: fixed dim {fixed.dim}, solved dim {solved.dim}")
+    if not 1 <= fixed.dim <= 128:
+        raise ValueError(f"als_half_step: dim {fixed.dim} outside [1, 128]")
+    a, b, reg = float(a), float(b), float(reg)
+    if not (np.isfinite(reg) and reg > 0):
+        raise ValueError(f"als_half_step: reg must be finite and > 0, got {reg!r}")
+    if not (np.isfinite(b) and b >= 0):
+        raise ValueError(f"als_half_step: b must be finite and >= 0, got {b!r}")
+    if csr.conf is None and not (np.isfinite(a) and a >= b):
+        raise ValueError(f"als_half_step: a = {a!r} must be finite and >= b = {b!r}")
+    if csr.shape != (solved.rows, fixed.rows):
+        raise ValueError(f"als_half_step: a CSR of shape {csr.shape} for tables of {solved.rows} and {fixed.rows} rows")
+    row0, nrows = _als_rows(rows, solved.rows)
+    fixed._sync_pending(); solved._sync_pending()
+    lib = fixed.ctx._lib
+    if csr.on_device:
+        ctx, ptr, cols, conf = csr._dev
+        if ctx is not fixed.ctx:
+            raise ValueError("als_half_step: the CSR was put on the device of another context")
+        check(lib.orx_als_half_step(ctx._h, fixed._h, solved._h, ptr.data_ptr(), cols.data_ptr(),
+                                    conf.data_ptr() if conf is not None else None, row0, nrows, a, b, reg, _ffi.ORX_IDS_DEVICE))
+    else:
+        check(lib.orx_als_half_step(fixed.ctx._h, fixed._h, solved._h, csr.ptr.ctypes.data, csr.cols.ctypes.data,
+                                    csr.conf.ctypes.data if csr.conf is not None else None, row0, nrows, a, b, reg, 0))
+    return solved
+
+
+def als_sweep(user, item, data, a=1.0, b=1.0, reg=0.1):
+    """One ALS sweep: the user half-step (items fixed), then the item half-step (users fixed).  `data`: an ALSData."""
+    als_half_step(item, user, data.by_user, a, b, reg)
+    als_half_step(user, item, data.by_item, a, b, reg)

@@ -18,6 +18,28 @@ class WRMF(PointwiseRecommender):
     def _point_args(self):
         return "wrmf", None, dict(a=self._a, b_w=self._b)
 
+    def fit_als(self, data, sweeps=1, reg=0.1, confidence=None):
+        """Beyond the reference API: train by alternating least squares (Hu / Koren / Volinsky) instead of sampled SGD --
+        `sweeps` times the user half-step then the item half-step of rt.als_sweep, each row solved in closed form over ALL
+        cells with the model's own a (observed) and b (unobserved) as confidences.  `data`: the structured array the
+        reference's Dataset takes, or an rt.ALSData built once; `confidence`: one float per record instead of `a` (only with
+        raw data).  ALS here has no bias term while `inference` adds the item bias, so the bias table must be all zero:
+        anything else is a ValueError.  Returns self."""
+        U, V, b = self._tables()
+        sweeps = int(sweeps)
+        if sweeps < 0:
+            raise ValueError(f"fit_als: sweeps = {sweeps}")
+        if isinstance(data, rt.ALSData):
+            if confidence is not None:
+                raise ValueError("fit_als: an ALSData carries its own confidences")
+        else:
+            data = rt.ALSData(data, U.rows, V.rows, confidence=confidence, ctx=U.ctx)
+        if b.read().any():
+            raise ValueError("fit_als: ALS has no bias term, but the item-bias table is not all zero (fill it with 0 first)")
+        for _ in range(sweeps):
+            rt.als_sweep(U, V, data, self._a, self._b, reg)
+        return self
+
     def inference(self, user_id):
         """wrmf.py:36-40:  U[user_id] @ V^T + b."""
         U, V, b = self._tables()
