@@ -910,6 +910,44 @@ int orx_als_half_step(orx_ctx* ctx, orx_table* fixed, orx_table* solved,
                       const int64_t* row_ptr, const int32_t* cols, const float* conf /* or NULL */,
                       int64_t row0, int64_t nrows, float a, float b, float reg, int flags);
 
+/* The same half-step solved INEXACTLY by cg_steps steps of conjugate gradient started from the row's current value (Takacs /
+ * Pilaszy / Tikk 2011): A_r is never formed and nothing is factorised.  The contract of a row:
+ *     A v  :=  b (G v) + reg v + sum_{j in O_r} (c_j - b) (f_j . v) f_j
+ *     x = the row's CURRENT value in `solved` (warm start);  r = y_r - A x;  p = r;  rs = r . r
+ *     repeat cg_steps times:
+ *         if rs <= 1e-20: the row is done, x stays            (a select that freezes the row, not a trip count)
+ *         Ap = A p;  alpha = rs / (p . Ap);  x += alpha p;  r -= alpha Ap
+ *         rsn = r . r;  p = r + (rsn / rs) p;  rs = rsn
+ *     store x (fp32)
+ * The sums behind A v and y_r are fp32; x, r and the scalars of the recurrence (rs, p . Ap, alpha, beta) with their D-length dot
+ * products are fp64, p is rounded to fp32 for the product.  A row without observations stores exact +0.0.  Every loop's trip count is
+ * an integer function of D, cg_steps and the row's length; NaN compares false in the guard and flows through: non-finite inputs give
+ * non-finite rows and never a hang.  No float atomics: x_r is a function of (F, the row's entries and current value, a, b, reg,
+ * cg_steps) alone -- the same bits whatever the call's row range, the other rows in the call, the order of calls, the scratch
+ * available, or where the CSR lives.  The code path of a row depends on its length and D only; orx_als_cg_row_breaks writes the
+ * lengths at which it changes (ascending, at most `cap` of them) and returns how many there are (0: none, or dim outside [1, 128]):
+ * rows up to the first keep their gathered f_j in LDS across the products, longer ones stream them per product, rows beyond the last
+ * are cut into segments of that many entries whose partials are formed by separate workgroups and added in segment order (a call
+ * has scratch for 65536 segments, fewer with the environment variable ORX_ALS_CG_SLOTS; a row beyond it is walked by one
+ * wavefront, segment by segment, to the same bits).
+ * Arguments, flags, index errors, lazy Adam and the solved table's version as for orx_als_half_step; in addition cg_steps outside
+ * [1, 128] is ORX_ERR_ARG before any launch. */
+int orx_als_half_step_cg(orx_ctx* ctx, orx_table* fixed, orx_table* solved,
+                         const int64_t* row_ptr, const int32_t* cols, const float* conf /* or NULL */,
+                         int64_t row0, int64_t nrows, float a, float b, float reg, int32_t cg_steps, int flags);
+int32_t orx_als_cg_row_breaks(int32_t dim, int32_t* out, int32_t cap);
+
+/* The objective both half-steps descend, for the user -> items CSR over ALL rows of `user`:
+ *     sum over all cells c (p - u.v)^2 + reg (|U|_F^2 + |V|_F^2)
+ *       = b <G_U, G_V>_F + sum_{(u,i) observed} [ c (1 - s)^2 - b s^2 ] + reg (tr G_U + tr G_V),     s = u . v
+ * from the two grams (fp32 slabs, added in fp64) and one pass over the CSR (s and everything after it in fp64).  Every reduction
+ * across rows, tiles or workgroups is fp64 in a fixed order, there are no atomics: two calls give the same bits.  The call
+ * synchronises and writes one double to *host_out.  Argument and index-error rules as for orx_als_half_step (a column outside the
+ * item table is left out of the sum and reported); a non-finite value in a table or a confidence gives a non-finite result. */
+int orx_als_objective(orx_ctx* ctx, orx_table* user, orx_table* item,
+                      const int64_t* row_ptr, const int32_t* cols, const float* conf /* or NULL */,
+                      float a, float b, float reg, int flags, double* host_out);
+
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,
  *                       PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads per range workgroup, threads of a big plan, references per

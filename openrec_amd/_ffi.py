@@ -94,6 +94,9 @@ SIGNATURES = {
     "orx_recommend_topk": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, c_int64, _p, _ip, c_int32, c_int, _ip, _fp]),
     "orx_als_segment_len": (c_int32, []),
     "orx_als_half_step": (c_int, [_p, _p, _p, _p, _ip, _fp, c_int64, c_int64, c_float, c_float, c_float, c_int]),
+    "orx_als_half_step_cg": (c_int, [_p, _p, _p, _p, _ip, _fp, c_int64, c_int64, c_float, c_float, c_float, c_int32, c_int]),
+    "orx_als_cg_row_breaks": (c_int32, [c_int32, _ip, c_int32]),
+    "orx_als_objective": (c_int, [_p, _p, _p, _p, _ip, _fp, c_float, c_float, c_float, c_int, POINTER(c_double)]),
     "orx_topk_rows": (c_int, [_p, _fp, c_int32, c_int64, c_int64, _p, _ip, c_int32, _ip, _fp]),
     "orx_sampler_create": (c_int, [_p, _ip, _ip, c_int64, _p, _ip, c_int64, c_int64, _pp]),
     "orx_sampler_destroy": (c_int, [_p]),

@@ -404,3 +404,29 @@ int orx_launch_als(orx_ctx* ctx, const float* F, int64_t M, int D, float* X, con
     orx_set_error("orx_als_half_step: dim %d outside [1, 128]", D);
     return ORX_ERR_ARG;
 }
+
+// the gram alone, for the callers that solve without A_r (kernels_als_cg.hip): Gm NULL leaves the slab partials unreduced
+template <int T>
+static int als_gram_T(orx_ctx* ctx, const float* F, int64_t M, int D, float* gram_part, float* Gm) {
+    using G = AlsGeom<T>;
+    const int nb = orx_als_gram_blocks(M);
+    ORX_LAUNCH(ctx, als_gram_kernel<T>, dim3(nb), dim3(ALS_THREADS), 0, F, M, D, gram_part);
+    if (Gm) ORX_LAUNCH(ctx, als_gram_reduce_kernel, dim3((G::Dp * G::Dp + 255) / 256), dim3(256), 0, (const float*)gram_part, nb, G::Dp, Gm);
+    ORX_HIP(hipGetLastError());
+    return ORX_OK;
+}
+
+int orx_launch_als_gram(orx_ctx* ctx, const float* F, int64_t M, int D, float* gram_part, float* Gm) {
+    switch ((D + 15) / 16) {
+        case 1: return als_gram_T<1>(ctx, F, M, D, gram_part, Gm);
+        case 2: return als_gram_T<2>(ctx, F, M, D, gram_part, Gm);
+        case 3: return als_gram_T<3>(ctx, F, M, D, gram_part, Gm);
+        case 4: return als_gram_T<4>(ctx, F, M, D, gram_part, Gm);
+        case 5: return als_gram_T<5>(ctx, F, M, D, gram_part, Gm);
+        case 6: return als_gram_T<6>(ctx, F, M, D, gram_part, Gm);
+        case 7: return als_gram_T<7>(ctx, F, M, D, gram_part, Gm);
+        case 8: return als_gram_T<8>(ctx, F, M, D, gram_part, Gm);
+    }
+    orx_set_error("ALS gram: dim %d outside [1, 128]", D);
+    return ORX_ERR_ARG;
+}

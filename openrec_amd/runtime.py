@@ -1470,47 +1470,95 @@ def _als_rows(rows, n):
     return row0, nrows
 
 
-def als_half_step(fixed, solved, csr, a=1.0, b=1.0, reg=0.1, rows=None):
+_ALS_SOLVERS = ("cholesky", "cg")
+
+
+def als_cg_row_breaks(dim):
+    """orx_als_cg_row_breaks: the row lengths at which the CG half-step changes its code path for tables of this dim, ascending
+    (entries kept in LDS / streamed per product / cut into segments across workgroups)"""
+    out = np.zeros(8, np.int32)
+    n = int(_ffi.load().orx_als_cg_row_breaks(int(dim), out.ctypes.data, out.size))
+    return [int(x) for x in out[:min(n, out.size)]]
+
+
+def _als_solver(what, solver, cg_steps):
+    if solver not in _ALS_SOLVERS:
+        raise ValueError(f"{what}: solver must be one of {_ALS_SOLVERS}, got {solver!r}")
+    cg_steps = int(cg_steps)
+    if not 1 <= cg_steps <= 128:
+        raise ValueError(f"{what}: cg_steps = {cg_steps} outside [1, 128]")
+    return cg_steps
+
+
+def _als_check(what, one, other, csr, a, b, reg):
+    """the argument rules the half-steps and the objective share -> (a, b, reg) as floats"""
+    if not isinstance(csr, ALSCsr):
+        raise ValueError(f"{what}: csr must be an ALSCsr (ALSData.by_user / .by_item)")
+    if one is other or one._h.value == other._h.value:
+        raise ValueError(f"{what}: fixed and solved are the same table")
+    if one.ctx is not other.ctx:
+        raise ValueError(f"{what}: the tables live on different contexts")
+    if one.dim != other.dim:
+        raise ValueError(f"{what}: fixed dim {one.dim}, solved dim {other.dim}")
+    if not 1 <= one.dim <= 128:
+        raise ValueError(f"{what}: dim {one.dim} outside [1, 128]")
+    a, b, reg = float(a), float(b), float(reg)
+    if not (np.isfinite(reg) and reg > 0):
+        raise ValueError(f"{what}: reg must be finite and > 0, got {reg!r}")
+    if not (np.isfinite(b) and b >= 0):
+        raise ValueError(f"{what}: b must be finite and >= 0, got {b!r}")
+    if csr.conf is None and not (np.isfinite(a) and a >= b):
+        raise ValueError(f"{what}: a = {a!r} must be finite and >= b = {b!r}")
+    if csr.shape != (other.rows, one.rows):
+        raise ValueError(f"{what}: a CSR of shape {csr.shape} for tables of {other.rows} and {one.rows} rows")
+    return a, b, reg
+
+
+def _als_csr_args(what, csr, ctx):
+    """-> (row_ptr, cols, conf, flags) as the library takes them"""
+    if csr.on_device:
+        dctx, ptr, cols, conf = csr._dev
+        if dctx is not ctx:
+            raise ValueError(f"{what}: the CSR was put on the device of another context")
+        return ptr.data_ptr(), cols.data_ptr(), conf.data_ptr() if conf is not None else None, _ffi.ORX_IDS_DEVICE
+    return csr.ptr.ctypes.data, csr.cols.ctypes.data, csr.conf.ctypes.data if csr.conf is not None else None, 0
+
+
+def als_half_step(fixed, solved, csr, a=1.0, b=1.0, reg=0.1, rows=None, solver="cholesky", cg_steps=3):
     """One ALS half-step of WRMF: `fixed` stays, rows `rows` (None: all; a range or (row0, nrows)) of `solved` are overwritten
     with the exact minimisers of  sum_cells c (p - x.f)^2 + reg |x|^2  given `fixed` -- observed cells (csr: an ALSCsr over the
     rows of `solved` and the rows of `fixed` as columns) have preference 1 and confidence csr.conf, or `a` when it is None;
     all others preference 0 and confidence `b`.  No bias term.  x is a function of the row's own data alone: the same bits for
-    any split into calls.  Bad arguments raise ValueError before the library is called; a column outside `fixed` IndexError."""
-    if not isinstance(csr, ALSCsr):
-        raise ValueError("als_half_step: csr must be an ALSCsr (ALSData.by_user / .by_item)")
-    if fixed is solved or fixed._h.value == solved._h.value:
-        raise ValueError("als_half_step: fixed and solved are the same table")
-    if fixed.ctx is not solved.ctx:
-        raise ValueError("als_half_step: the tables live on different contexts")
-    if fixed.dim != solved.dim:
-        raise ValueError(f"als_half_step: fixed dim {fixed.dim}, solved dim {solved.dim}")
-    if not 1 <= fixed.dim <= 128:
-        raise ValueError(f"als_half_step: dim {fixed.dim} outside [1, 128]")
-    a, b, reg = float(a), float(b), float(reg)
-    if not (np.isfinite(reg) and reg > 0):
-        raise ValueError(f"als_half_step: reg must be finite and > 0, got {reg!r}")
-    if not (np.isfinite(b) and b >= 0):
-        raise ValueError(f"als_half_step: b must be finite and >= 0, got {b!r}")
-    if csr.conf is None and not (np.isfinite(a) and a >= b):
-        raise ValueError(f"als_half_step: a = {a!r} must be finite and >= b = {b!r}")
-    if csr.shape != (solved.rows, fixed.rows):
-        raise ValueError(f"als_half_step: a CSR of shape {csr.shape} for tables of {solved.rows} and {fixed.rows} rows")
+    any split into calls.  solver="cg" replaces the exact minimiser by `cg_steps` steps of conjugate gradient started from the
+    row's current value (orx_als_half_step_cg): no factorisation, a descent step of the same objective (`als_objective`).
+    Bad arguments raise ValueError before the library is called; a column outside `fixed` IndexError."""
+    cg_steps = _als_solver("als_half_step", solver, cg_steps)
+    a, b, reg = _als_check("als_half_step", fixed, solved, csr, a, b, reg)
     row0, nrows = _als_rows(rows, solved.rows)
     fixed._sync_pending(); solved._sync_pending()
     lib = fixed.ctx._lib
-    if csr.on_device:
-        ctx, ptr, cols, conf = csr._dev
-        if ctx is not fixed.ctx:
-            raise ValueError("als_half_step: the CSR was put on the device of another context")
-        check(lib.orx_als_half_step(ctx._h, fixed._h, solved._h, ptr.data_ptr(), cols.data_ptr(),
-                                    conf.data_ptr() if conf is not None else None, row0, nrows, a, b, reg, _ffi.ORX_IDS_DEVICE))
+    ptr, cols, conf, flags = _als_csr_args("als_half_step", csr, fixed.ctx)
+    if solver == "cg":
+        check(lib.orx_als_half_step_cg(fixed.ctx._h, fixed._h, solved._h, ptr, cols, conf, row0, nrows, a, b, reg, cg_steps, flags))
     else:
-        check(lib.orx_als_half_step(fixed.ctx._h, fixed._h, solved._h, csr.ptr.ctypes.data, csr.cols.ctypes.data,
-                                    csr.conf.ctypes.data if csr.conf is not None else None, row0, nrows, a, b, reg, 0))
+        check(lib.orx_als_half_step(fixed.ctx._h, fixed._h, solved._h, ptr, cols, conf, row0, nrows, a, b, reg, flags))
     return solved
 
 
-def als_sweep(user, item, data, a=1.0, b=1.0, reg=0.1):
+def als_sweep(user, item, data, a=1.0, b=1.0, reg=0.1, solver="cholesky", cg_steps=3):
     """One ALS sweep: the user half-step (items fixed), then the item half-step (users fixed).  `data`: an ALSData."""
-    als_half_step(item, user, data.by_user, a, b, reg)
-    als_half_step(user, item, data.by_item, a, b, reg)
+    als_half_step(item, user, data.by_user, a, b, reg, solver=solver, cg_steps=cg_steps)
+    als_half_step(user, item, data.by_item, a, b, reg, solver=solver, cg_steps=cg_steps)
+
+
+def als_objective(user, item, data, a=1.0, b=1.0, reg=0.1):
+    """What the half-steps descend, on the device (orx_als_objective):  sum over ALL cells c (p - u.v)^2 + reg (|U|_F^2 + |V|_F^2)
+    from the two grams and one pass over the observations, reduced in fp64 in a fixed order (two calls give the same bits).
+    `data`: an ALSData, or the user -> items ALSCsr.  Synchronises; -> float."""
+    csr = data.by_user if isinstance(data, ALSData) else data
+    a, b, reg = _als_check("als_objective", item, user, csr, a, b, reg)
+    user._sync_pending(); item._sync_pending()
+    ptr, cols, conf, flags = _als_csr_args("als_objective", csr, user.ctx)
+    out = c_double()
+    check(user.ctx._lib.orx_als_objective(user.ctx._h, user._h, item._h, ptr, cols, conf, a, b, reg, flags, byref(out)))
+    return float(out.value)
