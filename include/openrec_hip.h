@@ -292,6 +292,60 @@ int orx_multineg_loss(orx_ctx* ctx, int loss_kind,
                       const float* weight /* NULL ok */, const float* neg_offset /* NULL ok */,
                       int64_t B, int32_t N, int flags, float* loss_out, float* l2_out);
 
+/* IN-BATCH NEGATIVES: K train steps of a dot-product model (BPR's tables) under the full-batch softmax of retrieval / two-tower
+ * training (Yi et al. 2019): the positive of every sample is scored against the positives of ALL samples of the batch.  No B x B
+ * matrix is stored.  Step s has B samples (uid[s*id_stride + i], pid[s*id_stride + i]); the item bias table is optional.
+ *   u_i = U[uid[i]],  v_j = V[pid[j]],  b_j = b[pid[j]]   (0 with bias == NULL)
+ *   s_ij = scale * (u_i . v_j + b_j) + off_j
+ * scale is finite and > 0 (1 / temperature).  off = item_offset[s*id_stride + j], 0 when item_offset == NULL: added to column j in
+ * every row, the diagonal included -- typically -log Q(pid[j]).  It must be finite and is not validated.
+ * Hit masking: hit(i, j) is true when ORX_IB_MASK_HITS is set, j != i and pid[j] == pid[i] (the row's own positive is not a
+ * negative).  N(i) = { j : not hit(i, j) } is the set of columns of row i, so i is always in N(i).
+ *   lse_i = logsumexp over j in N(i) of s_ij      evaluated with the maximum subtracted: |s| of 200 gives finite results
+ *   l_i   = lse_i - s_ii                          = log1p(sum over j != i of exp(s_ij - s_ii)) when the diagonal holds the maximum
+ *   loss    = (1/B) sum_i w_i l_i                 w_i = weight[s*id_stride + i], 1 when weight == NULL
+ *   l2_loss = 1/2 (sum_i |u_i|^2 + sum_i |v_i|^2) over the 2B looked-up rows: no biases, never weighted
+ *   J       = loss + l2_reg * l2_loss
+ * loss_out[s] is the loss, l2_out[s] the UNSCALED l2_loss, as in orx_multineg_step.  Gradients, per occurrence and on the pre-step
+ * tables, with c_i = w_i / B:
+ *   pi_ij = exp(s_ij - lse_i) for j in N(i), else 0;   A_i = sum over j != i of pi_ij  (the pi themselves, never 1 - pi_ii)
+ *   a_ij  = c_i pi_ij (j != i),   a_ii = -c_i A_i
+ *   g_u[i] = scale * sum_j a_ij v_j + l2_reg u_i,   g_v[j] = scale * sum_i a_ij u_i + l2_reg v_j,   g_b[j] = scale * sum_i a_ij
+ * The apply is orx_apply_rows': the user table with uid[B], then the item table and the bias with pid[B]; SGD accumulates every
+ * occurrence, Adagrad, momentum and Adam sum a row's occurrences first, Adam's counter advances once per step.  Lazily-applied
+ * Adam: exactly the rows a step reads are brought up to date before it.  A K-step call is K one-step calls, bit for bit;
+ * everything runs on the context's stream without a host synchronisation between steps, and loss_out == l2_out == NULL makes the
+ * call fully asynchronous.  weight and item_offset live where the ids live.  No float atomics in the step's own kernels or the
+ * loss sums: loss_out, l2_out and the row losses are bit-repeatable, and so are the tables when bias == NULL (the sorted apply).
+ * chunk_cols: 0 -- the launcher splits the columns of a row block into chunks as it sees fit, from (B, D) alone --, or a multiple
+ * of the tile width 64: that many columns per chunk.  flags: ORX_IDS_DEVICE, ORX_NO_L2, ORX_IB_MASK_HITS.
+ * B == 1: l = 0, only the l2 gradient moves the rows.  K == 0 or B == 0: ORX_OK, nothing is launched.
+ * ORX_ERR_ARG before any device work: scale not finite or <= 0; l2_reg negative or not finite; ORX_NO_L2 with l2_reg != 0;
+ * ORX_HOGWILD or ORX_CENSOR; user dim != item dim, or a dim above 256; a bias that is not [item rows, 1]; tables or optimizer on
+ * another context; chunk_cols negative or no multiple of 64; what orx_apply_rows refuses (ORX_ADAM_DENSE with a bias).
+ * An id outside its table: ORX_ERR_INDEX as orx_multineg_step reports it.  The bad id is never used as an address; its sample
+ * contributes no loss, no l2 and no gradient and leaves every other row's softmax as a column; the context stays usable.
+ * Not offered: UCML / L2 scoring, train masks, the sharded engines, a symmetric (item -> user) loss. */
+enum orx_inbatch_flags { ORX_IB_MASK_HITS = 0x1000 };
+int orx_inbatch_step(orx_ctx* ctx, orx_opt* opt,
+                     orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                     const int32_t* uid, const int32_t* pid,
+                     const float* weight /* NULL ok */, const float* item_offset /* NULL ok */,
+                     int64_t K, int64_t B, int64_t id_stride, float scale, float l2_reg, int32_t chunk_cols, int flags,
+                     float* loss_out, float* l2_out);
+/* Forward only, by the same kernels: (loss, l2_loss) of one batch -- the step's loss_out / l2_out bit for bit on the same tables
+ * -- and, if row_loss_out is not NULL, l_i of every sample ([B], where the ids live; 0 for a sample with an id out of range).
+ * No table changes.  flags: ORX_IDS_DEVICE, ORX_IB_MASK_HITS. */
+int orx_inbatch_loss(orx_ctx* ctx,
+                     orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                     const int32_t* uid, const int32_t* pid,
+                     const float* weight /* NULL ok */, const float* item_offset /* NULL ok */,
+                     int64_t B, float scale, int32_t chunk_cols, int flags,
+                     float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+/* What the launcher does for (B, D, chunk_cols): out = { own rows per workgroup, columns per tile, column chunks per row block,
+ * padded dim }.  No device is needed. */
+int orx_inbatch_geometry(int64_t B, int32_t D, int32_t chunk_cols, int32_t out[4]);
+
 /* K train steps of GMF.call / WRMF.call (gmf.py:22-34, wrmf.py:21-34,
  * pointwise_mse_loss.py:18-31).  w: GMF's Dense(1, use_bias=False) kernel as a
  * [D,1] table (NULL for WRMF).  a, b: WRMF confidence weights (wrmf.py:7). */

@@ -17,6 +17,7 @@ ORX_GMF, ORX_WRMF = 0, 1
 ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID, ORX_OUT_DEVICE = 1, 2, 4, 8, 16, 32
 ORX_TRAIN_USER, ORX_TRAIN_ITEM, ORX_TRAIN_BIAS = 1, 2, 4      # enum orx_train_mask
 ORX_MN_SOFTMAX, ORX_MN_LOGSIG = 0, 1                          # enum orx_multineg_kind
+ORX_IB_MASK_HITS = 0x1000                                     # enum orx_inbatch_flags
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
 ORX_DLRM_FP16_MLP = 32
@@ -69,6 +70,10 @@ SIGNATURES = {
     "orx_multineg_step": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int32, c_int64,
                                   c_float, c_int, _fp, _fp]),
     "orx_multineg_loss": (c_int, [_p, c_int, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, c_int64, c_int32, c_int, _fp, _fp]),
+    "orx_inbatch_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int64, c_float, c_float, c_int32, c_int,
+                                 _fp, _fp]),
+    "orx_inbatch_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _fp, _fp, c_int64, c_float, c_int32, c_int, _fp, _fp, _fp]),
+    "orx_inbatch_geometry": (c_int, [c_int64, c_int32, c_int32, POINTER(c_int32)]),
     "orx_sampler_pairwise_multi": (c_int, [_p, c_uint64, c_int64, c_int64, c_int32, _ip, _ip, _ip]),
     "orx_pointwise_step_l2reg": (c_int, [_p, c_int, _p, _p, _p, _p, _p, _ip, _ip, _fp, c_int64, c_int64, c_int64,
                                          c_float, c_float, c_float, c_int, c_int, _fp, _fp]),

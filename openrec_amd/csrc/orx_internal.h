@@ -914,6 +914,29 @@ int orx_multineg_nwaves(orx_ctx* ctx, int D, int64_t B);
 int orx_launch_multineg(orx_ctx* ctx, int kind /* orx_multineg_kind */, bool grads, const MultiNegArgs& a);
 int orx_launch_sample_multi(orx_ctx* ctx, const SamplerArgs& a, int M);      // a.nid [n * M]
 
+// kernels_inbatch.hip (orx_inbatch_step / orx_inbatch_loss): one step of the in-batch softmax.  Bp = B rounded up to 64, Dp = D
+// rounded up to 16; every [Bp] / [Bp][Dp] / [nch][..] array is scratch carved from the context's d_tmp
+struct InBatchArgs {
+    const float* U; const float* V; const float* b;       // read only; b NULL: no item bias
+    const int32_t* uid; const int32_t* pid;               // this step's ids [B]
+    const float* wt; const float* off;                    // [B] weights (NULL: all ones), [B] column offsets (NULL: 0)
+    int64_t B; int64_t Bp; int64_t NU; int64_t NI;
+    int D; int Dp; int gs; int nch; int tpc; int mask;    // nch column chunks of tpc tiles of 64; mask: ORX_IB_MASK_HITS
+    float scale; float invB; float l2w;
+    float* xu; float* xv;                                 // [Bp][Dp] the gathered rows
+    int32_t* key; float* cb; float* co; float* cw; float* sq;     // [Bp] pid or -1, bias, offset, w / B, |u|^2 + |v|^2
+    float* pm; float* pe; float* psd;                     // [nch][Bp] the chunks' running maximum, off-diagonal sum, diagonal score
+    float* rmax; float* cn; float* dcoef; float* rowloss; // [Bp] the row maximum m_i (+inf: a dead row), c_i / tot_i, -c_i A_i, l_i
+    float* gpu; float* gpv; float* bpart;                 // [nch][Bp][Dp] partial gradient tiles of the two sides, [nch][Bp] of the bias
+    float* gu; float* gi;                                 // [B][gs] gradient rows, the bias gradient in column D of gi
+    float* partial;                                       // [orx_inbatch_npartials(B)][2] loss / l2 partials of this step
+    int* err;
+};
+inline int orx_inbatch_npartials(int64_t B) { return (int)((((B + 63) & ~(int64_t)63) + 255) / 256); }
+void orx_inbatch_plan(int64_t B, int32_t D, int32_t chunk_cols, int32_t out[4], int* tiles_per_chunk = nullptr);
+int orx_launch_inbatch_forward(orx_ctx* ctx, const InBatchArgs& a);     // gather, LSE pass, finalize
+int orx_launch_inbatch_grads(orx_ctx* ctx, const InBatchArgs& a);       // the two gradient walks, the finishing pass
+
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {
     SamplerArgs s;

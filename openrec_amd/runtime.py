@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import ctypes
 import weakref
-from ctypes import byref, c_double, c_int64, c_void_p
+from ctypes import byref, c_double, c_int32, c_int64, c_void_p
 
 import os
 
@@ -481,6 +481,124 @@ def multineg_loss(loss, user, item, bias, uid, pid, nid, weights=None, neg_offse
     check(user.ctx._lib.orx_multineg_loss(user.ctx._h, kind, user._h, item._h, _bias_h(bias), *ptrs, B, N,
                                           _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
     return float(out[0][0]), float(out[1][0])
+
+
+def _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights, item_offset, scale, chunk):
+    """the checks and the pointers inbatch_step and inbatch_loss share; every bad argument is a ValueError raised here, before
+    the library is called"""
+    if user.shape[1] != item.shape[1]:
+        raise ValueError(f"{what}: user dim {user.shape[1]} != item dim {item.shape[1]} (dot scores only)")
+    if user.shape[1] > 256:
+        raise ValueError(f"{what}: dim {user.shape[1]} above 256")
+    if bias is not None and tuple(bias.shape) != (item.shape[0], 1):
+        raise ValueError(f"{what}: bias must be [{item.shape[0]}, 1], got {list(bias.shape)}")
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"{what}: scale must be finite and > 0 (got {scale})")
+    chunk = int(chunk)
+    if chunk < 0 or chunk % 64:
+        raise ValueError(f"{what}: chunk = {chunk}; 0 (the launcher's choice) or a multiple of the tile width 64")
+    pu, nu, du, k0 = _ids_arg(uid)
+    pp, npn, dp, k1 = _ids_arg(pid)
+    if du != dp:
+        raise ValueError(f"{what}: ids must be all on the host or all on the device")
+    K = int(K)
+    if K < 0:
+        raise ValueError(f"{what}: K = {K}")
+    if B is None:
+        B = nu // K if K else 0
+    B = int(B)
+    if id_stride is None:
+        id_stride = B
+    id_stride = int(id_stride)
+    if B < 0 or id_stride < B:
+        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
+    need = (K - 1) * id_stride + B if K and B else 0
+    if nu != npn or nu < need:
+        raise ValueError(f"{what}: {nu} user ids and {npn} positive ids for K = {K}, B = {B}, id_stride = {id_stride} "
+                         "(uid and pid alike)")
+    pw = po = None
+    keep = [k0, k1]
+    if weights is not None:
+        pw, kw = _weights_arg(weights, du, nu, what)
+        keep.append(kw)
+    if item_offset is not None:
+        po, no, do, ko = _label_arg(item_offset)
+        if do != du:
+            raise ValueError(f"{what}: item_offset on the {'device' if do else 'host'} with ids on the {'device' if du else 'host'} "
+                             "(the offsets live where the ids live)")
+        if no != nu:
+            raise ValueError(f"{what}: {no} offsets for {nu} ids (item_offset is shaped like pid)")
+        keep.append(ko)
+    user.ctx.after_torch(uid, pid, weights, item_offset)
+    return K, B, id_stride, du, (pu, pp, pw, po), scale, chunk, keep
+
+
+def inbatch_step(opt, user, item, bias, uid, pid, K=1, B=None, id_stride=None, weights=None, item_offset=None, scale=1.0,
+                 mask_hits=True, l2_reg=1.0, no_l2=False, want_loss=True, chunk=0):
+    """K train steps on in-batch negatives (orx_inbatch_step): the positive of every sample is scored against the positives of
+    all B samples of its step, s_ij = scale (u_i . v_j + b_j) + off_j, and the loss is the softmax over the row -- no sampler, no
+    B x B matrix.  uid / pid as in pairwise_step; bias=None: no item bias.  weights: per-sample weights; item_offset: added to
+    column j in every row (-log Q(pid[j]) is the log-Q correction); both shaped like the ids and living where they live.
+    scale = 1 / temperature.  mask_hits: a column with the row's own positive item (other than the diagonal) is no negative.
+    The objective is loss + l2_reg * l2_loss (no_l2=True: l2_reg = 0).  chunk: columns per chunk of a row block, 0 for the
+    launcher's choice.  Returns (loss[K], l2[K]) as numpy float32 -- l2 the unscaled l2_loss -- when want_loss, else None
+    (fully asynchronous).  Bad arguments raise ValueError before the library is called; an id outside its table IndexError."""
+    what = "inbatch_step"
+    if no_l2:
+        if l2_reg not in (None, 0, 0.0, 1.0):
+            raise ValueError(f"{what}: no_l2=True together with l2_reg = {l2_reg} (drop no_l2, or pass l2_reg=0.0)")
+        l2_reg = 0.0
+    l2c = float(1.0 if l2_reg is None else l2_reg)
+    if not (np.isfinite(l2c) and l2c >= 0.0):
+        raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+    K, B, id_stride, dev, ptrs, scale, chunk, keep = _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights,
+                                                                   item_offset, scale, chunk)
+    if want_loss:
+        out = np.empty(K, np.float32), np.empty(K, np.float32)
+        lp, l2p = out[0].ctypes.data, out[1].ctypes.data
+    else:
+        out = None
+        lp = l2p = None
+    flags = (_ffi.ORX_IDS_DEVICE if dev else 0) | (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0)
+    check(user.ctx._lib.orx_inbatch_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, id_stride, scale, l2c,
+                                         chunk, flags, lp, l2p))
+    _keep_tables(opt, (user, item, bias))
+    return out
+
+
+def inbatch_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, mask_hits=True, chunk=0, per_row=False):
+    """forward only: (loss, l2_loss) of one batch of inbatch_step -- the step's own numbers bit for bit on the same tables; no
+    table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+    _, B, _, dev, ptrs, scale, chunk, keep = _inbatch_args("inbatch_loss", user, item, bias, uid, pid, 1, None, None, weights,
+                                                           item_offset, scale, chunk)
+    out = np.empty(1, np.float32), np.empty(1, np.float32)
+    rows = rp = None
+    if per_row:
+        if dev:
+            import torch
+            rows = torch.empty(B, dtype=torch.float32, device=torch.device("cuda", user.ctx.device))
+            user.ctx.after_torch(rows)
+            rp = rows.data_ptr()
+        else:
+            rows = np.empty(B, np.float32)
+            rp = rows.ctypes.data
+    flags = (_ffi.ORX_IDS_DEVICE if dev else 0) | (_ffi.ORX_IB_MASK_HITS if mask_hits else 0)
+    check(user.ctx._lib.orx_inbatch_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, chunk, flags,
+                                         out[0].ctypes.data, out[1].ctypes.data, rp))
+    if not per_row:
+        return float(out[0][0]), float(out[1][0])
+    if dev:
+        rows = rows.cpu().numpy()          # (the call has synchronised the context's stream for the two sums)
+    return float(out[0][0]), float(out[1][0]), rows
+
+
+def inbatch_geometry(B, D, chunk=0):
+    """what the launcher of inbatch_step does for (B, D, chunk): a dict of own rows per workgroup, columns per tile, column
+    chunks per row block and the padded dim.  No device is needed."""
+    out = (c_int32 * 4)()
+    check(_ffi.load().orx_inbatch_geometry(int(B), int(D), int(chunk), out))
+    return dict(rows=int(out[0]), tile=int(out[1]), chunks=int(out[2]), dim=int(out[3]))
 
 
 def _label_arg(x):

@@ -355,3 +355,25 @@ class PairwiseRecommender(Recommender):
         off = _ids(neg_offset) if neg_offset is not None else None
         return rt.multineg_step(loss, opt, U, V, b, uid, pid, nid, K=K, weights=wts, neg_offset=off, l2_reg=self.l2_reg,
                                 want_loss=want_loss)
+
+    def train_steps_inbatch(self, optimizer, user_id, p_item_id, K=None, want_loss=True, sample_weight=None, item_offset=None,
+                            scale=1.0, mask_hits=True):
+        """Beyond the reference API: K consecutive steps on in-batch negatives in one device call (rt.inbatch_step): every
+        sample's positive against the positives of all samples of its step, under a softmax over the row.  user_id / p_item_id
+        shaped [K, B] (or [B]: one step).  sample_weight: per-sample weights; item_offset: added to column j of every row
+        (-log Q(item) is the log-Q correction); both shaped like the ids.  scale = 1 / temperature; mask_hits: a column with the
+        row's own positive item is no negative.  The objective is loss + l2_reg * l2_loss with the model's l2_reg; the returned
+        l2 is the unscaled l2_loss.  Dot-product models only: it goes through no tape, takes no train mask, and UCML raises
+        NotImplementedError."""
+        if self._model != "bpr":
+            raise NotImplementedError(f"{type(self).__name__}.train_steps_inbatch: the in-batch step scores by dot products "
+                                      "(u.v + b); UCML's squared-distance scores are not supported by it")
+        U, V, b = self._tables()
+        uid, pid = _ids(user_id), _ids(p_item_id)
+        if K is None:
+            K = uid.shape[0] if getattr(uid, "ndim", 1) == 2 else 1
+        opt = optimizer.native(U.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(item_offset) if item_offset is not None else None
+        return rt.inbatch_step(opt, U, V, b, uid, pid, K=K, weights=wts, item_offset=off, scale=scale, mask_hits=mask_hits,
+                               l2_reg=self.l2_reg, want_loss=want_loss)
