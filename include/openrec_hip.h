@@ -1002,6 +1002,78 @@ int orx_als_objective(orx_ctx* ctx, orx_table* user, orx_table* item,
                       const int64_t* row_ptr, const int32_t* cols, const float* conf /* or NULL */,
                       float a, float b, float reg, int flags, double* host_out);
 
+/* ---- graph propagation over a CSR (api_graph.hip, kernels_graph.hip; DESIGN.md "LightGCN") ----------------------------------
+ * One half-layer of LightGCN's propagation.  For rows [row0, row0 + nrows) of a CSR over the rows of `out`, whose columns index
+ * the rows of X:
+ *     y[r]    = row_scale[r] * sum_{e in row r, in CSR order} col_scale[cols[e]] * X[cols[e]]          (fp32)
+ *     out[r]  = y[r]
+ *     acc[r] += acc_alpha * y[r]                                                                       (acc != NULL)
+ * row_scale / col_scale are DEVICE arrays over all rows of out / X (NULL: 1).  An empty row writes exact +0.0 to out and leaves
+ * acc alone.  Rows of more than orx_graph_segment_len() entries are cut into segments of that many entries, each summed from
+ * zero by a wavefront of its own; the row adds the partial sums in segment order.  No float atomics anywhere: y[r] is a function
+ * of (X, the row's entries, the scales) alone -- the same bits for any row range, any split into calls, any other rows in the
+ * call, a host or a device CSR -- and the order in which a row's terms are added is a function of the row's length and the dim
+ * alone.  No trip count depends on a float: non-finite inputs give non-finite outputs.
+ *   long_segments   only read with a device CSR, where the host cannot see the row lengths: the number of segments of the CSR's
+ *           rows of more than orx_graph_segment_len() entries, sum over those rows of ceil(n / segment_len), counted once by the
+ *           caller (an upper bound serves every row range).  It sizes the scratch of the partial sums and, when 0, skips the plan
+ *           and the segment launch altogether.  A count that is too small is safe: a long row that finds no scratch slot walks its
+ *           segments itself, the same sums in the same order, the same bits.  < 0: unknown; the scratch is then sized from the
+ *           rows of X (a row's columns are distinct), up to 256 MiB that stay reserved on the context.
+ *   flags   ORX_IDS_DEVICE: row_ptr and cols are device pointers and the call runs on the context's stream without a host
+ *           synchronisation; else they are host arrays, the rows' part is copied over and the call returns after
+ *           orx_check_index_error.
+ * ORX_ERR_ARG before any launch: X == out or X == acc or out == acc; dims that differ or lie outside [1, 128]; acc with other
+ * rows than out; a row range outside out; a table on another context; unknown flags.  A column outside X is dropped from its
+ * row and reported (ORX_ERR_INDEX from this call with a host CSR, from orx_check_index_error with a device CSR).  nrows == 0
+ * launches nothing.  Lazily-applied Adam is finished on all three tables before they are touched. */
+int32_t orx_graph_segment_len(void);
+int orx_graph_spmm(orx_ctx* ctx, orx_table* X, orx_table* out, orx_table* acc /* or NULL */, float acc_alpha,
+                   const int64_t* row_ptr, const int32_t* cols,
+                   const float* row_scale /* or NULL */, const float* col_scale /* or NULL */,
+                   int64_t row0, int64_t nrows, int64_t long_segments, int flags);
+
+/* The Keras DENSE rule of `opt` on every element of `table` with the device gradient grad [rows][dim] (read only): SGD, momentum /
+ * Nesterov, Adagrad, Adam.  Adam's counter advances by one first (other tables lazily applied under `opt` are finished and leave
+ * the lazy set, as in orx_pairwise_step) and the step is taken at the new count; the table's lazily-applied Adam is finished
+ * before, so afterwards every row is current at that step and the table can go to orx_pairwise_step and back. */
+int orx_table_apply_dense(orx_ctx* ctx, orx_opt* opt, orx_table* table, const float* grad);
+
+/* ---- LightGCN (api_lightgcn.hip) -------------------------------------------------------------------------------------------
+ *     E(0) = [user ; item],  E(k+1) = A~ E(k) (k < layers),  E_f = sum_k layer_weights[k] E(k),
+ *     A~[u, i] = user_scale[u] * item_scale[i] on observed (u, i), symmetric
+ * The workspace keeps the layer tables, the propagated tables (user_final, item_final of orx_lightgcn_tables: ordinary tables of
+ * this context, owned by the workspace, valid until the next step or propagate) and the gradient tables.  It does NOT own the
+ * two CSRs (user -> items, item -> users: device arrays) and the two scale vectors (device, both NULL: a plain neighbour sum),
+ * which must outlive it.  layer_weights: host float[layers + 1] or NULL for 1 / (layers + 1).
+ *   propagate   (user, item) -> (user_final, item_final): 2 layers orx_graph_spmm calls with the layer sum fused through acc
+ *   step        one BPR step (no item bias) on the propagated rows of the triplets uid / pid / nid [B]:
+ *               loss = mean_B -log sigmoid(s_p - s_n),  l2 = l2_reg / B * sum_b (|user[u]|^2 + |item[p]|^2 + |item[n]|^2) / 2
+ *               over the LAYER-0 rows.  The per-occurrence gradients are summed into dense tables by a stable sort and sums in
+ *               position order, propagated by the same operator (backward = forward), the l2 gradient is added per occurrence,
+ *               and the dense rule of `opt` is applied to user and item (train_mask: ORX_TRAIN_USER | ORX_TRAIN_ITEM, 0 = both;
+ *               Adam's counter advances once).  No float atomics touch a table: two steps from one state give the same bits.
+ *               loss_out == l2_out == NULL and ORX_IDS_DEVICE: no host synchronisation.
+ *   loss        the forward alone -> (loss, l2); no table of the model changes.
+ * ORX_ERR_ARG before any device work: layers outside [1, ORX_LIGHTGCN_MAX_LAYERS]; dims that differ or lie outside [1, 128];
+ * user == item; a table or optimizer on another context; one scale vector without the other; l2_reg negative or not finite;
+ * mask bits outside the two; unknown flags.  An id outside its table: ORX_ERR_INDEX as orx_pairwise_step reports it; the id is
+ * never used as an address. */
+#define ORX_LIGHTGCN_MAX_LAYERS 8
+typedef struct orx_lightgcn orx_lightgcn;
+int orx_lightgcn_create(orx_ctx* ctx, orx_table* user, orx_table* item,
+                        const int64_t* user_ptr, const int32_t* user_cols, const int64_t* item_ptr, const int32_t* item_cols,
+                        const float* user_scale /* or NULL */, const float* item_scale /* or NULL */,
+                        int64_t user_long_segments, int64_t item_long_segments /* as orx_graph_spmm's, per CSR; < 0: unknown */,
+                        int32_t layers, const float* layer_weights /* or NULL */, orx_lightgcn** out);
+int orx_lightgcn_destroy(orx_lightgcn* g);
+int orx_lightgcn_tables(orx_lightgcn* g, orx_table** user_final, orx_table** item_final);
+int orx_lightgcn_propagate(orx_lightgcn* g);
+int orx_lightgcn_step(orx_lightgcn* g, orx_opt* opt, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t B,
+                      float l2_reg, int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_lightgcn_loss(orx_lightgcn* g, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t B,
+                      float l2_reg, int flags, float* loss_out, float* l2_out);
+
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,
  *                       PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads per range workgroup, threads of a big plan, references per

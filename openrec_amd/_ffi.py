@@ -102,6 +102,15 @@ SIGNATURES = {
     "orx_als_half_step_cg": (c_int, [_p, _p, _p, _p, _ip, _fp, c_int64, c_int64, c_float, c_float, c_float, c_int32, c_int]),
     "orx_als_cg_row_breaks": (c_int32, [c_int32, _ip, c_int32]),
     "orx_als_objective": (c_int, [_p, _p, _p, _p, _ip, _fp, c_float, c_float, c_float, c_int, POINTER(c_double)]),
+    "orx_graph_segment_len": (c_int32, []),
+    "orx_graph_spmm": (c_int, [_p, _p, _p, _p, c_float, _p, _ip, _fp, _fp, c_int64, c_int64, c_int64, c_int]),
+    "orx_table_apply_dense": (c_int, [_p, _p, _p, _fp]),
+    "orx_lightgcn_create": (c_int, [_p, _p, _p, _p, _ip, _p, _ip, _fp, _fp, c_int64, c_int64, c_int32, _fp, _pp]),
+    "orx_lightgcn_destroy": (c_int, [_p]),
+    "orx_lightgcn_tables": (c_int, [_p, _pp, _pp]),
+    "orx_lightgcn_propagate": (c_int, [_p]),
+    "orx_lightgcn_step": (c_int, [_p, _p, _ip, _ip, _ip, c_int64, c_float, c_int, c_int, POINTER(c_float), POINTER(c_float)]),
+    "orx_lightgcn_loss": (c_int, [_p, _ip, _ip, _ip, c_int64, c_float, c_int, POINTER(c_float), POINTER(c_float)]),
     "orx_topk_rows": (c_int, [_p, _fp, c_int32, c_int64, c_int64, _p, _ip, c_int32, _ip, _fp]),
     "orx_sampler_create": (c_int, [_p, _ip, _ip, c_int64, _p, _ip, c_int64, c_int64, _pp]),
     "orx_sampler_destroy": (c_int, [_p]),

@@ -320,16 +320,20 @@ int orx_rows_sort(orx_ctx* ctx, const int32_t* ids, int64_t K, int64_t n, int64_
     return ORX_OK;
 }
 
-static int csr_args(orx_ctx* ctx, orx_table* t, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride, CsrArgs* a) {
+static int csr_args_raw(orx_ctx* ctx, float* W, int64_t rows, int dim, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride, CsrArgs* a) {
     memset(a, 0, sizeof(*a));
-    ORX_ARG(t->dim <= 256, "rows apply: dims up to 256 (got %d)", t->dim);
-    a->sorted = sorted; a->n = n; a->rows = (uint32_t)t->rows; a->D = t->dim; a->grads = grads; a->g_stride = g_stride; a->W = t->w;
-    a->Dp = (t->dim + 3) & ~3;
+    ORX_ARG(dim <= 256, "rows apply: dims up to 256 (got %d)", dim);
+    a->sorted = sorted; a->n = n; a->rows = (uint32_t)rows; a->D = dim; a->grads = grads; a->g_stride = g_stride; a->W = W;
+    a->Dp = (dim + 3) & ~3;
     const size_t bytes = (size_t)((n + 63) / 64) * a->Dp * sizeof(float);
     if (orx_ensure((void**)&ctx->d_csr_part[0], &ctx->d_csr_part_cap[0], bytes) != ORX_OK) return ORX_ERR_OOM;
     if (orx_ensure((void**)&ctx->d_csr_part[1], &ctx->d_csr_part_cap[1], bytes) != ORX_OK) return ORX_ERR_OOM;
     a->part_lo = ctx->d_csr_part[0]; a->part_hi = ctx->d_csr_part[1];
     return ORX_OK;
+}
+
+static int csr_args(orx_ctx* ctx, orx_table* t, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride, CsrArgs* a) {
+    return csr_args_raw(ctx, t->w, t->rows, t->dim, sorted, n, grads, g_stride, a);
 }
 
 // SGD / Adagrad / momentum on the sorted list (one step)
@@ -390,6 +394,16 @@ int orx_csr_accum(orx_ctx* ctx, orx_table* t, const uint2* sorted, int64_t n, co
     if (int rc = csr_args(ctx, t, sorted, n, grads, g_stride, &a)) return rc;
     if (int rc = orx_table_scratch(t)) return rc;
     a.G = t->gsum;
+    return launch_csr<CSR_ACCUM>(ctx, a);
+}
+
+// the same into a dense buffer G [rows][dim] that belongs to no table: G[row] += sum of the row's gradient rows, in position order
+int orx_csr_accum_into(orx_ctx* ctx, float* G, int64_t rows, int dim, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride) {
+    if (n == 0) return ORX_OK;
+    ProfScope ps(ctx, ORX_K_DUPAPPLY);
+    CsrArgs a;
+    if (int rc = csr_args_raw(ctx, nullptr, rows, dim, sorted, n, grads, g_stride, &a)) return rc;
+    a.G = G;
     return launch_csr<CSR_ACCUM>(ctx, a);
 }
 

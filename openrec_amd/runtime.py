@@ -1574,17 +1574,17 @@ class ALSData:
             self.by_user, self.by_item = self.by_user.to_device(self.ctx), self.by_item.to_device(self.ctx)
 
 
-def _als_rows(rows, n):
+def _als_rows(rows, n, what="als_half_step", table="the solved table"):
     if rows is None:
         return 0, n
     if isinstance(rows, range):
         if rows.step != 1:
-            raise ValueError("als_half_step: rows must be a contiguous range")
+            raise ValueError(f"{what}: rows must be a contiguous range")
         row0, nrows = (rows.start, len(rows)) if len(rows) else (0, 0)
     else:
         row0, nrows = (int(x) for x in rows)
     if row0 < 0 or nrows < 0 or row0 + nrows > n:
-        raise ValueError(f"als_half_step: rows [{row0}, {row0 + nrows}) outside the solved table's {n} rows")
+        raise ValueError(f"{what}: rows [{row0}, {row0 + nrows}) outside {table}'s {n} rows")
     return row0, nrows
 
 
@@ -1680,3 +1680,277 @@ def als_objective(user, item, data, a=1.0, b=1.0, reg=0.1):
     out = c_double()
     check(user.ctx._lib.orx_als_objective(user.ctx._h, user._h, item._h, ptr, cols, conf, a, b, reg, flags, byref(out)))
     return float(out.value)
+
+
+# ---- graph propagation and LightGCN (orx_graph_spmm, orx_table_apply_dense, orx_lightgcn_*) ----------------------------------
+LIGHTGCN_MAX_LAYERS = 8
+_GRAPH_NORMS = ("sym", "none")
+
+
+def graph_segment_len():
+    """orx_graph_segment_len: rows of more entries than this are cut into segments, summed by separate wavefronts and added in
+    segment order"""
+    return int(_ffi.load().orx_graph_segment_len())
+
+
+def graph_scales(csr):
+    """the symmetric normalisation's scale of every row of `csr`, on the host in float32: 1 / sqrt(degree), exact 0 for degree 0
+    (the bits are NumPy's, not a device rsqrt's)"""
+    deg = np.diff(csr.ptr).astype(np.float32)
+    out = np.zeros(deg.shape, np.float32)
+    nz = deg > 0
+    out[nz] = np.float32(1) / np.sqrt(deg[nz])
+    return out
+
+
+def graph_long_segments(csr):
+    """the number of segments of the rows of `csr` that are longer than graph_segment_len(), sum of ceil(n / segment_len) over
+    those rows: what orx_graph_spmm sizes its scratch of partial sums from when the CSR lives on the device (0: no row is cut,
+    no plan and no segment launch).  Counted once from the host arrays and kept on the ALSCsr."""
+    n = getattr(csr, "_graph_long", None)
+    if n is None:
+        S = graph_segment_len()
+        deg = np.diff(csr.ptr)
+        deg = deg[deg > S]
+        n = csr._graph_long = int(((deg + S - 1) // S).sum())
+    return n
+
+
+class InteractionGraph:
+    """The user-item graph of an interaction set, prepared for propagation: both CSRs of an `ALSData` (user -> items, item ->
+    users) and the two scale vectors in HBM (needs torch).  `data_or_raw`: an ALSData, or the structured array ('user_id',
+    'item_id') ALSData takes, with total_users / total_items.  norm="sym": edge (u, i) weighs 1 / sqrt(deg u . deg i), formed as
+    a row scale times a column scale; norm="none": unit scales, a plain neighbour sum.  Confidences of the ALSCsr lists are
+    IGNORED: every observed pair is one unweighted edge."""
+
+    def __init__(self, data_or_raw, total_users=None, total_items=None, norm="sym", ctx=None):
+        if norm not in _GRAPH_NORMS:
+            raise ValueError(f"InteractionGraph: norm must be one of {_GRAPH_NORMS}, got {norm!r}")
+        if isinstance(data_or_raw, ALSData):
+            data = data_or_raw
+            if ctx is not None and ctx is not data.ctx:
+                raise ValueError("InteractionGraph: the ALSData lives on another context")
+            if (total_users is not None and int(total_users) != data.total_users) or \
+                    (total_items is not None and int(total_items) != data.total_items):
+                raise ValueError("InteractionGraph: total_users / total_items differ from the ALSData's")
+        else:
+            if total_users is None or total_items is None:
+                raise ValueError("InteractionGraph: raw records need total_users and total_items")
+            data = ALSData(data_or_raw, total_users, total_items, ctx=ctx)
+        self.data, self.ctx, self.norm = data, data.ctx, norm
+        self.total_users, self.total_items, self.nnz = data.total_users, data.total_items, data.nnz
+        self.by_user = data.by_user if data.by_user.on_device else data.by_user.to_device(self.ctx)
+        self.by_item = data.by_item if data.by_item.on_device else data.by_item.to_device(self.ctx)
+        self.user_scale_host = self.item_scale_host = None
+        self.user_scale = self.item_scale = None
+        if norm == "sym":
+            import torch
+            dv = torch.device("cuda", self.ctx.device)
+            self.user_scale_host, self.item_scale_host = graph_scales(self.by_user), graph_scales(self.by_item)
+            self.user_scale = torch.from_numpy(self.user_scale_host).to(dv)
+            self.item_scale = torch.from_numpy(self.item_scale_host).to(dv)
+            torch.cuda.current_stream(dv).synchronize()        # complete before the library's stream reads them
+
+    def _scale_ptrs(self):
+        if self.user_scale is None:
+            return None, None
+        return self.user_scale.data_ptr(), self.item_scale.data_ptr()
+
+
+def _graph_scale_arg(what, name, x, n, ctx):
+    """a scale vector -> (pointer or None, keepalive): a float32 device tensor of n entries, or a host array that is uploaded"""
+    if x is None:
+        return None, None
+    if not _is_device_tensor(x):
+        import torch
+        h = np.ascontiguousarray(np.asarray(x), np.float32).reshape(-1)
+        x = torch.from_numpy(h).to(torch.device("cuda", ctx.device))
+        torch.cuda.current_stream(x.device).synchronize()
+    if not str(x.dtype).endswith("float32") or x.numel() != n or not x.is_contiguous():
+        raise ValueError(f"{what}: {name} must be {n} contiguous float32 values")
+    ctx.after_torch(x)
+    return x.data_ptr(), x
+
+
+def _graph_check(what, X, out, acc, csr):
+    if not isinstance(csr, ALSCsr):
+        raise ValueError(f"{what}: csr must be an ALSCsr (InteractionGraph.by_user / .by_item)")
+    tabs = [("X", X), ("out", out)] + ([("acc", acc)] if acc is not None else [])
+    for i, (na, a) in enumerate(tabs):
+        for nb, b in tabs[i + 1:]:
+            if a is b or a._h.value == b._h.value:
+                raise ValueError(f"{what}: {na} and {nb} are the same table")
+    for name, t in tabs:
+        if t.ctx is not X.ctx:
+            raise ValueError(f"{what}: the tables live on different contexts")
+        if t.dim != X.dim:
+            raise ValueError(f"{what}: X dim {X.dim}, {name} dim {t.dim}")
+    if not 1 <= X.dim <= 128:
+        raise ValueError(f"{what}: dim {X.dim} outside [1, 128]")
+    if acc is not None and acc.rows != out.rows:
+        raise ValueError(f"{what}: acc has {acc.rows} rows, out {out.rows}")
+    if csr.shape != (out.rows, X.rows):
+        raise ValueError(f"{what}: a CSR of shape {csr.shape} for tables of {out.rows} and {X.rows} rows")
+
+
+def graph_spmm(X, out, csr, row_scale=None, col_scale=None, rows=None, acc=None, acc_alpha=0.0, long_segments=None):
+    """One half-layer of the graph propagation (orx_graph_spmm): for the rows `rows` (None: all; a range or (row0, nrows)) of
+    `csr` -- an ALSCsr over the rows of `out` whose columns index the rows of `X` --
+        out[r] = y[r] = row_scale[r] * sum_e col_scale[cols[e]] * X[cols[e]],      acc[r] += acc_alpha * y[r]  (acc given)
+    row_scale / col_scale: float32 vectors over ALL rows of out / X (device tensors, or host arrays that are uploaded), None: 1.
+    An empty row writes +0.0 and leaves acc alone.  y[r] has the same bits for any row range, split into calls, other rows in the
+    call, and a host or device CSR; no float atomics.  long_segments: None (counted from the CSR: graph_long_segments), or the
+    number of scratch slots the partial sums of rows longer than graph_segment_len() may take with a device CSR -- a long row
+    that finds no slot walks its segments itself and gives the same bits, only more slowly.  Bad arguments raise ValueError
+    before the library is called; a column outside `X` IndexError."""
+    _graph_check("graph_spmm", X, out, acc, csr)
+    row0, nrows = _als_rows(rows, out.rows, "graph_spmm", "out")
+    long_segments = graph_long_segments(csr) if long_segments is None else int(long_segments)
+    if long_segments < 0:
+        raise ValueError(f"graph_spmm: long_segments = {long_segments}")
+    ps, k0 = _graph_scale_arg("graph_spmm", "row_scale", row_scale, out.rows, X.ctx)
+    pc, k1 = _graph_scale_arg("graph_spmm", "col_scale", col_scale, X.rows, X.ctx)
+    for t in (X, out, acc):
+        if t is not None:
+            t._sync_pending()
+    ptr, cols, _, flags = _als_csr_args("graph_spmm", csr, X.ctx)
+    check(X.ctx._lib.orx_graph_spmm(X.ctx._h, X._h, out._h, acc._h if acc is not None else None, float(acc_alpha), ptr, cols, ps, pc,
+                                    row0, nrows, long_segments, flags))
+    if flags:
+        X.ctx.check_index_error()
+    return out
+
+
+def table_apply_dense(opt, table, grad):
+    """orx_table_apply_dense: the Keras dense rule of `opt` (SGD, momentum / Nesterov, Adagrad, Adam) on every element of `table`
+    with the gradient `grad` -- a float32 device tensor or a Table of the table's shape, read only.  Adam's counter advances by
+    one; a lazily-applied Adam on the table is finished first, so the table can go to pairwise_step and back."""
+    if isinstance(grad, Table):
+        if grad is table or grad.ctx is not table.ctx or (grad.rows, grad.dim) != (table.rows, table.dim):
+            raise ValueError("table_apply_dense: grad must be another table of the same context and shape")
+        grad._sync_pending()
+        gp = grad.device_ptr
+    else:
+        if not _is_device_tensor(grad) or not str(grad.dtype).endswith("float32") or not grad.is_contiguous() or \
+                grad.numel() != table.rows * table.dim:
+            raise ValueError(f"table_apply_dense: grad must be a contiguous float32 device tensor of {table.rows} x {table.dim} values")
+        table.ctx.after_torch(grad)
+        gp = grad.data_ptr()
+    table._sync_pending()
+    check(table.ctx._lib.orx_table_apply_dense(table.ctx._h, opt._h, table._h, gp))
+    _keep_tables(opt, (table,))
+    return table
+
+
+class LightGCN:
+    """LightGCN (He et al., SIGIR 2020) over the trainable tables U [users, D] and V [items, D] and an InteractionGraph:
+        E(0) = [U ; V],  E(k+1) = A~ E(k),  E_f = sum_k layer_weights[k] E(k)        (layer_weights: 1 / (layers + 1) by default)
+    The rows that are scored are E_f's.  `propagate()` gives them as two Tables that recommend_topk, rank_metrics_matrixfree,
+    score_candidates and the samplers take as they stand; `step` is one BPR step (no item bias) through the propagation."""
+
+    def __init__(self, U, V, graph, layers=3, layer_weights=None, bias=None):
+        what = "LightGCN"
+        if bias is not None:
+            raise ValueError(f"{what}: the model has no item bias (a bias table was passed)")
+        if not isinstance(graph, InteractionGraph):
+            raise ValueError(f"{what}: graph must be an InteractionGraph")
+        layers = int(layers)
+        if not 1 <= layers <= LIGHTGCN_MAX_LAYERS:
+            raise ValueError(f"{what}: layers = {layers} outside [1, {LIGHTGCN_MAX_LAYERS}]")
+        if layer_weights is not None:
+            layer_weights = np.ascontiguousarray(np.asarray(layer_weights, np.float32).reshape(-1))
+            if layer_weights.size != layers + 1:
+                raise ValueError(f"{what}: {layer_weights.size} layer weights for {layers} layers (one per layer and one for layer 0)")
+        if U is V or U._h.value == V._h.value:
+            raise ValueError(f"{what}: the user and the item table are the same table")
+        if U.ctx is not V.ctx or graph.ctx is not U.ctx:
+            raise ValueError(f"{what}: the tables and the graph live on different contexts")
+        if U.dim != V.dim:
+            raise ValueError(f"{what}: user dim {U.dim}, item dim {V.dim}")
+        if not 1 <= U.dim <= 128:
+            raise ValueError(f"{what}: dim {U.dim} outside [1, 128]")
+        if (graph.total_users, graph.total_items) != (U.rows, V.rows):
+            raise ValueError(f"{what}: a graph of {graph.total_users} x {graph.total_items} for tables of {U.rows} and {V.rows} rows")
+        self.U, self.V, self.graph, self.ctx = U, V, graph, U.ctx
+        self.layers = layers
+        self.layer_weights = layer_weights if layer_weights is not None else np.full(layers + 1, np.float32(1) / np.float32(layers + 1), np.float32)
+        _, up, uc, _ = graph.by_user._dev
+        _, ip, ic, _ = graph.by_item._dev
+        su, sv = graph._scale_ptrs()
+        h = c_void_p()
+        lib = self.ctx._lib
+        check(lib.orx_lightgcn_create(self.ctx._h, U._h, V._h, up.data_ptr(), uc.data_ptr(), ip.data_ptr(), ic.data_ptr(), su, sv,
+                                      graph_long_segments(graph.by_user), graph_long_segments(graph.by_item), layers, self.layer_weights.ctypes.data, byref(h)))
+        self._h = h
+        self._keep = (U, V, graph)
+        self._fin = weakref.finalize(self, lib.orx_lightgcn_destroy, h)
+        hu, hv = c_void_p(), c_void_p()
+        check(lib.orx_lightgcn_tables(h, byref(hu), byref(hv)))
+        self.Uf, self.Vf = _BorrowedTable(self.ctx, hu, self), _BorrowedTable(self.ctx, hv, self)
+        self._fresh = False
+
+    def invalidate(self):
+        """U or V were changed by anything but this object's own `step` (rt.pairwise_step, rt.table_apply_dense, Table.write,
+        a checkpoint load ...): the next propagate() recomputes.  Nothing else tells the object: without this call propagate()
+        goes on returning the tables of the last propagation."""
+        self._fresh = False
+
+    def propagate(self, force=False):
+        """-> (Uf, Vf), the propagated tables (valid until the next step); recomputed when `step` has run since, when
+        `invalidate()` was called, or with force=True.  A change of U or V from OUTSIDE this object (rt.pairwise_step,
+        rt.table_apply_dense, Table.write) is not seen: call invalidate() after it, or pass force=True."""
+        if force or not self._fresh:
+            self.U._sync_pending(); self.V._sync_pending()
+            check(self.ctx._lib.orx_lightgcn_propagate(self._h))
+            self._fresh = True
+        return self.Uf, self.Vf
+
+    def _ids(self, what, uid, pid, nid):
+        pu, nu, du, k0 = _ids_arg(uid)
+        pp, npn, dp, k1 = _ids_arg(pid)
+        pn, nn, dn, k2 = _ids_arg(nid)
+        if not (du == dp == dn):
+            raise ValueError(f"{what}: ids must be all host or all device")
+        if not (nu == npn == nn):
+            raise ValueError(f"{what}: id arrays differ in length")
+        self.ctx.after_torch(uid, pid, nid)
+        return pu, pp, pn, nu, (_ffi.ORX_IDS_DEVICE if du else 0), (k0, k1, k2)
+
+    @staticmethod
+    def _l2(what, l2_reg):
+        l2_reg = float(l2_reg)
+        if not (np.isfinite(l2_reg) and l2_reg >= 0):
+            raise ValueError(f"{what}: l2_reg must be finite and >= 0, got {l2_reg!r}")
+        return l2_reg
+
+    def step(self, opt, uid, pid, nid, l2_reg=0.0, train=None, want_loss=True):
+        """One train step on the triplets (uid, pid, nid): loss = mean -log sigmoid(s_p - s_n) on the propagated rows plus
+        l2_reg / B * sum (|U[u]|^2 + |V[p]|^2 + |V[n]|^2) / 2 on the layer-0 rows; the dense rule of `opt` on U and V (train:
+        None, or ("user",) / ("item",) to leave the other table bit for bit as it is).  -> (loss, l2) as floats when want_loss,
+        else None (no host synchronisation with device ids).  Bit-reproducible."""
+        what = "LightGCN.step"
+        mask = _train_mask(train, None)
+        l2_reg = self._l2(what, l2_reg)
+        pu, pp, pn, B, flags, keep = self._ids(what, uid, pid, nid)
+        self.U._sync_pending(); self.V._sync_pending()
+        loss, l2 = ctypes.c_float(), ctypes.c_float()
+        self._fresh = False
+        check(self.ctx._lib.orx_lightgcn_step(self._h, opt._h, pu, pp, pn, B, l2_reg, mask or 0, flags,
+                                              byref(loss) if want_loss else None, byref(l2) if want_loss else None))
+        _keep_tables(opt, (self.U, self.V))
+        if flags and want_loss:
+            self.ctx.check_index_error()
+        return (float(loss.value), float(l2.value)) if want_loss else None
+
+    def loss(self, uid, pid, nid, l2_reg=0.0):
+        """the forward alone -> (loss, l2); U and V do not change (the propagated tables are brought up to date)"""
+        what = "LightGCN.loss"
+        l2_reg = self._l2(what, l2_reg)
+        pu, pp, pn, B, flags, keep = self._ids(what, uid, pid, nid)
+        self.U._sync_pending(); self.V._sync_pending()
+        loss, l2 = ctypes.c_float(), ctypes.c_float()
+        check(self.ctx._lib.orx_lightgcn_loss(self._h, pu, pp, pn, B, l2_reg, flags, byref(loss), byref(l2)))
+        if flags:
+            self.ctx.check_index_error()
+        self._fresh = True
+        return float(loss.value), float(l2.value)

@@ -1,7 +1,8 @@
 """The recommenders of `openrec.tf2.recommenders` (same class names, constructor arguments and call signatures),
 each running its train step as a fused device call: see the file of the same name."""
-from . import bpr as _bpr, dlrm as _dlrm, gmf as _gmf, ucml as _ucml, wrmf as _wrmf
+from . import bpr as _bpr, dlrm as _dlrm, gmf as _gmf, lightgcn as _lightgcn, ucml as _ucml, wrmf as _wrmf
 
 BPR, UCML, GMF, WRMF, DLRM = _bpr.BPR, _ucml.UCML, _gmf.GMF, _wrmf.WRMF, _dlrm.DLRM
+LightGCN = _lightgcn.LightGCN
 
-__all__ = ["BPR", "UCML", "GMF", "WRMF", "DLRM"]
+__all__ = ["BPR", "UCML", "GMF", "WRMF", "DLRM", "LightGCN"]
