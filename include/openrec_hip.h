@@ -1074,6 +1074,64 @@ int orx_lightgcn_step(orx_lightgcn* g, orx_opt* opt, const int32_t* uid, const i
 int orx_lightgcn_loss(orx_lightgcn* g, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t B,
                       float l2_reg, int flags, float* loss_out, float* l2_out);
 
+/* ---- VBPR (api_vbpr.hip, kernels_vbpr.hip): BPR with item content features through a learned projection (He & McAuley, AAAI 2016).
+ * Tables: user [NU, D] with D = Dl + Dc (columns [0, Dl) = U_l, [Dl, D) = U_c); item [NI, Dl]; bias [NI, 1] or NULL; proj = E [Fd, Dc],
+ * a table like the others; F [NI, Fd]: fixed fp32 item features, a DEVICE pointer, row-major, never written.
+ *   theta_i = F[i] E
+ *   s(u, i) = U_l[u] . V[i] + U_c[u] . theta_i + b[i]
+ *   x_k     = s(u_k, p_k) - s(u_k, n_k) = U_l[u] . (V[p] - V[n]) + U_c[u] . ((F[p] - F[n]) E) + b[p] - b[n]
+ *   loss    = (1/B) sum_k w_k * -log_sigmoid(max(x_k, -30))            w_k = weight[s*id_stride + k], 1 when weight == NULL
+ *   l2_loss = 1/2 (sum_k |U[u_k]|^2 + |V[p_k]|^2 + |V[n_k]|^2)         the whole user row; no biases; never weighted
+ *   J       = loss + l2_reg * l2_loss + l2_proj * 1/2 |E|_F^2
+ * The projection has NO output bias (the reference's Dense layer has one): it cancels in every pair difference, its loss gradient is
+ * identically zero, and in serving it shifts all items of a user equally.  No activation, one layer.
+ * loss_out[s] is the loss, l2_out[s] the UNSCALED l2_loss of the rows (the caller forms J).  Gradients, per occurrence and on the
+ * pre-step tables, with g_k = -w_k sigmoid(-x_k) [x_k >= -30] / B, df_k = F[p_k] - F[n_k], Delta_k = df_k E:
+ *   g_U[k] = [ g_k (V[p] - V[n]) ; g_k Delta_k ] + l2_reg U[u]
+ *   g_V[p] = g_k U_l[u] + l2_reg V[p],   g_V[n] = -g_k U_l[u] + l2_reg V[n],   g_b[p] = g_k,   g_b[n] = -g_k
+ *   dE     = sum_k df_k^T (g_k U_c[u_k]) + l2_proj E                   [Fd, Dc], dense
+ * Both products over feature rows are fp32 MFMA products: every product is rounded once into an fp32 fma chain, no float atomics;
+ * dE is summed over chunks of the batch in chunk order, so the same state gives the same bits of dE.
+ *   orx_features_project   out[k*out_stride + out_col0 + c] = ((F[ia[k]] - F[ib[k]]) E)[c], c < Dc, k < n.  ib == NULL: no subtraction;
+ *                          ia == NULL: rows row0 + k.  out: a DEVICE pointer; other columns of its rows are not touched.  ia / ib are
+ *                          host arrays unless ORX_IDS_DEVICE.  An id outside [0, NI) sets the index error and zeroes its output row.
+ *   orx_vbpr_item_table    rows [row0, row0 + nrows) of W [NI, Dl + Dc]: columns [0, Dl) = item bit for bit, [Dl, D) = F E.  (user, W,
+ *                          bias) then go to the scorers, top-K, the metrics and the candidate paths as BPR's tables do.
+ *   orx_vbpr_step          K steps.  Per step: lazily-applied rows the step reads are brought up to date (user with uid, item and bias
+ *                          with pid and nid), the projection, the pass over the triplets, the projection gradient; Adam's counter
+ *                          advances once, after the reads and before the applies; orx_apply_rows of user with uid, of item and of bias
+ *                          with pid | nid (each as a table of its own: the sorted apply, so a table's bits do not depend on the mask);
+ *                          the dense rule on E at the step's count (E is synced first).  A K-step call is K one-step calls, bit for
+ *                          bit.  loss_out == l2_out == NULL with ORX_IDS_DEVICE: no host synchronisation.
+ *                          train_mask: ORX_TRAIN_USER | _ITEM | _BIAS | _PROJ, 0 = every table the call was given; a table outside
+ *                          the mask is read, never written, and its optimizer slots are untouched.
+ *                          batch_chunk: rows of the batch per partial of dE; 0 = the launcher's own choice from (B, Fd, Dc), else a
+ *                          positive multiple of 64.  flags: ORX_IDS_DEVICE, ORX_NO_L2 (then l2_reg == l2_proj == 0).
+ *   orx_vbpr_loss          the forward alone: (loss, l2_loss) of one batch, the step's numbers bit for bit; no table changes.
+ *   orx_vbpr_geometry      host only: out = { rows of the batch per chunk, chunks, Dc padded to the tile width, rows of E per workgroup }.
+ * ORX_ERR_ARG before any device work: Dl < 1; Dc outside [1, 128]; Dl + Dc > 256 or != the user dim; Fd outside [1, 8192] or != E's
+ * rows; B >= 2^31 - 256; NI != the item rows; a bias that is not [NI, 1]; l2_reg / l2_proj negative or not finite; ORX_NO_L2 with a
+ * coefficient != 0; ORX_HOGWILD, ORX_CENSOR; batch_chunk negative or no multiple of 64; mask bits outside the four; ORX_TRAIN_BIAS
+ * with bias == NULL; tables or optimizer on another context; what orx_apply_rows refuses (ORX_ADAM_DENSE with a bias).
+ * An id outside its table: ORX_ERR_INDEX as orx_multineg_step reports it; the id is never used as an address and its triplet
+ * contributes no loss, no l2 and no gradient.  NaN features propagate to exactly the outputs that depend on their row. */
+enum orx_vbpr_train_mask { ORX_TRAIN_PROJ = 8 };      /* a fourth bit beside orx_train_mask's three: the projection E */
+int orx_features_project(orx_ctx* ctx, const float* F, int64_t NI, int32_t Fd, orx_table* proj,
+                         const int32_t* ia /* NULL ok */, const int32_t* ib /* NULL ok */, int64_t row0, int64_t n,
+                         float* out, int64_t out_stride, int32_t out_col0, int flags);
+int orx_vbpr_item_table(orx_ctx* ctx, orx_table* item, orx_table* proj, const float* F, int64_t NI, int32_t Fd,
+                        int64_t row0, int64_t nrows, orx_table* W);
+int orx_vbpr_step(orx_ctx* ctx, orx_opt* opt, orx_table* user, orx_table* item, orx_table* bias /* NULL ok */, orx_table* proj,
+                  const float* F, int64_t NI, int32_t Fd,
+                  const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight /* NULL ok */,
+                  int64_t K, int64_t B, int64_t id_stride, float l2_reg, float l2_proj, int32_t batch_chunk, int train_mask, int flags,
+                  float* loss_out, float* l2_out);
+int orx_vbpr_loss(orx_ctx* ctx, orx_table* user, orx_table* item, orx_table* bias /* NULL ok */, orx_table* proj,
+                  const float* F, int64_t NI, int32_t Fd,
+                  const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight /* NULL ok */,
+                  int64_t B, int flags, float* loss_out, float* l2_out);
+int orx_vbpr_geometry(int64_t B, int32_t Fd, int32_t Dc, int32_t batch_chunk, int32_t out[4]);
+
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,
  *                       PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads per range workgroup, threads of a big plan, references per

@@ -948,3 +948,39 @@ struct WarpNegArgs {
     float* cand_score;                                    // [n * T] or NULL
 };
 int orx_launch_warpneg(orx_ctx* ctx, const WarpNegArgs& a);
+
+// kernels_vbpr.hip (orx_features_project / orx_vbpr_item_table / orx_vbpr_step / orx_vbpr_loss): VBPR's two products over gathered
+// feature rows and the pass over the triplets between them.  Np = Dc rounded up to 16 (registers and LDS only)
+struct VbprProjArgs {
+    const float* F; const float* E;                       // [NI][Fd] features, [Fd][Dc] projection
+    const int32_t* ia; const int32_t* ib;                 // [n] rows (NULL: row0 + k) and the rows subtracted from them (NULL: none)
+    int64_t row0; int64_t n; int64_t NI;
+    int Fd; int Dc; int Np; int vec;                      // vec: Fd % 4 == 0 and F 16-byte aligned
+    float* out; int64_t out_stride; int out_col0;         // out[k * out_stride + out_col0 + c], c < Dc
+    int* err;
+};
+struct VbprPairArgs {
+    const float* U; const float* V; const float* b;       // read only; [NU][Dl + Dc], [NI][Dl], [NI] or NULL
+    const float* delta;                                   // [B][Dc] (F[p] - F[n]) E
+    const int32_t* uid; const int32_t* pid; const int32_t* nid; const float* wt;      // this step's ids [B]; weights or NULL
+    float* gu; float* gi; float* R; int32_t* list;        // [B][gs]; [2B][gs], bias gradient in column Dl; [B][Dc] g_k U_c[u_k]; [2B] pid | nid
+    int64_t B; int64_t NU; int64_t NI;
+    int Dl; int Dc; int gs;
+    float invB; float l2w;
+    float* partial;                                       // [orx_vbpr_nwaves(ctx, B)][2] loss / l2 partials of this step
+    int* err;
+};
+struct VbprDprojArgs {
+    const float* F; const float* R;                       // [NI][Fd]; [B][Dc]
+    const int32_t* pid; const int32_t* nid;
+    int64_t B; int64_t NI; int64_t chunk_rows;
+    int Fd; int Dc; int Np; int vec; int nch;
+    float* part;                                          // [nch][Fd][Dc]
+    const float* E; float l2p; float* dE;                 // the finishing pass: dE = sum of the partials in chunk order + l2p E
+};
+int orx_vbpr_nwaves(orx_ctx* ctx, int64_t B);
+void orx_vbpr_plan(int64_t B, int32_t Fd, int32_t Dc, int32_t batch_chunk, int32_t out[4]);      // rows per chunk, chunks, padded Dc, tile rows
+int orx_launch_vbpr_project(orx_ctx* ctx, const VbprProjArgs& a);
+int orx_launch_vbpr_pairs(orx_ctx* ctx, bool grads, const VbprPairArgs& a);
+int orx_launch_vbpr_dproj(orx_ctx* ctx, const VbprDprojArgs& a);
+int orx_launch_vbpr_copy_cols(orx_ctx* ctx, const float* V, int Dl, float* W, int D, int64_t nrows);      // W[r][0:Dl] = V[r][0:Dl]

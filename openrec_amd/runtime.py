@@ -1954,3 +1954,275 @@ class LightGCN:
             self.ctx.check_index_error()
         self._fresh = True
         return float(loss.value), float(l2.value)
+
+
+# ---- VBPR: item content features through a learned projection (api_vbpr.hip) ----------------------------------------------------
+class ItemFeatures:
+    """Fixed fp32 item features F [items, Fd] in HBM: data, never trained.  A C-contiguous float32 NumPy array is uploaded once; a
+    float32 torch device tensor is wrapped without a copy and kept alive.  `.rows`, `.dim`."""
+
+    def __init__(self, array, ctx=None):
+        what = "ItemFeatures"
+        if _is_device_tensor(array):
+            if array.dim() != 2 or not str(array.dtype).endswith("float32") or not array.is_contiguous():
+                raise ValueError(f"{what}: a device tensor must be a contiguous float32 matrix [items, Fd]")
+            self.rows, self.dim = int(array.shape[0]), int(array.shape[1])
+            self._check_shape(what)
+            self.ctx = ctx or default_context()
+            self._tensor, self._table = array, None
+            self.ctx.after_torch(array)
+            self._ptr = int(array.data_ptr())
+        else:
+            a = np.asarray(array)
+            if a.ndim != 2 or a.dtype != np.float32 or not a.flags.c_contiguous:
+                raise ValueError(f"{what}: expected a C-contiguous float32 matrix [items, Fd], got {a.dtype} {list(a.shape)}")
+            self.rows, self.dim = int(a.shape[0]), int(a.shape[1])
+            self._check_shape(what)
+            self.ctx = ctx or default_context()
+            self._tensor, self._table = None, Table(self.rows, self.dim, self.ctx).write(a)
+            self._ptr = int(self._table.device_ptr)
+
+    def _check_shape(self, what):
+        if self.rows < 1:
+            raise ValueError(f"{what}: no item rows")
+        if not 1 <= self.dim <= 8192:
+            raise ValueError(f"{what}: feature dim Fd = {self.dim} outside [1, 8192]")
+
+    @property
+    def device_ptr(self):
+        return self._ptr
+
+    def write_rows(self, rows, values):
+        """F[rows] = values (float32 [len(rows), Fd]): the features of newly arrived items"""
+        rows = np.asarray(rows, np.int64).reshape(-1)
+        vals = np.ascontiguousarray(values, np.float32).reshape(-1, self.dim)
+        if vals.shape[0] != rows.size:
+            raise ValueError(f"ItemFeatures.write_rows: {vals.shape[0]} rows of values for {rows.size} row ids")
+        if rows.size and (rows.min() < 0 or rows.max() >= self.rows):
+            raise IndexError(f"ItemFeatures.write_rows: a row outside [0, {self.rows})")
+        if self._table is not None:
+            for r, v in zip(rows, vals):
+                self._table.write(v, row0=int(r))
+        else:
+            import torch
+            self.ctx.synchronize()                 # (steps already queued on the library's stream read the rows as they were)
+            self._tensor[torch.as_tensor(rows, device=self._tensor.device)] = torch.as_tensor(vals, device=self._tensor.device)
+            self.ctx.after_torch(self._tensor)
+
+    def read(self):
+        return self._table.read() if self._table is not None else self._tensor.cpu().numpy()
+
+
+def vbpr_geometry(B, Fd, Dc, batch_chunk=0):
+    """what the launcher of the projection gradient does for (B, Fd, Dc, batch_chunk): a dict of the rows of the batch per chunk, the
+    chunks, Dc padded to the tile width and the rows of E per workgroup.  No device is needed."""
+    out = (c_int32 * 4)()
+    check(_ffi.load().orx_vbpr_geometry(int(B), int(Fd), int(Dc), int(batch_chunk), out))
+    return dict(chunk_rows=int(out[0]), chunks=int(out[1]), dim=int(out[2]), tile_rows=int(out[3]))
+
+
+def _vbpr_check_proj(what, features, E):
+    if not isinstance(features, ItemFeatures):
+        raise ValueError(f"{what}: features must be an ItemFeatures")
+    if features.ctx is not E.ctx:
+        raise ValueError(f"{what}: the features and the projection live on different contexts")
+    if E.rows != features.dim:
+        raise ValueError(f"{what}: the projection has {E.rows} rows for features of dim {features.dim}")
+    if E.dim < 1:
+        raise ValueError(f"{what}: projection width Dc = {E.dim}; Dc must be in [1, 128]")
+    if E.dim > 128:
+        raise ValueError(f"{what}: projection width Dc = {E.dim} above 128")
+
+
+def features_project(features, E, out_table, ids=None, minus=None, rows=None, col0=0):
+    """out_table[k, col0 : col0 + Dc] = (F[ids[k]] - F[minus[k]]) E (orx_features_project).  minus=None: no subtraction; ids=None:
+    the rows (row0, n) given by `rows` (default: all).  Row k of out_table is written, its other columns are not touched.  ids and
+    minus live both on the host or both on the device.  -> out_table"""
+    what = "features_project"
+    _vbpr_check_proj(what, features, E)
+    if out_table.ctx is not E.ctx:
+        raise ValueError(f"{what}: the output table lives on a different context")
+    col0 = int(col0)
+    if col0 < 0 or col0 + E.dim > out_table.dim:
+        raise ValueError(f"{what}: columns [{col0}, {col0 + E.dim}) do not fit a table of dim {out_table.dim}")
+    pa = pb = None
+    dev = False
+    keep = []
+    if ids is not None:
+        if rows is not None:
+            raise ValueError(f"{what}: ids together with rows")
+        pa, n, dev, k0 = _ids_arg(ids)
+        keep.append(k0)
+        row0 = 0
+    else:
+        row0, n = (0, features.rows) if rows is None else (int(rows[0]), int(rows[1]))
+        if row0 < 0 or n < 0 or row0 + n > features.rows:
+            raise ValueError(f"{what}: rows ({row0}, {n}) outside the {features.rows} feature rows")
+    if minus is not None:
+        pb, nb, db, k1 = _ids_arg(minus)
+        keep.append(k1)
+        if ids is not None and db != dev:
+            raise ValueError(f"{what}: ids and minus must be both on the host or both on the device")
+        if nb != n:
+            raise ValueError(f"{what}: {nb} ids in minus for {n} rows")
+        dev = db
+    if n > out_table.rows:
+        raise ValueError(f"{what}: {n} rows for an output table of {out_table.rows}")
+    E._sync_pending(); out_table._sync_pending()
+    E.ctx.after_torch(ids, minus)
+    check(E.ctx._lib.orx_features_project(E.ctx._h, features.device_ptr, features.rows, features.dim, E._h, pa, pb, row0, n,
+                                          out_table.device_ptr, out_table.dim, col0, _ffi.ORX_IDS_DEVICE if dev else 0))
+    return out_table
+
+
+_VBPR_ROLES = dict(_TRAIN_ROLES, proj=_ffi.ORX_TRAIN_PROJ)
+
+
+class VBPR:
+    """VBPR (He & McAuley, AAAI 2016): BPR whose item vector is the latent row V[i] beside theta_i = F[i] E, a learned projection
+    (no output bias, no activation) of a fixed feature row:
+        s(u, i) = U[u, :Dl] . V[i] + U[u, Dl:] . (F[i] E) + b[i]
+    U [users, Dl + Dc], V [items, Dl], b [items, 1] or None, E [Fd, Dc] (a Table like the others), features an ItemFeatures.
+    `step` trains, `item_table()` gives [V | F E] as a Table that recommend_topk, rank_metrics_matrixfree, score_candidates and the
+    samplers take with U and b as they stand."""
+
+    def __init__(self, U, V, b, E, features):
+        what = "VBPR"
+        _vbpr_check_proj(what, features, E)
+        if not (U.ctx is V.ctx is E.ctx) or (b is not None and b.ctx is not U.ctx):
+            raise ValueError(f"{what}: the tables live on different contexts")
+        if V.dim < 1:
+            raise ValueError(f"{what}: latent dim {V.dim}")
+        if V.dim + E.dim > 256:
+            raise ValueError(f"{what}: D = Dl + Dc = {V.dim} + {E.dim} above 256")
+        if U.dim != V.dim + E.dim:
+            raise ValueError(f"{what}: user dim {U.dim} != item latent dim {V.dim} + projection width {E.dim}")
+        if features.rows != V.rows:
+            raise ValueError(f"{what}: {features.rows} feature rows for {V.rows} items")
+        if b is not None and tuple(b.shape) != (V.rows, 1):
+            raise ValueError(f"{what}: bias must be [{V.rows}, 1], got {list(b.shape)}")
+        self.U, self.V, self.b, self.E, self.features, self.ctx = U, V, b, E, features, U.ctx
+        self._W = None
+        self._fresh = False
+
+    def _train(self, what, train):
+        if train is None:
+            return 0
+        roles = [train] if isinstance(train, str) else list(train)
+        unknown = [r for r in roles if r not in _VBPR_ROLES]
+        if unknown:
+            raise ValueError(f"{what}: train: unknown table name(s) {unknown!r}; expected a subset of {sorted(_VBPR_ROLES)}")
+        if not roles:
+            raise ValueError(f"{what}: train: empty set (no table would be trained); pass None to train every table")
+        if "bias" in roles and self.b is None:
+            raise ValueError(f'{what}: train: "bias" named, but the model has no item-bias table (bias=None)')
+        mask = 0
+        for r in roles:
+            mask |= _VBPR_ROLES[r]
+        return mask
+
+    def _args(self, what, uid, pid, nid, K, B, id_stride, weights):
+        pu, nu, du, k0 = _ids_arg(uid)
+        pp, npn, dp, k1 = _ids_arg(pid)
+        pn, nn, dn, k2 = _ids_arg(nid)
+        if not (du == dp == dn):
+            raise ValueError(f"{what}: ids must be all on the host or all on the device")
+        K = int(K)
+        if K < 0:
+            raise ValueError(f"{what}: K = {K}")
+        if B is None:
+            B = nu // K if K else 0
+        B = int(B)
+        if id_stride is None:
+            id_stride = B
+        id_stride = int(id_stride)
+        if B < 0 or id_stride < B:
+            raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
+        if B >= 2 ** 31 - 256:
+            raise ValueError(f"{what}: B = {B}; B must be below 2^31 - 256")
+        need = (K - 1) * id_stride + B if K and B else 0
+        if not (nu == npn == nn) or nu < need:
+            raise ValueError(f"{what}: {nu} user ids, {npn} positive ids and {nn} negative ids for K = {K}, B = {B}, "
+                             f"id_stride = {id_stride} (the three alike)")
+        pw = None
+        keep = [k0, k1, k2]
+        if weights is not None:
+            pw, kw = _weights_arg(weights, du, nu, what)
+            keep.append(kw)
+        self.ctx.after_torch(uid, pid, nid, weights)
+        for t in (self.U, self.V, self.b, self.E):
+            if t is not None:
+                t._sync_pending()
+        return K, B, id_stride, du, (pu, pp, pn, pw), keep
+
+    @staticmethod
+    def _coef(what, name, x):
+        x = float(x)
+        if not (np.isfinite(x) and x >= 0.0):
+            raise ValueError(f"{what}: {name} must be finite and >= 0 (got {x})")
+        return x
+
+    def step(self, opt, uid, pid, nid, weights=None, l2_reg=0.0, l2_proj=0.0, train=None, K=1, B=None, id_stride=None,
+             batch_chunk=0, want_loss=True):
+        """K train steps (orx_vbpr_step) on the triplets: J = loss + l2_reg * l2_loss + l2_proj / 2 |E|^2.  weights: per-triplet
+        weights shaped like the ids, living where they live.  train: None, or a subset of ("user", "item", "bias", "proj") -- every
+        other table is read, never written.  batch_chunk: rows of the batch per partial sum of the projection gradient (0: the
+        launcher's choice; else a positive multiple of 64).  -> (loss[K], l2[K]) as numpy float32, l2 the unscaled l2_loss of the
+        rows, when want_loss, else None (no host synchronisation with device ids).  Bad arguments raise ValueError before the
+        library is called; an id outside its table IndexError."""
+        what = "VBPR.step"
+        mask = self._train(what, train)
+        l2_reg, l2_proj = self._coef(what, "l2_reg", l2_reg), self._coef(what, "l2_proj", l2_proj)
+        batch_chunk = int(batch_chunk)
+        if batch_chunk < 0 or batch_chunk % 64:
+            raise ValueError(f"{what}: batch_chunk = {batch_chunk}; 0 (the launcher's choice) or a positive multiple of 64")
+        K, B, id_stride, dev, ptrs, keep = self._args(what, uid, pid, nid, K, B, id_stride, weights)
+        if want_loss:
+            out = np.empty(K, np.float32), np.empty(K, np.float32)
+            lp, l2p = out[0].ctypes.data, out[1].ctypes.data
+        else:
+            out = None
+            lp = l2p = None
+        self._fresh = False
+        f = self.features
+        check(self.ctx._lib.orx_vbpr_step(self.ctx._h, opt._h, self.U._h, self.V._h, _bias_h(self.b), self.E._h, f.device_ptr, f.rows, f.dim,
+                                          *ptrs, K, B, id_stride, l2_reg, l2_proj, batch_chunk, mask, _ffi.ORX_IDS_DEVICE if dev else 0,
+                                          lp, l2p))
+        _keep_tables(opt, (self.U, self.V, self.b, self.E))
+        return out
+
+    def loss(self, uid, pid, nid, weights=None):
+        """forward only: (loss, l2_loss) of one batch -- the step's own numbers bit for bit on the same tables; no table changes"""
+        _, B, _, dev, ptrs, keep = self._args("VBPR.loss", uid, pid, nid, 1, None, None, weights)
+        out = np.empty(1, np.float32), np.empty(1, np.float32)
+        f = self.features
+        check(self.ctx._lib.orx_vbpr_loss(self.ctx._h, self.U._h, self.V._h, _bias_h(self.b), self.E._h, f.device_ptr, f.rows, f.dim,
+                                          *ptrs, B, _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
+        return float(out[0][0]), float(out[1][0])
+
+    def invalidate(self):
+        """V, E or the features were changed by anything but this object's own `step` (another train step, Table.write, a
+        checkpoint load ...): the next item_table() rebuilds.  Nothing else tells the object."""
+        self._fresh = False
+
+    def item_table(self, rows=None):
+        """-> the Table [items, Dl + Dc] = [V | F E], owned by this object and valid until the next call.  It is rebuilt when a
+        `step` has run since the last build or after invalidate(); rows=(row0, n) refreshes those rows only (newly arrived items)."""
+        what = "VBPR.item_table"
+        if self._W is None:
+            self._W = Table(self.V.rows, self.U.dim, self.ctx)
+            self._fresh = False
+        f = self.features
+        todo = None
+        if not self._fresh:
+            todo = (0, self.V.rows)
+        elif rows is not None:
+            todo = (int(rows[0]), int(rows[1]))
+            if todo[0] < 0 or todo[1] < 0 or todo[0] + todo[1] > self.V.rows:
+                raise ValueError(f"{what}: rows {todo} outside the {self.V.rows} items")
+        if todo is not None:
+            self.V._sync_pending(); self.E._sync_pending()
+            check(self.ctx._lib.orx_vbpr_item_table(self.ctx._h, self.V._h, self.E._h, f.device_ptr, f.rows, f.dim, todo[0], todo[1],
+                                                    self._W._h))
+            self._fresh = True
+        return self._W
