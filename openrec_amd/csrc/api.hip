@@ -600,28 +600,6 @@ static int check_pair_tables(orx_table* U, orx_table* V, orx_table* b, int model
     return ORX_OK;
 }
 
-// stage ids of K steps; returns device pointers + stride
-static int stage_triplets(orx_ctx* c, const int32_t* uid, const int32_t* pid, const int32_t* nid,
-                          int64_t K, int64_t B, int64_t id_stride, int flags,
-                          const int32_t** du, const int32_t** dp, const int32_t** dn, int64_t* dstride) {
-    if (flags & ORX_IDS_DEVICE) { *du = uid; *dp = pid; *dn = nid; *dstride = id_stride; return ORX_OK; }
-    const int64_t n = K * B;
-    ENSURE(c->d_ids, c->d_ids_cap, (size_t)3 * n * sizeof(int32_t));
-    if (id_stride == B || K == 1) {
-        CHECK(stage_ids(c, uid, n, 0));
-        CHECK(stage_ids(c, pid, n, n));
-        CHECK(stage_ids(c, nid, n, 2 * n));
-    } else {
-        for (int64_t s = 0; s < K; ++s) {
-            CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
-            CHECK(stage_ids(c, pid + s * id_stride, B, n + s * B));
-            CHECK(stage_ids(c, nid + s * id_stride, B, 2 * n + s * B));
-        }
-    }
-    *du = c->d_ids; *dp = c->d_ids + n; *dn = c->d_ids + 2 * n; *dstride = B;
-    return ORX_OK;
-}
-
 int fetch_losses(orx_ctx* c, int64_t K, float* loss_out, float* l2_out) {
     if (!loss_out && !l2_out) return ORX_OK;
     std::vector<double> h((size_t)2 * K);
@@ -999,18 +977,6 @@ int orx_adam_dense_step(orx_ctx* c, orx_opt* opt, std::initializer_list<std::pai
     return ORX_OK;
 }
 
-// per-triplet weights of K steps next to the ids: a device array as it is, a host array into d_lab (stride B, as stage_triplets
-// packs the ids); NULL stays NULL
-int stage_weights(orx_ctx* c, const float* weight, int64_t K, int64_t B, int64_t id_stride, int flags, const float** dw) {
-    *dw = weight;
-    if (!weight || (flags & ORX_IDS_DEVICE)) return ORX_OK;
-    ENSURE(c->d_lab, c->d_lab_cap, (size_t)K * B * sizeof(float));
-    for (int64_t s = 0; s < K; ++s)
-        ORX_HIP(hipMemcpyAsync(c->d_lab + s * B, weight + s * id_stride, (size_t)B * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    *dw = c->d_lab;
-    return ORX_OK;
-}
-
 extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
                                  orx_table* U, orx_table* V, orx_table* b,
                                  const int32_t* uid, const int32_t* pid, const int32_t* nid,
@@ -1269,8 +1235,9 @@ int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, or
     q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.K = K; q.B = B;
     q.kmodel = b ? model : MODEL_BPR_NB;        // b == NULL: the kernels of MODEL_BPR_NB, every use of the bias table is skipped
     q.want_loss = loss_out != nullptr || l2_out != nullptr;
-    CHECK(stage_triplets(c, uid, pid, nid, K, B, id_stride, flags, &q.du, &q.dp, &q.dn, &q.ds));
-    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &q.dw));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &in));
+    q.du = in.id[0]; q.dp = in.id[1]; q.dn = in.id[2]; q.dw = in.f[0]; q.ds = in.ds;
     ORX_ARG(!(flags & ORX_HOGWILD) || opt->kind != ORX_MOMENTUM, "orx_pairwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
     const int fb = orx_fallback_bits();
     q.f = pair_form(opt, U, V, b, K, flags, fb);
@@ -1321,10 +1288,8 @@ int orx_pairwise_loss_impl(orx_ctx* c, int model, orx_table* U, orx_table* V, or
     CHECK(check_pair_tables(U, V, b, model, flags));
     ORX_ARG(B > 0 && uid && pid && nid, "orx_pairwise_loss: empty batch or NULL ids");
     ORX_HIP(hipSetDevice(c->device));
-    const int32_t *du, *dp, *dn; int64_t ds;
-    CHECK(stage_triplets(c, uid, pid, nid, 1, B, B, flags, &du, &dp, &dn, &ds));
-    const float* dw;
-    CHECK(stage_weights(c, weight, 1, B, B, flags, &dw));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &in));
     const int nw = orx_fused_nwaves(U->dim, B);
     ENSURE(c->d_partial, c->d_partial_cap, (size_t)nw * 2 * sizeof(float));
     ENSURE(c->d_loss, c->d_loss_cap, 2 * sizeof(double));
@@ -1334,7 +1299,7 @@ int orx_pairwise_loss_impl(orx_ctx* c, int model, orx_table* U, orx_table* V, or
     a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
     a.margin = margin; a.invB = 1.0f / (float)B; a.l2w = 1.f;
     a.partial = c->d_partial; a.err = c->d_err;
-    a.uid = du; a.pid = dp; a.nid = dn; a.wt = dw;
+    a.uid = in.id[0]; a.pid = in.id[1]; a.nid = in.id[2]; a.wt = in.f[0];
     CHECK(orx_launch_fused(c, b ? model : MODEL_BPR_NB, ORX_SGD, MODE_LOSS, a));
     ReduceArgs r;
     r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nw;

@@ -232,11 +232,8 @@ extern "C" int orx_lightgcn_step(orx_lightgcn* g, orx_opt* opt, const int32_t* u
     const float* gu = g->grads; const float* gp = gu + (size_t)B * RS;
     ORX_HIP(hipMemsetAsync(g->G[0]->w, 0, (size_t)g->G[0]->rows * D * sizeof(float), c->stream));
     ORX_HIP(hipMemsetAsync(g->G[1]->w, 0, (size_t)g->G[1]->rows * D * sizeof(float), c->stream));
-    const uint2* sorted = nullptr;
-    CHECK(orx_rows_sort(c, du, 1, B, B, g->U->rows, &sorted));
-    ORX_HIP(hipMemcpyAsync(g->sortU, sorted, (size_t)B * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
-    CHECK(orx_rows_sort(c, g->ids2, 1, 2 * B, 2 * B, g->V->rows, &sorted));
-    ORX_HIP(hipMemcpyAsync(g->sortV, sorted, (size_t)2 * B * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
+    CHECK(orx_rows_sort_keep(c, du, 1, B, B, g->U->rows, g->sortU));
+    CHECK(orx_rows_sort_keep(c, g->ids2, 1, 2 * B, 2 * B, g->V->rows, g->sortV));
     CHECK(orx_csr_accum_into(c, g->G[0]->w, g->G[0]->rows, D, g->sortU, B, gu, RS));
     CHECK(orx_csr_accum_into(c, g->G[1]->w, g->G[1]->rows, D, g->sortV, 2 * B, gp, RS));
     g->G[0]->version++; g->G[1]->version++;

@@ -16,23 +16,6 @@ static int check_point_tables(int model, orx_table* U, orx_table* V, orx_table* 
     return ORX_OK;
 }
 
-// stage (uid, iid, label) of K steps: ids into d_ids [2][K*B], labels into d_lab [K*B]
-static int stage_point(orx_ctx* c, const int32_t* uid, const int32_t* iid, const float* label,
-                       int64_t K, int64_t B, int64_t id_stride, int flags,
-                       const int32_t** du, const int32_t** di, const float** dl, int64_t* ds) {
-    if (flags & ORX_IDS_DEVICE) { *du = uid; *di = iid; *dl = label; *ds = id_stride; return ORX_OK; }
-    const int64_t n = K * B;
-    ENSURE(c->d_ids, c->d_ids_cap, (size_t)2 * n * sizeof(int32_t));
-    ENSURE(c->d_lab, c->d_lab_cap, (size_t)n * sizeof(float));
-    for (int64_t s = 0; s < K; ++s) {
-        CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
-        CHECK(stage_ids(c, iid + s * id_stride, B, n + s * B));
-        ORX_HIP(hipMemcpyAsync(c->d_lab + s * B, label + s * id_stride, (size_t)B * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    }
-    *du = c->d_ids; *di = c->d_ids + n; *dl = c->d_lab; *ds = B;
-    return ORX_OK;
-}
-
 extern "C" int orx_pointwise_step(orx_ctx* c, int model, orx_opt* opt,
                                   orx_table* U, orx_table* V, orx_table* b, orx_table* w,
                                   const int32_t* uid, const int32_t* iid, const float* label,
@@ -53,8 +36,9 @@ int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, o
     ORX_ARG(K == 0 || (uid && iid && label), "orx_pointwise_step: NULL id/label pointer");
     if (K == 0) return ORX_OK;
     ORX_HIP(hipSetDevice(c->device));
-    const int32_t *du, *di; const float* dl; int64_t ds;
-    CHECK(stage_point(c, uid, iid, label, K, B, id_stride, flags, &du, &di, &dl, &ds));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {iid, 1}}, {{label, 1}}, &in));
+    const int32_t *du = in.id[0], *di = in.id[1]; const float* dl = in.f[0]; const int64_t ds = in.ds;
     const bool hogwild = (flags & ORX_HOGWILD) != 0;
     ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pointwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
     const int fb = orx_fallback_bits();
@@ -222,8 +206,8 @@ extern "C" int orx_pointwise_loss(orx_ctx* c, int model, orx_table* U, orx_table
     CHECK(check_point_tables(model, U, V, b, w));
     ORX_ARG(B > 0 && uid && iid && label, "orx_pointwise_loss: empty batch or NULL pointer");
     ORX_HIP(hipSetDevice(c->device));
-    const int32_t *du, *di; const float* dl; int64_t ds;
-    CHECK(stage_point(c, uid, iid, label, 1, B, B, flags, &du, &di, &dl, &ds));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {iid, 1}}, {{label, 1}}, &in));
     const int D = U->dim;
     const int nw = orx_point_nwaves(D, B);
     const int nslot = nw + (model == ORX_GMF ? 1 : 0);
@@ -236,7 +220,7 @@ extern "C" int orx_pointwise_loss(orx_ctx* c, int model, orx_table* U, orx_table
     a.invB = 1.0f / (float)B; a.l2w = 1.f; a.a_w = a_w; a.b_w = b_w;
     a.sigmoid = (model == ORX_WRMF && (flags & ORX_POINT_SIGMOID)) ? 1 : 0;
     a.partial = c->d_partial; a.err = c->d_err;
-    a.uid = du; a.iid = di; a.label = dl;
+    a.uid = in.id[0]; a.iid = in.id[1]; a.label = in.f[0];
     CHECK(orx_launch_point_fused(c, model, ORX_SGD, MODE_LOSS, a));
     if (model == ORX_GMF) CHECK(orx_launch_dense_reduce(c, nullptr, 0, D, w->w, 0.f, nullptr, c->d_partial + 2 * nw, nullptr, -1, 0.f, 0.f));
     ReduceArgs r;
@@ -471,8 +455,7 @@ extern "C" int orx_apply_rows(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_tabl
     if (t && !lazy) CHECK(orx_table_sync(t));
     if (bias && !lazy) CHECK(orx_table_sync(bias));
     ORX_ARG(ctx && opt && t && (n == 0 || (ids && grads)), "orx_apply_rows: NULL argument");
-    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM || (opt->kind == ORX_ADAM && (!bias || lazy)),
-            "orx_apply_rows: the whole-table-sweep form of Adam (ORX_ADAM_DENSE) takes no bias column");
+    CHECK(orx_check_apply_rows_opt(opt, t, bias));
     ORX_ARG(g_stride >= t->dim + (bias ? 1 : 0), "orx_apply_rows: g_stride too small");
     ORX_ARG(!bias || (bias->dim == 1 && bias->rows == t->rows), "orx_apply_rows: bias must be [%lld, 1]", (long long)t->rows);
     if (n == 0) return ORX_OK;
@@ -482,9 +465,7 @@ extern "C" int orx_apply_rows(orx_ctx* ctx, orx_opt* opt, orx_table* t, orx_tabl
         // order, apply the rule once per distinct row
         const uint2* sorted = nullptr;
         CHECK(orx_rows_sort(ctx, ids, 1, n, n, t->rows, &sorted));
-        if (lazy) return orx_adam_rows_sorted(ctx, opt, t, sorted, n, grads, g_stride, true);
-        if (opt->kind == ORX_ADAM) return orx_adam_dense_sorted(ctx, opt, t, sorted, n, grads, g_stride);
-        return orx_csr_apply(ctx, opt, t, sorted, n, grads, g_stride);
+        return orx_apply_rows_sorted(ctx, opt, t, sorted, n, grads, g_stride);
     }
     RowsArgs a;
     memset(&a, 0, sizeof(a));

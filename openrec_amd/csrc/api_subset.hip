@@ -1,23 +1,19 @@
 // C-ABI entry points of the partial train step: orx_pairwise_step_subset / orx_pointwise_step_subset (include/openrec_hip.h has
 // the semantics).  A mask that names every table is the full step itself; a strict subset takes the route below.
 //
-// Per call (in chunks of up to SUBSET_CHUNK steps): the id lists of the trained tables are sorted once for all steps of the
-// chunk (kernels_rowsort.hip, one launch set with grid.y = step; the item table and the bias share one sort of the
-// concatenated positive | negative ids).  Per step: [lazy Adam: the rows the step reads from a trained table are replayed to
-// the optimizer's step], ONE gradient launch (kernels_subset.hip) that writes gradient rows for the trained roles only, then
-// the sorted row apply of every trained table -- the deterministic route of orx_apply_rows, all four optimizer kinds.  The
-// gradient launch ends before the applies begin, so every gradient is taken on the pre-step tables.  Frozen tables are
-// arguments of the gradient launch alone, as const pointers; no optimizer slot is looked up for them.
+// Per chunk of steps: the id lists of the trained tables are sorted once for all steps of the chunk (kernels_rowsort.hip, one
+// launch set with grid.y = step; the item table and the bias share one sort of the concatenated positive | negative ids).  Per
+// step: [lazy Adam: the rows the step reads from a trained table are replayed to the optimizer's step], ONE gradient launch
+// (kernels_subset.hip) that writes gradient rows for the trained roles only, then orx_apply_rows_sorted of every trained table,
+// all four optimizer kinds.  The gradient launch ends before the applies begin, so every gradient is taken on the pre-step
+// tables.  Frozen tables are arguments of the gradient launch alone, as const pointers; no optimizer slot is looked up for them.
 #include <algorithm>
-#include <cmath>
 #include <cstring>
-#include <vector>
 
 #include "orx_internal.h"
 
 namespace {
 
-constexpr int64_t SUBSET_CHUNK = 32;          // steps whose id lists are sorted together
 constexpr int ORX_TRAIN_ALL = ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS;
 
 // the mask checks both entry points share; *full: the mask names every table the call was given
@@ -29,34 +25,25 @@ int check_mask(const char* fn, int mask, const orx_table* bias, bool* full) {
     return ORX_OK;
 }
 
-struct Carve {                                // consecutive 256-byte aligned pieces of one device buffer
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
-};
-
 // one trained table of a step
 struct Trained { orx_table* t; const uint2* sorted; int64_t n; float* grads; int64_t g_stride; };
 
-// what the two models have in common: everything but the staging of the inputs and the gradient launch's model arguments
+// what the two models have in common: everything but the gradient launch's model arguments
 struct SubsetCall {
     orx_ctx* c; orx_opt* opt; orx_table* U; orx_table* V; orx_table* b;
     int mask; int kmodel;                     // orx_launch_subset_grads' model
     int refs;                                 // item lookups per sample: 2 (pairwise: positive, negative) or 1 (WRMF)
-    const int32_t* du; const int32_t* di; const int32_t* dn; const float* dl; int64_t ds;      // device inputs, elements between steps
-    const float* dw;                          // pairwise: per-triplet weights at the ids' stride, NULL: all ones
+    int flags;
+    StepInputs in;                            // id: uid, pid / iid, nid (pairwise)
+    const float* dl; const float* dw;         // of in.f: WRMF's labels; pairwise: per-triplet weights, NULL: all ones
     int64_t K, B;
     SubsetArgs a;                             // model constants filled in by the caller
 };
 
-int apply_sorted(orx_ctx* c, orx_opt* opt, const Trained& tr) {
-    if (orx_adam_rows_lazy(opt, tr.t)) return orx_adam_rows_sorted(c, opt, tr.t, tr.sorted, tr.n, tr.grads, tr.g_stride, true);
-    if (opt->kind == ORX_ADAM) return orx_adam_dense_sorted(c, opt, tr.t, tr.sorted, tr.n, tr.grads, tr.g_stride);
-    return orx_csr_apply(c, opt, tr.t, tr.sorted, tr.n, tr.grads, tr.g_stride);
-}
-
-int run_subset(SubsetCall& q, float* loss_out, float* l2_out, bool host_ids) {
+int run_subset(SubsetCall& q, float* loss_out, float* l2_out) {
     orx_ctx* c = q.c; orx_opt* opt = q.opt;
-    const int64_t K = q.K, B = q.B, nI = q.refs * B;
+    const int64_t K = q.K, B = q.B, nI = q.refs * B, ds = q.in.ds;
+    const int32_t* du = q.in.id[0]; const int32_t* di = q.in.id[1]; const int32_t* dn = q.in.id[2];
     const int D = q.U->dim;
     const bool tU = (q.mask & ORX_TRAIN_USER) != 0, tV = (q.mask & ORX_TRAIN_ITEM) != 0, tb = (q.mask & ORX_TRAIN_BIAS) != 0;
     const bool adam = opt->kind == ORX_ADAM;
@@ -75,11 +62,8 @@ int run_subset(SubsetCall& q, float* loss_out, float* l2_out, bool host_ids) {
         if (!(adam && orx_adam_rows_lazy(opt, keep[i]) && keep[i]->lazy == opt)) CHECK(orx_table_sync(keep[i]));
     if (adam) CHECK(orx_adam_lrt(opt, opt->t + K + 1));
 
-    const int nw = orx_fused_nwaves(D, B);
-    const int64_t chunk = std::min<int64_t>(K, SUBSET_CHUNK);
-    ENSURE(c->d_partial, c->d_partial_cap, (size_t)chunk * nw * 2 * sizeof(float));
-    ENSURE(c->d_loss, c->d_loss_cap, (size_t)K * 2 * sizeof(double));
     // scratch, one buffer: sorted lists of the chunk, the concatenated item ids, one step's gradient rows
+    const int64_t chunk = std::min<int64_t>(K, ORX_STEP_CHUNK);
     Carve cv;
     const size_t o_su = cv.take(tU ? (size_t)chunk * B * sizeof(uint2) : 0);
     const size_t o_si = cv.take((tV || tb) ? (size_t)chunk * nI * sizeof(uint2) : 0);
@@ -99,47 +83,36 @@ int run_subset(SubsetCall& q, float* loss_out, float* l2_out, bool host_ids) {
     a.gb = tb ? reinterpret_cast<float*>(base + o_gb) : nullptr;
     a.B = B; a.NU = q.U->rows; a.NI = q.V->rows; a.D = D; a.err = c->d_err;
 
-    for (int64_t s0 = 0; s0 < K; s0 += chunk) {
-        const int64_t kc = std::min<int64_t>(chunk, K - s0);
-        const uint2* sorted = nullptr;
+    auto sort_chunk = [&](int64_t s0, int64_t kc) -> int {
         if (tV || tb) {
-            const int32_t* ids = q.di + s0 * q.ds; int64_t stride = q.ds;
+            const int32_t* ids = di + s0 * ds; int64_t stride = ds;
             if (q.refs == 2) {
-                CHECK(orx_launch_subset_concat_ids(c, q.di + s0 * q.ds, q.dn + s0 * q.ds, q.ds, kc, B, catI));
+                CHECK(orx_launch_subset_concat_ids(c, di + s0 * ds, dn + s0 * ds, ds, kc, B, catI));
                 ids = catI; stride = nI;
             }
-            CHECK(orx_rows_sort(c, ids, kc, nI, stride, q.V->rows, &sorted));
-            ORX_HIP(hipMemcpyAsync(sortI, sorted, (size_t)kc * nI * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
+            CHECK(orx_rows_sort_keep(c, ids, kc, nI, stride, q.V->rows, sortI));
         }
-        if (tU) {
-            CHECK(orx_rows_sort(c, q.du + s0 * q.ds, kc, B, q.ds, q.U->rows, &sorted));
-            ORX_HIP(hipMemcpyAsync(sortU, sorted, (size_t)kc * B * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
-        }
-        for (int64_t i = 0; i < kc; ++i) {
-            const int64_t s = s0 + i;
-            Trained tr[3]; int nt = 0;
-            if (tU) tr[nt++] = Trained{q.U, sortU + i * B, B, a.gu, D};
-            if (tV) tr[nt++] = Trained{q.V, sortI + i * nI, nI, a.gi, D};
-            if (tb) tr[nt++] = Trained{q.b, sortI + i * nI, nI, a.gb, 1};
-            // lazy Adam: the rows of a trained table this step reads are brought to the optimizer's present step first
-            if (adam)
-                for (int k = 0; k < nt; ++k)
-                    if (tr[k].t->lazy == opt) CHECK(orx_adam_rows_sorted(c, opt, tr[k].t, tr[k].sorted, tr[k].n, nullptr, 0, false));
-            a.uid = q.du + s * q.ds; a.pid = q.di + s * q.ds; a.nid = q.dn ? q.dn + s * q.ds : nullptr;
-            a.label = q.dl ? q.dl + s * q.ds : nullptr;
-            a.wt = q.dw ? q.dw + s * q.ds : nullptr;
-            a.partial = c->d_partial + (size_t)i * nw * 2;
-            CHECK(orx_launch_subset_grads(c, q.kmodel, a));
-            if (adam) opt->t += 1;            // once per step, whatever the mask
-            for (int k = 0; k < nt; ++k) CHECK(apply_sorted(c, opt, tr[k]));
-        }
-        ReduceArgs r;
-        r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
-        CHECK(orx_launch_loss_reduce(c, r, kc));
-    }
-    CHECK(fetch_losses(c, K, loss_out, l2_out));
-    if (host_ids) return orx_check_index_error(c);
-    return ORX_OK;
+        if (tU) CHECK(orx_rows_sort_keep(c, du + s0 * ds, kc, B, ds, q.U->rows, sortU));
+        return ORX_OK;
+    };
+    return orx_run_steps(c, K, orx_fused_nwaves(D, B), q.flags, loss_out, l2_out, sort_chunk, [&](int64_t s, int64_t i, float* partial) -> int {
+        Trained tr[3]; int nt = 0;
+        if (tU) tr[nt++] = Trained{q.U, sortU + i * B, B, a.gu, D};
+        if (tV) tr[nt++] = Trained{q.V, sortI + i * nI, nI, a.gi, D};
+        if (tb) tr[nt++] = Trained{q.b, sortI + i * nI, nI, a.gb, 1};
+        // lazy Adam: the rows of a trained table this step reads are brought to the optimizer's present step first
+        if (adam)
+            for (int k = 0; k < nt; ++k)
+                if (tr[k].t->lazy == opt) CHECK(orx_adam_rows_sorted(c, opt, tr[k].t, tr[k].sorted, tr[k].n, nullptr, 0, false));
+        a.uid = du + s * ds; a.pid = di + s * ds; a.nid = dn ? dn + s * ds : nullptr;
+        a.label = q.dl ? q.dl + s * ds : nullptr;
+        a.wt = q.dw ? q.dw + s * ds : nullptr;
+        a.partial = partial;
+        CHECK(orx_launch_subset_grads(c, q.kmodel, a));
+        if (adam) opt->t += 1;                // once per step, whatever the mask
+        for (int k = 0; k < nt; ++k) CHECK(orx_apply_rows_sorted(c, opt, tr[k].t, tr[k].sorted, tr[k].n, tr[k].grads, tr[k].g_stride));
+        return ORX_OK;
+    });
 }
 
 }  // namespace
@@ -175,21 +148,11 @@ int orx_pairwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, 
     ORX_HIP(hipSetDevice(c->device));
     SubsetCall q;
     memset(&q, 0, sizeof(q));
-    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.mask = train_mask; q.kmodel = b ? model : MODEL_BPR_NB; q.refs = 2; q.K = K; q.B = B;
-    if (flags & ORX_IDS_DEVICE) { q.du = uid; q.di = pid; q.dn = nid; q.ds = id_stride; }
-    else {
-        const int64_t n = K * B;
-        ENSURE(c->d_ids, c->d_ids_cap, (size_t)3 * n * sizeof(int32_t));
-        for (int64_t s = 0; s < K; ++s) {
-            CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
-            CHECK(stage_ids(c, pid + s * id_stride, B, n + s * B));
-            CHECK(stage_ids(c, nid + s * id_stride, B, 2 * n + s * B));
-        }
-        q.du = c->d_ids; q.di = c->d_ids + n; q.dn = c->d_ids + 2 * n; q.ds = B;
-    }
-    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &q.dw));      // (host weights travel like the ids: d_lab is free in a pairwise call)
+    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.mask = train_mask; q.kmodel = b ? model : MODEL_BPR_NB; q.refs = 2; q.flags = flags; q.K = K; q.B = B;
+    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &q.in));
+    q.dw = q.in.f[0];
     q.a.margin = margin; q.a.invB = 1.0f / (float)B; q.a.l2w = l2w;
-    return run_subset(q, loss_out, l2_out, !(flags & ORX_IDS_DEVICE));
+    return run_subset(q, loss_out, l2_out);
 }
 
 extern "C" int orx_pointwise_step_subset(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
@@ -220,20 +183,10 @@ int orx_pointwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U,
     ORX_HIP(hipSetDevice(c->device));
     SubsetCall q;
     memset(&q, 0, sizeof(q));
-    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.mask = train_mask; q.kmodel = -1; q.refs = 1; q.K = K; q.B = B;
-    if (flags & ORX_IDS_DEVICE) { q.du = uid; q.di = iid; q.dl = label; q.ds = id_stride; }
-    else {
-        const int64_t n = K * B;
-        ENSURE(c->d_ids, c->d_ids_cap, (size_t)2 * n * sizeof(int32_t));
-        ENSURE(c->d_lab, c->d_lab_cap, (size_t)n * sizeof(float));
-        for (int64_t s = 0; s < K; ++s) {
-            CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
-            CHECK(stage_ids(c, iid + s * id_stride, B, n + s * B));
-            ORX_HIP(hipMemcpyAsync(c->d_lab + s * B, label + s * id_stride, (size_t)B * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        }
-        q.du = c->d_ids; q.di = c->d_ids + n; q.dl = c->d_lab; q.ds = B;
-    }
+    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.mask = train_mask; q.kmodel = -1; q.refs = 1; q.flags = flags; q.K = K; q.B = B;
+    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {iid, 1}}, {{label, 1}}, &q.in));
+    q.dl = q.in.f[0];
     q.a.invB = 1.0f / (float)B; q.a.l2w = l2w; q.a.a_w = a_w; q.a.b_w = b_w;
     q.a.sigmoid = (flags & ORX_POINT_SIGMOID) ? 1 : 0;
-    return run_subset(q, loss_out, l2_out, !(flags & ORX_IDS_DEVICE));
+    return run_subset(q, loss_out, l2_out);
 }

@@ -1,16 +1,13 @@
 // C-ABI entry points of VBPR: orx_features_project, orx_vbpr_item_table, orx_vbpr_step, orx_vbpr_loss and orx_vbpr_geometry
 // (include/openrec_hip.h has the semantics, kernels_vbpr.hip the kernels).
 //
-// Per step, all on the context's stream: [lazy Adam: the rows the step reads are replayed to the optimizer's step -- the user table
-// with uid, the item table and the bias with pid and with nid], the projection Delta = (F[pid] - F[nid]) E, the pass over the
-// triplets (gradient rows, coefficient rows R, loss partials), the projection gradient dE = df^T R + l2_proj E, [Adam: the counter
-// advances], then orx_apply_rows of the user table with uid, of the item table and of the bias with pid | nid, and the dense rule on
-// E at the step's count.  No kernel before the applies writes a table, so every gradient is taken on the pre-step tables.  The item
-// table and the bias are applied as two tables with the same id list -- orx_apply_rows' sorted route on ONE sort of the list, no
-// float atomics --, so a table gets the same bits whichever other tables the train mask names.  The loss partials of up to
-// VB_CHUNK steps are summed by one loss_reduce launch.  The scratch of a step is carved from the context's grow-only d_tmp and
-// reused by every step.
-#include <algorithm>
+// Per step: the touch of (uid; pid, nid), the projection Delta = (F[pid] - F[nid]) E, the pass over the triplets (gradient rows,
+// coefficient rows R, loss partials), the projection gradient dE = df^T R + l2_proj E, [Adam: the counter advances], then
+// orx_apply_rows of the user table with uid, of the item table and of the bias with pid | nid, and the dense rule on E at the
+// step's count.  No kernel before the applies writes a table, so every gradient is taken on the pre-step tables.  The item table
+// and the bias are applied as two tables with the same id list -- orx_apply_rows_sorted on ONE sort of the list, no float atomics
+// --, so a table gets the same bits whichever other tables the train mask names.  The scratch of a step is carved from the
+// context's grow-only d_tmp and reused by every step.
 #include <cmath>
 #include <cstring>
 
@@ -19,14 +16,9 @@
 
 namespace {
 
-constexpr int64_t VB_CHUNK = 32;              // steps whose loss partials are summed by one launch
 constexpr int64_t VB_MAX_B = 0x7fffffffLL - 256;
 constexpr int VB_TRAIN_ALL = ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS | ORX_TRAIN_PROJ;
-
-struct Carve {                                // consecutive 256-byte aligned pieces of one device buffer
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
-};
+constexpr int VB_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_HOGWILD | ORX_CENSOR;
 
 int check_features(const char* fn, orx_ctx* c, const float* F, int64_t NI, int32_t Fd, orx_table* E) {
     ORX_ARG(c && F && E, "%s: NULL context, feature matrix or projection", fn);
@@ -45,43 +37,17 @@ int check_chunk(const char* fn, int64_t B, int32_t batch_chunk) {
     return ORX_OK;
 }
 
-// what the step and the forward share
-int check_model(const char* fn, orx_ctx* c, orx_table* U, orx_table* V, orx_table* b, orx_table* E, const float* F, int64_t NI, int32_t Fd,
-                int64_t B, int32_t batch_chunk, int flags) {
+// what the step and the forward check before the shared checks (which then find U->dim == V->dim + E->dim)
+int check_own(const char* fn, orx_ctx* c, orx_table* U, orx_table* V, orx_table* E, const float* F, int64_t NI, int32_t Fd,
+              int64_t B, int32_t batch_chunk) {
     ORX_ARG(c && U && V, "%s: NULL context/table", fn);
     CHECK(check_features(fn, c, F, NI, Fd, E));
-    ORX_ARG(U->ctx == c && V->ctx == c && (!b || b->ctx == c), "%s: the tables belong to a different context", fn);
     ORX_ARG(V->dim >= 1, "%s: latent dim %d", fn, V->dim);
     ORX_ARG(V->dim + E->dim <= 256, "%s: D = Dl + Dc = %d + %d above 256", fn, V->dim, E->dim);
     ORX_ARG(U->dim == V->dim + E->dim, "%s: user dim %d != item latent dim %d + projection width %d", fn, U->dim, V->dim, E->dim);
     ORX_ARG(V->rows == NI, "%s: %lld feature rows for %lld items", fn, (long long)NI, (long long)V->rows);
-    ORX_ARG(!b || (b->dim == 1 && b->rows == V->rows), "%s: item_bias must be [%lld, 1]", fn, (long long)V->rows);
     ORX_ARG(B >= 0 && B < VB_MAX_B, "%s: B = %lld (B < 2^31 - 256)", fn, (long long)B);
-    CHECK(check_chunk(fn, B, batch_chunk));
-    ORX_ARG((flags & ~(ORX_IDS_DEVICE | ORX_NO_L2 | ORX_HOGWILD | ORX_CENSOR)) == 0, "%s: unknown flags", fn);
-    ORX_ARG(!(flags & ORX_HOGWILD), "%s: ORX_HOGWILD is a speed-comparison mode of the plain pairwise step only", fn);
-    ORX_ARG(!(flags & ORX_CENSOR), "%s: ORX_CENSOR belongs to UCML; this step scores by dot products only (UCML / L2 scoring is not offered)", fn);
-    return ORX_OK;
-}
-
-// the inputs of K steps on the device: arrays that are there already as they are (stride ds = id_stride), host arrays packed at
-// stride B into the context's staging buffers (ids: d_ids, weights: d_lab)
-struct Inputs { const int32_t* du; const int32_t* dp; const int32_t* dn; const float* dw; int64_t ds; };
-
-int stage_inputs(orx_ctx* c, const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
-                 int64_t K, int64_t B, int64_t id_stride, int flags, Inputs* in) {
-    if (flags & ORX_IDS_DEVICE) { *in = Inputs{uid, pid, nid, weight, id_stride}; return ORX_OK; }
-    const int64_t n = K * B;
-    ENSURE(c->d_ids, c->d_ids_cap, (size_t)n * 3 * sizeof(int32_t));
-    for (int64_t s = 0; s < K; ++s) {
-        CHECK(stage_ids(c, uid + s * id_stride, B, s * B));
-        CHECK(stage_ids(c, pid + s * id_stride, B, n + s * B));
-        CHECK(stage_ids(c, nid + s * id_stride, B, 2 * n + s * B));
-    }
-    const float* dw = nullptr;
-    CHECK(stage_weights(c, weight, K, B, id_stride, flags, &dw));
-    *in = Inputs{c->d_ids, c->d_ids + n, c->d_ids + 2 * n, dw, B};
-    return ORX_OK;
+    return check_chunk(fn, B, batch_chunk);
 }
 
 struct StepArgs { VbprProjArgs pj; VbprPairArgs pa; VbprDprojArgs dp; uint2* sorted; };      // sorted: [2B] the item list's (row, position) pairs
@@ -121,14 +87,6 @@ int make_args(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b, orx_table* E
     }
     *out = s;
     return ORX_OK;
-}
-
-// orx_apply_rows' deterministic route on a list that is sorted already: the item table and the bias share one sort of pid | nid
-int apply_sorted(orx_ctx* c, orx_opt* opt, orx_table* t, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride) {
-    if (orx_adam_rows_lazy(opt, t)) return orx_adam_rows_sorted(c, opt, t, sorted, n, grads, g_stride, true);
-    CHECK(orx_table_sync(t));
-    if (opt->kind == ORX_ADAM) return orx_adam_dense_sorted(c, opt, t, sorted, n, grads, g_stride);
-    return orx_csr_apply(c, opt, t, sorted, n, grads, g_stride);
 }
 
 }  // namespace
@@ -205,40 +163,25 @@ extern "C" int orx_vbpr_step(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* 
                              int64_t K, int64_t B, int64_t id_stride, float l2_reg, float l2_proj, int32_t batch_chunk, int train_mask,
                              int flags, float* loss_out, float* l2_out) {
     static const char* fn = "orx_vbpr_step";
-    ORX_ARG(opt, "%s: NULL optimizer", fn);
-    CHECK(check_model(fn, c, U, V, b, E, F, NI, Fd, B, batch_chunk, flags));
-    ORX_ARG(opt->ctx == c, "%s: the optimizer belongs to a different context", fn);
-    ORX_ARG(std::isfinite(l2_reg) && l2_reg >= 0.f, "%s: l2_reg must be finite and >= 0 (got %g)", fn, (double)l2_reg);
+    CHECK(check_own(fn, c, U, V, E, F, NI, Fd, B, batch_chunk));
+    CHECK(orx_check_dot_step(fn, c, opt, U, V, b, E->dim, K, B, id_stride, l2_reg, flags, VB_FLAGS));
     ORX_ARG(std::isfinite(l2_proj) && l2_proj >= 0.f, "%s: l2_proj must be finite and >= 0 (got %g)", fn, (double)l2_proj);
-    ORX_ARG(!(flags & ORX_NO_L2) || (l2_reg == 0.f && l2_proj == 0.f), "%s: ORX_NO_L2 together with l2_reg = %g, l2_proj = %g (drop the flag, or pass 0)",
-            fn, (double)l2_reg, (double)l2_proj);
-    ORX_ARG(K >= 0 && id_stride >= 0, "%s: negative K or id_stride", fn);
+    ORX_ARG(!(flags & ORX_NO_L2) || l2_proj == 0.f, "%s: ORX_NO_L2 together with l2_proj = %g (drop the flag, or pass 0)", fn, (double)l2_proj);
     ORX_ARG((train_mask & ~VB_TRAIN_ALL) == 0, "%s: train mask 0x%x has bits outside ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS | ORX_TRAIN_PROJ",
             fn, train_mask);
     ORX_ARG(b != nullptr || !(train_mask & ORX_TRAIN_BIAS), "%s: ORX_TRAIN_BIAS without a bias table (bias is NULL)", fn);
-    // what orx_apply_rows would refuse for this optimizer and these tables, with its message, before anything is launched
-    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_ADAGRAD || opt->kind == ORX_MOMENTUM || (opt->kind == ORX_ADAM && (!b || orx_adam_rows_lazy(opt, V))),
-            "orx_apply_rows: the whole-table-sweep form of Adam (ORX_ADAM_DENSE) takes no bias column");
     if (train_mask == 0) train_mask = ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_PROJ | (b ? ORX_TRAIN_BIAS : 0);
     if (K == 0 || B == 0) return ORX_OK;
     ORX_ARG(uid && pid && nid, "%s: NULL id pointer", fn);
-    ORX_ARG(K == 1 || id_stride >= B, "%s: id_stride %lld below B = %lld", fn, (long long)id_stride, (long long)B);
-    const bool adam = opt->kind == ORX_ADAM;
-    ORX_ARG(!adam || opt->t + K < 0x7fffffff, "%s: step counter overflow", fn);
     ORX_HIP(hipSetDevice(c->device));
     const bool tU = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0,
                tE = (train_mask & ORX_TRAIN_PROJ) != 0;
 
-    Inputs in;
-    CHECK(stage_inputs(c, uid, pid, nid, weight, K, B, id_stride, flags, &in));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &in));
     StepArgs a;
     CHECK(make_args(c, U, V, b, E, F, NI, Fd, B, l2_reg, l2_proj, batch_chunk, true, &a));
     const int Dl = V->dim, gs = a.pa.gs;
-    const int nw = orx_vbpr_nwaves(c, B);
-    const int64_t chunk = std::min<int64_t>(K, VB_CHUNK);
-    const bool want = loss_out != nullptr || l2_out != nullptr;
-    ENSURE(c->d_partial, c->d_partial_cap, (size_t)chunk * nw * 2 * sizeof(float));
-    if (want) ENSURE(c->d_loss, c->d_loss_cap, (size_t)K * 2 * sizeof(double));
     // a table outside the mask is finished under the old counter (whatever optimizer it is lazy under), then only read; the
     // projection is a dense parameter: every row current before the step reads it
     orx_table* keep[4]; int n_keep = 0;
@@ -248,49 +191,34 @@ extern "C" int orx_vbpr_step(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* 
     CHECK(orx_table_sync(E));
     if (tE) keep[n_keep++] = E;
 
-    for (int64_t s0 = 0; s0 < K; s0 += chunk) {
-        const int64_t kc = std::min<int64_t>(chunk, K - s0);
-        for (int64_t i = 0; i < kc; ++i) {
-            const int64_t s = s0 + i;
-            const int32_t* du = in.du + s * in.ds; const int32_t* dp = in.dp + s * in.ds; const int32_t* dn = in.dn + s * in.ds;
-            a.pj.ia = dp; a.pj.ib = dn;
-            a.pa.uid = du; a.pa.pid = dp; a.pa.nid = dn; a.pa.wt = in.dw ? in.dw + s * in.ds : nullptr;
-            a.pa.partial = c->d_partial + (size_t)i * nw * 2;
-            a.dp.pid = dp; a.dp.nid = dn;
-            // a lazily-applied table: exactly the rows this step reads (no-ops for a table that is current)
-            CHECK(orx_table_touch(U, du, B));
-            CHECK(orx_table_touch(V, dp, B)); CHECK(orx_table_touch(V, dn, B));
-            if (b) { CHECK(orx_table_touch(b, dp, B)); CHECK(orx_table_touch(b, dn, B)); }
-            CHECK(orx_launch_vbpr_project(c, a.pj));
-            CHECK(orx_launch_vbpr_pairs(c, true, a.pa));
-            if (tE) CHECK(orx_launch_vbpr_dproj(c, a.dp));
-            if (adam) CHECK(orx_opt_advance(opt, keep, n_keep));       // once per step: after the step's reads, before its applies
-            if (tU) CHECK(orx_apply_rows(c, opt, U, nullptr, du, B, a.pa.gu, gs));
-            if (tV || tb) {               // one sort of pid | nid for both (kept aside: the user table's apply sorts again)
-                const uint2* sorted = nullptr;
-                CHECK(orx_rows_sort(c, a.pa.list, 1, 2 * B, 2 * B, V->rows, &sorted));
-                ORX_HIP(hipMemcpyAsync(a.sorted, sorted, (size_t)2 * B * sizeof(uint2), hipMemcpyDeviceToDevice, c->stream));
-                if (tV) CHECK(apply_sorted(c, opt, V, a.sorted, 2 * B, a.pa.gi, gs));
-                if (tb) CHECK(apply_sorted(c, opt, b, a.sorted, 2 * B, a.pa.gi + Dl, gs));
-            }
-            if (tE) CHECK(orx_table_apply_dense_at(c, opt, E, a.dp.dE));
+    return orx_run_steps(c, K, orx_vbpr_nwaves(c, B), flags, loss_out, l2_out, nullptr, [&](int64_t s, int64_t, float* partial) -> int {
+        const int32_t* du = in.id[0] + s * in.ds; const int32_t* dp = in.id[1] + s * in.ds; const int32_t* dn = in.id[2] + s * in.ds;
+        a.pj.ia = dp; a.pj.ib = dn;
+        a.pa.uid = du; a.pa.pid = dp; a.pa.nid = dn; a.pa.wt = in.f[0] ? in.f[0] + s * in.ds : nullptr;
+        a.pa.partial = partial;
+        a.dp.pid = dp; a.dp.nid = dn;
+        CHECK(orx_touch_step(U, V, b, du, B, dp, B, dn, B));
+        CHECK(orx_launch_vbpr_project(c, a.pj));
+        CHECK(orx_launch_vbpr_pairs(c, true, a.pa));
+        if (tE) CHECK(orx_launch_vbpr_dproj(c, a.dp));
+        if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
+        if (tU) CHECK(orx_apply_rows(c, opt, U, nullptr, du, B, a.pa.gu, gs));
+        if (tV || tb) {                   // one sort of pid | nid for both (kept aside: the user table's apply sorts again)
+            CHECK(orx_rows_sort_keep(c, a.pa.list, 1, 2 * B, 2 * B, V->rows, a.sorted));
+            if (tV) CHECK(orx_apply_rows_sorted(c, opt, V, a.sorted, 2 * B, a.pa.gi, gs));
+            if (tb) CHECK(orx_apply_rows_sorted(c, opt, b, a.sorted, 2 * B, a.pa.gi + Dl, gs));
         }
-        if (want) {
-            ReduceArgs r;
-            r.partial = c->d_partial; r.out = c->d_loss + 2 * s0; r.nwaves = nw;
-            CHECK(orx_launch_loss_reduce(c, r, kc));
-        }
-    }
-    CHECK(fetch_losses(c, K, loss_out, l2_out));
-    if (!(flags & ORX_IDS_DEVICE)) return orx_check_index_error(c);
-    return ORX_OK;
+        if (tE) CHECK(orx_table_apply_dense_at(c, opt, E, a.dp.dE));
+        return ORX_OK;
+    });
 }
 
 extern "C" int orx_vbpr_loss(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b, orx_table* E, const float* F, int64_t NI, int32_t Fd,
                              const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight, int64_t B, int flags,
                              float* loss_out, float* l2_out) {
     static const char* fn = "orx_vbpr_loss";
-    CHECK(check_model(fn, c, U, V, b, E, F, NI, Fd, B, 0, flags));
+    CHECK(check_own(fn, c, U, V, E, F, NI, Fd, B, 0));
+    CHECK(orx_check_dot_model(fn, c, U, V, b, E->dim, flags, VB_FLAGS));
     ORX_ARG(!(flags & ORX_NO_L2), "%s: ORX_NO_L2 belongs to the step (the forward has no objective)", fn);
     if (B == 0) {
         if (loss_out) *loss_out = 0.f;
@@ -299,25 +227,17 @@ extern "C" int orx_vbpr_loss(orx_ctx* c, orx_table* U, orx_table* V, orx_table* 
     }
     ORX_ARG(uid && pid && nid, "%s: NULL id pointer", fn);
     ORX_HIP(hipSetDevice(c->device));
-    Inputs in;
-    CHECK(stage_inputs(c, uid, pid, nid, weight, 1, B, B, flags, &in));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &in));
     StepArgs a;
     CHECK(make_args(c, U, V, b, E, F, NI, Fd, B, 0.f, 0.f, 0, false, &a));
-    const int nw = orx_vbpr_nwaves(c, B);
-    ENSURE(c->d_partial, c->d_partial_cap, (size_t)nw * 2 * sizeof(float));
-    ENSURE(c->d_loss, c->d_loss_cap, 2 * sizeof(double));
-    a.pj.ia = in.dp; a.pj.ib = in.dn;
-    a.pa.uid = in.du; a.pa.pid = in.dp; a.pa.nid = in.dn; a.pa.wt = in.dw; a.pa.partial = c->d_partial;
-    CHECK(orx_table_sync(E));
-    CHECK(orx_table_touch(U, in.du, B));
-    CHECK(orx_table_touch(V, in.dp, B)); CHECK(orx_table_touch(V, in.dn, B));
-    if (b) { CHECK(orx_table_touch(b, in.dp, B)); CHECK(orx_table_touch(b, in.dn, B)); }
-    CHECK(orx_launch_vbpr_project(c, a.pj));
-    CHECK(orx_launch_vbpr_pairs(c, false, a.pa));
-    ReduceArgs r;
-    r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nw;
-    CHECK(orx_launch_loss_reduce(c, r, 1));
-    float dummy;
-    CHECK(fetch_losses(c, 1, loss_out ? loss_out : &dummy, l2_out));
-    return orx_check_index_error(c);
+    a.pj.ia = in.id[1]; a.pj.ib = in.id[2];
+    a.pa.uid = in.id[0]; a.pa.pid = in.id[1]; a.pa.nid = in.id[2]; a.pa.wt = in.f[0];
+    return orx_run_forward(c, orx_vbpr_nwaves(c, B), loss_out, l2_out, [&](float* partial) -> int {
+        a.pa.partial = partial;
+        CHECK(orx_table_sync(E));
+        CHECK(orx_touch_step(U, V, b, a.pa.uid, B, a.pa.pid, B, a.pa.nid, B));
+        CHECK(orx_launch_vbpr_project(c, a.pj));
+        return orx_launch_vbpr_pairs(c, false, a.pa);
+    });
 }

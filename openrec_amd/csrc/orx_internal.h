@@ -194,8 +194,44 @@ int orx_table_side(orx_table* t);                               // allocate the 
 int orx_opt_slots(orx_opt* opt, orx_table* t, OptSlots* out);   // allocate optimizer slots
 int stage_ids(orx_ctx* c, const int32_t* host, int64_t n, int64_t off);   // H2D into ctx->d_ids
 int fetch_losses(orx_ctx* c, int64_t K, float* loss_out, float* l2_out);
-// per-triplet weights of K steps: a device array as it is, a host array into ctx->d_lab packed at stride B; NULL stays NULL
-int stage_weights(orx_ctx* c, const float* weight, int64_t K, int64_t B, int64_t id_stride, int flags, const float** dw);
+
+// ---------------------------------- the host driver of the train steps (api_steps.hip) ---
+struct Carve {                                // consecutive 256-byte aligned pieces of one device buffer
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t at = off; off += (bytes + 255) & ~(size_t)255; return at; }
+};
+// One input list of a K-step call, `width` 4-byte elements per sample (p NULL: the call has no such list), and where the lists
+// are once staged: the elements of step s of a list begin at its pointer + s * ds * width.
+struct StepList { const void* p; int width; };
+struct StepInputs { const int32_t* id[3]; const float* f[2]; int64_t ds; };
+// Device lists (ORX_IDS_DEVICE) pass through with ds = id_stride; host lists are packed at B * width elements per step, the ids
+// into ctx->d_ids and the floats into ctx->d_lab (one copy per list where the host array is packed already), with ds = B.
+int orx_stage_steps(orx_ctx* c, int64_t K, int64_t B, int64_t id_stride, int flags, std::initializer_list<StepList> ids,
+                    std::initializer_list<StepList> floats, StepInputs* in);
+constexpr int64_t ORX_STEP_CHUNK = 32;        // steps whose loss partials one loss_reduce launch sums (and whose id lists the subset route sorts together)
+// K steps in chunks of min(K, ORX_STEP_CHUNK): chunk(s0, kc) before a chunk's steps (empty: nothing), step(s, i, partial) for step
+// s = s0 + i with the np (loss, l2) partials it writes, one loss_reduce per chunk when a loss is wanted; then the losses are
+// fetched and, for host ids, the index flag is looked at.  d_partial and d_loss are sized here, before the first pointer into them.
+int orx_run_steps(orx_ctx* c, int64_t K, int np, int flags, float* loss_out, float* l2_out,
+                  const std::function<int(int64_t, int64_t)>& chunk, const std::function<int(int64_t, int64_t, float*)>& step);
+// a forward-only entry point: forward(partial) launches one step's forward; its np partials are summed and fetched, the index flag
+// is looked at wherever the ids live
+int orx_run_forward(orx_ctx* c, int np, float* loss_out, float* l2_out, const std::function<int(float*)>& forward);
+// The checks every family that scores by dot products over (U, V, b) makes, with `fn` in front of each message.  The model
+// (step and forward alike): NULLs, contexts, U->dim == V->dim + extra_dim (VBPR: the projection width), the bias shape, flags outside `allowed`, ORX_HOGWILD / ORX_CENSOR.
+// The step: the model's, then the optimizer, l2_reg, ORX_NO_L2, K / B / id_stride, what orx_apply_rows would refuse, the counter.
+int orx_check_dot_model(const char* fn, orx_ctx* c, orx_table* U, orx_table* V, orx_table* b, int extra_dim, int flags, int allowed);
+int orx_check_dot_step(const char* fn, orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, int extra_dim,
+                       int64_t K, int64_t B, int64_t id_stride, float l2_reg, int flags, int allowed);
+int orx_check_apply_rows_opt(const orx_opt* opt, const orx_table* t, const orx_table* bias);      // orx_apply_rows' refusal of an optimizer kind, with its message
+// lazy tables: the rows a step reads are replayed to the optimizer's step (no-ops for a table that is current) -- U with the user
+// list, V and b with each item list (i1 NULL: one list)
+int orx_touch_step(orx_table* U, orx_table* V, orx_table* b, const int32_t* uid, int64_t nu, const int32_t* i0, int64_t n0,
+                   const int32_t* i1, int64_t n1);
+// orx_rows_sort of K lists with the pairs left in `keep` ([K][n], the caller's): the sort's own output lasts until the context's next sort
+int orx_rows_sort_keep(orx_ctx* c, const int32_t* ids, int64_t K, int64_t n, int64_t id_stride, int64_t rows, uint2* keep);
+// orx_apply_rows' deterministic route on a list that is sorted already: the table is synced unless it is lazy under `opt`
+int orx_apply_rows_sorted(orx_ctx* c, orx_opt* opt, orx_table* t, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride);
 // the bodies of the train steps with the objective's two knobs exposed (api_weighted.hip): per-triplet weights (NULL: all ones) and
 // the coefficient l2w of l2_loss; the plain entry points pass NULL and 0 / 1
 int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,

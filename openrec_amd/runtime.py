@@ -298,12 +298,54 @@ def _weights_arg(weights, ids_on_device, n_ids, what):
     return pw, kw
 
 
-def _l2_reg_arg(l2_reg, no_l2, what):
-    if l2_reg is None:
-        return 0.0 if no_l2 else 1.0
+def _l2_arg(what, l2_reg, no_l2, default_is_one=False):
+    """l2_reg (None: 1) and no_l2 (the coefficient 0) of a step -> the coefficient of l2_loss.  no_l2 goes with no l2_reg of the
+    caller's own: None, and where the step's signature defaults l2_reg to 1.0 (default_is_one) also that value and 0."""
     if no_l2:
-        raise ValueError(f"{what}: no_l2=True together with l2_reg (drop no_l2, or pass l2_reg=0.0)")
-    return float(l2_reg)
+        if l2_reg is not None and not (default_is_one and l2_reg in (0, 0.0, 1.0)):
+            raise ValueError(f"{what}: no_l2=True together with l2_reg = {l2_reg} (drop no_l2, or pass l2_reg=0.0)")
+        return 0.0
+    l2c = float(1.0 if l2_reg is None else l2_reg)
+    if not (np.isfinite(l2c) and l2c >= 0.0):
+        raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+    return l2c
+
+
+def _step_shape(what, K, B, id_stride, n_ids):
+    """K, B and id_stride of a K-step call over id lists of n_ids elements (B None: n_ids // K; id_stride None: B) -> the three
+    as ints and the elements a list needs"""
+    K = int(K)
+    if K < 0:
+        raise ValueError(f"{what}: K = {K}")
+    if B is None:
+        B = n_ids // K if K else 0
+    B = int(B)
+    if id_stride is None:
+        id_stride = B
+    id_stride = int(id_stride)
+    if B < 0 or id_stride < B:
+        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
+    return K, B, id_stride, ((K - 1) * id_stride + B if K and B else 0)
+
+
+def _loss_outputs(K, want_loss):
+    """-> ((loss[K], l2[K]) as numpy float32 or None, and the two pointers for the library)"""
+    if not want_loss:
+        return None, None, None
+    out = np.empty(K, np.float32), np.empty(K, np.float32)
+    return out, out[0].ctypes.data, out[1].ctypes.data
+
+
+def _offsets_arg(what, name, offsets, ids_on_device, n, like):
+    """an optional float list beside the ids (neg_offset, item_offset) -> (pointer, keepalive); it lives where the ids live and
+    has n elements, shaped like the id list `like`"""
+    po, no, do, ko = _label_arg(offsets)
+    if do != ids_on_device:
+        raise ValueError(f"{what}: {name} on the {'device' if do else 'host'} with ids on the {'device' if ids_on_device else 'host'} "
+                         "(the offsets live where the ids live)")
+    if no != n:
+        raise ValueError(f"{what}: {no} offsets for {n} {'negative ids' if like == 'nid' else 'ids'} ({name} is shaped like {like})")
+    return po, ko
 
 
 def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None,
@@ -319,7 +361,7 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
     mask = _train_mask(train, bias)
     weighted = weights is not None or l2_reg is not None
     if weighted:
-        l2c = _l2_reg_arg(l2_reg, no_l2, "pairwise_step")
+        l2c = _l2_arg("pairwise_step", l2_reg, no_l2)
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pp, npn, dp, k1 = _ids_arg(pid)
@@ -334,13 +376,7 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
     flags = ((_ffi.ORX_IDS_DEVICE if du else 0) | (_ffi.ORX_HOGWILD if hogwild else 0)
              | (_ffi.ORX_NO_L2 if no_l2 else 0) | (_ffi.ORX_CENSOR if censor else 0))
     mid = {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
-    if want_loss:
-        loss = np.empty(K, np.float32)
-        l2 = np.empty(K, np.float32)
-        lp, l2p = loss.ctypes.data, l2.ctypes.data
-    else:
-        loss = l2 = None
-        lp = l2p = None
+    out, lp, l2p = _loss_outputs(K, want_loss)
     if weighted:
         pw = kw = None
         if weights is not None:
@@ -356,7 +392,7 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
         check(lib.orx_pairwise_step_subset(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
                                            int(K), int(B), int(id_stride), float(margin), flags, mask, lp, l2p))
     _keep_tables(opt, (user, item, bias))
-    return (loss, l2) if want_loss else None
+    return out
 
 
 def pairwise_reserve(opt, user, item, bias, K, B):
@@ -408,18 +444,7 @@ def _multineg_args(what, loss, user, item, bias, uid, pid, nid, K, B, id_stride,
     pn, nn, dn, k2 = _ids_arg(nid)
     if not (du == dp == dn):
         raise ValueError(f"{what}: ids must be all on the host or all on the device")
-    K = int(K)
-    if K < 0:
-        raise ValueError(f"{what}: K = {K}")
-    if B is None:
-        B = nu // K if K else 0
-    B = int(B)
-    if id_stride is None:
-        id_stride = B
-    id_stride = int(id_stride)
-    if B < 0 or id_stride < B:
-        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
-    need = (K - 1) * id_stride + B if K and B else 0
+    K, B, id_stride, need = _step_shape(what, K, B, id_stride, nu)
     if nu != npn or nu < need or nn != nu * N:
         raise ValueError(f"{what}: {nu} user ids, {npn} positive ids and {nn} negative ids for K = {K}, B = {B}, "
                          f"id_stride = {id_stride}, N = {N} (uid and pid alike, nid N times as long)")
@@ -429,12 +454,7 @@ def _multineg_args(what, loss, user, item, bias, uid, pid, nid, K, B, id_stride,
         pw, kw = _weights_arg(weights, du, nu, what)
         keep.append(kw)
     if neg_offset is not None:
-        po, no, do, ko = _label_arg(neg_offset)
-        if do != du:
-            raise ValueError(f"{what}: neg_offset on the {'device' if do else 'host'} with ids on the {'device' if du else 'host'} "
-                             "(the offsets live where the ids live)")
-        if no != nn:
-            raise ValueError(f"{what}: {no} offsets for {nn} negative ids (neg_offset is shaped like nid)")
+        po, ko = _offsets_arg(what, "neg_offset", neg_offset, du, nn, "nid")
         keep.append(ko)
     user.ctx.after_torch(uid, pid, nid, weights, neg_offset)
     return _MN_KIND[loss], N, K, B, id_stride, du, (pu, pp, pn, pw, po), keep
@@ -451,21 +471,10 @@ def multineg_step(loss, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_st
     unscaled l2_loss -- when want_loss, else None (fully asynchronous).  Bad arguments raise ValueError before the library is
     called; an id outside its table raises IndexError."""
     what = "multineg_step"
-    if no_l2:
-        if l2_reg not in (None, 0, 0.0, 1.0):
-            raise ValueError(f"{what}: no_l2=True together with l2_reg = {l2_reg} (drop no_l2, or pass l2_reg=0.0)")
-        l2_reg = 0.0
-    l2c = float(1.0 if l2_reg is None else l2_reg)
-    if not (np.isfinite(l2c) and l2c >= 0.0):
-        raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+    l2c = _l2_arg(what, l2_reg, no_l2, default_is_one=True)
     kind, N, K, B, id_stride, dev, ptrs, keep = _multineg_args(what, loss, user, item, bias, uid, pid, nid, K, B, id_stride,
                                                                 weights, neg_offset)
-    if want_loss:
-        out = np.empty(K, np.float32), np.empty(K, np.float32)
-        lp, l2p = out[0].ctypes.data, out[1].ctypes.data
-    else:
-        out = None
-        lp = l2p = None
+    out, lp, l2p = _loss_outputs(K, want_loss)
     check(user.ctx._lib.orx_multineg_step(user.ctx._h, kind, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, N, id_stride,
                                           l2c, _ffi.ORX_IDS_DEVICE if dev else 0, lp, l2p))
     _keep_tables(opt, (user, item, bias))
@@ -502,18 +511,7 @@ def _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights, it
     pp, npn, dp, k1 = _ids_arg(pid)
     if du != dp:
         raise ValueError(f"{what}: ids must be all on the host or all on the device")
-    K = int(K)
-    if K < 0:
-        raise ValueError(f"{what}: K = {K}")
-    if B is None:
-        B = nu // K if K else 0
-    B = int(B)
-    if id_stride is None:
-        id_stride = B
-    id_stride = int(id_stride)
-    if B < 0 or id_stride < B:
-        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
-    need = (K - 1) * id_stride + B if K and B else 0
+    K, B, id_stride, need = _step_shape(what, K, B, id_stride, nu)
     if nu != npn or nu < need:
         raise ValueError(f"{what}: {nu} user ids and {npn} positive ids for K = {K}, B = {B}, id_stride = {id_stride} "
                          "(uid and pid alike)")
@@ -523,12 +521,7 @@ def _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights, it
         pw, kw = _weights_arg(weights, du, nu, what)
         keep.append(kw)
     if item_offset is not None:
-        po, no, do, ko = _label_arg(item_offset)
-        if do != du:
-            raise ValueError(f"{what}: item_offset on the {'device' if do else 'host'} with ids on the {'device' if du else 'host'} "
-                             "(the offsets live where the ids live)")
-        if no != nu:
-            raise ValueError(f"{what}: {no} offsets for {nu} ids (item_offset is shaped like pid)")
+        po, ko = _offsets_arg(what, "item_offset", item_offset, du, nu, "pid")
         keep.append(ko)
     user.ctx.after_torch(uid, pid, weights, item_offset)
     return K, B, id_stride, du, (pu, pp, pw, po), scale, chunk, keep
@@ -545,21 +538,10 @@ def inbatch_step(opt, user, item, bias, uid, pid, K=1, B=None, id_stride=None, w
     launcher's choice.  Returns (loss[K], l2[K]) as numpy float32 -- l2 the unscaled l2_loss -- when want_loss, else None
     (fully asynchronous).  Bad arguments raise ValueError before the library is called; an id outside its table IndexError."""
     what = "inbatch_step"
-    if no_l2:
-        if l2_reg not in (None, 0, 0.0, 1.0):
-            raise ValueError(f"{what}: no_l2=True together with l2_reg = {l2_reg} (drop no_l2, or pass l2_reg=0.0)")
-        l2_reg = 0.0
-    l2c = float(1.0 if l2_reg is None else l2_reg)
-    if not (np.isfinite(l2c) and l2c >= 0.0):
-        raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+    l2c = _l2_arg(what, l2_reg, no_l2, default_is_one=True)
     K, B, id_stride, dev, ptrs, scale, chunk, keep = _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights,
                                                                    item_offset, scale, chunk)
-    if want_loss:
-        out = np.empty(K, np.float32), np.empty(K, np.float32)
-        lp, l2p = out[0].ctypes.data, out[1].ctypes.data
-    else:
-        out = None
-        lp = l2p = None
+    out, lp, l2p = _loss_outputs(K, want_loss)
     flags = (_ffi.ORX_IDS_DEVICE if dev else 0) | (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0)
     check(user.ctx._lib.orx_inbatch_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, id_stride, scale, l2c,
                                          chunk, flags, lp, l2p))
@@ -621,7 +603,7 @@ def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None
     l2_reg: the objective loss + l2_reg * l2_loss (orx_pointwise_step_l2reg); the returned l2 stays the unscaled l2_loss."""
     mask = _train_mask(train, bias)
     if l2_reg is not None:
-        l2c = _l2_reg_arg(l2_reg, no_l2, "pointwise_step")
+        l2c = _l2_arg("pointwise_step", l2_reg, no_l2)
     lib = user.ctx._lib
     pu, nu, du, k0 = _ids_arg(uid)
     pi, ni, di, k1 = _ids_arg(iid)
@@ -634,19 +616,17 @@ def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None
         id_stride = B
     flags = (_ffi.ORX_IDS_DEVICE if du else 0) | (_ffi.ORX_HOGWILD if hogwild else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0) \
         | (_ffi.ORX_POINT_SIGMOID if sigmoid else 0)
-    loss = np.empty(K, np.float32) if want_loss else None
-    l2 = np.empty(K, np.float32) if want_loss else None
+    out, *outs = _loss_outputs(K, want_loss)
     args = (user.ctx._h, _POINT[model], opt._h, user._h, item._h, bias._h, w._h if w is not None else None, pu, pi, pl,
             int(K), int(B), int(id_stride), float(a), float(b_w), flags)
-    outs = (loss.ctypes.data if want_loss else None, l2.ctypes.data if want_loss else None)
     if l2_reg is not None:
         check(lib.orx_pointwise_step_l2reg(*args[:-1], l2c, flags & ~_ffi.ORX_NO_L2, mask or 0, *outs))
     elif mask is None:
         check(lib.orx_pointwise_step(*args, *outs))
     else:
         check(lib.orx_pointwise_step_subset(*args, mask, *outs))
-    opt._tables = list({id(t): t for t in (opt._tables + [user, item, bias] + ([w] if w is not None else []))}.values())
-    return (loss, l2) if want_loss else None
+    _keep_tables(opt, (user, item, bias, w))
+    return out
 
 
 def pointwise_loss(model, user, item, bias, w, uid, iid, label, a=1.0, b_w=1.0, sigmoid=False):
@@ -2127,20 +2107,9 @@ class VBPR:
         pn, nn, dn, k2 = _ids_arg(nid)
         if not (du == dp == dn):
             raise ValueError(f"{what}: ids must be all on the host or all on the device")
-        K = int(K)
-        if K < 0:
-            raise ValueError(f"{what}: K = {K}")
-        if B is None:
-            B = nu // K if K else 0
-        B = int(B)
-        if id_stride is None:
-            id_stride = B
-        id_stride = int(id_stride)
-        if B < 0 or id_stride < B:
-            raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
+        K, B, id_stride, need = _step_shape(what, K, B, id_stride, nu)
         if B >= 2 ** 31 - 256:
             raise ValueError(f"{what}: B = {B}; B must be below 2^31 - 256")
-        need = (K - 1) * id_stride + B if K and B else 0
         if not (nu == npn == nn) or nu < need:
             raise ValueError(f"{what}: {nu} user ids, {npn} positive ids and {nn} negative ids for K = {K}, B = {B}, "
                              f"id_stride = {id_stride} (the three alike)")
@@ -2177,12 +2146,7 @@ class VBPR:
         if batch_chunk < 0 or batch_chunk % 64:
             raise ValueError(f"{what}: batch_chunk = {batch_chunk}; 0 (the launcher's choice) or a positive multiple of 64")
         K, B, id_stride, dev, ptrs, keep = self._args(what, uid, pid, nid, K, B, id_stride, weights)
-        if want_loss:
-            out = np.empty(K, np.float32), np.empty(K, np.float32)
-            lp, l2p = out[0].ctypes.data, out[1].ctypes.data
-        else:
-            out = None
-            lp = l2p = None
+        out, lp, l2p = _loss_outputs(K, want_loss)
         self._fresh = False
         f = self.features
         check(self.ctx._lib.orx_vbpr_step(self.ctx._h, opt._h, self.U._h, self.V._h, _bias_h(self.b), self.E._h, f.device_ptr, f.rows, f.dim,

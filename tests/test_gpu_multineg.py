@@ -169,6 +169,20 @@ def test_host_and_device_inputs_give_the_same_tables(opt):
     host, _, lh = _run(case, w=w, off=off, check=False)
     dev, _, ld = _run(case, w=w, off=off, device=True, check=False)
     assert _same(_bits(*host), _bits(*dev)) and np.array_equal(lh[0], ld[0]) and np.array_equal(lh[1], ld[1])
+    # host lists with id_stride > B: every list is packed step by step, the lists of width N too
+    rt = _rt()
+    U, V, b, uid, pid, nid = mc.make(case)
+    S = 80
+
+    def pad(x, fill):
+        out = np.full((3, S) + x.shape[2:], fill, x.dtype)
+        out[:, :65] = x
+        return out
+
+    tabs = _tables(rt, U, V, b)
+    lp = rt.multineg_step(case["kind"], _dev_opt(rt, opt), *tabs, pad(uid, 299), pad(pid, 399), pad(nid, 399), K=3, B=65, id_stride=S,
+                          weights=pad(w, 7.0), neg_offset=pad(off, 3.0))
+    assert _same(_bits(*host), _bits(*tabs)) and np.array_equal(lh[0], lp[0]) and np.array_equal(lh[1], lp[1])
 
 
 @pytest.mark.parametrize("opt", mc.OPTS)
