@@ -11,21 +11,6 @@ static constexpr size_t ORX_TOPK_DENSE_BYTES = (size_t)256 << 20;   // dense sco
 static constexpr size_t ORX_TOPK_BATCH_BYTES = (size_t)512 << 20;   // sample rows + candidate lists of one batch of users
 static constexpr int ORX_TOPK_MAX_K = 1024;
 
-// the exclusion lists: offsets from 0, never decreasing, ids inside [0, items)
-static int topk_check_excl(const char* fn, const int64_t* ptr, const int32_t* items, int64_t n, int64_t NI) {
-    if (ptr == nullptr) return ORX_OK;
-    ORX_ARG(ptr[0] == 0, "%s: the exclusion lists start at offset 0", fn);
-    for (int64_t q = 0; q < n; ++q) ORX_ARG(ptr[q + 1] >= ptr[q], "%s: exclusion offsets must not decrease", fn);
-    ORX_ARG(ptr[n] == 0 || items, "%s: NULL exclusion item list", fn);
-    for (int64_t i = 0; i < ptr[n]; ++i) {
-        if (items[i] < 0 || items[i] >= NI) {
-            orx_set_error("%s: exclusion id %d outside [0, %lld)", fn, items[i], (long long)NI);
-            return ORX_ERR_INDEX;
-        }
-    }
-    return ORX_OK;
-}
-
 // device scratch of one batch of nb users (d_topk), 256-byte aligned pieces
 struct TopkScratch {
     float* theta; int* cnt; float* cs; int32_t* ci;
@@ -39,9 +24,8 @@ static int topk_scratch(orx_ctx* c, int64_t nb, int C, int64_t max_excl, int k, 
     const size_t sizes[12] = {(size_t)nb * 4, (size_t)nb * 4, (size_t)nb * C * 4, (size_t)nb * C * 4, (size_t)(nb + 1) * 8,
                               (size_t)max_excl * 4, (size_t)nb * 4, (size_t)nb * 4, (size_t)nb * k * 4, (size_t)nb * k * 4,
                               pool * 8, pool * 4};
-    size_t off[12], total = 0;
-    for (int i = 0; i < 12; ++i) { off[i] = total; total += (sizes[i] + 255) & ~(size_t)255; }
-    ENSURE(c->d_topk, c->d_topk_cap, total);
+    size_t off[12];
+    ENSURE(c->d_topk, c->d_topk_cap, orx_layout(sizes, 12, off));
     unsigned char* p = c->d_topk;
     s->theta = (float*)(p + off[0]); s->cnt = (int*)(p + off[1]); s->cs = (float*)(p + off[2]); s->ci = (int32_t*)(p + off[3]);
     s->eptr = (int64_t*)(p + off[4]); s->eitems = (int32_t*)(p + off[5]); s->rowmap = (int32_t*)(p + off[6]);
@@ -60,19 +44,11 @@ static int64_t topk_max_excl(const int64_t* ptr, int64_t n, int64_t nb) {
 static int topk_stage_excl(orx_ctx* c, const int64_t* ptr, const int32_t* items, int64_t q0, int64_t nq, const TopkScratch& s,
                            std::vector<int64_t>& hp, std::vector<int32_t>& hi) {
     hp.resize(nq + 1);
-    const int64_t base = ptr[q0], ne = ptr[q0 + nq] - base;
-    for (int64_t q = 0; q <= nq; ++q) hp[q] = ptr[q0 + q] - base;
-    hi.assign(items + base, items + base + ne);
-    for (int64_t q = 0; q < nq; ++q)
-        if (!std::is_sorted(hi.begin() + hp[q], hi.begin() + hp[q + 1])) std::sort(hi.begin() + hp[q], hi.begin() + hp[q + 1]);
-    ORX_HIP(hipMemcpyAsync(s.eptr, hp.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (ne) ORX_HIP(hipMemcpyAsync(s.eitems, hi.data(), (size_t)ne * 4, hipMemcpyHostToDevice, c->stream));
-    return ORX_OK;
+    return orx_stage_csr(c, ptr, items, q0, nq, hp.data(), &hi, s.eptr, s.eitems, nullptr);
 }
 
 // the given batch users scored densely, a bounded number of rows at a time, and selected: the direct route and the fallback.
-// wide: the call has more than 64 users, and so does every scorer launch here where there are that many rows -- the scorer's
-// tile holds 128 users then, and its L2 norms are only bit-stable within one tile shape (kernels_topk.hip)
+// wide: the call has more than 64 users, and so does every scorer launch here where there are that many rows (orx_dense_rows)
 static int topk_dense_users(orx_ctx* c, int kind, orx_table* U, orx_table* V, orx_table* b, orx_table* w, const int32_t* huid,
                             const std::vector<int32_t>& local, const TopkScratch& s, bool excl, bool wide, int k, int32_t* oi,
                             float* os, std::vector<int32_t>& huid_sub) {
@@ -102,24 +78,13 @@ static int topk_dense_users(orx_ctx* c, int kind, orx_table* U, orx_table* V, or
 extern "C" int orx_recommend_topk(orx_ctx* c, int kind, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
                                   const int32_t* uid, int64_t n, const int64_t* excl_ptr, const int32_t* excl_items, int32_t k,
                                   int flags, int32_t* out_items, float* out_scores) {
-    if (U) CHECK(orx_table_sync(U));
-    if (V) CHECK(orx_table_sync(V));
-    if (b) CHECK(orx_table_sync(b));
-    if (w) CHECK(orx_table_sync(w));
-    ORX_ARG(c && U && V && n >= 0 && (n == 0 || (uid && out_items && out_scores)), "orx_recommend_topk: NULL argument");
-    ORX_ARG(k >= 1 && k <= ORX_TOPK_MAX_K, "orx_recommend_topk: k = %d outside [1, %d]", k, ORX_TOPK_MAX_K);
-    ORX_ARG((flags & ~ORX_OUT_DEVICE) == 0, "orx_recommend_topk: unknown flags 0x%x", flags);
-    ORX_ARG(kind >= 0 && kind <= 2, "orx_recommend_topk: unknown kind %d", kind);
-    ORX_ARG(U->dim == V->dim && (!b || (b->rows == V->rows && b->dim == 1)), "orx_recommend_topk: table shapes do not match");
-    ORX_ARG(kind != 2 || (w && w->rows == U->dim && w->dim == 1), "orx_recommend_topk: GMF needs w [D, 1]");
-    ORX_ARG(U->dim <= 1024, "orx_recommend_topk: dim too large for the LDS user tile");
-    CHECK(topk_check_excl("orx_recommend_topk", excl_ptr, excl_items, n, V->rows));
-    for (int64_t q = 0; q < n; ++q) {
-        if (uid[q] < 0 || uid[q] >= U->rows) {
-            orx_set_error("orx_recommend_topk: user id %d outside [0, %lld)", uid[q], (long long)U->rows);
-            return ORX_ERR_INDEX;
-        }
-    }
+    static const char* fn = "orx_recommend_topk";
+    CHECK(orx_sync_tables({U, V, b, w}));
+    ORX_ARG(c && U && V && n >= 0 && (n == 0 || (uid && out_items && out_scores)), "%s: NULL argument", fn);
+    ORX_ARG(k >= 1 && k <= ORX_TOPK_MAX_K, "%s: k = %d outside [1, %d]", fn, k, ORX_TOPK_MAX_K);
+    ORX_ARG((flags & ~ORX_OUT_DEVICE) == 0, "%s: unknown flags 0x%x", fn, flags);
+    CHECK(orx_check_scorer(fn, c, kind, U, V, b, w, uid, n, true));
+    if (excl_ptr) CHECK(orx_check_lists(fn, "exclusion", excl_ptr, excl_items, n, V->rows, false, nullptr));
     if (n == 0) return ORX_OK;
     ORX_HIP(hipSetDevice(c->device));
     const int64_t NI = V->rows;
@@ -188,7 +153,7 @@ extern "C" int orx_topk_rows(orx_ctx* c, const float* scores, int32_t scores_on_
                              const int64_t* excl_ptr, const int32_t* excl_items, int32_t k, int32_t* out_items, float* out_scores) {
     ORX_ARG(c && n >= 0 && m >= 1 && (n == 0 || (scores && out_items && out_scores)), "orx_topk_rows: NULL argument");
     ORX_ARG(k >= 1 && k <= ORX_TOPK_MAX_K, "orx_topk_rows: k = %d outside [1, %d]", k, ORX_TOPK_MAX_K);
-    CHECK(topk_check_excl("orx_topk_rows", excl_ptr, excl_items, n, m));
+    if (excl_ptr) CHECK(orx_check_lists("orx_topk_rows", "exclusion", excl_ptr, excl_items, n, m, false, nullptr));
     if (n == 0) return ORX_OK;
     ORX_HIP(hipSetDevice(c->device));
     const int64_t nb = scores_on_device ? std::min<int64_t>(n, 4096)

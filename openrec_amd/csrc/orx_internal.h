@@ -232,6 +232,49 @@ int orx_touch_step(orx_table* U, orx_table* V, orx_table* b, const int32_t* uid,
 int orx_rows_sort_keep(orx_ctx* c, const int32_t* ids, int64_t K, int64_t n, int64_t id_stride, int64_t rows, uint2* keep);
 // orx_apply_rows' deterministic route on a list that is sorted already: the table is synced unless it is lazy under `opt`
 int orx_apply_rows_sorted(orx_ctx* c, orx_opt* opt, orx_table* t, const uint2* sorted, int64_t n, const float* grads, int64_t g_stride);
+// ---------------------------------- the host driver of the scoring, top-K and ranking-metric calls (api_eval.hip) ---
+constexpr int ORX_EVAL_NAT = 16;              // most cut-offs of one metrics call (the kernels keep them in a fixed array)
+int orx_sync_tables(std::initializer_list<orx_table*> tables);        // orx_table_sync of each (NULL entries skipped): first, before the argument checks
+// The scorer's argument checks (U and V not NULL), `fn` in front of each message: kind, U->dim == V->dim and the bias [items, 1], GMF's
+// w [D, 1], dim <= 1024 -- ORX_ERR_ARG -- and, for the calls that check their host user ids before any device work, ORX_ERR_INDEX
+int orx_check_scorer(const char* fn, orx_ctx* c, int kind, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
+                     const int32_t* uid, int64_t n, bool check_uid_on_host);
+// CSR lists over n users (ptr not NULL): offsets from 0 that never decrease, ids inside [0, NI) (ORX_ERR_INDEX, naming the user),
+// with `ascending` every row strictly ascending; *longest (may be NULL): the longest row
+int orx_check_lists(const char* fn, const char* what, const int64_t* ptr, const int32_t* items, int64_t n, int64_t NI,
+                    bool ascending, int64_t* longest);
+// The lists of users [q0, q0 + nq) of a CSR, offsets rebased to 0 (hp [nq + 1], the caller's, alive until the stream is synchronised):
+// one async copy per piece on c->stream (sorted not NULL: the item slice goes through it, sorted inside each row), or offsets and item
+// slice written into a caller's packed host buffer
+struct CsrSlice { int64_t first, count, longest; };   // items [first, first + count) of the CSR; the batch's longest row
+int orx_stage_csr(orx_ctx* c, const int64_t* ptr, const int32_t* items, int64_t q0, int64_t nq, int64_t* hp,
+                  std::vector<int32_t>* sorted, int64_t* d_ptr, int32_t* d_items, CsrSlice* out);
+CsrSlice orx_pack_csr(const int64_t* ptr, const int32_t* items, int64_t q0, int64_t nq, int64_t* hp, void* hi);
+size_t orx_layout(const size_t* sizes, int n, size_t* off);           // consecutive 256-byte aligned pieces: their offsets, the total
+int64_t orx_largest_batch(int64_t lo, int64_t hi, const std::function<bool(int64_t)>& fits);     // the largest m in [lo, hi] that fits (fits monotone; lo if none does)
+// Score rows of a batch of nq users in a call of n users on the dense route.  A call of more than 64 users scores at least 65 rows
+// in every launch: the scorer's tile holds 128 users then, and its L2 norms are only bit-stable within one tile shape
+// (kernels_topk.hip) -- so a short last batch computes what the one-batch call computes.
+inline int64_t orx_dense_rows(int64_t n, int64_t nq) { return n > 64 && nq < 65 ? 65 : nq; }
+int orx_stage_uid_rows(orx_ctx* c, const int32_t* uid, int64_t nq, int64_t rows);     // nq host ids into d_ids (grown here), padded to `rows` with the first
+int orx_evalbits_reserve(orx_ctx* c, size_t bytes);                   // grow d_evalbits; a new buffer starts out all zero
+// buckets of the rank kernels: 2^STEPS, STEPS from the call's longest positive list as rank_sweep_kernel picks it
+inline int orx_rank_buckets(int64_t max_pos) { return max_pos <= 7 ? 8 : (max_pos <= 15 ? 16 : 64); }
+// async copies of the metrics of users [q0, q0 + nq) to the host outputs that are not NULL
+int orx_fetch_metrics(orx_ctx* c, const float* d_auc, const float* d_ndcg, const float* d_rec, int64_t q0, int64_t nq, int nat,
+                      float* auc, float* ndcg, float* recall);
+// One batch of the CSR metrics over users [q0, q0 + nq) of a call of n users: one packed upload (the lists rebased, the cut-offs), the
+// bitmaps, the scores (host pred, device pred, or the scorer over orx_dense_rows rows when pred is NULL), the sweeps, one packed
+// download; outputs land at row q0.  Leaves the bitmaps all zero whether it succeeds or not.
+struct RankCsrCall {
+    const char* fn; int kind; orx_table* U; orx_table* V; orx_table* b; orx_table* w; const int32_t* uid;
+    const float* pred; bool pred_on_device;               // [n, items], NULL: the scorer
+    int64_t n, items;
+    const int64_t* pos_ptr; const int32_t* pos_items; const int64_t* excl_ptr; const int32_t* excl_items;
+    const float* at; int nat; int64_t max_pos;            // max_pos: the CALL's longest positive list (every batch takes the call's chunking)
+    float* auc; float* ndcg; float* recall;
+};
+int orx_rank_csr_run(orx_ctx* c, const RankCsrCall& k, int64_t q0, int64_t nq);
 // the bodies of the train steps with the objective's two knobs exposed (api_weighted.hip): per-triplet weights (NULL: all ones) and
 // the coefficient l2w of l2_loss; the plain entry points pass NULL and 0 / 1
 int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,

@@ -688,14 +688,21 @@ class DeviceScores(_HostView):
         return self.tensor.cpu().numpy()
 
 
-class SparseMask(_HostView):
-    """A batch of boolean item masks [n, items] as one sorted list of distinct items per row (CSR): what
-    `Dataset.evaluation` hands out instead of the dense rows of openrec/tf2/data/dataset.py:60-82.  Dense on demand."""
-    dtype = np.dtype(bool)
+class _ItemLists:
+    """One list of item ids per row over `n_items` items: `ptr` int64 [n + 1] from 0, `items` int32, `shape` (n, n_items)."""
 
     def __init__(self, ptr, items, n_items):
         self.ptr = np.ascontiguousarray(ptr, np.int64); self.items = np.ascontiguousarray(items, np.int32)
         self.shape = (self.ptr.size - 1, int(n_items))
+
+    def row(self, q):
+        return self.items[self.ptr[q]:self.ptr[q + 1]]
+
+
+class SparseMask(_ItemLists, _HostView):
+    """A batch of boolean item masks [n, items] as one sorted list of distinct items per row (CSR): what
+    `Dataset.evaluation` hands out instead of the dense rows of openrec/tf2/data/dataset.py:60-82.  Dense on demand."""
+    dtype = np.dtype(bool)
 
     @classmethod
     def from_lists(cls, lists, n_items):
@@ -713,23 +720,44 @@ class SparseMask(_HostView):
         ptr = np.zeros(m.shape[0] + 1, np.int64); np.cumsum(np.bincount(r, minlength=m.shape[0]), out=ptr[1:])
         return cls(ptr, c.astype(np.int32), m.shape[1])
 
-    def row(self, q):
-        return self.items[self.ptr[q]:self.ptr[q + 1]]
-
     def _dense(self):
         m = np.zeros(self.shape, bool)
         m[np.repeat(np.arange(self.shape[0]), np.diff(self.ptr)), self.items] = True
         return m
 
 
+def _kind_arg(kind):
+    return {"dot": 0, "l2": 1, "gmf": 2}[kind]
+
+
+def _scorer_head(user, item, bias, w):
+    """the table handles of a scorer call: user, item, bias (None: no "+ b"), GMF's w"""
+    return user._h, item._h, _bias_h(bias), w._h if w is not None else None
+
+
+def _host_uid(what, uid, n=None):
+    """host user ids -> (pointer, count, the array to keep alive); `n`: the rows of the masks they go with"""
+    ptr, nn, dev, keep = _ids_arg(uid)
+    if dev:
+        raise ValueError(f"{what} takes host ids")
+    if n is not None and nn != n:
+        raise ValueError(f"{nn} user ids for masks of {n} rows")
+    return ptr, nn, keep
+
+
+def _metric_outputs(n, at):
+    """-> (cut-offs float32 [nat], auc [n], ndcg [n, nat], recall [n, nat], the dict of the three a metrics call returns)"""
+    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
+    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
+    return atv, auc, ndcg, rec, dict(auc=auc, ndcg=ndcg, recall=rec)
+
+
 def score_all_items(kind, user, item, bias, uid, w=None, device=False):
     """Recommender.inference: scores of the given users against ALL items -> [n, item_rows] (host array, or with
     `device=True` a DeviceScores that stays in HBM until someone reads it).  bias=None: no "+ b" (bias-free models)."""
     lib = user.ctx._lib
-    ptr, n, dev, keep = _ids_arg(uid)
-    if dev:
-        raise ValueError("score_all_items takes host ids")
-    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    ptr, n, keep = _host_uid("score_all_items", uid)
+    head = (user.ctx._h, _kind_arg(kind), *_scorer_head(user, item, bias, w), ptr, n)
     if device:
         try:
             import torch
@@ -738,12 +766,10 @@ def score_all_items(kind, user, item, bias, uid, w=None, device=False):
     if device and torch is not None:
         out = torch.empty((n, item.rows), dtype=torch.float32, device=torch.device("cuda", user.ctx.device))
         user.ctx.after_torch(out)            # (a cached block may still have work of torch's stream pending: the library's stream waits for it)
-        check(lib.orx_score_all_items_device(user.ctx._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None,
-                                             ptr, n, out.data_ptr()))
+        check(lib.orx_score_all_items_device(*head, out.data_ptr()))
         return DeviceScores(user.ctx, out)
     out = np.empty((n, item.rows), np.float32)
-    check(lib.orx_score_all_items(user.ctx._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None,
-                                  ptr, n, out.ctypes.data))
+    check(lib.orx_score_all_items(*head, out.ctypes.data))
     return out
 
 
@@ -774,13 +800,11 @@ def recommend_topk(kind, user, item, bias, uid, k, excl=None, w=None, device=Fal
     `excl` (a SparseMask, or a dense bool mask [n, item_rows]) and NaN scores are skipped, and a row with fewer than k such
     items ends in item -1 / score -inf.  `device=True`: two torch tensors in HBM instead of host arrays."""
     lib = user.ctx._lib
-    ptr, n, dev, keep = _ids_arg(uid)
-    if dev:
-        raise ValueError("recommend_topk takes host ids")
+    ptr, n, keep = _host_uid("recommend_topk", uid)
     k = _topk_k(k)
-    kd = {"dot": 0, "l2": 1, "gmf": 2}[kind]
+    kd = _kind_arg(kind)
     ep, ei = _excl_lists(excl, n, item.rows)
-    head = (user.ctx._h, kd, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+    head = (user.ctx._h, kd, *_scorer_head(user, item, bias, w), ptr, n,
             ep.ctypes.data if ep is not None else None, ei.ctypes.data if ei is not None else None, k)
     if device:
         import torch
@@ -931,9 +955,8 @@ def rank_metrics(pos_mask, excl_mask, at, pred=None, kind=None, user=None, item=
     pos = np.ascontiguousarray(pos_mask, np.uint8)
     excl = np.ascontiguousarray(excl_mask, np.uint8)
     n, items = pos.shape
-    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
+    atv, auc, ndcg, rec, result = _metric_outputs(n, at)
     c = ctx or (user.ctx if user is not None else default_context())
-    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
     if pred is not None:
         pr = np.ascontiguousarray(pred, np.float32)
         assert pr.shape == (n, items)
@@ -942,11 +965,10 @@ def rank_metrics(pos_mask, excl_mask, at, pred=None, kind=None, user=None, item=
     else:
         ptr, nn, dev, keep = _ids_arg(uid)
         assert nn == n and not dev
-        k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
-        check(c._lib.orx_rank_metrics(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, None,
+        check(c._lib.orx_rank_metrics(c._h, _kind_arg(kind), *_scorer_head(user, item, bias, w), ptr, None,
                                       pos.ctypes.data, excl.ctypes.data, n, items, atv.ctypes.data, atv.size,
                                       auc.ctypes.data, ndcg.ctypes.data, rec.ctypes.data))
-    return dict(auc=auc, ndcg=ndcg, recall=rec)
+    return result
 
 
 def rank_metrics_csr(pos, excl, at, pred=None, kind=None, user=None, item=None, bias=None, w=None, uid=None, ctx=None):
@@ -954,9 +976,8 @@ def rank_metrics_csr(pos, excl, at, pred=None, kind=None, user=None, item=None, 
     on the device (`pred` a DeviceScores, or None with the tables + user ids)."""
     assert isinstance(pos, SparseMask) and isinstance(excl, SparseMask) and pos.shape == excl.shape
     n, items = pos.shape
-    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
+    atv, auc, ndcg, rec, result = _metric_outputs(n, at)
     c = ctx or (user.ctx if user is not None else (pred.ctx if isinstance(pred, DeviceScores) else default_context()))
-    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
     tail = (n, items, pos.ptr.ctypes.data, pos.items.ctypes.data, excl.ptr.ctypes.data, excl.items.ctypes.data,
             atv.ctypes.data, atv.size, auc.ctypes.data, ndcg.ctypes.data, rec.ctypes.data)
     if pred is not None:
@@ -971,18 +992,16 @@ def rank_metrics_csr(pos, excl, at, pred=None, kind=None, user=None, item=None, 
     else:
         ptr, nn, dev, keep = _ids_arg(uid)
         assert nn == n and not dev
-        k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
-        check(c._lib.orx_rank_metrics_csr(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, None, 0, *tail))
-    return dict(auc=auc, ndcg=ndcg, recall=rec)
+        check(c._lib.orx_rank_metrics_csr(c._h, _kind_arg(kind), *_scorer_head(user, item, bias, w), ptr, None, 0, *tail))
+    return result
 
 
 def rank_metrics_matrixfree_scratch(n, items, dim, kind, max_pos, max_excl, scratch_bytes=0, ctx=None):
     """(bytes, users_per_batch): the device scratch `rank_metrics_matrixfree` would make for such a call, and the users it
     would take per batch.  Host only."""
     lib = ctx._lib if ctx is not None else _ffi.load()
-    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
     b, u = ctypes.c_int64(), ctypes.c_int64()
-    check(lib.orx_rank_metrics_matrixfree_scratch(int(n), int(items), int(dim), k, int(max_pos), int(max_excl), int(scratch_bytes),
+    check(lib.orx_rank_metrics_matrixfree_scratch(int(n), int(items), int(dim), _kind_arg(kind), int(max_pos), int(max_excl), int(scratch_bytes),
                                                   byref(b), byref(u)))
     return int(b.value), int(u.value)
 
@@ -1005,29 +1024,19 @@ def rank_metrics_matrixfree(pos, excl, at, kind, user, item, bias, uid, w=None, 
     n, items = pos.shape
     if items != item.rows:
         raise ValueError(f"masks over {items} items, the item table has {item.rows} rows")
-    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
-    ptr, nn, dev, keep = _ids_arg(uid)
-    if dev:
-        raise ValueError("rank_metrics_matrixfree takes host ids")
-    if nn != n:
-        raise ValueError(f"{nn} user ids for masks of {n} rows")
+    atv, auc, ndcg, rec, result = _metric_outputs(n, at)
+    ptr, _, keep = _host_uid("rank_metrics_matrixfree", uid, n)
     c = user.ctx
-    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
-    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
-    check(c._lib.orx_rank_metrics_matrixfree(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+    check(c._lib.orx_rank_metrics_matrixfree(c._h, _kind_arg(kind), *_scorer_head(user, item, bias, w), ptr, n,
                                              pos.ptr.ctypes.data, pos.items.ctypes.data, excl.ptr.ctypes.data, excl.items.ctypes.data,
                                              atv.ctypes.data, atv.size, int(scratch_bytes), auc.ctypes.data, ndcg.ctypes.data,
                                              rec.ctypes.data))
-    return dict(auc=auc, ndcg=ndcg, recall=rec)
+    return result
 
 
-class CandidateLists:
+class CandidateLists(_ItemLists):
     """One list of item ids per user, kept in the GIVEN order and with its repeats (a re-ranker's input is ordered by the
     retrieval stage): `ptr` int64 [n + 1] from 0, `items` int32.  `SparseMask` is the sorted, distinct form."""
-
-    def __init__(self, ptr, items, n_items):
-        self.ptr = np.ascontiguousarray(ptr, np.int64); self.items = np.ascontiguousarray(items, np.int32)
-        self.shape = (self.ptr.size - 1, int(n_items))
 
     @classmethod
     def from_lists(cls, lists, n_items):
@@ -1037,9 +1046,6 @@ class CandidateLists:
         if items.size and (items.min() < 0 or items.max() >= n_items):
             raise IndexError(f"item id outside [0, {n_items})")
         return cls(ptr, items.astype(np.int32), n_items)
-
-    def row(self, q):
-        return self.items[self.ptr[q]:self.ptr[q + 1]]
 
 
 def as_candidate_lists(cand, n_items):
@@ -1055,15 +1061,12 @@ def score_candidates(kind, user, item, bias, uid, cand, w=None, device=False):
     given order (repeats allowed).  Every score equals `score_all_items(...)[q, item]` bit for bit; only the listed items are
     scored, so neither work nor memory grows with users x items."""
     lib = user.ctx._lib
-    ptr, n, dev, keep = _ids_arg(uid)
-    if dev:
-        raise ValueError("score_candidates takes host ids")
+    ptr, n, keep = _host_uid("score_candidates", uid)
     cand = as_candidate_lists(cand, item.rows)
     if cand.shape != (n, item.rows):
         raise ValueError(f"candidate lists of shape {cand.shape}, expected {(n, item.rows)}")
-    kd = {"dot": 0, "l2": 1, "gmf": 2}[kind]
     total = int(cand.ptr[-1])
-    head = (user.ctx._h, kd, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+    head = (user.ctx._h, _kind_arg(kind), *_scorer_head(user, item, bias, w), ptr, n,
             cand.ptr.ctypes.data, cand.items.ctypes.data)
     if device:
         import torch
@@ -1096,20 +1099,14 @@ def rank_metrics_candidates(pos, cand, at, kind, user, item, bias, uid, w=None, 
     n, items = pos.shape
     if items != item.rows:
         raise ValueError(f"masks over {items} items, the item table has {item.rows} rows")
-    atv = np.ascontiguousarray(at, np.float32).reshape(-1)
-    ptr, nn, dev, keep = _ids_arg(uid)
-    if dev:
-        raise ValueError("rank_metrics_candidates takes host ids")
-    if nn != n:
-        raise ValueError(f"{nn} user ids for masks of {n} rows")
+    atv, auc, ndcg, rec, result = _metric_outputs(n, at)
+    ptr, _, keep = _host_uid("rank_metrics_candidates", uid, n)
     c = user.ctx
-    auc = np.empty(n, np.float32); ndcg = np.empty((n, atv.size), np.float32); rec = np.empty((n, atv.size), np.float32)
-    k = {"dot": 0, "l2": 1, "gmf": 2}[kind]
-    check(c._lib.orx_rank_metrics_candidates(c._h, k, user._h, item._h, _bias_h(bias), w._h if w is not None else None, ptr, n,
+    check(c._lib.orx_rank_metrics_candidates(c._h, _kind_arg(kind), *_scorer_head(user, item, bias, w), ptr, n,
                                              pos.ptr.ctypes.data, pos.items.ctypes.data, cand.ptr.ctypes.data, cand.items.ctypes.data,
                                              atv.ctypes.data, atv.size, int(scratch_bytes), auc.ctypes.data, ndcg.ctypes.data,
                                              rec.ctypes.data))
-    return dict(auc=auc, ndcg=ndcg, recall=rec)
+    return result
 
 
 CKPT_PIECE_BYTES = 256 << 20          # tables and slots move through the host in pieces of at most this many bytes

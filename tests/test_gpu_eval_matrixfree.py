@@ -178,6 +178,39 @@ def test_batches_equal_one_batch(kind):
     assert_equal(many, one, f"{kind} {-(-n // per)} batches")
 
 
+def test_dense_route_batches_after_a_failed_csr_call():
+    """L2 takes the dense route: the CSR metrics batch of rank_metrics_csr, once per batch.  Two batches of the wide tile shape
+    (65 .. 129 of 130 users each), positive lists of 0 / 7 / 8 / 16 / 70 items (8, 16 and 64 buckets among the users, the call's
+    chunking from the longest), right after a rank_metrics_csr call that failed on the device: equal to rank_metrics_csr over the
+    same users in one call, bit for bit."""
+    rt = _rt()
+    NU, NI, n, D = 150, 300, 130, 8
+    U, V, b, w = tables(rt, NU, NI, D, True, seed=41)
+    rng = np.random.default_rng(42)
+    uid = rng.integers(0, NU, n).astype(np.int32)
+    lengths = (0, 7, 8, 16, 70)
+    pos = [np.sort(rng.choice(NI, lengths[q % len(lengths)], replace=False)) for q in range(n)]
+    excl = [np.setdiff1d(rng.choice(NI, int(rng.integers(0, 40)), replace=False), pos[q]) for q in range(n)]
+    pm, em = rt.SparseMask.from_lists(pos, NI), rt.SparseMask.from_lists(excl, NI)
+    mp, me = max(map(len, pos)), max(map(len, excl))
+    assert mp == 70
+    full, per = rt.rank_metrics_matrixfree_scratch(n, NI, D, "l2", mp, me)
+    assert per == n
+    lo, hi = 1, full                                             # the smallest budget that takes 65 users per batch
+    while lo < hi:
+        mid = (lo + hi) // 2
+        if rt.rank_metrics_matrixfree_scratch(n, NI, D, "l2", mp, me, mid)[1] >= 65: hi = mid
+        else: lo = mid + 1
+    _, per = rt.rank_metrics_matrixfree_scratch(n, NI, D, "l2", mp, me, lo)
+    assert 65 <= per <= 129, per
+    want = rt.rank_metrics_csr(pm, em, AT, kind="l2", user=U, item=V, bias=b, uid=uid)
+    items = pm.items.copy(); items[-1] = NI
+    with pytest.raises(IndexError):
+        rt.rank_metrics_csr(rt.SparseMask(pm.ptr, items, NI), em, AT, kind="l2", user=U, item=V, bias=b, uid=uid)
+    got = rt.rank_metrics_matrixfree(pm, em, AT, "l2", U, V, b, uid, scratch_bytes=lo)
+    assert_equal(got, want, f"l2, {per} users per batch")
+
+
 def test_repeated_call_and_recovery_after_an_index_error():
     rt = _rt()
     NU, NI, n, D = 100, 4099, 70, 64

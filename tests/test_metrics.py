@@ -122,8 +122,13 @@ def test_csr_metrics_reject_bad_lists():
     oob = rt.SparseMask(np.array([0, 1, 2]), np.array([5, 100], np.int32), 100)
     with pytest.raises(IndexError):
         rt.rank_metrics_csr(oob, empty, [10], pred=pred)
-    ok = rt.rank_metrics_csr(rt.SparseMask.from_lists([[5], [7]], 100), empty, [10], pred=pred)   # the context still works
+    # the context still works: both failures left its bitmaps all zero, so it computes what a context that saw no failure computes
+    good = rt.SparseMask.from_lists([[5], [7]], 100)
+    ok = rt.rank_metrics_csr(good, empty, [10], pred=pred)
+    fresh = rt.rank_metrics_csr(good, empty, [10], pred=pred, ctx=rt.Context(0))
     assert np.all(np.isfinite(ok["auc"]))
+    for name in ("auc", "ndcg", "recall"):
+        assert np.array_equal(ok[name], fresh[name], equal_nan=True), name
 
 
 @pytest.mark.gpu
