@@ -1,5 +1,6 @@
-// C-ABI entry points of the pointwise step and its loss, of the sharded building blocks (row gather, pair gradients, the
-// applies of gradient rows with lazy Adam and the planned apply, the device-side exchange plan) and of the device sampler.
+// C-ABI entry points of the pointwise step and its loss and of the sharded building blocks (row gather, pair gradients, the
+// applies of gradient rows with lazy Adam and the planned apply, the device-side exchange plan).  The device sampler's are in
+// api_sampler.hip.
 #include <vector>
 #include <cmath>
 #include <cstring>
@@ -732,99 +733,4 @@ extern "C" int orx_shard_grads_sgd(orx_ctx* ctx, int model, orx_opt* opt, orx_ta
     ORX_ARG(opt && dup_u && u_apply, "orx_shard_grads_sgd: NULL argument");
     return orx_shard_grads_impl(ctx, model, opt, user, rows_in, nullptr, u_loc, slot, dupref, sorted, seglist, segcount, gdup, dup_u, T, row_stride,
                                 B_global, margin, flags, gu, u_apply, send_g, nullptr, loss_l2_accum);
-}
-
-// ------------------------------------------------------------- device sampler ---
-extern "C" int orx_sampler_create(orx_ctx* ctx, const int32_t* rec_user, const int32_t* rec_item, int64_t n_records,
-                                  const int64_t* csr_ptr, const int32_t* csr_items, int64_t total_users, int64_t total_items,
-                                  orx_sampler** out) {
-    ORX_ARG(ctx && rec_user && rec_item && csr_ptr && csr_items && out, "orx_sampler_create: NULL argument");
-    ORX_ARG(n_records > 0 && total_users > 0 && total_items > 0, "orx_sampler_create: sizes must be positive");
-    ORX_HIP(hipSetDevice(ctx->device));
-    orx_sampler* s = new orx_sampler();
-    s->ctx = ctx; s->R = n_records; s->total_users = total_users; s->total_items = total_items;
-    while ((1ll << (2 * s->h)) < n_records) s->h++;
-    const int64_t nnz = csr_ptr[total_users];
-    ORX_HIP(hipMalloc((void**)&s->rec_user, sizeof(int32_t) * n_records));
-    ORX_HIP(hipMalloc((void**)&s->rec_item, sizeof(int32_t) * n_records));
-    ORX_HIP(hipMalloc((void**)&s->ptr, sizeof(int64_t) * (total_users + 1)));
-    ORX_HIP(hipMalloc((void**)&s->items, sizeof(int32_t) * (nnz > 0 ? nnz : 1)));
-    ORX_HIP(hipMemcpy(s->rec_user, rec_user, sizeof(int32_t) * n_records, hipMemcpyHostToDevice));
-    ORX_HIP(hipMemcpy(s->rec_item, rec_item, sizeof(int32_t) * n_records, hipMemcpyHostToDevice));
-    ORX_HIP(hipMemcpy(s->ptr, csr_ptr, sizeof(int64_t) * (total_users + 1), hipMemcpyHostToDevice));
-    if (nnz > 0) ORX_HIP(hipMemcpy(s->items, csr_items, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
-    *out = s;
-    return ORX_OK;
-}
-
-extern "C" int orx_sampler_destroy(orx_sampler* s) {
-    if (!s) return ORX_OK;
-    hipSetDevice(s->ctx->device);
-    hipStreamSynchronize(s->ctx->stream);
-    hipFree(s->rec_user); hipFree(s->rec_item); hipFree(s->ptr); hipFree(s->items);
-    hipFree(s->d_counter); hipFree(s->d_blockcnt); hipFree(s->d_blockbase); hipFree(s->d_prop); hipFree(s->d_recw);
-    hipFree(s->d_warpw);
-    delete s;
-    return ORX_OK;
-}
-
-extern "C" int orx_sampler_pairwise(orx_sampler* s, uint64_t seed, int64_t first, int64_t n,
-                                    int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev) {
-    ORX_ARG(s && uid_dev && pid_dev && nid_dev && first >= 0 && n >= 0, "orx_sampler_pairwise: bad argument");
-    ORX_HIP(hipSetDevice(s->ctx->device));
-    SamplerArgs a;
-    a.rec_user = s->rec_user; a.rec_item = s->rec_item; a.R = s->R; a.ptr = s->ptr; a.items = s->items;
-    a.total_items = s->total_items; a.total_users = s->total_users; a.seed = seed; a.first = first; a.n = n; a.h = s->h;
-    a.uid = uid_dev; a.pid = pid_dev; a.nid = nid_dev;
-    a.prop = s->prop_on ? s->d_prop : nullptr;
-    return orx_launch_sample_pairwise(s->ctx, a);
-}
-
-static void sampler_args(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, int32_t* uid, int32_t* iid, SamplerArgs* a) {
-    a->rec_user = s->rec_user; a->rec_item = s->rec_item; a->R = s->R; a->ptr = s->ptr; a->items = s->items;
-    a->total_items = s->total_items; a->total_users = s->total_users; a->seed = seed; a->first = first; a->n = n; a->h = s->h;
-    a->uid = uid; a->pid = iid; a->nid = nullptr;
-}
-
-extern "C" int orx_sampler_stratified(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, float pos_ratio,
-                                      int32_t* uid_dev, int32_t* iid_dev, float* label_dev) {
-    ORX_ARG(s && uid_dev && iid_dev && label_dev && first >= 0 && n >= 0, "orx_sampler_stratified: bad argument");
-    ORX_ARG(pos_ratio >= 0.f && pos_ratio <= 1.f, "orx_sampler_stratified: pos_ratio must lie in [0, 1]");
-    ORX_ARG(!s->prop_on, "orx_sampler_stratified: a proposal is set (orx_sampler_set_proposal) and the pointwise producers draw "
-            "uniform negatives only; set it to NULL first");
-    ORX_ARG(first == 0 || (first == s->strat_next && seed == s->strat_seed),
-            "orx_sampler_stratified: the stream is sequential (a positive's place in the epoch counts the positives before it): "
-            "continue at sample %lld of the same seed, or restart at 0", (long long)s->strat_next);
-    ORX_HIP(hipSetDevice(s->ctx->device));
-    if (!s->d_counter) ORX_HIP(hipMalloc((void**)&s->d_counter, sizeof(int64_t)));
-    if (first == 0) ORX_HIP(hipMemsetAsync(s->d_counter, 0, sizeof(int64_t), s->ctx->stream));
-    const size_t nblocks = (size_t)((n + 255) / 256);
-    if (s->block_cap < nblocks) {
-        ORX_HIP(hipStreamSynchronize(s->ctx->stream));
-        hipFree(s->d_blockcnt); hipFree(s->d_blockbase); s->d_blockcnt = nullptr; s->d_blockbase = nullptr; s->block_cap = 0;
-        ORX_HIP(hipMalloc((void**)&s->d_blockcnt, sizeof(int) * nblocks));
-        ORX_HIP(hipMalloc((void**)&s->d_blockbase, sizeof(int64_t) * nblocks));
-        s->block_cap = nblocks;
-    }
-    SamplerArgs a;
-    sampler_args(s, seed, first, n, uid_dev, iid_dev, &a);
-    s->strat_next = first + n; s->strat_seed = seed;
-    return orx_launch_sample_stratified(s->ctx, a, pos_ratio, label_dev, s->d_blockcnt, s->d_blockbase, s->d_counter);
-}
-
-extern "C" int orx_sampler_per_pos_stratified(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, double pos_ratio,
-                                              int32_t* uid_dev, int32_t* iid_dev, float* label_dev) {
-    ORX_ARG(s && uid_dev && iid_dev && label_dev && first >= 0 && n >= 0, "orx_sampler_per_pos_stratified: bad argument");
-    ORX_ARG(pos_ratio > 0.0 && pos_ratio <= 1.0, "orx_sampler_per_pos_stratified: pos_ratio must lie in (0, 1]");
-    ORX_ARG(!s->prop_on, "orx_sampler_per_pos_stratified: a proposal is set (orx_sampler_set_proposal) and the pointwise producers "
-            "draw uniform negatives only; set it to NULL first");
-    // dataset.py:40 computes int((1 - pos_ratio) / pos_ratio) in Python doubles; in fp32 the quotient lands on the other side of
-    // an integer for common ratios (0.05: 19 instead of 18; 1/3: 1 instead of 2), i.e. another group size than the reference's
-    const int nneg = (int)((1.0 - pos_ratio) / pos_ratio);
-    ORX_ARG(nneg + 1 <= s->total_items, "orx_sampler_per_pos_stratified: %d negatives per positive need more than %lld items "
-            "(random.sample would raise ValueError)", nneg, (long long)s->total_items);
-    ORX_HIP(hipSetDevice(s->ctx->device));
-    SamplerArgs a;
-    sampler_args(s, seed, first, n, uid_dev, iid_dev, &a);
-    return orx_launch_sample_perpos(s->ctx, a, nneg, label_dev);
 }

@@ -1,5 +1,6 @@
-// C-ABI entry points of the one-positive-against-N-negatives objective: orx_multineg_step, orx_multineg_loss and
-// orx_sampler_pairwise_multi (include/openrec_hip.h has the semantics, kernels_multineg.hip the kernels).
+// C-ABI entry points of the one-positive-against-N-negatives objective: orx_multineg_step and orx_multineg_loss
+// (include/openrec_hip.h has the semantics, kernels_multineg.hip the kernels; orx_sampler_pairwise_multi, which delivers the
+// negatives, is in api_sampler.hip).
 //
 // Per step: the touch of (uid; pid, nid), ONE gradient launch that writes per-occurrence gradient rows and the concatenated item id
 // list pid | nid, [Adam: the counter advances], then orx_apply_rows of the user table and of the item table with the bias.  The
@@ -93,19 +94,4 @@ extern "C" int orx_multineg_loss(orx_ctx* c, int kind, orx_table* U, orx_table* 
         CHECK(orx_touch_step(U, V, b, a.uid, B, a.pid, B, a.nid, B * N));
         return orx_launch_multineg(c, kind, false, a);
     });
-}
-
-extern "C" int orx_sampler_pairwise_multi(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, int32_t n_neg,
-                                          int32_t* uid_dev, int32_t* pid_dev, int32_t* nid_dev) {
-    static const char* fn = "orx_sampler_pairwise_multi";
-    ORX_ARG(s && first >= 0 && n >= 0 && (n == 0 || (uid_dev && pid_dev && nid_dev)), "%s: bad argument", fn);
-    ORX_ARG(n_neg >= 1 && n_neg <= 64, "%s: n_neg must be in [1, 64], got %d", fn, n_neg);
-    if (n == 0) return ORX_OK;
-    ORX_HIP(hipSetDevice(s->ctx->device));
-    SamplerArgs a;
-    a.rec_user = s->rec_user; a.rec_item = s->rec_item; a.R = s->R; a.ptr = s->ptr; a.items = s->items;
-    a.total_items = s->total_items; a.total_users = s->total_users; a.seed = seed; a.first = first; a.n = n; a.h = s->h;
-    a.uid = uid_dev; a.pid = pid_dev; a.nid = nid_dev;
-    a.prop = s->prop_on ? s->d_prop : nullptr;
-    return orx_launch_sample_multi(s->ctx, a, n_neg);
 }

@@ -1,5 +1,6 @@
 // C-ABI entry points of the weighted objective (include/openrec_hip.h has the semantics): the pairwise step with per-triplet
-// weights and an l2 coefficient, its forward, the pointwise steps with the coefficient, and the sampler's per-record weights.
+// weights and an l2 coefficient, its forward, and the pointwise steps with the coefficient.  (The sampler's per-record weights,
+// which deliver the weights of a pairwise draw, are in api_sampler.hip.)
 //
 // Nothing is computed here.  The entry points check what only they can refuse and hand over to the bodies of the plain steps
 // (orx_pairwise_step_impl and its kin: api.hip, api_subset.hip, api_more.hip), which carry the two knobs as arguments: the weight
@@ -43,30 +44,4 @@ extern "C" int orx_pointwise_step_l2reg(orx_ctx* c, int model, orx_opt* opt, orx
     CHECK(check_objective("orx_pointwise_step_l2reg", l2_reg, flags));
     if (train_mask == 0) return orx_pointwise_step_impl(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, l2_reg, flags, loss_out, l2_out);
     return orx_pointwise_subset_impl(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, l2_reg, flags, train_mask, loss_out, l2_out);
-}
-
-extern "C" int orx_sampler_set_record_weights(orx_sampler* s, const float* host_w) {
-    ORX_ARG(s, "orx_sampler_set_record_weights: NULL sampler");
-    if (!host_w) { s->recw_on = false; return ORX_OK; }       // launches already enqueued carry the array's pointer themselves
-    ORX_HIP(hipSetDevice(s->ctx->device));
-    if (!s->d_recw) ORX_HIP(hipMalloc((void**)&s->d_recw, sizeof(float) * (size_t)s->R));
-    ORX_HIP(hipStreamSynchronize(s->ctx->stream));            // reads enqueued before this call see the old weights
-    ORX_HIP(hipMemcpy(s->d_recw, host_w, sizeof(float) * (size_t)s->R, hipMemcpyHostToDevice));
-    s->recw_on = true;
-    return ORX_OK;
-}
-
-extern "C" int orx_sampler_pairwise_weights(orx_sampler* s, uint64_t seed, int64_t first, int64_t n, float* w_dev) {
-    ORX_ARG(s && first >= 0 && n >= 0 && (n == 0 || w_dev), "orx_sampler_pairwise_weights: bad argument");
-    if (!s->recw_on) {
-        orx_set_error("orx_sampler_pairwise_weights: no record weights are set (orx_sampler_set_record_weights)");
-        return ORX_ERR_STATE;
-    }
-    if (n == 0) return ORX_OK;
-    ORX_HIP(hipSetDevice(s->ctx->device));
-    SamplerArgs a{};                                          // (every field zero; the kernel reads R, h, seed, first, n)
-    a.rec_user = s->rec_user; a.rec_item = s->rec_item; a.R = s->R; a.ptr = s->ptr; a.items = s->items;
-    a.total_items = s->total_items; a.total_users = s->total_users; a.seed = seed; a.first = first; a.n = n; a.h = s->h;
-    a.uid = nullptr; a.pid = nullptr; a.nid = nullptr;
-    return orx_launch_sample_weights(s->ctx, a, s->d_recw, w_dev);
 }

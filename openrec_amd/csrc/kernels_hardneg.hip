@@ -1,16 +1,12 @@
 // Dynamic negative sampling on the device (orx_sampler_pairwise_hard): every triplet's negative is the hardest of M uniform
 // candidates under the current model.
 //
-// Stream.  Sample g = first + i takes (u, p) exactly as sample_pairwise_kernel does for (seed, g) (kernels_sampler.hip; mix64 and
-// feistel_perm are restated here unchanged).  Candidate c in [0, M) is a uniform item, re-drawn while it is a positive of u (the same
-// binary search in the CSR row, at most 256 attempts):
-//     seed_c  = c == 0 ? seed : mix64(seed + c * 0xD1B54A32D192ED03)
-//     cand(c) = mix64(seed_c ^ (g * 0x9E3779B97F4A7C15) ^ (attempt << 56) ^ 0xA5A5A5A5) % total_items
-// so candidate c depends on (seed, g, c) only -- never on M, n, first or the launch shape -- and candidate 0 is bit for bit the
-// negative orx_sampler_pairwise writes for (seed, g).  Candidates of one sample are independent draws and may repeat.
-// With a proposal (SamplerArgs::prop, the PROP = true instantiations) the word r under the modulus picks the column j = r %
-// total_items of the alias table and t = (uint32)(mix64(r ^ 0x5851F42D4C957F2D) >> 32) takes j if t < thr[j], else alias[j]: one
-// more dependent 8-byte load per attempt of phase B, in front of the CSR search; phases A, C and D do not know about it.
+// Stream.  Sample g = first + i takes (u, p) through smp_rec, as sample_pairwise_kernel does for (seed, g), and candidate c in
+// [0, M) through smp_draw<PROP>(a, g, c, u) (orx_sampler_device.h has the formula): a uniform item, re-drawn while it is a positive
+// of u.  Candidate c depends on (seed, g, c) only -- never on M, n, first or the launch shape -- and candidate 0 is the negative
+// orx_sampler_pairwise writes for (seed, g), the same call.  Candidates of one sample are independent draws and may repeat.
+// With a proposal (SamplerArgs::prop, the PROP = true instantiations) the draw costs one more dependent 8-byte load per attempt
+// of phase B, in front of the CSR search; phases A, C and D do not know about it.
 //
 // Score, fp32, the kinds of orx_score_all_items: BPR U[u].V[c] + b[c], UCML -||U[u] - V[c]||^2 + b[c] (no "+ b" without a bias
 // table).  Summation order: a lane adds its four products as (x0 + x1) + (x2 + x3), the lanes of a row are added by a butterfly
@@ -28,49 +24,7 @@
 //      the same.  The reduction is DPP inside 16 lanes, shuffles beyond
 //   D  lane j takes the arg-max of sample j's M scores; the scores go out coalesced
 // D % 4 != 0 or D > 256: the plain path, the whole wavefront on one slot with scalar loads.
-#include "orx_device.h"
-
-__device__ __forceinline__ uint64_t hn_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// keyed permutation of [0, n): 4-round Feistel on 2*h bits (2^(2h) >= n) + cycle walking
-__device__ __forceinline__ uint64_t hn_feistel_perm(uint64_t x, uint64_t n, int h, uint64_t key) {
-    const uint64_t mask = (1ull << h) - 1;
-    do {
-        uint64_t l = x >> h, r = x & mask;
-#pragma unroll
-        for (int round = 0; round < 4; ++round) {
-            const uint64_t f = hn_mix64(r ^ (key + 0x632BE59BD9B4E019ull * (round + 1))) & mask;
-            const uint64_t t = l ^ f;
-            l = r; r = t;
-        }
-        x = (l << h) | r;
-    } while (x >= n);
-    return x;
-}
-
-template <bool PROP>
-__device__ __forceinline__ int hn_draw(const SamplerArgs& a, uint64_t g, int c, int u) {
-    const uint64_t seed_c = c == 0 ? a.seed : hn_mix64(a.seed + (uint64_t)c * 0xD1B54A32D192ED03ull);
-    const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
-    int ng = 0;
-    for (int attempt = 0; attempt < 256; ++attempt) {
-        const uint64_t r = hn_mix64(seed_c ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull);
-        ng = (int)(r % (uint64_t)a.total_items);
-        if (PROP) {
-            const uint2 rec = a.prop[ng];
-            if (!((uint32_t)(hn_mix64(r ^ 0x5851F42D4C957F2Dull) >> 32) < rec.x)) ng = (int)rec.y;
-        }
-        int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
-        if (!(lo < hi0 && a.items[lo] == ng)) break;
-    }
-    return ng;
-}
+#include "orx_sampler_device.h"
 
 constexpr int HN_SLOTS = 128;       // slots (sample, candidate) of one wavefront's chunk; a chunk holds at most 64 samples
 
@@ -97,8 +51,7 @@ __global__ __launch_bounds__(256) void hardneg_kernel(HardNegArgs h, int S) {
         // ---- A: (u, p) of sample i0 + lane
         if (lane < ns) {
             const uint64_t g = (uint64_t)(a.first + i0 + lane);
-            const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
-            const uint64_t rec = hn_feistel_perm(pos, (uint64_t)a.R, a.h, hn_mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+            const uint64_t rec = smp_rec(a, g);
             const int u = a.rec_user[rec];
             su[lane] = u; a.uid[i0 + lane] = u; a.pid[i0 + lane] = a.rec_item[rec];
         }
@@ -106,7 +59,7 @@ __global__ __launch_bounds__(256) void hardneg_kernel(HardNegArgs h, int S) {
         // ---- B: the candidates
         for (int f = lane; f < nslots; f += 64) {
             const int smp = f / M, c = f - smp * M;
-            const int ng = hn_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
+            const int ng = smp_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
             sc[f] = ng;
             if (h.cand) h.cand[i0 * M + f] = ng;
         }

@@ -1,5 +1,5 @@
-// One positive against N sampled negatives (orx_multineg_step / orx_multineg_loss, include/openrec_hip.h has the semantics), and
-// the sampler that delivers the N negatives (orx_sampler_pairwise_multi).
+// One positive against N sampled negatives (orx_multineg_step / orx_multineg_loss, include/openrec_hip.h has the semantics).  The
+// sampler that delivers the N negatives (orx_sampler_pairwise_multi) is sample_multi_kernel of kernels_sampler.hip.
 //
 // multineg_grads_kernel.  One launch per step.  It reads the rows of a sample straight from the tables by id -- no gathered
 // intermediate --, scores the positive and the N negatives in fp32, normalises, and writes per-occurrence gradient rows for
@@ -310,77 +310,6 @@ void mn_launch(orx_ctx* ctx, int lpr, dim3 g, const MultiNegArgs& a) {
     }
 }
 
-// ---- the sampler: phases A and B of hardneg_kernel (kernels_hardneg.hip), whose stream is restated here unchanged
-__device__ __forceinline__ uint64_t mn_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ uint64_t mn_feistel_perm(uint64_t x, uint64_t n, int h, uint64_t key) {
-    const uint64_t mask = (1ull << h) - 1;
-    do {
-        uint64_t l = x >> h, r = x & mask;
-#pragma unroll
-        for (int round = 0; round < 4; ++round) {
-            const uint64_t f = mn_mix64(r ^ (key + 0x632BE59BD9B4E019ull * (round + 1))) & mask;
-            const uint64_t t = l ^ f;
-            l = r; r = t;
-        }
-        x = (l << h) | r;
-    } while (x >= n);
-    return x;
-}
-
-template <bool PROP>
-__device__ __forceinline__ int mn_draw(const SamplerArgs& a, uint64_t g, int c, int u) {
-    const uint64_t seed_c = c == 0 ? a.seed : mn_mix64(a.seed + (uint64_t)c * 0xD1B54A32D192ED03ull);
-    const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
-    int ng = 0;
-    for (int attempt = 0; attempt < 256; ++attempt) {
-        const uint64_t r = mn_mix64(seed_c ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull);
-        ng = (int)(r % (uint64_t)a.total_items);
-        if (PROP) {
-            const uint2 rec = a.prop[ng];
-            if (!((uint32_t)(mn_mix64(r ^ 0x5851F42D4C957F2Dull) >> 32) < rec.x)) ng = (int)rec.y;
-        }
-        int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
-        if (!(lo < hi0 && a.items[lo] == ng)) break;
-    }
-    return ng;
-}
-
-constexpr int MN_SLOTS = 128;       // slots (sample, negative) of one wavefront's chunk, as hardneg_kernel's
-
-// a wavefront owns S consecutive samples: lane j draws (u, p) of sample j, then lane f negative f % M of sample f / M into nid
-template <bool PROP>
-__global__ __launch_bounds__(256) void sample_multi_kernel(SamplerArgs a, int M, int S) {
-    __shared__ int s_user[4][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int* su = s_user[wave];
-    const int64_t nchunks = (a.n + S - 1) / S;
-    for (int64_t chunk0 = (int64_t)blockIdx.x * 4; chunk0 < nchunks; chunk0 += (int64_t)gridDim.x * 4) {
-        const int64_t i0 = (chunk0 + wave) * S;
-        const int ns = i0 >= a.n ? 0 : (int)(a.n - i0 < S ? a.n - i0 : S);
-        const int nslots = ns * M;
-        if (lane < ns) {
-            const uint64_t g = (uint64_t)(a.first + i0 + lane);
-            const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
-            const uint64_t rec = mn_feistel_perm(pos, (uint64_t)a.R, a.h, mn_mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
-            const int u = a.rec_user[rec];
-            su[lane] = u; a.uid[i0 + lane] = u; a.pid[i0 + lane] = a.rec_item[rec];
-        }
-        __syncthreads();
-        for (int f = lane; f < nslots; f += 64) {
-            const int smp = f / M, c = f - smp * M;
-            a.nid[i0 * M + f] = mn_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
-        }
-        __syncthreads();
-    }
-}
-
 }  // namespace
 
 int orx_multineg_nwaves(orx_ctx* ctx, int D, int64_t B) { return (int)(mn_blocks(ctx->num_cu, D, B) * 4); }
@@ -392,17 +321,6 @@ int orx_launch_multineg(orx_ctx* ctx, int kind, bool grads, const MultiNegArgs& 
     const dim3 g((unsigned)mn_blocks(ctx->num_cu, a.D, a.B));
     if (kind == ORX_MN_SOFTMAX) { if (grads) mn_launch<ORX_MN_SOFTMAX, true>(ctx, lpr, g, a); else mn_launch<ORX_MN_SOFTMAX, false>(ctx, lpr, g, a); }
     else { if (grads) mn_launch<ORX_MN_LOGSIG, true>(ctx, lpr, g, a); else mn_launch<ORX_MN_LOGSIG, false>(ctx, lpr, g, a); }
-    ORX_HIP(hipGetLastError());
-    return ORX_OK;
-}
-
-int orx_launch_sample_multi(orx_ctx* ctx, const SamplerArgs& a, int M) {
-    if (a.n == 0) return ORX_OK;
-    int S = MN_SLOTS / M; if (S < 1) S = 1; if (S > 64) S = 64;
-    const int64_t nchunks = (a.n + S - 1) / S;
-    int64_t g = (nchunks + 3) / 4; if (g > (int64_t)ctx->num_cu * 16) g = (int64_t)ctx->num_cu * 16;
-    if (a.prop) ORX_LAUNCH(ctx, sample_multi_kernel<true>, dim3((unsigned)g), dim3(256), 0, a, M, S);
-    else ORX_LAUNCH(ctx, sample_multi_kernel<false>, dim3((unsigned)g), dim3(256), 0, a, M, S);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }

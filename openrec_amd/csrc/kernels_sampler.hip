@@ -12,53 +12,18 @@
 //               j = r % total_items and a second word t = (uint32)(mix64(r ^ 0x5851F42D4C957F2D) >> 32) decides between the
 //               column's own item (t < thr[j]) and its alias: one 8-byte load per attempt in front of the CSR search.  The
 //               uniform kernel is the PROP = false instantiation and does not see the table
-#include "orx_device.h"
-
-__device__ __forceinline__ uint64_t mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// keyed permutation of [0, n): 4-round Feistel on 2*h bits (2^(2h) >= n) + cycle walking
-__device__ __forceinline__ uint64_t feistel_perm(uint64_t x, uint64_t n, int h, uint64_t key) {
-    const uint64_t mask = (1ull << h) - 1;
-    do {
-        uint64_t l = x >> h, r = x & mask;
-#pragma unroll
-        for (int round = 0; round < 4; ++round) {
-            const uint64_t f = mix64(r ^ (key + 0x632BE59BD9B4E019ull * (round + 1))) & mask;
-            const uint64_t t = l ^ f;
-            l = r; r = t;
-        }
-        x = (l << h) | r;
-    } while (x >= n);
-    return x;
-}
-
+// The stream's functions (mix64, the Feistel permutation, the record lookup, the rejection draw) are orx_sampler_device.h's, shared
+// with kernels_hardneg.hip and kernels_warp.hip.
+#include "orx_sampler_device.h"
 
 template <bool PROP>
 __global__ __launch_bounds__(256) void sample_pairwise_kernel(SamplerArgs a) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         const uint64_t g = (uint64_t)(a.first + i);
-        const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
-        const uint64_t rec = feistel_perm(pos, (uint64_t)a.R, a.h, mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+        const uint64_t rec = smp_rec(a, g);
         const int u = a.rec_user[rec], p = a.rec_item[rec];
-        const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
-        int ng = 0;
-        for (int attempt = 0; attempt < 256; ++attempt) {
-            const uint64_t r = mix64(a.seed ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull);
-            ng = (int)(r % (uint64_t)a.total_items);
-            if (PROP) {
-                const uint2 rec = a.prop[ng];
-                if (!((uint32_t)(mix64(r ^ 0x5851F42D4C957F2Dull) >> 32) < rec.x)) ng = (int)rec.y;
-            }
-            int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
-            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
-            if (!(lo < hi0 && a.items[lo] == ng)) break;
-        }
+        const int ng = smp_draw<PROP>(a, g, 0, u);
         a.uid[i] = u; a.pid[i] = p; a.nid[i] = ng;
     }
 }
@@ -72,15 +37,53 @@ int orx_launch_sample_pairwise(orx_ctx* ctx, const SamplerArgs& a) {
     return ORX_OK;
 }
 
+// The N negatives of orx_sampler_pairwise_multi: phases A and B of hardneg_kernel (kernels_hardneg.hip) and nothing else.
+constexpr int MN_SLOTS = 128;       // slots (sample, negative) of one wavefront's chunk, as hardneg_kernel's
+
+// a wavefront owns S consecutive samples: lane j draws (u, p) of sample j, then lane f negative f % M of sample f / M into nid
+template <bool PROP>
+__global__ __launch_bounds__(256) void sample_multi_kernel(SamplerArgs a, int M, int S) {
+    __shared__ int s_user[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int* su = s_user[wave];
+    const int64_t nchunks = (a.n + S - 1) / S;
+    for (int64_t chunk0 = (int64_t)blockIdx.x * 4; chunk0 < nchunks; chunk0 += (int64_t)gridDim.x * 4) {
+        const int64_t i0 = (chunk0 + wave) * S;
+        const int ns = i0 >= a.n ? 0 : (int)(a.n - i0 < S ? a.n - i0 : S);
+        const int nslots = ns * M;
+        if (lane < ns) {
+            const uint64_t g = (uint64_t)(a.first + i0 + lane);
+            const uint64_t rec = smp_rec(a, g);
+            const int u = a.rec_user[rec];
+            su[lane] = u; a.uid[i0 + lane] = u; a.pid[i0 + lane] = a.rec_item[rec];
+        }
+        __syncthreads();
+        for (int f = lane; f < nslots; f += 64) {
+            const int smp = f / M, c = f - smp * M;
+            a.nid[i0 * M + f] = smp_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), c, su[smp]);
+        }
+        __syncthreads();
+    }
+}
+
+int orx_launch_sample_multi(orx_ctx* ctx, const SamplerArgs& a, int M) {
+    if (a.n == 0) return ORX_OK;
+    int S = MN_SLOTS / M; if (S < 1) S = 1; if (S > 64) S = 64;
+    const int64_t nchunks = (a.n + S - 1) / S;
+    int64_t g = (nchunks + 3) / 4; if (g > (int64_t)ctx->num_cu * 16) g = (int64_t)ctx->num_cu * 16;
+    if (a.prop) ORX_LAUNCH(ctx, sample_multi_kernel<true>, dim3((unsigned)g), dim3(256), 0, a, M, S);
+    else ORX_LAUNCH(ctx, sample_multi_kernel<false>, dim3((unsigned)g), dim3(256), 0, a, M, S);
+    ORX_HIP(hipGetLastError());
+    return ORX_OK;
+}
+
 // The weight of the record each pairwise sample draws as its positive (orx_sampler_pairwise_weights): the same keyed permutation as
 // sample_pairwise_kernel, one 4-byte gather per sample; nothing of the negatives' draw is repeated.
 __global__ __launch_bounds__(256) void sample_weights_kernel(SamplerArgs a, const float* rec_w, float* out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         const uint64_t g = (uint64_t)(a.first + i);
-        const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
-        const uint64_t rec = feistel_perm(pos, (uint64_t)a.R, a.h, mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
-        out[i] = rec_w[rec];
+        out[i] = rec_w[smp_rec(a, g)];
     }
 }
 
@@ -105,14 +108,7 @@ int orx_launch_sample_weights(orx_ctx* ctx, const SamplerArgs& a, const float* r
 // previous one stopped; first = 0 restarts it), and deterministic.
 __device__ __forceinline__ bool strat_coin(uint64_t seed, uint64_t g, float pos_ratio) {
     // random.random() <= pos_ratio with 24 random bits
-    return (float)(mix64(seed ^ (g * 0xC2B2AE3D27D4EB4Full) ^ 0x1234567ull) >> 40) * (1.0f / 16777216.0f) <= pos_ratio;
-}
-
-__device__ __forceinline__ bool is_positive(const SamplerArgs& a, int u, int item) {
-    const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
-    int64_t lo = lo0, hi = hi0;
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < item) lo = mid + 1; else hi = mid; }
-    return lo < hi0 && a.items[lo] == item;
+    return (float)(smp_mix64(seed ^ (g * 0xC2B2AE3D27D4EB4Full) ^ 0x1234567ull) >> 40) * (1.0f / 16777216.0f) <= pos_ratio;
 }
 
 __global__ __launch_bounds__(256) void strat_count_kernel(SamplerArgs a, float pos_ratio, int* blockcnt) {
@@ -157,17 +153,15 @@ __global__ __launch_bounds__(256) void strat_emit_kernel(SamplerArgs a, float po
     for (int k = 0; k < wave; ++k) before += wave_cnt[k];
     if (!live) return;
     if (head) {
-        const uint64_t position = (uint64_t)(blockbase[blockIdx.x] + before);
-        const uint64_t epoch = position / (uint64_t)a.R, pos = position % (uint64_t)a.R;
-        const uint64_t rec = feistel_perm(pos, (uint64_t)a.R, a.h, mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+        const uint64_t rec = smp_rec(a, (uint64_t)(blockbase[blockIdx.x] + before));
         a.uid[i] = a.rec_user[rec]; a.pid[i] = a.rec_item[rec]; label[i] = 1.0f;
     } else {
         int u = 0, item = 0;
         for (int attempt = 0; attempt < 256; ++attempt) {       // dataset.py:29-33: both ids are re-drawn while the pair is a positive
-            const uint64_t r = mix64(a.seed ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0x5A5A5A5Aull);
+            const uint64_t r = smp_mix64(a.seed ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0x5A5A5A5Aull);
             u = (int)((r >> 32) % (uint64_t)a.total_users);
             item = (int)((r & 0xffffffffull) % (uint64_t)a.total_items);
-            if (!is_positive(a, u, item)) break;
+            if (!smp_is_positive(a, u, item)) break;
         }
         a.uid[i] = u; a.pid[i] = item; label[i] = 0.0f;
     }
@@ -183,15 +177,14 @@ __global__ __launch_bounds__(256) void perpos_kernel(SamplerArgs a, int nneg, in
         const uint64_t g = (uint64_t)(a.first + i);
         const uint64_t q = g / (uint64_t)(nneg + 1);
         const int slot = (int)(g % (uint64_t)(nneg + 1));
-        const uint64_t epoch = q / (uint64_t)a.R, pos = q % (uint64_t)a.R;
-        const uint64_t rec = feistel_perm(pos, (uint64_t)a.R, a.h, mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+        const uint64_t rec = smp_rec(a, q);
         const int u = a.rec_user[rec], p = a.rec_item[rec];
         int item = p; float lab = 1.0f;
         if (slot > 0) {
-            const uint64_t key = mix64(a.seed ^ (q * 0x9FB21C651E98DF25ull) ^ 0x77ull);
+            const uint64_t key = smp_mix64(a.seed ^ (q * 0x9FB21C651E98DF25ull) ^ 0x77ull);
             int taken = 0;
             for (int j = 0; j <= nneg; ++j) {
-                const int c = (int)feistel_perm((uint64_t)j, (uint64_t)a.total_items, hi_items, key);
+                const int c = (int)smp_feistel_perm((uint64_t)j, (uint64_t)a.total_items, hi_items, key);
                 if (c == p) continue;
                 if (++taken == slot) { item = c; break; }
             }

@@ -1,10 +1,9 @@
 // WARP negatives on the device (orx_sampler_pairwise_warp): every triplet's negative is the FIRST of up to T candidates that violates
 // the margin against the positive under the current model, and the triplet's weight is a table entry of the trial count.
 //
-// Stream.  (u, p) of sample g = first + i and candidate c of it are orx_sampler_pairwise_hard's (kernels_hardneg.hip: seed_c, the
-// rejection loop against the user's CSR row, at most 256 attempts, the alias table when a proposal is set).  mix64, feistel_perm and
-// the draw are restated here unchanged (wn_*), as kernels_hardneg.hip restates the sampler's: that file and the kernels it compiles
-// to are not touched.
+// Stream.  (u, p) of sample g = first + i and candidate c of it are orx_sampler_pairwise_hard's: smp_rec and smp_draw<PROP> of
+// orx_sampler_device.h (seed_c, the rejection loop against the user's CSR row, at most 256 attempts, the alias table when a
+// proposal is set), the calls kernels_hardneg.hip makes.
 //
 // Score, fp32: BPR U[u].V[j] + b[j], UCML -||U[u] - V[j]||^2 + b[j] (no "+ b" without a bias table), for the positive (s_p) and the
 // candidates (s_c) by ONE row scorer.  Summation order: a lane adds its four products as (x0 + x1) + (x2 + x3), the lanes of a row
@@ -30,49 +29,7 @@
 //   D  the lane of an open sample scans its R scores IN CANDIDATE ORDER for the first violator and writes that prefix of cand_score
 // Because the scan is in candidate order, the result does not depend on R, S, the budget, r0 or the launch shape; candidates scored
 // past a violator in the same round are the only wasted gathers.  S = 16, budget = 128, r0 = 2 are measured choices.  D % 4 != 0 or D > 256: the plain path, the whole wavefront on one slot.
-#include "orx_device.h"
-
-__device__ __forceinline__ uint64_t wn_mix64(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// keyed permutation of [0, n): 4-round Feistel on 2*h bits (2^(2h) >= n) + cycle walking
-__device__ __forceinline__ uint64_t wn_feistel_perm(uint64_t x, uint64_t n, int h, uint64_t key) {
-    const uint64_t mask = (1ull << h) - 1;
-    do {
-        uint64_t l = x >> h, r = x & mask;
-#pragma unroll
-        for (int round = 0; round < 4; ++round) {
-            const uint64_t f = wn_mix64(r ^ (key + 0x632BE59BD9B4E019ull * (round + 1))) & mask;
-            const uint64_t t = l ^ f;
-            l = r; r = t;
-        }
-        x = (l << h) | r;
-    } while (x >= n);
-    return x;
-}
-
-template <bool PROP>
-__device__ __forceinline__ int wn_draw(const SamplerArgs& a, uint64_t g, int c, int u) {
-    const uint64_t seed_c = c == 0 ? a.seed : wn_mix64(a.seed + (uint64_t)c * 0xD1B54A32D192ED03ull);
-    const int64_t lo0 = a.ptr[u], hi0 = a.ptr[u + 1];
-    int ng = 0;
-    for (int attempt = 0; attempt < 256; ++attempt) {
-        const uint64_t r = wn_mix64(seed_c ^ (g * 0x9E3779B97F4A7C15ull) ^ ((uint64_t)attempt << 56) ^ 0xA5A5A5A5ull);
-        ng = (int)(r % (uint64_t)a.total_items);
-        if (PROP) {
-            const uint2 rec = a.prop[ng];
-            if (!((uint32_t)(wn_mix64(r ^ 0x5851F42D4C957F2Dull) >> 32) < rec.x)) ng = (int)rec.y;
-        }
-        int64_t lo = lo0, hi = hi0;                     // binary search: is ng a positive of u?
-        while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (a.items[mid] < ng) lo = mid + 1; else hi = mid; }
-        if (!(lo < hi0 && a.items[lo] == ng)) break;
-    }
-    return ng;
-}
+#include "orx_sampler_device.h"
 
 constexpr int WN_SLOTS = 128;       // slots (sample, item) of one round; a chunk holds at most 64 samples
 
@@ -160,8 +117,7 @@ __global__ __launch_bounds__(64) void warpneg_kernel(WarpNegArgs h, int S, int b
         // ---- A: (u, p) of sample i0 + lane
         if (lane < ns) {
             const uint64_t g = (uint64_t)(a.first + i0 + lane);
-            const uint64_t epoch = g / (uint64_t)a.R, pos = g % (uint64_t)a.R;
-            const uint64_t rec = wn_feistel_perm(pos, (uint64_t)a.R, a.h, wn_mix64(a.seed ^ (epoch * 0xD6E8FEB86659FD93ull)));
+            const uint64_t rec = smp_rec(a, g);
             const int u = a.rec_user[rec], p = a.rec_item[rec];
             s_user[lane] = u; s_item[lane] = p; s_smp[lane] = lane;
             a.uid[i0 + lane] = u; a.pid[i0 + lane] = p;
@@ -188,7 +144,7 @@ __global__ __launch_bounds__(64) void warpneg_kernel(WarpNegArgs h, int S, int b
             // ---- B: the candidates tried .. tried + R - 1 of the open samples
             for (int f = lane; f < nslots; f += 64) {
                 const int kk = f / R, smp = s_open[kk];
-                s_item[f] = wn_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), tried + (f - kk * R), s_user[smp]);
+                s_item[f] = smp_draw<PROP>(a, (uint64_t)(a.first + i0 + smp), tried + (f - kk * R), s_user[smp]);
                 s_smp[f] = smp;
             }
             __syncthreads();

@@ -935,7 +935,7 @@ int orx_launch_cand_pick(orx_ctx* ctx, const float* rows, int64_t NI, const int6
                          int64_t E, float* out);
 int orx_launch_cand_rank(orx_ctx* ctx, const CandRankArgs& a, int64_t nq);
 
-// kernels_sampler.hip (on-device triplet sampler)
+// kernels_sampler.hip (on-device triplet sampler); filled by sampler_args of api_sampler.hip and nowhere else
 struct SamplerArgs {
     const int32_t* rec_user; const int32_t* rec_item; int64_t R;      // interaction records
     const int64_t* ptr; const int32_t* items;                          // CSR of positives (sorted per user)
@@ -950,8 +950,10 @@ int orx_launch_sample_stratified(orx_ctx* ctx, const SamplerArgs& a, float pos_r
 int orx_launch_sample_perpos(orx_ctx* ctx, const SamplerArgs& a, int nneg, float* label);
 // out[i] = rec_w[record of sample a.first + i] (the positives' permutation of sample_pairwise_kernel); reads a.R, a.h, a.seed, a.first, a.n
 int orx_launch_sample_weights(orx_ctx* ctx, const SamplerArgs& a, const float* rec_w, float* out);
+// the first M candidates of orx_launch_hardneg for every sample, a.nid [n * M]; no table is read
+int orx_launch_sample_multi(orx_ctx* ctx, const SamplerArgs& a, int M);
 
-// the sampler object (api_more.hip creates it)
+// the sampler object (api_sampler.hip creates it and holds every call on it)
 struct orx_sampler {
     orx_ctx* ctx = nullptr;
     int32_t *rec_user = nullptr, *rec_item = nullptr, *items = nullptr;
@@ -961,11 +963,11 @@ struct orx_sampler {
     // stratified pointwise stream: positives consumed so far (device), next sample index and seed the counter belongs to
     int64_t* d_counter = nullptr; int64_t strat_next = -1; uint64_t strat_seed = 0;
     int* d_blockcnt = nullptr; int64_t* d_blockbase = nullptr; size_t block_cap = 0;
-    // proposal of the negatives (api_proposal.hip): [total_items] records (thr, alias), allocated by the first orx_sampler_set_proposal
+    // proposal of the negatives: [total_items] records (thr, alias), allocated by the first orx_sampler_set_proposal
     uint2* d_prop = nullptr; bool prop_on = false;
-    // per-record weights (api_weighted.hip): [R] in the records' order, allocated by the first orx_sampler_set_record_weights
+    // per-record weights: [R] in the records' order, allocated by the first orx_sampler_set_record_weights
     float* d_recw = nullptr; bool recw_on = false;
-    // WARP's trial-weight table (api_warp.hip): the device copy and the host floats it holds, uploaded only when they change
+    // WARP's trial-weight table: the device copy and the host floats it holds, uploaded only when they change
     float* d_warpw = nullptr; float h_warpw[256]; int warpw_n = 0;
 };
 
@@ -992,7 +994,6 @@ struct MultiNegArgs {
 };
 int orx_multineg_nwaves(orx_ctx* ctx, int D, int64_t B);
 int orx_launch_multineg(orx_ctx* ctx, int kind /* orx_multineg_kind */, bool grads, const MultiNegArgs& a);
-int orx_launch_sample_multi(orx_ctx* ctx, const SamplerArgs& a, int M);      // a.nid [n * M]
 
 // kernels_inbatch.hip (orx_inbatch_step / orx_inbatch_loss): one step of the in-batch softmax.  Bp = B rounded up to 64, Dp = D
 // rounded up to 16; every [Bp] / [Bp][Dp] / [nch][..] array is scratch carved from the context's d_tmp

@@ -1270,6 +1270,32 @@ def warp_weights(total_items, max_trials, kind="log", normalize=False):
     return w.astype(np.float32)
 
 
+# The sampler's argument helpers (plain functions with positional arguments: a producer call is a few microseconds of host time)
+def _sampler_out(arg, x, n, what, optional=False):
+    """the pointer of the DEVICE output buffer `x` of at least n elements -- int32 for arg = _ids_arg, float32 for _label_arg --;
+    None where `optional` and not given"""
+    if x is None and optional:
+        return None
+    ptr, size, on_device, _ = arg(x)
+    assert on_device and size >= n, "%s: the sampler writes a device buffer of %d" % (what, n)
+    return ptr
+
+
+def _sampler_model(model):
+    return int(model if isinstance(model, int) else {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model])
+
+
+def _seed_arg(seed):
+    return int(seed) & (2 ** 64 - 1)
+
+
+def _scorer_handles(U, V, b):
+    for t in (U, V, b):
+        if t is not None:
+            t._sync_pending()
+    return U._h, V._h, _bias_h(b)
+
+
 class DeviceSampler:
     """On-device pairwise sampler over an interaction set (see kernels_sampler.hip).  `raw_data`: the
     structured array the reference's Dataset takes ('user_id', 'item_id')."""
@@ -1334,9 +1360,8 @@ class DeviceSampler:
     def pairwise(self, seed, first, n, uid, pid, nid):
         """Fill the DEVICE int32 buffers uid / pid / nid (torch tensors or DevicePtr) with samples
         [first, first + n) of stream `seed`.  Negatives: uniform over the user's non-positives, or from `set_proposal`'s."""
-        pu, nu, du, _ = _ids_arg(uid); pp, _, dp, _ = _ids_arg(pid); pn, _, dn, _ = _ids_arg(nid)
-        assert du and dp and dn and nu >= n, "the sampler writes device buffers"
-        check(self._lib.orx_sampler_pairwise(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), pu, pp, pn))
+        check(self._lib.orx_sampler_pairwise(self._h, _seed_arg(seed), int(first), int(n), _sampler_out(_ids_arg, uid, n, "uid"),
+                                             _sampler_out(_ids_arg, pid, n, "pid"), _sampler_out(_ids_arg, nid, n, "nid")))
 
     def set_record_weights(self, weights=None):
         """One weight per interaction record, in the order of `raw_data` (float32; not validated), kept on the device for
@@ -1354,9 +1379,7 @@ class DeviceSampler:
         is the weight of the (user, positive) record that `pairwise` / `pairwise_hard` write at i for the same (seed, first),
         with or without a proposal -- ready to be `pairwise_step`'s weights.  Raises OrxError (ORX_ERR_STATE) while no record
         weights are set."""
-        po, no, do, _ = _label_arg(out)
-        assert do and no >= n, "the sampler writes device buffers"
-        check(self._lib.orx_sampler_pairwise_weights(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), po))
+        check(self._lib.orx_sampler_pairwise_weights(self._h, _seed_arg(seed), int(first), int(n), _sampler_out(_label_arg, out, n, "out")))
 
     def pairwise_hard(self, seed, first, n, uid, pid, nid, model, U, V, b=None, candidates=8,
                       cand_out=None, cand_score_out=None):
@@ -1368,21 +1391,11 @@ class DeviceSampler:
         candidate and its score.  All buffers are device buffers; the call runs on the context's stream without a host
         synchronisation, so its output can feed `pairwise_step` directly.  1 <= candidates <= 64.  With `set_proposal` the
         candidates come from the proposal instead of uniformly; everything else stays as described."""
-        pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
-        assert du and dp and dn and min(nu, np_, nn) >= n, "the sampler writes device buffers"
-        pc = ps = None
-        if cand_out is not None:
-            pc, nc, dc, _ = _ids_arg(cand_out)
-            assert dc and nc >= n * int(candidates), "cand_out: a device int32 buffer of n * candidates"
-        if cand_score_out is not None:
-            ps, nsc, ds, _ = _label_arg(cand_score_out)
-            assert ds and nsc >= n * int(candidates), "cand_score_out: a device float32 buffer of n * candidates"
-        mid = model if isinstance(model, int) else {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
-        for t in (U, V, b):
-            if t is not None:
-                t._sync_pending()
-        check(self._lib.orx_sampler_pairwise_hard(self._h, int(mid), U._h, V._h, _bias_h(b), int(seed) & (2 ** 64 - 1), int(first),
-                                                  int(n), int(candidates), pu, pp, pn, pc, ps))
+        M = int(candidates)
+        outs = (_sampler_out(_ids_arg, uid, n, "uid"), _sampler_out(_ids_arg, pid, n, "pid"), _sampler_out(_ids_arg, nid, n, "nid"),
+                _sampler_out(_ids_arg, cand_out, n * M, "cand_out", True), _sampler_out(_label_arg, cand_score_out, n * M, "cand_score_out", True))
+        check(self._lib.orx_sampler_pairwise_hard(self._h, _sampler_model(model), *_scorer_handles(U, V, b), _seed_arg(seed),
+                                                  int(first), int(n), M, *outs))
 
     def pairwise_multi(self, seed, first, n, uid, pid, nid, negatives=16):
         """The negatives of `multineg_step`: uid / pid as `pairwise(seed, first, n)` writes them, and nid -- a DEVICE int32
@@ -1392,9 +1405,8 @@ class DeviceSampler:
         N = int(negatives)
         if not 1 <= N <= 64:
             raise ValueError(f"pairwise_multi: negatives = {N}; must be in [1, 64]")
-        pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
-        assert du and dp and dn and min(nu, np_) >= n and nn >= n * N, "the sampler writes device buffers (nid: n * negatives)"
-        check(self._lib.orx_sampler_pairwise_multi(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), N, pu, pp, pn))
+        check(self._lib.orx_sampler_pairwise_multi(self._h, _seed_arg(seed), int(first), int(n), N, _sampler_out(_ids_arg, uid, n, "uid"),
+                                                   _sampler_out(_ids_arg, pid, n, "pid"), _sampler_out(_ids_arg, nid, n * N, "nid")))
 
     def pairwise_warp(self, seed, first, n, uid, pid, nid, weight, model, U, V, b=None, max_trials=10, margin=1.0,
                       rank_weight="log", trials_out=None, pos_score_out=None, cand_score_out=None):
@@ -1426,30 +1438,15 @@ class DeviceSampler:
             table = np.ascontiguousarray(rank_weight, dtype=np.float32).reshape(-1)
             if table.size != T:
                 raise ValueError("pairwise_warp: rank_weight has %d entries, max_trials is %d" % (table.size, T))
-        pu, nu, du, _ = _ids_arg(uid); pp, np_, dp, _ = _ids_arg(pid); pn, nn, dn, _ = _ids_arg(nid)
-        pw, nw, dw, _ = _label_arg(weight)
-        assert du and dp and dn and dw and min(nu, np_, nn, nw) >= n, "the sampler writes device buffers"
-        pt = pps = pcs = None
-        if trials_out is not None:
-            pt, nt, dt, _ = _ids_arg(trials_out)
-            assert dt and nt >= n, "trials_out: a device int32 buffer of n"
-        if pos_score_out is not None:
-            pps, nps, dps, _ = _label_arg(pos_score_out)
-            assert dps and nps >= n, "pos_score_out: a device float32 buffer of n"
-        if cand_score_out is not None:
-            pcs, ncs, dcs, _ = _label_arg(cand_score_out)
-            assert dcs and ncs >= n * T, "cand_score_out: a device float32 buffer of n * max_trials"
-        mid = model if isinstance(model, int) else {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
-        for t in (U, V, b):
-            if t is not None:
-                t._sync_pending()
-        check(self._lib.orx_sampler_pairwise_warp(self._h, int(mid), U._h, V._h, _bias_h(b), int(seed) & (2 ** 64 - 1), int(first),
-                                                  int(n), T, float(margin), table.ctypes.data, pu, pp, pn, pw, pt, pps, pcs))
+        outs = (_sampler_out(_ids_arg, uid, n, "uid"), _sampler_out(_ids_arg, pid, n, "pid"), _sampler_out(_ids_arg, nid, n, "nid"),
+                _sampler_out(_label_arg, weight, n, "weight"), _sampler_out(_ids_arg, trials_out, n, "trials_out", True),
+                _sampler_out(_label_arg, pos_score_out, n, "pos_score_out", True), _sampler_out(_label_arg, cand_score_out, n * T, "cand_score_out", True))
+        check(self._lib.orx_sampler_pairwise_warp(self._h, _sampler_model(model), *_scorer_handles(U, V, b), _seed_arg(seed),
+                                                  int(first), int(n), T, float(margin), table.ctypes.data, *outs))
 
     def _pointwise(self, fn, seed, first, n, pos_ratio, uid, iid, label):
-        pu, nu, du, _ = _ids_arg(uid); pi, _, di, _ = _ids_arg(iid); pl, nl, dl, _ = _label_arg(label)
-        assert du and di and dl and nu >= n and nl >= n, "the sampler writes device buffers"
-        check(fn(self._h, int(seed) & (2 ** 64 - 1), int(first), int(n), float(pos_ratio), pu, pi, pl))
+        check(fn(self._h, _seed_arg(seed), int(first), int(n), float(pos_ratio), _sampler_out(_ids_arg, uid, n, "uid"),
+                 _sampler_out(_ids_arg, iid, n, "iid"), _sampler_out(_label_arg, label, n, "label")))
 
     def stratified_pointwise(self, seed, first, n, pos_ratio, uid, iid, label):
         """(user, item, label) samples [first, first + n) of `Dataset.stratified_pointwise` into DEVICE buffers; the stream

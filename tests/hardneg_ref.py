@@ -1,5 +1,5 @@
-"""NumPy uint64 restatement of the hard-negative sampler's stream (kernels_hardneg.hip) and of its selection rule, shared by
-tests/test_hardneg_cpu.py and tests/test_gpu_hardneg.py.
+"""NumPy uint64 restatement of the sampler's stream (orx_sampler_device.h) and of the hard-negative selection rule
+(kernels_hardneg.hip), shared by tests/test_hardneg_cpu.py, tests/test_gpu_hardneg.py and the other sampler tests.
 
 Sample g of stream `seed`: the record perm_e(g mod R) of epoch e = g // R (keyed 4-round Feistel permutation with cycle walking)
 gives (u, p); candidate c is a uniform item re-drawn (at most 256 attempts) while it is a positive of u, keyed by

@@ -1,4 +1,4 @@
-"""NumPy uint64 restatement of the sampler's draw from a weighted item proposal (kernels_sampler.hip, kernels_hardneg.hip), shared by
+"""NumPy uint64 restatement of the sampler's draw from a weighted item proposal (smp_draw<true> of orx_sampler_device.h), shared by
 tests/test_proposal_cpu.py and tests/test_gpu_proposal.py.  mix64, the (u, p) record stream and seed_c are tests/hardneg_ref.py's.
 
 With an alias table (thr, alias), attempt a of candidate c of sample g is

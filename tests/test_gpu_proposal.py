@@ -1,4 +1,4 @@
-"""Negatives from a weighted item proposal on the device (DeviceSampler.set_proposal, kernels_sampler.hip, kernels_hardneg.hip):
+"""Negatives from a weighted item proposal on the device (DeviceSampler.set_proposal, smp_draw<true> of orx_sampler_device.h):
 the table on the device is alias_build's, `pairwise` and the candidates of `pairwise_hard` equal tests/proposal_ref.py bit for
 bit with the table read back, the selection is exact on the kernel's own scores, the uniform stream keeps its bits, and the
 plumbing (replacing, resetting, errors, the pointwise producers' refusal, feeding the fused step)."""

@@ -146,3 +146,99 @@ def test_per_pos_group_size_is_the_python_double_quotient(ratio):
     assert (L[:, 0] == 1.0).all() and (L[:, 1:] == 0.0).all()
     U = u.cpu().numpy().reshape(-1, grp)
     assert (U == U[:, :1]).all()
+
+
+# ---- the pointwise producers bit for bit (tests/pointwise_sampler_ref.py), and the refusal of short output buffers ----------------
+def _pointwise_data(shape):
+    import pointwise_sampler_ref as pr
+    return pr.data(pr.SPARSE if shape == "sparse" else pr.DENSE)
+
+
+def _int_float_bufs(n):
+    import torch
+    dev = torch.device("cuda", 0)
+    return (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+            torch.empty(n, dtype=torch.float32, device=dev))
+
+
+@pytest.mark.parametrize("shape", ["sparse", "dense"])
+def test_stratified_stream_is_the_restatement_bit_for_bit(shape):
+    """pos_ratio 0.5, 3001 samples in three calls cut at 1000 and 2500 (no multiple of 256; twelve blocks; ~1500 heads cross two
+    epoch boundaries of 701): uid, iid and label equal pointwise_sampler_ref.stratified and one call of 3001.  The dense set makes
+    more than a tenth of the tails re-draw (tests/test_pointwise_sampler_cpu.py)."""
+    import torch
+    import pointwise_sampler_ref as pr
+    from openrec_amd import runtime as rt
+    raw, NU, NI = _pointwise_data(shape)
+    sm = rt.DeviceSampler(raw, NU, NI)
+    n, ratio, seed = 3001, 0.5, 11
+    u, i, lab = _int_float_bufs(n)
+    cuts = [0, 1000, 2500, n]
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        sm.stratified_pointwise(seed, lo, hi - lo, ratio, u[lo:hi], i[lo:hi], lab[lo:hi])
+    sm.ctx.synchronize()
+    wu, wi, wl, _ = pr.stratified(raw, NU, NI, seed, n, ratio)
+    assert np.array_equal(u.cpu().numpy(), wu) and np.array_equal(i.cpu().numpy(), wi)
+    assert np.array_equal(lab.cpu().numpy().view(np.int32), wl.view(np.int32))
+    u2, i2, l2 = _int_float_bufs(n)
+    sm.stratified_pointwise(seed, 0, n, ratio, u2, i2, l2); sm.ctx.synchronize()
+    assert torch.equal(u, u2) and torch.equal(i, i2) and torch.equal(lab, l2)
+
+
+@pytest.mark.parametrize("shape", ["sparse", "dense"])
+def test_per_pos_stream_is_the_restatement_bit_for_bit(shape):
+    """pos_ratio 0.2 (groups of 5), the window first = 2000, n = 3001: it starts inside a group and crosses the epoch boundary at
+    sample 3505.  On the dense set some group skips a candidate equal to its positive (tests/test_pointwise_sampler_cpu.py)."""
+    import pointwise_sampler_ref as pr
+    from openrec_amd import runtime as rt
+    raw, NU, NI = _pointwise_data(shape)
+    sm = rt.DeviceSampler(raw, NU, NI)
+    first, n, ratio, seed = 2000, 3001, 0.2, 12
+    u, i, lab = _int_float_bufs(n)
+    sm.per_pos_stratified_pointwise(seed, first, n, ratio, u, i, lab); sm.ctx.synchronize()
+    wu, wi, wl, _ = pr.per_pos(raw, NI, seed, np.arange(first, first + n), ratio)
+    assert np.array_equal(u.cpu().numpy(), wu) and np.array_equal(i.cpu().numpy(), wi)
+    assert np.array_equal(lab.cpu().numpy().view(np.int32), wl.view(np.int32))
+
+
+def test_short_output_buffers_are_refused_before_the_call():
+    """Every producer, each output buffer in turn one element short: an AssertionError before anything is launched (the buffers keep
+    their fill), and the sampler goes on to produce the reference window."""
+    import torch
+    import hardneg_ref as hr
+    import pointwise_sampler_ref as pr
+    from openrec_amd import runtime as rt
+    raw, NU, NI = _pointwise_data("sparse")
+    sm = rt.DeviceSampler(raw, NU, NI)
+    dev = torch.device("cuda", 0)
+    n, M, T, first, seed = 100, 3, 4, 650, 5
+    U = rt.Table(NU, 8).init_uniform(seed=1); V = rt.Table(NI, 8).init_uniform(seed=2)
+
+    def ints(k):
+        return torch.full((k,), -7, dtype=torch.int32, device=dev)
+
+    def floats(k):
+        return torch.full((k,), -7.0, dtype=torch.float32, device=dev)
+
+    # (call, the sizes its output buffers need, which of them are float32)
+    cases = [
+        (lambda b: sm.pairwise(seed, first, n, *b), [n, n, n], ()),
+        (lambda b: sm.pairwise_hard(seed, first, n, b[0], b[1], b[2], "bpr", U, V, None, candidates=M, cand_out=b[3], cand_score_out=b[4]),
+         [n, n, n, n * M, n * M], (4,)),
+        (lambda b: sm.pairwise_multi(seed, first, n, *b, negatives=M), [n, n, n * M], ()),
+        (lambda b: sm.pairwise_warp(seed, first, n, b[0], b[1], b[2], b[3], "bpr", U, V, None, max_trials=T, trials_out=b[4],
+                                    pos_score_out=b[5], cand_score_out=b[6]), [n, n, n, n, n, n, n * T], (3, 5, 6)),
+        (lambda b: sm.stratified_pointwise(seed, 0, n, 0.5, *b), [n, n, n], (2,)),
+        (lambda b: sm.per_pos_stratified_pointwise(seed, first, n, 0.2, *b), [n, n, n], (2,)),
+    ]
+    for call, sizes, fl in cases:
+        for short in range(len(sizes)):
+            bufs = [(floats if k in fl else ints)(sz - (k == short)) for k, sz in enumerate(sizes)]
+            with pytest.raises(AssertionError):
+                call(bufs)
+            sm.ctx.synchronize()
+            assert all((b == -7).all() for b in bufs)
+    u, p, ng = ints(n), ints(n), ints(n)
+    sm.pairwise(seed, first, n, u, p, ng); sm.ctx.synchronize()
+    wu, wp, wc = hr.candidates(raw, NI, seed, np.arange(first, first + n), 1)
+    assert np.array_equal(u.cpu().numpy(), wu) and np.array_equal(p.cpu().numpy(), wp) and np.array_equal(ng.cpu().numpy(), wc[:, 0])
