@@ -1002,7 +1002,7 @@ int orx_als_objective(orx_ctx* ctx, orx_table* user, orx_table* item,
                       const int64_t* row_ptr, const int32_t* cols, const float* conf /* or NULL */,
                       float a, float b, float reg, int flags, double* host_out);
 
-/* ---- graph propagation over a CSR (api_graph.hip, kernels_graph.hip; DESIGN.md "LightGCN") ----------------------------------
+/* ---- graph propagation over a CSR (api_csr.hip, kernels_graph.hip; DESIGN.md "LightGCN") ------------------------------------
  * One half-layer of LightGCN's propagation.  For rows [row0, row0 + nrows) of a CSR over the rows of `out`, whose columns index
  * the rows of X:
  *     y[r]    = row_scale[r] * sum_{e in row r, in CSR order} col_scale[cols[e]] * X[cols[e]]          (fp32)

@@ -209,6 +209,38 @@ extern "C" int orx_lightgcn_loss(orx_lightgcn* g, const int32_t* uid, const int3
     return ORX_OK;
 }
 
+// ---- the dense optimizer apply (orx_table_apply_dense; step 6 here and VBPR's projection, api_vbpr.hip, call the _at form) ----
+// the rule on one table at the step the optimizer's counter stands at.  The caller has finished a lazily-applied Adam on the table
+// (orx_table_sync: every row current at the step before, the table has left the lazy set) and only then advanced the counter.
+int orx_table_apply_dense_at(orx_ctx* c, orx_opt* opt, orx_table* t, const float* grad) {
+    OptSlots st;
+    CHECK(orx_opt_slots(opt, t, &st));
+    float lr = opt->lr, eps = orx_rule_eps(opt), b1 = 0.f, b2 = 0.f;
+    if (opt->kind == ORX_ADAM) {
+        CHECK(orx_adam_lrt(opt, opt->t));
+        lr = opt->h_lrt[(size_t)opt->t]; b1 = opt->p0; b2 = opt->p1; eps = opt->p2;
+    }
+    CHECK(orx_launch_apply_dense(c, opt->kind, t->w, st.s0, st.s1, grad, t->rows * t->dim, lr, eps, b1, b2));
+    t->version++;
+    return ORX_OK;
+}
+
+extern "C" int orx_table_apply_dense(orx_ctx* c, orx_opt* opt, orx_table* t, const float* grad) {
+    static const char* fn = "orx_table_apply_dense";
+    ORX_ARG(c && opt && t && grad, "%s: NULL argument", fn);
+    ORX_ARG(t->ctx == c && opt->ctx == c, "%s: the table or the optimizer lives on another context", fn);
+    ORX_ARG(opt->kind == ORX_SGD || opt->kind == ORX_MOMENTUM || opt->kind == ORX_ADAGRAD || opt->kind == ORX_ADAM,
+            "%s: unknown optimizer kind %d", fn, opt->kind);
+    ORX_ARG(opt->kind != ORX_ADAM || opt->t + 1 < 0x7fffffff, "%s: step counter overflow", fn);
+    ORX_HIP(hipSetDevice(c->device));
+    CHECK(orx_table_sync(t));                              // (lazy under this or another optimizer: every row current first)
+    if (opt->kind == ORX_ADAM) {
+        CHECK(orx_opt_isolate(opt, &t, 1));                // (a shared optimizer: see orx_opt_isolate)
+        opt->t += 1;
+    }
+    return orx_table_apply_dense_at(c, opt, t, grad);
+}
+
 extern "C" int orx_lightgcn_step(orx_lightgcn* g, orx_opt* opt, const int32_t* uid, const int32_t* pid, const int32_t* nid, int64_t B,
                                  float l2_reg, int train_mask, int flags, float* loss_out, float* l2_out) {
     static const char* fn = "orx_lightgcn_step";

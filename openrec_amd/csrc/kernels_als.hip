@@ -1,4 +1,4 @@
-// Alternating least squares for WRMF (orx_als_half_step, api_als.hip): with one table F [M, D] held fixed, every row x_r of the
+// Alternating least squares for WRMF (orx_als_half_step, api_csr.hip): with one table F [M, D] held fixed, every row x_r of the
 // other table solves
 //     A_r x_r = y_r,   A_r = b G + sum_{j in O_r} (c_rj - b) f_j f_j^T + reg I,   y_r = sum_{j in O_r} c_rj f_j,   G = F^T F
 // in closed form (Hu / Koren / Volinsky 2008).  Three kernels, fp32 throughout, no float atomics anywhere:
@@ -6,8 +6,9 @@
 //   gram      als_gram_kernel<T>: G = F^T F.  The rows of F are cut into als_gram_blocks(M) equal slabs (a function of M alone), one
 //             workgroup per slab; a slab's partial G stays in MFMA accumulators and goes to scratch, als_gram_reduce_kernel adds the
 //             partials in slab order.
-//   segments  als_plan_kernel + als_segment_kernel<T>: a row of more than ALS_SEG entries is cut into segments of ALS_SEG entries
-//             (the last one shorter); one workgroup per segment writes its partial (A, y) -- started from zero -- to a scratch slot.
+//   segments  seg_plan_kernel<ALS_SEG> (orx_seg_plan.h) + als_segment_kernel<T>: a row of more than ALS_SEG entries is cut into
+//             segments of ALS_SEG entries (the last one shorter); one workgroup per segment writes its partial (A, y) -- started
+//             from zero -- to a scratch slot.
 //   solve     als_solve_kernel<T>: one workgroup per row.  total = sum over the row's segments IN SEGMENT ORDER of the segment's
 //             partial, read from its slot or, where the row got no slots (scratch budget) or has one segment only, formed from zero by
 //             the workgroup itself with the very statements of the segment kernel: the bits of x_r are a function of the row alone,
@@ -30,16 +31,13 @@
 // KiB per workgroup: 2 workgroups (8 wavefronts) per CU at D = 128; at D <= 64 registers, not LDS, set the limit (5 workgroups).
 //
 // Non-finite inputs give non-finite x_r: every loop's trip count is an integer function of D and the row's length.
-#include "orx_internal.h"
+#include "orx_als.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int ALS_SEG = 1024;      // L: entries per segment of a long row (orx_als_segment_len)
 constexpr int ALS_CH = 32;         // gathered rows of F per LDS chunk
 constexpr int ALS_WAVES = 4;
 constexpr int ALS_THREADS = 64 * ALS_WAVES;
-
-int orx_als_seg_len() { return ALS_SEG; }
 
 template <int T>
 struct AlsGeom {
@@ -195,31 +193,6 @@ __global__ __launch_bounds__(256) void als_gram_reduce_kernel(const float* __res
 }
 
 // --------------------------------------------------------------------------------------- segments ---
-// One thread per row of the call: a row of more than ALS_SEG entries takes nseg consecutive scratch slots (an integer counter: the
-// slot NUMBERS depend on the launch, what is written into a slot does not) and lists its segments; a row that does not fit into
-// the `cap` slots any more gets none and is walked by its solver workgroup alone.
-__global__ __launch_bounds__(256) void als_plan_kernel(const int64_t* __restrict__ rp, int64_t nrows, int cap, unsigned long long* __restrict__ counter,
-                                                       int* __restrict__ seg_base, int2* __restrict__ list) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrows) return;
-    const int64_t n = rp[i + 1] - rp[i];
-    int base = -1;
-    if (n > ALS_SEG) {
-        const int64_t nseg64 = (n + ALS_SEG - 1) / ALS_SEG;
-        if (nseg64 <= cap) {
-            const int nseg = (int)nseg64;
-            const unsigned long long got = atomicAdd(counter, (unsigned long long)nseg);      // 64 bits: it never wraps
-            if (got + nseg <= (unsigned long long)cap) {
-                base = (int)got;
-                for (int sg = 0; sg < nseg; ++sg) list[base + sg] = make_int2((int)i, sg);
-            } else if (got < (unsigned long long)cap) {
-                for (int sg = (int)got; sg < cap; ++sg) list[sg] = make_int2(-1, -1);      // slots nobody uses
-            }
-        }
-    }
-    seg_base[i] = base;
-}
-
 struct AlsArgs {
     const float* F; int64_t M; int D;              // the fixed table
     const float* Gm;                               // [Dp][Dp] gram, tiles on and below the diagonal
@@ -228,8 +201,7 @@ struct AlsArgs {
     const int32_t* cols; const float* conf;        // entry e of the CSR is cols[e - ebase]: both pointers are already shifted by -ebase
     int64_t nrows;
     float a, b, reg;
-    const int* seg_base; const int2* list; const unsigned long long* counter; int cap;
-    float* slots;                                  // [cap][SLOT]
+    SegPlan plan;                                  // slots: [cap][SLOT]
     int* err;
 };
 
@@ -237,10 +209,9 @@ template <int T>
 __global__ __launch_bounds__(ALS_THREADS) void als_segment_kernel(AlsArgs p) {
     using G = AlsGeom<T>;
     __shared__ __attribute__((aligned(16))) AlsLds<T> s;
-    const unsigned long long used = *p.counter;
-    const int count = used < (unsigned long long)p.cap ? (int)used : p.cap;
+    const int count = seg_plan_count(p.plan);
     for (int it = blockIdx.x; it < count; it += gridDim.x) {
-        const int2 w = p.list[it];
+        const int2 w = p.plan.list[it];
         if (w.x < 0) continue;
         const int64_t r0 = p.rp[w.x], r1 = p.rp[w.x + 1];
         const int64_t e0 = r0 + (int64_t)w.y * ALS_SEG;
@@ -250,7 +221,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_segment_kernel(AlsArgs p) {
         for (int t = 0; t < G::MAXT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         float yv = 0.f;
         als_accumulate<T, true>(s, p.F, p.M, p.D, p.cols, p.conf, p.a, p.b, e0, e1, acc, yv, p.err);
-        float* out = p.slots + (size_t)it * G::SLOT;
+        float* out = p.plan.slots + (size_t)it * G::SLOT;
         als_for_each<T>([&](int t, int r, int i, int j) { out[i * G::Dp + j] = acc[t][r]; });
         if (threadIdx.x < G::Dp) out[G::Dp * G::Dp + threadIdx.x] = yv;
     }
@@ -276,7 +247,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(AlsArgs p) {
     }
     const int64_t n = r1 - r0;
     const int64_t nseg = (n + ALS_SEG - 1) / ALS_SEG;
-    const int base = p.seg_base ? p.seg_base[row] : -1;
+    const int base = p.plan.seg_base ? p.plan.seg_base[row] : -1;
     f32x4 tot[G::MAXT];
 #pragma unroll
     for (int t = 0; t < G::MAXT; ++t) tot[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -287,7 +258,7 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(AlsArgs p) {
         for (int t = 0; t < G::MAXT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         float yv = 0.f;
         if (base >= 0) {
-            const float* in = p.slots + (size_t)(base + sg) * G::SLOT;
+            const float* in = p.plan.slots + (size_t)(base + sg) * G::SLOT;
             als_for_each<T>([&](int t, int r, int i, int j) { acc[t][r] = in[i * G::Dp + j]; });
             if (tid < G::Dp) yv = in[G::Dp * G::Dp + tid];
         } else {
@@ -363,49 +334,44 @@ __global__ __launch_bounds__(ALS_THREADS) void als_solve_kernel(AlsArgs p) {
 }
 
 // ---------------------------------------------------------------------------------------- launchers ---
+// fn(std::integral_constant<int, T>) for T = ceil(D / 16)
+template <class Fn>
+static int als_dispatch(int D, Fn fn) {
+    switch ((D + 15) / 16) {
+        case 1: return fn(std::integral_constant<int, 1>{});
+        case 2: return fn(std::integral_constant<int, 2>{});
+        case 3: return fn(std::integral_constant<int, 3>{});
+        case 4: return fn(std::integral_constant<int, 4>{});
+        case 5: return fn(std::integral_constant<int, 5>{});
+        case 6: return fn(std::integral_constant<int, 6>{});
+        case 7: return fn(std::integral_constant<int, 7>{});
+        case 8: return fn(std::integral_constant<int, 8>{});
+    }
+    orx_set_error("ALS: dim %d outside [1, 128]", D);
+    return ORX_ERR_ARG;
+}
+
 template <int T>
-static int als_launch_T(orx_ctx* ctx, const AlsArgs& p, float* gram_part, float* Gm, bool plan, int64_t nrows) {
-    using G = AlsGeom<T>;
-    const int nb = orx_als_gram_blocks(p.M);
-    ORX_LAUNCH(ctx, als_gram_kernel<T>, dim3(nb), dim3(ALS_THREADS), 0, p.F, p.M, p.D, gram_part);
-    ORX_LAUNCH(ctx, als_gram_reduce_kernel, dim3((G::Dp * G::Dp + 255) / 256), dim3(256), 0, (const float*)gram_part, nb, G::Dp, Gm);
-    if (plan) {
-        const int grid = p.cap < 2048 ? p.cap : 2048;
+static int als_launch_T(orx_ctx* ctx, const AlsArgs& p) {
+    if (p.plan.seg_base) {
+        const int grid = p.plan.cap < 2048 ? p.plan.cap : 2048;
         ORX_LAUNCH(ctx, als_segment_kernel<T>, dim3(grid), dim3(ALS_THREADS), 0, p);
     }
-    ORX_LAUNCH(ctx, als_solve_kernel<T>, dim3((unsigned)nrows), dim3(ALS_THREADS), 0, p);
+    ORX_LAUNCH(ctx, als_solve_kernel<T>, dim3((unsigned)p.nrows), dim3(ALS_THREADS), 0, p);
     ORX_HIP(hipGetLastError());
     return ORX_OK;
 }
 
-// the whole half-step on the context's stream: gram, segment plan + partials (cap > 0), solve.  gram_part: [als_gram_blocks][Dp * Dp]
 int orx_launch_als(orx_ctx* ctx, const float* F, int64_t M, int D, float* X, const int64_t* rp, const int32_t* cols, const float* conf,
-                   int64_t nrows, float a, float b, float reg, float* gram_part, float* Gm,
-                   int cap, unsigned long long* counter, int* seg_base, int2* list, float* slots) {
+                   int64_t nrows, float a, float b, float reg, const float* Gm, const SegScratch& s) {
     AlsArgs p;
     p.F = F; p.M = M; p.D = D; p.Gm = Gm; p.X = X; p.rp = rp; p.cols = cols; p.conf = conf; p.nrows = nrows;
     p.a = a; p.b = b; p.reg = reg; p.err = ctx->d_err;
-    const bool plan = cap > 0;
-    p.seg_base = plan ? seg_base : nullptr; p.list = list; p.counter = counter; p.cap = cap; p.slots = slots;
-    if (plan) {
-        ORX_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
-        ORX_LAUNCH(ctx, als_plan_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, rp, nrows, cap, counter, seg_base, list);
-    }
-    switch ((D + 15) / 16) {
-        case 1: return als_launch_T<1>(ctx, p, gram_part, Gm, plan, nrows);
-        case 2: return als_launch_T<2>(ctx, p, gram_part, Gm, plan, nrows);
-        case 3: return als_launch_T<3>(ctx, p, gram_part, Gm, plan, nrows);
-        case 4: return als_launch_T<4>(ctx, p, gram_part, Gm, plan, nrows);
-        case 5: return als_launch_T<5>(ctx, p, gram_part, Gm, plan, nrows);
-        case 6: return als_launch_T<6>(ctx, p, gram_part, Gm, plan, nrows);
-        case 7: return als_launch_T<7>(ctx, p, gram_part, Gm, plan, nrows);
-        case 8: return als_launch_T<8>(ctx, p, gram_part, Gm, plan, nrows);
-    }
-    orx_set_error("orx_als_half_step: dim %d outside [1, 128]", D);
-    return ORX_ERR_ARG;
+    CHECK(seg_plan_launch<ALS_SEG>(ctx, rp, nrows, s, &p.plan));
+    return als_dispatch(D, [&](auto t) { return als_launch_T<decltype(t)::value>(ctx, p); });
 }
 
-// the gram alone, for the callers that solve without A_r (kernels_als_cg.hip): Gm NULL leaves the slab partials unreduced
+// the gram: Gm NULL leaves the slab partials unreduced
 template <int T>
 static int als_gram_T(orx_ctx* ctx, const float* F, int64_t M, int D, float* gram_part, float* Gm) {
     using G = AlsGeom<T>;
@@ -417,16 +383,5 @@ static int als_gram_T(orx_ctx* ctx, const float* F, int64_t M, int D, float* gra
 }
 
 int orx_launch_als_gram(orx_ctx* ctx, const float* F, int64_t M, int D, float* gram_part, float* Gm) {
-    switch ((D + 15) / 16) {
-        case 1: return als_gram_T<1>(ctx, F, M, D, gram_part, Gm);
-        case 2: return als_gram_T<2>(ctx, F, M, D, gram_part, Gm);
-        case 3: return als_gram_T<3>(ctx, F, M, D, gram_part, Gm);
-        case 4: return als_gram_T<4>(ctx, F, M, D, gram_part, Gm);
-        case 5: return als_gram_T<5>(ctx, F, M, D, gram_part, Gm);
-        case 6: return als_gram_T<6>(ctx, F, M, D, gram_part, Gm);
-        case 7: return als_gram_T<7>(ctx, F, M, D, gram_part, Gm);
-        case 8: return als_gram_T<8>(ctx, F, M, D, gram_part, Gm);
-    }
-    orx_set_error("ALS gram: dim %d outside [1, 128]", D);
-    return ORX_ERR_ARG;
+    return als_dispatch(D, [&](auto t) { return als_gram_T<decltype(t)::value>(ctx, F, M, D, gram_part, Gm); });
 }

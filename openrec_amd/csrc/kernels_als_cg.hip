@@ -1,5 +1,5 @@
 // Conjugate gradient for the ALS half-step of WRMF (orx_als_half_step_cg) and the objective the half-steps descend
-// (orx_als_objective); api_als_cg.hip has the entry points, include/openrec_hip.h the contract, kernels_als.hip the notation.
+// (orx_als_objective); api_csr.hip has the entry points, include/openrec_hip.h the contract, kernels_als.hip the notation.
 //
 // A row never forms A_r.  One product A v = b (G v) + reg v + sum_j (c_j - b) (f_j . v) f_j is
 //   gram      G v from the full square of G (als_gram_kernel's tiles mirrored across the diagonal by als_cg_square_kernel), lane d
@@ -14,8 +14,8 @@
 //
 // Code paths, by the row's length n and D alone (orx_als_cg_row_breaks):
 //   n <= CH        the gathered entries stay in LDS across the cg_steps + 1 products;
-//   n <= CG_SEG    they are streamed again for every product;
-//   n >  CG_SEG    the row is cut into segments of CG_SEG entries.  als_cg_plan_kernel gives it a state slot and one scratch slot per
+//   n <= ALS_SEG   they are streamed again for every product;
+//   n >  ALS_SEG   the row is cut into segments of ALS_SEG entries.  als_cg_plan_kernel gives it a state slot and one scratch slot per
 //                  segment; per product als_cg_long_partial_kernel forms every segment's partial -- from zero, one wavefront each,
 //                  over the whole device -- and als_cg_long_update_kernel adds them IN SEGMENT ORDER and takes the CG step.  A long
 //                  row that got no slots (scratch budget) is walked by its own wavefront in als_cg_rows_kernel with the very
@@ -25,10 +25,8 @@
 // The objective: both grams by als_gram_kernel (slab partials, added here in fp64 in slab order), the observed cells by one
 // wavefront per OBJ_EPW consecutive entries of the CSR (the dot product summed in fp64 by the butterfly), one workgroup adds
 // everything in fp64 in a fixed order.
-#include "orx_internal.h"
-#include "orx_als_cg.h"
+#include "orx_als.h"
 
-constexpr int CG_SEG = 1024;       // entries per segment of a long row
 constexpr int OBJ_EPW = 256;       // entries per wavefront of the objective's pass
 constexpr int OBJ_B = 8;           // of them in flight
 constexpr int OBJ_THREADS = 1024;
@@ -48,11 +46,10 @@ struct CgGeom {
 
 int orx_als_cg_breaks(int D, int32_t* out, int cap) {
     if (D < 1 || D > 128) return 0;
-    const int32_t b[2] = {D <= 64 ? CgGeom<1>::CH : CgGeom<2>::CH, CG_SEG};
+    const int32_t b[2] = {D <= 64 ? CgGeom<1>::CH : CgGeom<2>::CH, ALS_SEG};
     for (int i = 0; i < 2 && i < cap; ++i) out[i] = b[i];
     return 2;
 }
-int orx_als_cg_seg() { return CG_SEG; }
 int64_t orx_als_cg_slot_floats(int D) { return 2 * (D <= 64 ? 64 : 128); }
 int64_t orx_als_cg_square_floats(int D) { const int Dp = D <= 64 ? 64 : 128; return (int64_t)Dp * (Dp + 4); }
 int64_t orx_als_cg_state_bytes(int D) { return (int64_t)(D <= 64 ? 64 : 128) * 20; }      // x, r fp64 and p fp32 per element
@@ -216,7 +213,7 @@ __device__ __forceinline__ void cg_row(const CgArgs& p, const float* Gsrc, float
         for (int e = 0; e < NE; ++e) if (lane + 64 * e < D) xrow[lane + 64 * e] = 0.f;
         return;
     }
-    const int64_t n = r1 - r0, nseg = (n + CG_SEG - 1) / CG_SEG;
+    const int64_t n = r1 - r0, nseg = (n + ALS_SEG - 1) / ALS_SEG;
     const bool resident = n <= G::CH;
     float x0[NE];
 #pragma unroll
@@ -228,7 +225,7 @@ __device__ __forceinline__ void cg_row(const CgArgs& p, const float* Gsrc, float
         for (int e = 0; e < NE; ++e) { v[e] = it == 0 ? x0[e] : st.p[e]; tot[e] = 0.f; ytot[e] = 0.f; }
         cg_publish<NE>(vs, v);
         for (int64_t sg = 0; sg < nseg; ++sg) {            // segment order, each partial from zero
-            const int64_t e0 = r0 + sg * CG_SEG, e1 = e0 + CG_SEG < r1 ? e0 + CG_SEG : r1;
+            const int64_t e0 = r0 + sg * ALS_SEG, e1 = e0 + ALS_SEG < r1 ? e0 + ALS_SEG : r1;
             float part[NE], yp[NE];
 #pragma unroll
             for (int e = 0; e < NE; ++e) { part[e] = 0.f; yp[e] = 0.f; }
@@ -273,7 +270,7 @@ __global__ __launch_bounds__(CgGeom<NE>::THREADS) void als_cg_rows_kernel(CgArgs
 }
 
 // ------------------------------------------------------------------------------------- long rows ---
-// One thread per row of the call: a row of more than CG_SEG entries takes one state slot and nseg consecutive scratch slots (integer
+// One thread per row of the call: a row of more than ALS_SEG entries takes one state slot and nseg consecutive scratch slots (integer
 // counters: the slot NUMBERS depend on the launch, what is written into a slot does not); a row that does not fit gets none.
 __global__ __launch_bounds__(256) void als_cg_plan_kernel(const int64_t* __restrict__ rp, int64_t nrows, int cap_rows, int cap_slots,
                                                           unsigned long long* __restrict__ counter, int* __restrict__ long_idx,
@@ -282,8 +279,8 @@ __global__ __launch_bounds__(256) void als_cg_plan_kernel(const int64_t* __restr
     if (i >= nrows) return;
     const int64_t n = rp[i + 1] - rp[i];
     int idx = -1;
-    if (n > CG_SEG) {
-        const int64_t nseg64 = (n + CG_SEG - 1) / CG_SEG;
+    if (n > ALS_SEG) {
+        const int64_t nseg64 = (n + ALS_SEG - 1) / ALS_SEG;
         if (nseg64 <= cap_slots) {
             const unsigned long long nseg = (unsigned long long)nseg64;
             const unsigned long long got = atomicAdd(counter, (1ull << 32) | nseg);      // 32 bits of slots: never carries into the rows
@@ -317,7 +314,7 @@ __global__ __launch_bounds__(CgGeom<NE>::THREADS) void als_cg_long_partial_kerne
     if (w.x < 0) return;
     const int64_t row = p.rowlist[w.x].x;
     const int64_t r0 = p.rp[row], r1 = p.rp[row + 1];
-    const int64_t e0 = r0 + (int64_t)w.y * CG_SEG, e1 = e0 + CG_SEG < r1 ? e0 + CG_SEG : r1;
+    const int64_t e0 = r0 + (int64_t)w.y * ALS_SEG, e1 = e0 + ALS_SEG < r1 ? e0 + ALS_SEG : r1;
     float v[NE], part[NE], yp[NE];
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
@@ -346,7 +343,7 @@ __global__ __launch_bounds__(256) void als_cg_long_update_kernel(CgArgs p, int i
     const int2 w = p.rowlist[ri];
     if (w.x < 0) return;
     const int64_t row = w.x;
-    const int64_t n = p.rp[row + 1] - p.rp[row], nseg = (n + CG_SEG - 1) / CG_SEG;
+    const int64_t n = p.rp[row + 1] - p.rp[row], nseg = (n + ALS_SEG - 1) / ALS_SEG;
     float* xrow = p.X + (size_t)row * p.D;
     const size_t so = (size_t)ri * G::Dp;
     CgState<NE> st;

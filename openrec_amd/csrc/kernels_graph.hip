@@ -12,7 +12,7 @@
 //
 // Segments.  A row of n entries is cut into ceil(n / GS_SEG) segments of GS_SEG entries (the last one shorter).  Every segment is
 // summed from zero by the walk above; a row's value is the segments' sums added in segment order, times row_scale.  Rows of one
-// segment are summed and finished by their own wavefront.  The segments of longer rows are listed by a plan kernel (one thread per
+// segment are summed and finished by their own wavefront.  The segments of longer rows are listed by seg_plan_kernel (one thread per
 // row; an INTEGER counter hands out scratch slots, so slot numbers depend on the launch but nothing written into a slot does),
 // summed by separate wavefronts into the slots, and added in segment order by the row's wavefront.  A row that found no slot
 // walks its segments itself, the same sums in the same order.  So y[r] is a function of X, the row's entries and the scales
@@ -25,7 +25,6 @@
 
 namespace {
 
-constexpr int GS_SEG = 512;        // entries per segment (orx_graph_segment_len)
 constexpr int GS_UN = 4;           // load instructions in flight per wavefront
 
 struct SpmmArgs {
@@ -35,8 +34,7 @@ struct SpmmArgs {
     const int32_t* cols;                           // entry e of the CSR is cols[e] (the pointer is already shifted for a staged copy)
     const float* rs; const float* cs;              // row scales of the call's first row on / column scales (NULL: 1)
     int64_t nrows;
-    const int* seg_base; const int2* list; const unsigned long long* counter; int cap;
-    float* slots;                                  // [cap][D]
+    SegPlan plan;                                  // slots: [cap][D]
     int* err;
 };
 
@@ -101,39 +99,16 @@ __device__ __forceinline__ void seg_sum_gen(const SpmmArgs& p, int64_t e0, int64
 
 __device__ __forceinline__ int64_t seg_end(int64_t e0, int64_t r1) { return e0 + GS_SEG < r1 ? e0 + GS_SEG : r1; }
 
-__global__ __launch_bounds__(256) void graph_plan_kernel(const int64_t* __restrict__ rp, int64_t nrows, int cap, unsigned long long* __restrict__ counter,
-                                                         int* __restrict__ seg_base, int2* __restrict__ list) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nrows) return;
-    const int64_t n = rp[i + 1] - rp[i];
-    int base = -1;
-    if (n > GS_SEG) {
-        const int64_t nseg64 = (n + GS_SEG - 1) / GS_SEG;
-        if (nseg64 <= cap) {
-            const int nseg = (int)nseg64;
-            const unsigned long long got = atomicAdd(counter, (unsigned long long)nseg);      // (integer: 64 bits never wrap)
-            if (got + nseg <= (unsigned long long)cap) {
-                base = (int)got;
-                for (int sg = 0; sg < nseg; ++sg) list[base + sg] = make_int2((int)i, sg);
-            } else if (got < (unsigned long long)cap) {
-                for (int sg = (int)got; sg < cap; ++sg) list[sg] = make_int2(-1, -1);      // slots nobody uses
-            }
-        }
-    }
-    seg_base[i] = base;
-}
-
 // one wavefront per listed segment: its sum, from zero, into its slot
 template <int LPR>
 __global__ __launch_bounds__(256) void graph_segment_kernel(SpmmArgs p) {
     const int lane = threadIdx.x & 63;
-    const unsigned long long used = *p.counter;
-    const int count = used < (unsigned long long)p.cap ? (int)used : p.cap;
+    const int count = seg_plan_count(p.plan);
     for (int it = blockIdx.x * 4 + (threadIdx.x >> 6); it < count; it += gridDim.x * 4) {
-        const int2 w = p.list[it];
+        const int2 w = p.plan.list[it];
         if (w.x < 0) continue;
         const int64_t r1 = p.rp[w.x + 1], e0 = p.rp[w.x] + (int64_t)w.y * GS_SEG, e1 = seg_end(e0, r1);
-        float* slot = p.slots + (size_t)it * p.D;
+        float* slot = p.plan.slots + (size_t)it * p.D;
         if constexpr (LPR > 0) {
             const f4 s = seg_sum_vec<LPR>(p, e0, e1, lane);
             if (lane < LPR) *reinterpret_cast<f4*>(slot + 4 * lane) = s;
@@ -154,7 +129,7 @@ __global__ __launch_bounds__(256) void graph_row_kernel(SpmmArgs p) {
     if (r >= p.nrows) return;
     const int64_t r0 = p.rp[r], r1 = p.rp[r + 1];
     const int64_t nseg = r1 > r0 ? (r1 - r0 + GS_SEG - 1) / GS_SEG : 0;
-    const int base = (nseg > 1 && p.seg_base != nullptr) ? p.seg_base[r] : -1;
+    const int base = (nseg > 1 && p.plan.seg_base != nullptr) ? p.plan.seg_base[r] : -1;
     const float scale = p.rs ? p.rs[r] : 1.0f;
     float* o = p.out + (size_t)r * p.D;
     float* a = p.acc ? p.acc + (size_t)r * p.D : nullptr;
@@ -163,7 +138,7 @@ __global__ __launch_bounds__(256) void graph_row_kernel(SpmmArgs p) {
         f4 s = {0.f, 0.f, 0.f, 0.f};
         for (int64_t sg = 0; sg < nseg; ++sg) {
             f4 q;
-            if (base >= 0) q = *reinterpret_cast<const f4*>(p.slots + (size_t)(base + sg) * p.D + 4 * (lane % L));
+            if (base >= 0) q = *reinterpret_cast<const f4*>(p.plan.slots + (size_t)(base + sg) * p.D + 4 * (lane % L));
             else { const int64_t e0 = r0 + sg * GS_SEG; q = seg_sum_vec<L>(p, e0, seg_end(e0, r1), lane); }
             if (sg == 0) s = q; else { s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w; }
         }
@@ -182,7 +157,7 @@ __global__ __launch_bounds__(256) void graph_row_kernel(SpmmArgs p) {
         for (int64_t sg = 0; sg < nseg; ++sg) {
             float q0 = 0.f, q1 = 0.f;
             if (base >= 0) {
-                const float* slot = p.slots + (size_t)(base + sg) * p.D;
+                const float* slot = p.plan.slots + (size_t)(base + sg) * p.D;
                 if (lane < p.D) q0 = slot[lane];
                 if (lane + 64 < p.D) q1 = slot[lane + 64];
             } else { const int64_t e0 = r0 + sg * GS_SEG; seg_sum_gen(p, e0, seg_end(e0, r1), lane, q0, q1); }
@@ -201,9 +176,9 @@ __global__ __launch_bounds__(256) void graph_row_kernel(SpmmArgs p) {
 }
 
 template <int LPR>
-int launch_spmm_T(orx_ctx* ctx, const SpmmArgs& p, bool plan) {
-    if (plan) {
-        const int blocks = std::max(1, std::min(ctx->num_cu * 8, (p.cap + 3) / 4));
+int launch_spmm_T(orx_ctx* ctx, const SpmmArgs& p) {
+    if (p.plan.seg_base) {
+        const int blocks = std::max(1, std::min(ctx->num_cu * 8, (p.plan.cap + 3) / 4));
         ORX_LAUNCH(ctx, graph_segment_kernel<LPR>, dim3((unsigned)blocks), dim3(256), 0, p);
     }
     ORX_LAUNCH(ctx, graph_row_kernel<LPR>, dim3((unsigned)((p.nrows + 3) / 4)), dim3(256), 0, p);
@@ -264,32 +239,24 @@ inline unsigned grid_cap(int64_t n, int per) {
 
 }  // namespace
 
-int orx_graph_seg_len() { return GS_SEG; }
-
 // the whole product on the context's stream: plan + segment sums (cap > 0), then the rows.  vec_ok: every row of X, out and acc
 // starts on a 16-byte boundary
 int orx_launch_graph_spmm(orx_ctx* ctx, const float* X, int64_t M, int D, float* out, float* acc, float acc_alpha, const int64_t* rp,
-                          const int32_t* cols, const float* rs, const float* cs, int64_t nrows, bool vec_ok,
-                          int cap, unsigned long long* counter, int* seg_base, int2* list, float* slots) {
+                          const int32_t* cols, const float* rs, const float* cs, int64_t nrows, bool vec_ok, const SegScratch& s) {
     SpmmArgs p;
     p.X = X; p.M = M; p.D = D; p.out = out; p.acc = acc; p.acc_alpha = acc_alpha; p.rp = rp; p.cols = cols; p.rs = rs; p.cs = cs;
     p.nrows = nrows; p.err = ctx->d_err;
-    const bool plan = cap > 0;
-    p.seg_base = plan ? seg_base : nullptr; p.list = list; p.counter = counter; p.cap = cap; p.slots = slots;
-    if (plan) {
-        ORX_HIP(hipMemsetAsync(counter, 0, sizeof(unsigned long long), ctx->stream));
-        ORX_LAUNCH(ctx, graph_plan_kernel, dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, rp, nrows, cap, counter, seg_base, list);
-    }
+    CHECK(seg_plan_launch<GS_SEG>(ctx, rp, nrows, s, &p.plan));
     ProfScope ps(ctx, ORX_K_FUSED);
     if (vec_ok) {
         switch (D) {
-            case 16: return launch_spmm_T<4>(ctx, p, plan);
-            case 32: return launch_spmm_T<8>(ctx, p, plan);
-            case 64: return launch_spmm_T<16>(ctx, p, plan);
-            case 128: return launch_spmm_T<32>(ctx, p, plan);
+            case 16: return launch_spmm_T<4>(ctx, p);
+            case 32: return launch_spmm_T<8>(ctx, p);
+            case 64: return launch_spmm_T<16>(ctx, p);
+            case 128: return launch_spmm_T<32>(ctx, p);
         }
     }
-    return launch_spmm_T<0>(ctx, p, plan);
+    return launch_spmm_T<0>(ctx, p);
 }
 
 int orx_launch_graph_scale(orx_ctx* ctx, const float* in, float* out, int64_t n, float alpha) {

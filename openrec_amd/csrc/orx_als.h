@@ -1,6 +1,10 @@
-// What kernels_als_cg.hip and api_als_cg.hip share: the arguments of the CG half-step and of the ALS objective.
+// What the ALS translation units share (kernels_als.hip, kernels_als_cg.hip, api_csr.hip): the segment length, the arguments of the CG
+// half-step and of the ALS objective, the launchers.
 #pragma once
 #include "orx_internal.h"
+#include "orx_seg_plan.h"
+
+constexpr int ALS_SEG = 1024;      // L: entries per segment of a long row, Cholesky and CG alike (orx_als_segment_len)
 
 struct CgArgs {
     const float* F; int64_t M; int D;
@@ -34,7 +38,6 @@ struct ObjArgs {
 };
 
 int orx_als_cg_breaks(int D, int32_t* out, int cap);
-int orx_als_cg_seg();
 int64_t orx_als_cg_slot_floats(int D);
 int64_t orx_als_cg_state_bytes(int D);
 int64_t orx_als_cg_square_floats(int D);
@@ -46,3 +49,7 @@ int orx_launch_als_objective(orx_ctx* ctx, ObjArgs p);
 // sum in slab order into Gm [Dp16][Dp16] (tiles on and below the diagonal)
 int orx_als_gram_blocks(int64_t M);
 int orx_launch_als_gram(orx_ctx* ctx, const float* F, int64_t M, int D, float* gram_part, float* Gm);
+// the Cholesky half-step after the gram: segment plan + partials (s.cap > 0), solve.  s.slots: [s.cap][orx_als_slot_floats(D)]
+int64_t orx_als_slot_floats(int D);
+int orx_launch_als(orx_ctx* ctx, const float* F, int64_t M, int D, float* X, const int64_t* rp, const int32_t* cols, const float* conf,
+                   int64_t nrows, float a, float b, float reg, const float* Gm, const SegScratch& s);
