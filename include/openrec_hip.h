@@ -1132,6 +1132,63 @@ int orx_vbpr_loss(orx_ctx* ctx, orx_table* user, orx_table* item, orx_table* bia
                   int64_t B, int flags, float* loss_out, float* l2_out);
 int orx_vbpr_geometry(int64_t B, int32_t Fd, int32_t Dc, int32_t batch_chunk, int32_t out[4]);
 
+/* ---- History-pooled sequence recommender (api_seqrec.hip, kernels_bag.hip): the user vector is pooled from the embeddings of the
+ * items the user just interacted with, so there is no user table and a user never trained on is served from a history alone
+ * (the depth-0 YouTube retrieval tower, FISM, item2vec).
+ * Tables: hist = H [NI, D], item = V [NI, D], bias [NI, 1] or NULL; D <= 256.  Bags in ragged form, the (input, offsets) form of an
+ * EmbeddingBag: bag_ptr int32 [B + 1], bag_items int32 [n], bag i = bag_items[bag_ptr[i] .. bag_ptr[i + 1]); n is the length of
+ * bag_items.  Both arrays live where the ids live (host, or device under ORX_IDS_DEVICE).  Contract: bag_ptr[0] == 0, non-decreasing,
+ * bag_ptr[B] == n, n < 2^31.
+ *   q_i     = c_i * sum over e in bag i, in list order, of H[bag_items[e]]
+ *             c_i = 1.0f / (float)len_i (ORX_BAG_MEAN)  |  1.0f / denom (ORX_BAG_FIXED; denom = 1: a sum, denom = max_seq_len: a
+ *             mean over a padded axis)
+ *   s(q, j) = q . V[j] + b[j]
+ * The sum is an fp32 chain whose order depends on (len_i, D) alone; c_i is rounded once, the product once; an empty bag gives +0.
+ * The bits of q_i depend on its own list and on H: not on B, not on the other bags, not on out_row0, not on where the lists live.
+ * No float atomics.
+ *   orx_bag_pool      rows [out_row0, out_row0 + B) of out (another table of H's dim) = q_i; nothing else is touched.  Rows of H that
+ *                     are lazily applied under Adam are brought up to date first.  ORX_IDS_DEVICE: no host synchronisation (a bad
+ *                     list then shows at the next orx_check_index_error).
+ *   orx_seqrec_step   ONE train step of orx_multineg_step's objective with u_i replaced by q_i: kinds ORX_MN_SOFTMAX / ORX_MN_LOGSIG,
+ *                     N in [1, 64] negatives per sample, weight [B], neg_offset [B][N] as there.
+ *                       l2_loss = 1/2 (sum_i |q_i|^2 + sum |V[p]|^2 + sum |V[n]|^2);   J = loss + l2_reg * l2_loss
+ *                     The l2 term sits on the POOLED vector, not on the len_i history rows (the reference's l2_reg_embed sits on the
+ *                     looked-up rows).  With g_q[i] = orx_multineg_step's g_u of sample i, occurrence e of bag i has the gradient row
+ *                     c_i * g_q[i], each element rounded once, and hist is applied with orx_apply_rows' semantics on the list
+ *                     bag_items[n] with those rows: a row's occurrences are summed in list order, the rule runs once per distinct row.
+ *                     The n x D occurrence rows are never materialised: scratch is O(n) words plus O(B (1 + N) D).  item and bias
+ *                     are applied exactly as orx_multineg_step applies them (one list, pid | nid).  Adam's counter advances once,
+ *                     after the reads and before the applies.  loss_out / l2_out: the loss and the UNSCALED l2_loss; both NULL with
+ *                     ORX_IDS_DEVICE: no host synchronisation.
+ *                     train_mask: ORX_TRAIN_USER (the history table) | _ITEM | _BIAS, 0 = every table the call was given; a table
+ *                     outside the mask is read, never written, and its optimizer slots are untouched.  flags: ORX_IDS_DEVICE, ORX_NO_L2.
+ *   orx_seqrec_loss   the forward alone: (loss, l2_loss) of one batch, the step's numbers bit for bit; no table changes.
+ * ORX_ERR_ARG before any device work: hist and item the same table, or their dims or rows differ; dim > 256; a bias that is not
+ * [NI, 1]; a mode outside the two; denom not finite or <= 0; N outside [1, 64]; l2_reg negative or not finite; ORX_NO_L2 with
+ * l2_reg != 0; ORX_HOGWILD, ORX_CENSOR; what orx_apply_rows refuses (ORX_ADAM_DENSE with a bias); B outside [0, 2^31 - 1), n outside
+ * [0, 2^31), B (1 + N) >= 2^31; a host bag_ptr that breaks the contract; out rows outside the output table, out == H.
+ * A device bag_ptr that breaks the contract, or an item id outside [0, NI) in a bag, in pid or in nid: ORX_ERR_INDEX (host lists:
+ * from the call; device lists: from the call when it returns losses, else at the next orx_check_index_error).  The id is never used
+ * as an address, a bag that holds one pools to +0 and its sample is dropped, and the context stays usable; the tables are then
+ * only guaranteed to be in bounds and finite.
+ * Not offered: tied tables (hist == item); per-occurrence weights (recency decay); the reference's hidden Dense(D) layer and
+ * dropout; the full softmax over all items; in-batch negatives; K-step calls (a step at realistic sizes is hundreds of
+ * microseconds); the sharded engines. */
+enum orx_bag_mode { ORX_BAG_MEAN = 0, ORX_BAG_FIXED = 1 };
+int orx_bag_pool(orx_ctx* ctx, orx_table* H, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode,
+                 float denom, orx_table* out, int64_t out_row0, int flags);
+int orx_seqrec_step(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */, orx_opt* opt,
+                    orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */, const int32_t* nid /* [B][N] */,
+                    const float* weight /* NULL ok */, const float* neg_offset /* NULL ok */,
+                    int64_t B, int64_t n, int32_t N, int mode, float denom, float l2_reg, int train_mask, int flags,
+                    float* loss_out, float* l2_out);
+int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
+                    orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */, const int32_t* nid /* [B][N] */,
+                    const float* weight /* NULL ok */, const float* neg_offset /* NULL ok */,
+                    int64_t B, int64_t n, int32_t N, int mode, float denom, int flags, float* loss_out, float* l2_out);
+
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,
  *                       PL_PAIR_CAP, ORX_SEG_DIRECT, ORX_PIECE, threads per range workgroup, threads of a big plan, references per

@@ -18,6 +18,7 @@ ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID, ORX_OUT_D
 ORX_TRAIN_USER, ORX_TRAIN_ITEM, ORX_TRAIN_BIAS = 1, 2, 4      # enum orx_train_mask
 ORX_TRAIN_PROJ = 8                                            # (orx_vbpr_step: the projection)
 ORX_MN_SOFTMAX, ORX_MN_LOGSIG = 0, 1                          # enum orx_multineg_kind
+ORX_BAG_MEAN, ORX_BAG_FIXED = 0, 1                            # enum orx_bag_mode
 ORX_IB_MASK_HITS = 0x1000                                     # enum orx_inbatch_flags
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
@@ -112,6 +113,11 @@ SIGNATURES = {
                               c_float, c_float, c_int32, c_int, c_int, _fp, _fp]),
     "orx_vbpr_loss": (c_int, [_p, _p, _p, _p, _p, _fp, c_int64, c_int32, _ip, _ip, _ip, _fp, c_int64, c_int, _fp, _fp]),
     "orx_vbpr_geometry": (c_int, [c_int64, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "orx_bag_pool": (c_int, [_p, _p, _ip, _ip, c_int64, c_int64, c_int, c_float, _p, c_int64, c_int]),
+    "orx_seqrec_step": (c_int, [_p, c_int, _p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int32, c_int, c_float,
+                                c_float, c_int, c_int, _fp, _fp]),
+    "orx_seqrec_loss": (c_int, [_p, c_int, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int32, c_int, c_float,
+                                c_int, _fp, _fp]),
     "orx_lightgcn_create": (c_int, [_p, _p, _p, _p, _ip, _p, _ip, _fp, _fp, c_int64, c_int64, c_int32, _fp, _pp]),
     "orx_lightgcn_destroy": (c_int, [_p]),
     "orx_lightgcn_tables": (c_int, [_p, _pp, _pp]),

@@ -995,6 +995,21 @@ struct MultiNegArgs {
 int orx_multineg_nwaves(orx_ctx* ctx, int D, int64_t B);
 int orx_launch_multineg(orx_ctx* ctx, int kind /* orx_multineg_kind */, bool grads, const MultiNegArgs& a);
 
+// kernels_bag.hip (orx_bag_pool / orx_seqrec_step / orx_seqrec_loss): pooling of ragged item lists, one wavefront per bag, and the
+// two kernels between the gradient launch and the sorted apply of the history table
+struct BagArgs {
+    const float* H; int64_t rows; int D;                  // the table the lists index
+    const int32_t* ptr; const int32_t* items;             // DEVICE [B + 1] offsets, [n] ids
+    int64_t B; int64_t n;
+    int mode; float inv_denom;                            // orx_bag_mode; 1.0f / denom (ORX_BAG_FIXED)
+    float* out;                                           // [B][D] q_i, rows of the call's first bag on
+    int32_t* uid; float* coef; int32_t* owner;            // the step's (NULL: not kept): [B] i or -1 (a dead bag), [B] c_i (0: dead or empty), [n] the bag of a list position
+    int* err;
+};
+int orx_launch_bag_pool(orx_ctx* ctx, const BagArgs& a);
+int orx_launch_bag_scale_rows(orx_ctx* ctx, float* g, const float* coef, int64_t B, int D, int gs);           // g[i][0 .. D) *= coef[i]
+int orx_launch_bag_owner_pairs(orx_ctx* ctx, const uint2* sorted, const int32_t* owner, int64_t n, int64_t B, uint2* out);   // (row, position) -> (row, owner[position])
+
 // kernels_inbatch.hip (orx_inbatch_step / orx_inbatch_loss): one step of the in-batch softmax.  Bp = B rounded up to 64, Dp = D
 // rounded up to 16; every [Bp] / [Bp][Dp] / [nch][..] array is scratch carved from the context's d_tmp
 struct InBatchArgs {

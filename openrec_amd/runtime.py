@@ -2184,3 +2184,247 @@ class VBPR:
                                                     self._W._h))
             self._fresh = True
         return self._W
+
+
+# ---- history-pooled sequence recommender (orx_bag_pool / orx_seqrec_step / orx_seqrec_loss) -----------------------------------
+_SEQ_ROLES = {"history": _ffi.ORX_TRAIN_USER, "item": _ffi.ORX_TRAIN_ITEM, "bias": _ffi.ORX_TRAIN_BIAS}
+
+
+def _pool_arg(what, pool):
+    """pool: "mean" | "sum" | ("fixed", denom) -> (orx_bag_mode, denom)"""
+    if isinstance(pool, str):
+        if pool == "mean":
+            return _ffi.ORX_BAG_MEAN, 1.0
+        if pool == "sum":
+            return _ffi.ORX_BAG_FIXED, 1.0
+    elif isinstance(pool, (tuple, list)) and len(pool) == 2 and pool[0] == "fixed":
+        try:
+            denom = float(pool[1])
+        except (TypeError, ValueError):
+            denom = float("nan")
+        if not (np.isfinite(denom) and denom > 0.0):
+            raise ValueError(f"{what}: pool = ('fixed', denom) needs a finite denom > 0 (got {pool[1]!r})")
+        return _ffi.ORX_BAG_FIXED, denom
+    raise ValueError(f"{what}: unknown pool {pool!r}; expected 'mean', 'sum' or ('fixed', denom)")
+
+
+def bags_to_ragged(seq, seq_len):
+    """The padded pair of the reference's samplers -- seq [B, L] item ids, seq_len [B] -- as ragged lists (ptr int32 [B + 1],
+    items int32 [n]): bag i is seq[i, :seq_len[i]].  Positions t >= seq_len[i] are never read, whatever they hold.  NumPy in,
+    NumPy out; torch device tensors in, device tensors out (one host synchronisation: n is a data-dependent size)."""
+    what = "bags_to_ragged"
+    if _is_device_tensor(seq) or _is_device_tensor(seq_len):
+        import torch
+        if not (_is_device_tensor(seq) and _is_device_tensor(seq_len)):
+            raise ValueError(f"{what}: seq and seq_len must both be on the host or both on the device")
+        if seq.dim() != 2 or seq_len.dim() != 1 or seq_len.shape[0] != seq.shape[0]:
+            raise ValueError(f"{what}: seq {tuple(seq.shape)} and seq_len {tuple(seq_len.shape)}; expected [B, L] and [B]")
+        L = seq.shape[1]
+        ln = seq_len.to(torch.int64).clamp(0, L)
+        mask = torch.arange(L, device=seq.device)[None, :] < ln[:, None]
+        items = seq[mask].to(torch.int32).contiguous()
+        ptr = torch.zeros(seq.shape[0] + 1, dtype=torch.int64, device=seq.device)
+        ptr[1:] = torch.cumsum(ln, 0)
+        return ptr.to(torch.int32).contiguous(), items
+    seq = np.asarray(_host_array(seq))
+    ln = np.asarray(_host_array(seq_len)).astype(np.int64).reshape(-1)
+    if seq.ndim != 2 or ln.shape[0] != seq.shape[0]:
+        raise ValueError(f"{what}: seq {seq.shape} and seq_len {ln.shape}; expected [B, L] and [B]")
+    L = seq.shape[1]
+    if ln.size and (ln.min() < 0 or ln.max() > L):
+        raise ValueError(f"{what}: seq_len outside [0, {L}]")
+    if ln.sum() >= 2 ** 31:
+        raise ValueError(f"{what}: {int(ln.sum())} list entries; n must be below 2^31")
+    mask = np.arange(L)[None, :] < ln[:, None]
+    items = np.ascontiguousarray(seq[mask], dtype=np.int32)
+    ptr = np.zeros(seq.shape[0] + 1, np.int32)
+    ptr[1:] = np.cumsum(ln)
+    return ptr, items
+
+
+def _host_array(x):
+    return x.numpy() if hasattr(x, "numpy") and not isinstance(x, np.ndarray) else x
+
+
+def _bags_arg(what, bags):
+    """bags: (ptr [B + 1], items [n]) -- ragged, no host synchronisation wherever it lives -- or the padded pair (seq [B, L],
+    seq_len [B]), converted here (padded input on the device costs one host synchronisation).
+    -> (ptr pointer, items pointer, B, n, on_device, keepalive); a host ptr that breaks the contract is a ValueError here"""
+    if not isinstance(bags, (tuple, list)) or len(bags) != 2:
+        raise ValueError(f"{what}: bags must be (ptr, items) or the padded pair (seq [B, L], seq_len [B])")
+    first, second = bags
+    shape = tuple(getattr(first, "shape", ())) if not isinstance(first, DevicePtr) else ()
+    if len(shape) == 2:
+        first, second = bags_to_ragged(first, second)
+    pp, npn, dp, k0 = _ids_arg(first)
+    pi, n, di, k1 = _ids_arg(second)
+    if dp != di:
+        raise ValueError(f"{what}: bags must be all on the host or all on the device")
+    if npn < 1:
+        raise ValueError(f"{what}: bag offsets need B + 1 entries (got {npn})")
+    B = npn - 1
+    if n >= 2 ** 31:
+        raise ValueError(f"{what}: {n} list entries; n must be below 2^31")
+    if not dp:
+        ptr = k0
+        if ptr[0] != 0 or (B and (np.diff(ptr) < 0).any()) or ptr[B] != n:
+            raise ValueError(f"{what}: bag offsets must start at 0, never decrease and end at n = {n} "
+                             f"(got ptr[0] = {int(ptr[0])}, ptr[B] = {int(ptr[B])}"
+                             f"{', decreasing' if B and (np.diff(ptr) < 0).any() else ''})")
+    return pp, pi, B, n, dp, (k0, k1, first, second)
+
+
+def _seqrec_check_tables(what, H, V, b):
+    if H is V:
+        raise ValueError(f"{what}: the history table and the item table are the same table (tied tables are not offered)")
+    if H.ctx is not V.ctx or (b is not None and b.ctx is not H.ctx):
+        raise ValueError(f"{what}: the tables live on different contexts")
+    if (H.rows, H.dim) != (V.rows, V.dim):
+        raise ValueError(f"{what}: history table [{H.rows}, {H.dim}] and item table [{V.rows}, {V.dim}] differ in shape")
+    if H.dim > 256:
+        raise ValueError(f"{what}: dim {H.dim} above 256")
+    if b is not None and (b.rows, b.dim) != (V.rows, 1):
+        raise ValueError(f"{what}: bias must be [{V.rows}, 1], got [{b.rows}, {b.dim}]")
+
+
+def bag_pool(H, bags, out, pool="mean", rows=None):
+    """out[row0 + i] = c_i * sum of H[items of bag i] in list order (orx_bag_pool): an EmbeddingBag over per-call ragged lists.
+    bags: (ptr, items) or the padded pair (seq, seq_len) -- see _bags_arg; pool: "mean" (c_i = 1 / len_i), "sum", or
+    ("fixed", denom) (c_i = 1 / denom).  rows: (row0, B) of `out` to write (None: (0, B)); `out` is another Table of H's dim and
+    nothing else of it is touched.  An empty bag pools to +0.  Bad arguments raise ValueError before the library is called; an id
+    outside H raises IndexError (device lists: at the context's next check_index_error)."""
+    what = "bag_pool"
+    mode, denom = _pool_arg(what, pool)
+    if out is H:
+        raise ValueError(f"{what}: the output is the table that is pooled")
+    if out.dim != H.dim:
+        raise ValueError(f"{what}: output dim {out.dim} != table dim {H.dim}")
+    if H.dim > 256:
+        raise ValueError(f"{what}: dim {H.dim} above 256")
+    pp, pi, B, n, dev, keep = _bags_arg(what, bags)
+    row0 = 0
+    if rows is not None:
+        row0 = int(rows[0])
+        if int(rows[1]) != B:
+            raise ValueError(f"{what}: rows = {tuple(rows)} for {B} bags")
+    if row0 < 0 or row0 + B > out.rows:
+        raise ValueError(f"{what}: rows [{row0}, {row0 + B}) outside the {out.rows} output rows")
+    H.ctx.after_torch(*keep[2:])
+    H._sync_pending(); out._sync_pending()
+    check(H.ctx._lib.orx_bag_pool(H.ctx._h, H._h, pp, pi, B, n, mode, denom, out._h, row0, _ffi.ORX_IDS_DEVICE if dev else 0))
+    return out
+
+
+class SeqRec:
+    """A recommender without a user table: the user vector is pooled from the history table's rows of the items the user just
+    interacted with,
+        q = pool(H[history]);   s(q, i) = q . V[i] + b[i]
+    (the depth-0 YouTube retrieval tower, FISM, item2vec).  H, V [items, D] are two Tables (never the same one), b [items, 1] or
+    None.  pool: "mean", "sum" or ("fixed", denom).  `step` trains on one positive against N negatives per history
+    (rt.multineg_step's objective with the user row replaced by q); `user_table(bags)` gives the pooled rows as a Table that
+    recommend_topk, rank_metrics_matrixfree, score_candidates and the samplers take with V and b as they stand, uid = the row
+    number -- so a user never trained on is served from a history alone."""
+
+    def __init__(self, H, V, b=None, pool="mean"):
+        what = "SeqRec"
+        _seqrec_check_tables(what, H, V, b)
+        self._mode, self._denom = _pool_arg(what, pool)
+        self.H, self.V, self.b, self.ctx, self.pool = H, V, b, H.ctx, pool
+        self._Q = None
+
+    def _train(self, what, train):
+        if train is None:
+            return 0
+        roles = [train] if isinstance(train, str) else list(train)
+        unknown = [r for r in roles if r not in _SEQ_ROLES]
+        if unknown:
+            raise ValueError(f"{what}: train: unknown table name(s) {unknown!r}; expected a subset of {sorted(_SEQ_ROLES)}")
+        if not roles:
+            raise ValueError(f"{what}: train: empty set (no table would be trained); pass None to train every table")
+        if "bias" in roles and self.b is None:
+            raise ValueError(f'{what}: train: "bias" named, but the model has no item-bias table (bias=None)')
+        mask = 0
+        for r in roles:
+            mask |= _SEQ_ROLES[r]
+        return mask
+
+    def _args(self, what, loss, bags, pid, nid, weights, neg_offset):
+        if loss not in _MN_KIND:
+            raise ValueError(f"{what}: unknown loss {loss!r}; expected one of {sorted(_MN_KIND)}")
+        shape = tuple(getattr(nid, "shape", ()))
+        if isinstance(nid, DevicePtr) or len(shape) != 2:
+            raise ValueError(f"{what}: nid must be an array shaped [B, N] (N is taken from its last axis)")
+        N = int(shape[-1])
+        if not 1 <= N <= 64:
+            raise ValueError(f"{what}: N = {N} negatives per positive; N must be in [1, 64]")
+        pp, pi, B, n, dev, keep = _bags_arg(what, bags)
+        ppid, npid, dpid, k1 = _ids_arg(pid)
+        pnid, nnid, dnid, k2 = _ids_arg(nid)
+        if not (dev == dpid == dnid):
+            raise ValueError(f"{what}: bags and ids must be all on the host or all on the device")
+        if npid != B or nnid != B * N:
+            raise ValueError(f"{what}: {B} bags, {npid} positive ids and {nnid} negative ids for N = {N} "
+                             "(one positive per bag, nid N times as long)")
+        if B * (1 + N) >= 2 ** 31:
+            raise ValueError(f"{what}: B * (1 + N) = {B * (1 + N)} must be below 2^31")
+        pw = po = None
+        keep = [keep, k1, k2]
+        if weights is not None:
+            pw, kw = _weights_arg(weights, dev, B, what)
+            keep.append(kw)
+        if neg_offset is not None:
+            po, ko = _offsets_arg(what, "neg_offset", neg_offset, dev, nnid, "nid")
+            keep.append(ko)
+        self.ctx.after_torch(*keep[0][2:], pid, nid, weights, neg_offset)
+        for t in (self.H, self.V, self.b):
+            if t is not None:
+                t._sync_pending()
+        return _MN_KIND[loss], N, B, n, dev, (pp, pi, ppid, pnid, pw, po), keep
+
+    def step(self, opt, bags, pid, nid, loss="softmax", weights=None, neg_offset=None, l2_reg=0.0, train=None, want_loss=True):
+        """One train step (orx_seqrec_step) on B histories: bag i against its positive pid[i] and the N negatives nid[i]
+        ([B, N], N in 1 .. 64).  loss: "softmax" | "logsig"; weights [B]; neg_offset [B, N]; all live where the bags live.
+        J = loss + l2_reg * l2_loss, the l2 term on the POOLED vector and the looked-up item rows.  train: None, or a subset of
+        ("history", "item", "bias") -- every other table is read, never written.  -> (loss[1], l2[1]) as numpy float32, l2 the
+        unscaled l2_loss, when want_loss, else None (ragged lists on the device: no host synchronisation).  Bad arguments raise
+        ValueError before the library is called; a malformed device list or an id outside its table IndexError."""
+        what = "SeqRec.step"
+        mask = self._train(what, train)
+        l2c = float(l2_reg)
+        if not (np.isfinite(l2c) and l2c >= 0.0):
+            raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+        kind, N, B, n, dev, ptrs, keep = self._args(what, loss, bags, pid, nid, weights, neg_offset)
+        out, lp, l2p = _loss_outputs(1, want_loss)
+        check(self.ctx._lib.orx_seqrec_step(self.ctx._h, kind, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, N,
+                                            self._mode, self._denom, l2c, mask, _ffi.ORX_IDS_DEVICE if dev else 0, lp, l2p))
+        _keep_tables(opt, (self.H, self.V, self.b))
+        return out
+
+    def loss(self, bags, pid, nid, loss="softmax", weights=None, neg_offset=None):
+        """forward only: (loss, l2_loss) of one batch -- the step's own numbers bit for bit on the same tables; no table changes"""
+        kind, N, B, n, dev, ptrs, keep = self._args("SeqRec.loss", loss, bags, pid, nid, weights, neg_offset)
+        out = np.empty(1, np.float32), np.empty(1, np.float32)
+        check(self.ctx._lib.orx_seqrec_loss(self.ctx._h, kind, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, N, self._mode,
+                                            self._denom, _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
+        return float(out[0][0]), float(out[1][0])
+
+    def user_table(self, bags, out=None):
+        """-> a Table [B, D] of the pooled rows q_i of `bags` (out: a Table of that shape to write; None: one owned by this
+        object, valid until the next call with another B).  With (V, b) it goes wherever a user table goes, uid = the row number."""
+        what = "SeqRec.user_table"
+        pp, pi, B, n, dev, keep = _bags_arg(what, bags)
+        if B < 1:
+            raise ValueError(f"{what}: no bags")
+        if out is None:
+            if self._Q is None or self._Q.rows != B:
+                self._Q = Table(B, self.H.dim, self.ctx)
+            out = self._Q
+        elif (out.rows, out.dim) != (B, self.H.dim):
+            raise ValueError(f"{what}: out is [{out.rows}, {out.dim}] for {B} bags of dim {self.H.dim}")
+        return bag_pool(self.H, keep[2:], out, self.pool)           # (the ragged lists: a padded pair is converted once)
+
+    def recommend(self, bags, k, excl=None):
+        """the k best items for each history -> (item ids int32 [B, k], scores float32 [B, k]): recommend_topk("dot", ...) on
+        user_table(bags); excl: a SparseMask or a dense bool mask [B, items] of items never returned (the history itself, say)"""
+        Q = self.user_table(bags)
+        return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl)

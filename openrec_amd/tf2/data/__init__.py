@@ -1,1 +1,2 @@
 from .dataset import Dataset, InteractionIndex  # noqa: F401
+from .temporal import temporal_batches, temporal_evaluation  # noqa: F401

@@ -1,0 +1,103 @@
+"""VanillaYouTubeRec (the reference's tf1/recommenders/vanilla_youtube_rec.py with tf1/modules/interactions/mlp_softmax.py): the
+user vector is pooled from the embeddings of the items the user just interacted with, and items are scored by a dot product
+plus a bias (rt.SeqRec),
+    q = pool(H[seq_item_id[:seq_len]]);   s(q, i) = q . V[i] + b[i].
+There is no user table: a history never trained on is served like any other.  Three deviations from the reference:
+  * no hidden layer -- the reference puts Dense(dim_item_embed) layers (and dropout) between the pooled vector and the softmax;
+    this is the depth-0 tower, the pooled vector itself meets the item table;
+  * a sampled softmax (or the log-sigmoid pair loss) over the label and N negatives the caller draws, instead of the full
+    softmax over all items;
+  * the l2 term sits on the POOLED vector and the looked-up rows of the item table; the reference's l2_reg_embed sits on every
+    looked-up row of the sequence embedding.
+The default pooling divides by max_seq_len, which is the reference's reduce_mean over the zero-masked padded axis;
+pool="mean" divides by the history's own length.  Training goes through `train_steps` (no tape); `inference`, `recommend`,
+`score` and `evaluate` take histories where the other recommenders take user ids and run on (pooled rows, V, b) through the base
+class's paths."""
+import numpy as np
+
+from ._base import Recommender, _ids
+from ... import runtime as rt
+
+
+class VanillaYouTubeRec(Recommender):
+
+    def __init__(self, dim_item_embed, max_seq_len, total_items, l2_reg_embed=None, use_item_bias=True, pool=None, ctx=None):
+        """pool: None -- ("fixed", max_seq_len) --, "mean", "sum" or ("fixed", denom); l2_reg_embed: the coefficient of the l2 term
+        (None: 0)"""
+        from ..modules import LatentFactor
+        what = "VanillaYouTubeRec"
+        D, L = int(dim_item_embed), int(max_seq_len)
+        if not 1 <= D <= 256:
+            raise ValueError(f"{what}: dim_item_embed = {D} outside [1, 256]")
+        if L < 1:
+            raise ValueError(f"{what}: max_seq_len = {L}; at least 1")
+        self.pool = ("fixed", L) if pool is None else pool
+        rt._pool_arg(what, self.pool)
+        self._set_l2_reg(0.0 if l2_reg_embed is None else l2_reg_embed)
+        self.max_seq_len = L
+        self.seq_item_latent_factor = LatentFactor(num_instances=total_items, dim=D, name='seq_item_latent_factor', ctx=ctx)
+        ctx = self.seq_item_latent_factor.table.ctx
+        self.item_latent_factor = LatentFactor(num_instances=total_items, dim=D, name='item_latent_factor', ctx=ctx)
+        self.item_bias = LatentFactor(num_instances=total_items, dim=1, name='item_bias', ctx=ctx) if use_item_bias else None
+        self.user_latent_factor = None          # (the base class's name for the user side: this model pools it per call)
+        self._queue = None
+        self._net = rt.SeqRec(self.seq_item_latent_factor.table, self.item_latent_factor.table,
+                              self.item_bias.table if self.item_bias is not None else None, pool=self.pool)
+        self._history = None
+
+    def _factors(self):
+        return [lf for lf in (self.seq_item_latent_factor, self.item_latent_factor, self.item_bias) if lf is not None]
+
+    def _bags(self, seq_item_id, seq_len):
+        seq, ln = _ids(seq_item_id), _ids(seq_len)
+        shape = tuple(getattr(seq, "shape", ()))
+        if len(shape) != 2 or shape[1] > self.max_seq_len:
+            raise ValueError(f"{type(self).__name__}: seq_item_id shaped {shape}; expected [B, L] with L <= max_seq_len = {self.max_seq_len}")
+        return (seq, ln)
+
+    def train_steps(self, optimizer, seq_item_id, seq_len, label, n_item_id, loss="softmax", sample_weight=None, neg_offset=None,
+                    want_loss=True, train=None):
+        """One train step in one device call (rt.SeqRec.step): histories seq_item_id [B, L] of which seq_len [B] entries count,
+        the next item label [B], negatives n_item_id [B, N].  loss: "softmax" | "logsig"; sample_weight [B]; neg_offset [B, N];
+        train: None, or a subset of ("history", "item", "bias").  The objective is loss + l2_reg_embed * l2_loss.
+        -> (loss[1], l2[1]) as float32 arrays when want_loss, else None"""
+        opt = optimizer.native(self._net.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(neg_offset) if neg_offset is not None else None
+        return self._net.step(opt, self._bags(seq_item_id, seq_len), _ids(label), _ids(n_item_id), loss=loss, weights=wts,
+                              neg_offset=off, l2_reg=self.l2_reg, train=train, want_loss=want_loss)
+
+    def loss(self, seq_item_id, seq_len, label, n_item_id, loss="softmax", sample_weight=None, neg_offset=None):
+        """the forward alone -> (loss, l2)"""
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(neg_offset) if neg_offset is not None else None
+        return self._net.loss(self._bags(seq_item_id, seq_len), _ids(label), _ids(n_item_id), loss=loss, weights=wts, neg_offset=off)
+
+    def _tables(self, flush=True):
+        """what the scoring paths see: (the pooled rows of the histories last handed over, V, b)"""
+        if self._history is None:
+            raise ValueError(f"{type(self).__name__}: no histories to score (pass seq_item_id and seq_len)")
+        return self._net.user_table(self._history), self._net.V, self._net.b
+
+    def _rows(self, seq_item_id, seq_len):
+        """the histories become the user table of the call that follows -> their row numbers, the ids that call takes"""
+        self._history = self._bags(seq_item_id, seq_len)
+        return np.arange(int(self._history[0].shape[0]), dtype=np.int32)
+
+    def inference(self, seq_item_id, seq_len):
+        """pool(H[history]) @ V^T + b -> [B, total_items]"""
+        uid = self._rows(seq_item_id, seq_len)
+        Q, V, b = self._tables()
+        return rt.score_all_items("dot", Q, V, b, uid, device=True)
+
+    def recommend(self, seq_item_id, seq_len, k, excl_mask=None):
+        """the k best items of each history -> (item ids [B, k], scores [B, k]); see Recommender.recommend"""
+        return super().recommend(self._rows(seq_item_id, seq_len), k, excl_mask)
+
+    def score(self, seq_item_id, seq_len, candidates):
+        """the scores of each history's own candidate list; see Recommender.score"""
+        return super().score(self._rows(seq_item_id, seq_len), candidates)
+
+    def evaluate(self, seq_item_id, seq_len, pos_mask, excl_mask=None, at=(100,), score_matrix=True, cand_mask=None):
+        """AUC / NDCG / Recall of each history against its positives; see Recommender.evaluate"""
+        return super().evaluate(self._rows(seq_item_id, seq_len), pos_mask, excl_mask, at, score_matrix, cand_mask)
