@@ -42,6 +42,17 @@ def _ids_arg(x):
     return a.ctypes.data, a.size, False, a
 
 
+def _label_arg(x):
+    """a float32 list -> (pointer, n, on_device, keepalive)"""
+    if _is_device_tensor(x):
+        assert str(x.dtype).endswith("float32") and x.is_contiguous()
+        return x.data_ptr(), x.numel(), True, x
+    if hasattr(x, "numpy") and not isinstance(x, np.ndarray):
+        x = x.numpy()
+    a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
+    return a.ctypes.data, a.size, False, a
+
+
 class Context:
     def __init__(self, device=0, stream=None):
         self._lib = _ffi.load()
@@ -264,38 +275,46 @@ def _keep_tables(opt, tables):
 
 
 _TRAIN_ROLES = {"user": _ffi.ORX_TRAIN_USER, "item": _ffi.ORX_TRAIN_ITEM, "bias": _ffi.ORX_TRAIN_BIAS}
+_MN_KIND = {"softmax": _ffi.ORX_MN_SOFTMAX, "logsig": _ffi.ORX_MN_LOGSIG}
 
 
-def _train_mask(train, bias):
-    """`train` of the step functions -> orx_train_mask, or None for today's full step.  An iterable of "user" / "item" /
-    "bias": the tables that receive the steps' updates; every other table is read, never written."""
+# ---- the argument layer of the train-step and forward-loss calls ---------------------------------------------------
+# Every step / loss entry point below reads its arguments through these functions, each check written once.  The order of
+# refusals is the same everywhere: `train` and the coefficients first (_mask_arg, _coef_arg, _l2_arg: no table, optimizer or
+# context is touched), then the family's own bounds and _dot_tables (shapes only), then the lists (_list_args or its parts:
+# sides, K / B / id_stride, lengths), and only then the context -- after_torch for every device buffer handed over, the
+# tables' _sync_pending where the family flushes, `_lib`.  Every refusal is a ValueError that names the call.
+def _mask_arg(what, train, roles, has_bias):
+    """`train` of a step -> the OR of the named tables' bits in `roles` (a family's role dictionary), or None for train=None:
+    every table.  A name or an iterable of names: the tables that receive the step's updates; every other table is read,
+    never written."""
     if train is None:
         return None
-    if isinstance(train, str):
-        train = (train,)
-    roles = list(train)
-    unknown = [r for r in roles if r not in _TRAIN_ROLES]
+    names = [train] if isinstance(train, str) else list(train)
+    unknown = [r for r in names if r not in roles]
     if unknown:
-        raise ValueError(f"train: unknown table name(s) {unknown!r}; expected a subset of {sorted(_TRAIN_ROLES)}")
-    if not roles:
-        raise ValueError("train: empty set (no table would be trained); pass None to train every table")
-    if "bias" in roles and bias is None:
-        raise ValueError('train: "bias" named, but the model has no item-bias table (bias=None)')
+        raise ValueError(f"{what}: train: unknown table name(s) {unknown!r}; expected a subset of {sorted(roles)}")
+    if not names:
+        raise ValueError(f"{what}: train: empty set (no table would be trained); pass None to train every table")
+    if "bias" in names and not has_bias:
+        raise ValueError(f'{what}: train: "bias" named, but the model has no item-bias table (bias=None)')
     mask = 0
-    for r in roles:
-        mask |= _TRAIN_ROLES[r]
+    for r in names:
+        mask |= roles[r]
     return mask
 
 
-def _weights_arg(weights, ids_on_device, n_ids, what):
-    """per-triplet weights -> (pointer, keepalive); they live where the ids live and are shaped like them"""
-    pw, nw, dw, kw = _label_arg(weights)
-    if dw != ids_on_device:
-        raise ValueError(f"{what}: weights on the {'device' if dw else 'host'} with ids on the {'device' if ids_on_device else 'host'} "
-                         "(the weights live where the ids live)")
-    if nw != n_ids:
-        raise ValueError(f"{what}: {nw} weights for {n_ids} ids (weights are shaped like the ids)")
-    return pw, kw
+def _train_mask(train, bias, what="step"):
+    """`train` of the user / item / bias steps -> orx_train_mask, or None for the full step"""
+    return _mask_arg(what, train, _TRAIN_ROLES, bias is not None)
+
+
+def _coef_arg(what, name, x):
+    """a coefficient of the objective (l2_reg, l2_proj) -> a float that is finite and >= 0"""
+    x = float(x)
+    if not (np.isfinite(x) and x >= 0.0):
+        raise ValueError(f"{what}: {name} must be finite and >= 0 (got {x})")
+    return x
 
 
 def _l2_arg(what, l2_reg, no_l2, default_is_one=False):
@@ -305,15 +324,64 @@ def _l2_arg(what, l2_reg, no_l2, default_is_one=False):
         if l2_reg is not None and not (default_is_one and l2_reg in (0, 0.0, 1.0)):
             raise ValueError(f"{what}: no_l2=True together with l2_reg = {l2_reg} (drop no_l2, or pass l2_reg=0.0)")
         return 0.0
-    l2c = float(1.0 if l2_reg is None else l2_reg)
-    if not (np.isfinite(l2c) and l2c >= 0.0):
-        raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
-    return l2c
+    return _coef_arg(what, "l2_reg", 1.0 if l2_reg is None else l2_reg)
 
 
-def _step_shape(what, K, B, id_stride, n_ids):
+def _negatives_arg(what, loss, nid, exact=False):
+    """the loss kind and the negatives of an N-negatives call -> (orx_multineg_kind, N); N is nid's last axis, nid shaped
+    [..., B, N] (exact: [B, N] and nothing in front)"""
+    if loss not in _MN_KIND:
+        raise ValueError(f"{what}: unknown loss {loss!r}; expected one of {sorted(_MN_KIND)}")
+    shape = tuple(getattr(nid, "shape", ()))
+    if isinstance(nid, DevicePtr) or (len(shape) != 2 if exact else len(shape) < 2):
+        raise ValueError(f"{what}: nid must be an array shaped [{'' if exact else '..., '}B, N] (N is taken from its last axis)")
+    N = int(shape[-1])
+    if not 1 <= N <= 64:
+        raise ValueError(f"{what}: N = {N} negatives per positive; N must be in [1, 64]")
+    return _MN_KIND[loss], N
+
+
+def _dot_tables(what, user_dim, item_dim, items, bias):
+    """the tables of a dot-product family (shapes only): the user side's dim is the item side's, the bias is [items, 1] or None"""
+    if user_dim != item_dim:
+        raise ValueError(f"{what}: user dim {user_dim} != item dim {item_dim} (dot scores only)")
+    if bias is not None and tuple(bias.shape) != (items, 1):
+        raise ValueError(f"{what}: bias must be [{items}, 1], got {list(bias.shape)}")
+
+
+def _id_lists(what, lists, dev=None):
+    """the id lists of a call, all on one side (dev: the side something else of the call has settled already)
+    -> (pointers, lengths, on_device, keepalives)"""
+    ptrs, ns, keep = [], [], []
+    for x in lists:
+        p, n, d, k = _ids_arg(x)
+        if dev is None:
+            dev = d
+        elif d != dev:
+            raise ValueError(f"{what}: ids must be all on the host or all on the device")
+        ptrs.append(p); ns.append(n); keep.append(k)
+    return ptrs, ns, dev, keep
+
+
+def _floats_arg(what, name, x, ids_on_device, n, like):
+    """a float32 list beside the ids (label, weights, neg_offset, item_offset; None: absent) -> (pointer, keepalive); it lives
+    where the ids live and has n elements, shaped like the list `like`"""
+    if x is None:
+        return None, None
+    p, nx, dx, k = _label_arg(x)
+    if dx != ids_on_device:
+        raise ValueError(f"{what}: {name} on the {'device' if dx else 'host'} with ids on the {'device' if ids_on_device else 'host'} "
+                         f"({name} lives where the ids live)")
+    if nx != n:
+        raise ValueError(f"{what}: {nx} {name} for {n} ids ({name} is shaped like {like})")
+    return p, k
+
+
+def _step_shape(what, K, B, id_stride, n_ids, overlap=False):
     """K, B and id_stride of a K-step call over id lists of n_ids elements (B None: n_ids // K; id_stride None: B) -> the three
-    as ints and the elements a list needs"""
+    as ints and the elements a list needs.  id_stride >= B, as the C side of the dot-product families has it; overlap (the
+    pairwise and pointwise steps, whose C side takes any stride): steps may share ids, down to id_stride = 0 for one batch K
+    times, and only a stride that would step in front of the lists is refused (K = 1 never looks at it)."""
     K = int(K)
     if K < 0:
         raise ValueError(f"{what}: K = {K}")
@@ -323,8 +391,8 @@ def _step_shape(what, K, B, id_stride, n_ids):
     if id_stride is None:
         id_stride = B
     id_stride = int(id_stride)
-    if B < 0 or id_stride < B:
-        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= B >= 0)")
+    if B < 0 or (id_stride < 0 and K > 1 if overlap else id_stride < B):
+        raise ValueError(f"{what}: B = {B}, id_stride = {id_stride} (id_stride >= {'0' if overlap else 'B'}, B >= 0)")
     return K, B, id_stride, ((K - 1) * id_stride + B if K and B else 0)
 
 
@@ -336,16 +404,39 @@ def _loss_outputs(K, want_loss):
     return out, out[0].ctypes.data, out[1].ctypes.data
 
 
-def _offsets_arg(what, name, offsets, ids_on_device, n, like):
-    """an optional float list beside the ids (neg_offset, item_offset) -> (pointer, keepalive); it lives where the ids live and
-    has n elements, shaped like the id list `like`"""
-    po, no, do, ko = _label_arg(offsets)
-    if do != ids_on_device:
-        raise ValueError(f"{what}: {name} on the {'device' if do else 'host'} with ids on the {'device' if ids_on_device else 'host'} "
-                         "(the offsets live where the ids live)")
-    if no != n:
-        raise ValueError(f"{what}: {no} offsets for {n} {'negative ids' if like == 'nid' else 'ids'} ({name} is shaped like {like})")
-    return po, ko
+def _loss_pair(out):
+    """the (loss, l2) of a forward-only call, written by the library into _loss_outputs(1, True)'s arrays, as two floats"""
+    return float(out[0][0]), float(out[1][0])
+
+
+def _flags(ids_on_device, bits=0):
+    """the flag word of a call: ORX_IDS_DEVICE where the lists live on the device, OR-ed with the call's own bits"""
+    return bits | _ffi.ORX_IDS_DEVICE if ids_on_device else bits
+
+
+def _list_args(what, names, ids, floats, K=1, B=None, id_stride=None, N=1, overlap=False):
+    """The lists of a K-step call (a forward-only call: K = 1 over the whole lists).  ids: the id lists, called `names`, alike
+    in length and the last N times as long; floats: (name, list or None, index of the id list it is shaped like) triples.  All
+    live on one side, and every id list holds what K steps of B at id_stride read (overlap: as in _step_shape).
+    -> K, B, id_stride, on_device, the pointers (ids, then floats; None for an absent list), the keepalives.  The keepalives
+    are the caller's to hold until the library has returned and to hand to after_torch: device tensors are among them as they
+    came."""
+    ptrs, ns, dev, keep = _id_lists(what, ids)
+    n = ns[0]
+    K, B, id_stride, need = _step_shape(what, K, B, id_stride, n, overlap)
+    if n < need or ns[-1] != n * N or not all(m == n for m in ns[:-1]):
+        raise ValueError(f"{what}: " + ", ".join(f"{m} {name}" for name, m in zip(names, ns)) + f" ids for K = {K}, B = {B}, "
+                         f"id_stride = {id_stride} (the lists alike{f', {names[-1]} N = {N} times as long' if N != 1 else ''}, "
+                         f"at least {need} each)")
+    for name, x, like in floats:
+        p, k = _floats_arg(what, name, x, dev, ns[like], names[like])
+        ptrs.append(p); keep.append(k)
+    return K, B, id_stride, dev, ptrs, keep
+
+
+def _triplet_args(what, uid, pid, nid, weights=None, K=1, B=None, id_stride=None, overlap=False):
+    """_list_args of a call over (user, positive, negative) triplets with optional per-triplet weights"""
+    return _list_args(what, ("uid", "pid", "nid"), (uid, pid, nid), (("weights", weights, 0),), K, B, id_stride, 1, overlap)
 
 
 def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None,
@@ -357,40 +448,28 @@ def pairwise_step(model, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_s
     bit-for-bit as they are (orx_pairwise_step_subset).
     weights / l2_reg (orx_pairwise_step_weighted): the objective loss_w + l2_reg * l2_loss, where weights[i] multiplies triplet
     i's term inside BPR's mean / UCML's sum.  weights: a float32 numpy array or device tensor shaped like the ids and living where
-    they live; the returned loss is the weighted one, l2 the unscaled l2_loss.  Both None: the plain step, as ever."""
-    mask = _train_mask(train, bias)
+    they live; the returned loss is the weighted one, l2 the unscaled l2_loss.  Both None: the plain step, as ever.
+    uid / pid / nid: alike in length and on one side, each at least (K - 1) * id_stride + B long (B None: len // K; id_stride
+    None: B); K = 0 is the library's no-op.  Bad arguments raise ValueError before the library is called."""
+    what = "pairwise_step"
+    mask = _train_mask(train, bias, what)
     weighted = weights is not None or l2_reg is not None
     if weighted:
-        l2c = _l2_arg("pairwise_step", l2_reg, no_l2)
+        l2c = _l2_arg(what, l2_reg, no_l2)
+    K, B, id_stride, dev, (pu, pp, pn, pw), keep = _triplet_args(what, uid, pid, nid, weights, K, B, id_stride, True)
+    user.ctx.after_torch(*keep)
     lib = user.ctx._lib
-    pu, nu, du, k0 = _ids_arg(uid)
-    pp, npn, dp, k1 = _ids_arg(pid)
-    pn, nn, dn, k2 = _ids_arg(nid)
-    assert du == dp == dn, "ids must be all host or all device"
-    assert nu == npn == nn, "id arrays differ in length"
-    user.ctx.after_torch(uid, pid, nid)
-    if B is None:
-        B = nu // K
-    if id_stride is None:
-        id_stride = B
-    flags = ((_ffi.ORX_IDS_DEVICE if du else 0) | (_ffi.ORX_HOGWILD if hogwild else 0)
-             | (_ffi.ORX_NO_L2 if no_l2 else 0) | (_ffi.ORX_CENSOR if censor else 0))
+    flags = _flags(dev, (_ffi.ORX_HOGWILD if hogwild else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0) | (_ffi.ORX_CENSOR if censor else 0))
     mid = {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
     out, lp, l2p = _loss_outputs(K, want_loss)
+    head = (user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn)
     if weighted:
-        pw = kw = None
-        if weights is not None:
-            pw, kw = _weights_arg(weights, du, nu, "pairwise_step")
-            user.ctx.after_torch(weights)
-        check(lib.orx_pairwise_step_weighted(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn, pw,
-                                             int(K), int(B), int(id_stride), float(margin), l2c, flags & ~_ffi.ORX_NO_L2,
+        check(lib.orx_pairwise_step_weighted(*head, pw, K, B, id_stride, float(margin), l2c, flags & ~_ffi.ORX_NO_L2,
                                              mask or 0, lp, l2p))
     elif mask is None:
-        check(lib.orx_pairwise_step(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
-                                    int(K), int(B), int(id_stride), float(margin), flags, lp, l2p))
+        check(lib.orx_pairwise_step(*head, K, B, id_stride, float(margin), flags, lp, l2p))
     else:
-        check(lib.orx_pairwise_step_subset(user.ctx._h, mid, opt._h, user._h, item._h, _bias_h(bias), pu, pp, pn,
-                                           int(K), int(B), int(id_stride), float(margin), flags, mask, lp, l2p))
+        check(lib.orx_pairwise_step_subset(*head, K, B, id_stride, float(margin), flags, mask, lp, l2p))
     _keep_tables(opt, (user, item, bias))
     return out
 
@@ -403,61 +482,29 @@ def pairwise_reserve(opt, user, item, bias, K, B):
 
 def pairwise_loss(model, user, item, bias, uid, pid, nid, margin=0.5, weights=None):
     """forward only: (loss, l2_loss) of one batch; weights: per-triplet weights as in pairwise_step"""
+    what = "pairwise_loss"
+    _, B, _, dev, (pu, pp, pn, pw), keep = _triplet_args(what, uid, pid, nid, weights)
+    user.ctx.after_torch(*keep)
     lib = user.ctx._lib
-    pu, nu, du, k0 = _ids_arg(uid)
-    pp, _, dp, k1 = _ids_arg(pid)
-    pn, _, dn, k2 = _ids_arg(nid)
     mid = {"bpr": _ffi.ORX_BPR, "ucml": _ffi.ORX_UCML}[model]
-    loss = np.empty(1, np.float32)
-    l2 = np.empty(1, np.float32)
+    out, lp, l2p = _loss_outputs(1, True)
+    head = (user.ctx._h, mid, user._h, item._h, _bias_h(bias), pu, pp, pn)
     if weights is not None:
-        pw, kw = _weights_arg(weights, du, nu, "pairwise_loss")
-        user.ctx.after_torch(weights)
-        check(lib.orx_pairwise_loss_weighted(user.ctx._h, mid, user._h, item._h, _bias_h(bias), pu, pp, pn, pw, nu, float(margin),
-                                             _ffi.ORX_IDS_DEVICE if du else 0, loss.ctypes.data, l2.ctypes.data))
-        return float(loss[0]), float(l2[0])
-    check(lib.orx_pairwise_loss(user.ctx._h, mid, user._h, item._h, _bias_h(bias), pu, pp, pn, nu, float(margin),
-                                _ffi.ORX_IDS_DEVICE if du else 0, loss.ctypes.data, l2.ctypes.data))
-    return float(loss[0]), float(l2[0])
-
-
-_MN_KIND = {"softmax": _ffi.ORX_MN_SOFTMAX, "logsig": _ffi.ORX_MN_LOGSIG}
+        check(lib.orx_pairwise_loss_weighted(*head, pw, B, float(margin), _flags(dev), lp, l2p))
+    else:
+        check(lib.orx_pairwise_loss(*head, B, float(margin), _flags(dev), lp, l2p))
+    return _loss_pair(out)
 
 
 def _multineg_args(what, loss, user, item, bias, uid, pid, nid, K, B, id_stride, weights, neg_offset):
     """the checks and the pointers multineg_step and multineg_loss share; every bad argument is a ValueError raised here,
     before the library is called"""
-    if loss not in _MN_KIND:
-        raise ValueError(f"{what}: unknown loss {loss!r}; expected one of {sorted(_MN_KIND)}")
-    shape = tuple(getattr(nid, "shape", ()))
-    if isinstance(nid, DevicePtr) or len(shape) < 2:
-        raise ValueError(f"{what}: nid must be an array shaped [..., B, N] (N is taken from its last axis)")
-    N = int(shape[-1])
-    if not 1 <= N <= 64:
-        raise ValueError(f"{what}: N = {N} negatives per positive; N must be in [1, 64]")
-    if user.shape[1] != item.shape[1]:
-        raise ValueError(f"{what}: user dim {user.shape[1]} != item dim {item.shape[1]} (dot scores only)")
-    if bias is not None and tuple(bias.shape) != (item.shape[0], 1):
-        raise ValueError(f"{what}: bias must be [{item.shape[0]}, 1], got {list(bias.shape)}")
-    pu, nu, du, k0 = _ids_arg(uid)
-    pp, npn, dp, k1 = _ids_arg(pid)
-    pn, nn, dn, k2 = _ids_arg(nid)
-    if not (du == dp == dn):
-        raise ValueError(f"{what}: ids must be all on the host or all on the device")
-    K, B, id_stride, need = _step_shape(what, K, B, id_stride, nu)
-    if nu != npn or nu < need or nn != nu * N:
-        raise ValueError(f"{what}: {nu} user ids, {npn} positive ids and {nn} negative ids for K = {K}, B = {B}, "
-                         f"id_stride = {id_stride}, N = {N} (uid and pid alike, nid N times as long)")
-    pw = po = None
-    keep = [k0, k1, k2]
-    if weights is not None:
-        pw, kw = _weights_arg(weights, du, nu, what)
-        keep.append(kw)
-    if neg_offset is not None:
-        po, ko = _offsets_arg(what, "neg_offset", neg_offset, du, nn, "nid")
-        keep.append(ko)
-    user.ctx.after_torch(uid, pid, nid, weights, neg_offset)
-    return _MN_KIND[loss], N, K, B, id_stride, du, (pu, pp, pn, pw, po), keep
+    kind, N = _negatives_arg(what, loss, nid)
+    _dot_tables(what, user.shape[1], item.shape[1], item.shape[0], bias)
+    K, B, id_stride, dev, ptrs, keep = _list_args(what, ("uid", "pid", "nid"), (uid, pid, nid),
+                                                  (("weights", weights, 0), ("neg_offset", neg_offset, 2)), K, B, id_stride, N)
+    user.ctx.after_torch(*keep)
+    return kind, N, K, B, id_stride, dev, ptrs, keep
 
 
 def multineg_step(loss, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_stride=None, weights=None, neg_offset=None,
@@ -476,7 +523,7 @@ def multineg_step(loss, opt, user, item, bias, uid, pid, nid, K=1, B=None, id_st
                                                                 weights, neg_offset)
     out, lp, l2p = _loss_outputs(K, want_loss)
     check(user.ctx._lib.orx_multineg_step(user.ctx._h, kind, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, N, id_stride,
-                                          l2c, _ffi.ORX_IDS_DEVICE if dev else 0, lp, l2p))
+                                          l2c, _flags(dev), lp, l2p))
     _keep_tables(opt, (user, item, bias))
     return out
 
@@ -486,45 +533,27 @@ def multineg_loss(loss, user, item, bias, uid, pid, nid, weights=None, neg_offse
     table changes"""
     kind, N, _, B, _, dev, ptrs, keep = _multineg_args("multineg_loss", loss, user, item, bias, uid, pid, nid, 1, None, None,
                                                        weights, neg_offset)
-    out = np.empty(1, np.float32), np.empty(1, np.float32)
-    check(user.ctx._lib.orx_multineg_loss(user.ctx._h, kind, user._h, item._h, _bias_h(bias), *ptrs, B, N,
-                                          _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
-    return float(out[0][0]), float(out[1][0])
+    out, lp, l2p = _loss_outputs(1, True)
+    check(user.ctx._lib.orx_multineg_loss(user.ctx._h, kind, user._h, item._h, _bias_h(bias), *ptrs, B, N, _flags(dev), lp, l2p))
+    return _loss_pair(out)
 
 
 def _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights, item_offset, scale, chunk):
     """the checks and the pointers inbatch_step and inbatch_loss share; every bad argument is a ValueError raised here, before
     the library is called"""
-    if user.shape[1] != item.shape[1]:
-        raise ValueError(f"{what}: user dim {user.shape[1]} != item dim {item.shape[1]} (dot scores only)")
+    _dot_tables(what, user.shape[1], item.shape[1], item.shape[0], bias)
     if user.shape[1] > 256:
         raise ValueError(f"{what}: dim {user.shape[1]} above 256")
-    if bias is not None and tuple(bias.shape) != (item.shape[0], 1):
-        raise ValueError(f"{what}: bias must be [{item.shape[0]}, 1], got {list(bias.shape)}")
     scale = float(scale)
     if not (np.isfinite(scale) and scale > 0.0):
         raise ValueError(f"{what}: scale must be finite and > 0 (got {scale})")
     chunk = int(chunk)
     if chunk < 0 or chunk % 64:
         raise ValueError(f"{what}: chunk = {chunk}; 0 (the launcher's choice) or a multiple of the tile width 64")
-    pu, nu, du, k0 = _ids_arg(uid)
-    pp, npn, dp, k1 = _ids_arg(pid)
-    if du != dp:
-        raise ValueError(f"{what}: ids must be all on the host or all on the device")
-    K, B, id_stride, need = _step_shape(what, K, B, id_stride, nu)
-    if nu != npn or nu < need:
-        raise ValueError(f"{what}: {nu} user ids and {npn} positive ids for K = {K}, B = {B}, id_stride = {id_stride} "
-                         "(uid and pid alike)")
-    pw = po = None
-    keep = [k0, k1]
-    if weights is not None:
-        pw, kw = _weights_arg(weights, du, nu, what)
-        keep.append(kw)
-    if item_offset is not None:
-        po, ko = _offsets_arg(what, "item_offset", item_offset, du, nu, "pid")
-        keep.append(ko)
-    user.ctx.after_torch(uid, pid, weights, item_offset)
-    return K, B, id_stride, du, (pu, pp, pw, po), scale, chunk, keep
+    K, B, id_stride, dev, ptrs, keep = _list_args(what, ("uid", "pid"), (uid, pid),
+                                                  (("weights", weights, 0), ("item_offset", item_offset, 1)), K, B, id_stride)
+    user.ctx.after_torch(*keep)
+    return K, B, id_stride, dev, ptrs, scale, chunk, keep
 
 
 def inbatch_step(opt, user, item, bias, uid, pid, K=1, B=None, id_stride=None, weights=None, item_offset=None, scale=1.0,
@@ -542,7 +571,7 @@ def inbatch_step(opt, user, item, bias, uid, pid, K=1, B=None, id_stride=None, w
     K, B, id_stride, dev, ptrs, scale, chunk, keep = _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights,
                                                                    item_offset, scale, chunk)
     out, lp, l2p = _loss_outputs(K, want_loss)
-    flags = (_ffi.ORX_IDS_DEVICE if dev else 0) | (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0)
+    flags = _flags(dev, (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0))
     check(user.ctx._lib.orx_inbatch_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, id_stride, scale, l2c,
                                          chunk, flags, lp, l2p))
     _keep_tables(opt, (user, item, bias))
@@ -554,7 +583,7 @@ def inbatch_loss(user, item, bias, uid, pid, weights=None, item_offset=None, sca
     table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
     _, B, _, dev, ptrs, scale, chunk, keep = _inbatch_args("inbatch_loss", user, item, bias, uid, pid, 1, None, None, weights,
                                                            item_offset, scale, chunk)
-    out = np.empty(1, np.float32), np.empty(1, np.float32)
+    out, lp, l2p = _loss_outputs(1, True)
     rows = rp = None
     if per_row:
         if dev:
@@ -565,14 +594,13 @@ def inbatch_loss(user, item, bias, uid, pid, weights=None, item_offset=None, sca
         else:
             rows = np.empty(B, np.float32)
             rp = rows.ctypes.data
-    flags = (_ffi.ORX_IDS_DEVICE if dev else 0) | (_ffi.ORX_IB_MASK_HITS if mask_hits else 0)
-    check(user.ctx._lib.orx_inbatch_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, chunk, flags,
-                                         out[0].ctypes.data, out[1].ctypes.data, rp))
+    flags = _flags(dev, _ffi.ORX_IB_MASK_HITS if mask_hits else 0)
+    check(user.ctx._lib.orx_inbatch_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, chunk, flags, lp, l2p, rp))
     if not per_row:
-        return float(out[0][0]), float(out[1][0])
+        return _loss_pair(out)
     if dev:
         rows = rows.cpu().numpy()          # (the call has synchronised the context's stream for the two sums)
-    return float(out[0][0]), float(out[1][0]), rows
+    return (*_loss_pair(out), rows)
 
 
 def inbatch_geometry(B, D, chunk=0):
@@ -583,16 +611,6 @@ def inbatch_geometry(B, D, chunk=0):
     return dict(rows=int(out[0]), tile=int(out[1]), chunks=int(out[2]), dim=int(out[3]))
 
 
-def _label_arg(x):
-    if _is_device_tensor(x):
-        assert str(x.dtype).endswith("float32") and x.is_contiguous()
-        return x.data_ptr(), x.numel(), True, x
-    if hasattr(x, "numpy") and not isinstance(x, np.ndarray):
-        x = x.numpy()
-    a = np.ascontiguousarray(x, dtype=np.float32).reshape(-1)
-    return a.ctypes.data, a.size, False, a
-
-
 _POINT = {"gmf": _ffi.ORX_GMF, "wrmf": _ffi.ORX_WRMF}
 
 
@@ -600,25 +618,21 @@ def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None
                    a=1.0, b_w=1.0, hogwild=False, no_l2=False, want_loss=True, sigmoid=False, train=None, l2_reg=None):
     """K fused GMF / WRMF train steps (gmf.py:22-34, wrmf.py:21-34); sigmoid: PointwiseMSELoss(sigmoid=True)
     (pointwise_mse_loss.py:24-25; WRMF only).  train: as in pairwise_step (WRMF; GMF takes the full set only).
-    l2_reg: the objective loss + l2_reg * l2_loss (orx_pointwise_step_l2reg); the returned l2 stays the unscaled l2_loss."""
-    mask = _train_mask(train, bias)
+    l2_reg: the objective loss + l2_reg * l2_loss (orx_pointwise_step_l2reg); the returned l2 stays the unscaled l2_loss.
+    uid / iid / label (float32): alike in length and on one side, each at least (K - 1) * id_stride + B long (B None:
+    len // K; id_stride None: B); K = 0 is the library's no-op.  Bad arguments raise ValueError before the library is called."""
+    what = "pointwise_step"
+    mask = _train_mask(train, bias, what)
     if l2_reg is not None:
-        l2c = _l2_arg("pointwise_step", l2_reg, no_l2)
+        l2c = _l2_arg(what, l2_reg, no_l2)
+    K, B, id_stride, dev, (pu, pi, pl), keep = _list_args(what, ("uid", "iid"), (uid, iid), (("label", label, 0),), K, B, id_stride, 1, True)
+    user.ctx.after_torch(*keep)
     lib = user.ctx._lib
-    pu, nu, du, k0 = _ids_arg(uid)
-    pi, ni, di, k1 = _ids_arg(iid)
-    pl, nl, dl, k2 = _label_arg(label)
-    assert du == di == dl and nu == ni == nl
-    user.ctx.after_torch(uid, iid, label)
-    if B is None:
-        B = nu // K
-    if id_stride is None:
-        id_stride = B
-    flags = (_ffi.ORX_IDS_DEVICE if du else 0) | (_ffi.ORX_HOGWILD if hogwild else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0) \
-        | (_ffi.ORX_POINT_SIGMOID if sigmoid else 0)
+    flags = _flags(dev, (_ffi.ORX_HOGWILD if hogwild else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0)
+                   | (_ffi.ORX_POINT_SIGMOID if sigmoid else 0))
     out, *outs = _loss_outputs(K, want_loss)
     args = (user.ctx._h, _POINT[model], opt._h, user._h, item._h, bias._h, w._h if w is not None else None, pu, pi, pl,
-            int(K), int(B), int(id_stride), float(a), float(b_w), flags)
+            K, B, id_stride, float(a), float(b_w), flags)
     if l2_reg is not None:
         check(lib.orx_pointwise_step_l2reg(*args[:-1], l2c, flags & ~_ffi.ORX_NO_L2, mask or 0, *outs))
     elif mask is None:
@@ -630,16 +644,15 @@ def pointwise_step(model, opt, user, item, bias, w, uid, iid, label, K=1, B=None
 
 
 def pointwise_loss(model, user, item, bias, w, uid, iid, label, a=1.0, b_w=1.0, sigmoid=False):
-    lib = user.ctx._lib
-    pu, nu, du, k0 = _ids_arg(uid)
-    pi, _, di, k1 = _ids_arg(iid)
-    pl, _, dl, k2 = _label_arg(label)
-    loss = np.empty(1, np.float32)
-    l2 = np.empty(1, np.float32)
-    check(lib.orx_pointwise_loss(user.ctx._h, _POINT[model], user._h, item._h, bias._h,
-                                 w._h if w is not None else None, pu, pi, pl, nu, float(a), float(b_w),
-                                 (_ffi.ORX_IDS_DEVICE if du else 0) | (_ffi.ORX_POINT_SIGMOID if sigmoid else 0), loss.ctypes.data, l2.ctypes.data))
-    return float(loss[0]), float(l2[0])
+    """forward only: (loss, l2_loss) of one batch of pointwise_step"""
+    what = "pointwise_loss"
+    _, B, _, dev, (pu, pi, pl), keep = _list_args(what, ("uid", "iid"), (uid, iid), (("label", label, 0),))
+    user.ctx.after_torch(*keep)
+    out, lp, l2p = _loss_outputs(1, True)
+    check(user.ctx._lib.orx_pointwise_loss(user.ctx._h, _POINT[model], user._h, item._h, bias._h, w._h if w is not None else None,
+                                           pu, pi, pl, B, float(a), float(b_w),
+                                           _flags(dev, _ffi.ORX_POINT_SIGMOID if sigmoid else 0), lp, l2p))
+    return _loss_pair(out)
 
 
 class _HostView(np.lib.mixins.NDArrayOperatorsMixin):
@@ -1879,23 +1892,12 @@ class LightGCN:
             self._fresh = True
         return self.Uf, self.Vf
 
-    def _ids(self, what, uid, pid, nid):
-        pu, nu, du, k0 = _ids_arg(uid)
-        pp, npn, dp, k1 = _ids_arg(pid)
-        pn, nn, dn, k2 = _ids_arg(nid)
-        if not (du == dp == dn):
-            raise ValueError(f"{what}: ids must be all host or all device")
-        if not (nu == npn == nn):
-            raise ValueError(f"{what}: id arrays differ in length")
-        self.ctx.after_torch(uid, pid, nid)
-        return pu, pp, pn, nu, (_ffi.ORX_IDS_DEVICE if du else 0), (k0, k1, k2)
-
-    @staticmethod
-    def _l2(what, l2_reg):
-        l2_reg = float(l2_reg)
-        if not (np.isfinite(l2_reg) and l2_reg >= 0):
-            raise ValueError(f"{what}: l2_reg must be finite and >= 0, got {l2_reg!r}")
-        return l2_reg
+    def _args(self, what, uid, pid, nid):
+        """-> B, the flag word, the three pointers, the keepalives; U and V are flushed"""
+        _, B, _, dev, (pu, pp, pn, _), keep = _triplet_args(what, uid, pid, nid)
+        self.ctx.after_torch(*keep)
+        self.U._sync_pending(); self.V._sync_pending()
+        return B, _flags(dev), (pu, pp, pn), keep
 
     def step(self, opt, uid, pid, nid, l2_reg=0.0, train=None, want_loss=True):
         """One train step on the triplets (uid, pid, nid): loss = mean -log sigmoid(s_p - s_n) on the propagated rows plus
@@ -1903,13 +1905,12 @@ class LightGCN:
         None, or ("user",) / ("item",) to leave the other table bit for bit as it is).  -> (loss, l2) as floats when want_loss,
         else None (no host synchronisation with device ids).  Bit-reproducible."""
         what = "LightGCN.step"
-        mask = _train_mask(train, None)
-        l2_reg = self._l2(what, l2_reg)
-        pu, pp, pn, B, flags, keep = self._ids(what, uid, pid, nid)
-        self.U._sync_pending(); self.V._sync_pending()
+        mask = _train_mask(train, None, what)
+        l2_reg = _coef_arg(what, "l2_reg", l2_reg)
+        B, flags, ptrs, keep = self._args(what, uid, pid, nid)
         loss, l2 = ctypes.c_float(), ctypes.c_float()
         self._fresh = False
-        check(self.ctx._lib.orx_lightgcn_step(self._h, opt._h, pu, pp, pn, B, l2_reg, mask or 0, flags,
+        check(self.ctx._lib.orx_lightgcn_step(self._h, opt._h, *ptrs, B, l2_reg, mask or 0, flags,
                                               byref(loss) if want_loss else None, byref(l2) if want_loss else None))
         _keep_tables(opt, (self.U, self.V))
         if flags and want_loss:
@@ -1919,11 +1920,10 @@ class LightGCN:
     def loss(self, uid, pid, nid, l2_reg=0.0):
         """the forward alone -> (loss, l2); U and V do not change (the propagated tables are brought up to date)"""
         what = "LightGCN.loss"
-        l2_reg = self._l2(what, l2_reg)
-        pu, pp, pn, B, flags, keep = self._ids(what, uid, pid, nid)
-        self.U._sync_pending(); self.V._sync_pending()
+        l2_reg = _coef_arg(what, "l2_reg", l2_reg)
+        B, flags, ptrs, keep = self._args(what, uid, pid, nid)
         loss, l2 = ctypes.c_float(), ctypes.c_float()
-        check(self.ctx._lib.orx_lightgcn_loss(self._h, pu, pp, pn, B, l2_reg, flags, byref(loss), byref(l2)))
+        check(self.ctx._lib.orx_lightgcn_loss(self._h, *ptrs, B, l2_reg, flags, byref(loss), byref(l2)))
         if flags:
             self.ctx.check_index_error()
         self._fresh = True
@@ -2069,61 +2069,24 @@ class VBPR:
             raise ValueError(f"{what}: latent dim {V.dim}")
         if V.dim + E.dim > 256:
             raise ValueError(f"{what}: D = Dl + Dc = {V.dim} + {E.dim} above 256")
-        if U.dim != V.dim + E.dim:
+        if U.dim != V.dim + E.dim:          # (said in VBPR's own words, ahead of _dot_tables' same test)
             raise ValueError(f"{what}: user dim {U.dim} != item latent dim {V.dim} + projection width {E.dim}")
         if features.rows != V.rows:
             raise ValueError(f"{what}: {features.rows} feature rows for {V.rows} items")
-        if b is not None and tuple(b.shape) != (V.rows, 1):
-            raise ValueError(f"{what}: bias must be [{V.rows}, 1], got {list(b.shape)}")
+        _dot_tables(what, U.dim, V.dim + E.dim, V.rows, b)
         self.U, self.V, self.b, self.E, self.features, self.ctx = U, V, b, E, features, U.ctx
         self._W = None
         self._fresh = False
 
-    def _train(self, what, train):
-        if train is None:
-            return 0
-        roles = [train] if isinstance(train, str) else list(train)
-        unknown = [r for r in roles if r not in _VBPR_ROLES]
-        if unknown:
-            raise ValueError(f"{what}: train: unknown table name(s) {unknown!r}; expected a subset of {sorted(_VBPR_ROLES)}")
-        if not roles:
-            raise ValueError(f"{what}: train: empty set (no table would be trained); pass None to train every table")
-        if "bias" in roles and self.b is None:
-            raise ValueError(f'{what}: train: "bias" named, but the model has no item-bias table (bias=None)')
-        mask = 0
-        for r in roles:
-            mask |= _VBPR_ROLES[r]
-        return mask
-
     def _args(self, what, uid, pid, nid, K, B, id_stride, weights):
-        pu, nu, du, k0 = _ids_arg(uid)
-        pp, npn, dp, k1 = _ids_arg(pid)
-        pn, nn, dn, k2 = _ids_arg(nid)
-        if not (du == dp == dn):
-            raise ValueError(f"{what}: ids must be all on the host or all on the device")
-        K, B, id_stride, need = _step_shape(what, K, B, id_stride, nu)
+        K, B, id_stride, dev, ptrs, keep = _triplet_args(what, uid, pid, nid, weights, K, B, id_stride)
         if B >= 2 ** 31 - 256:
             raise ValueError(f"{what}: B = {B}; B must be below 2^31 - 256")
-        if not (nu == npn == nn) or nu < need:
-            raise ValueError(f"{what}: {nu} user ids, {npn} positive ids and {nn} negative ids for K = {K}, B = {B}, "
-                             f"id_stride = {id_stride} (the three alike)")
-        pw = None
-        keep = [k0, k1, k2]
-        if weights is not None:
-            pw, kw = _weights_arg(weights, du, nu, what)
-            keep.append(kw)
-        self.ctx.after_torch(uid, pid, nid, weights)
+        self.ctx.after_torch(*keep)
         for t in (self.U, self.V, self.b, self.E):
             if t is not None:
                 t._sync_pending()
-        return K, B, id_stride, du, (pu, pp, pn, pw), keep
-
-    @staticmethod
-    def _coef(what, name, x):
-        x = float(x)
-        if not (np.isfinite(x) and x >= 0.0):
-            raise ValueError(f"{what}: {name} must be finite and >= 0 (got {x})")
-        return x
+        return K, B, id_stride, dev, ptrs, keep
 
     def step(self, opt, uid, pid, nid, weights=None, l2_reg=0.0, l2_proj=0.0, train=None, K=1, B=None, id_stride=None,
              batch_chunk=0, want_loss=True):
@@ -2134,8 +2097,8 @@ class VBPR:
         rows, when want_loss, else None (no host synchronisation with device ids).  Bad arguments raise ValueError before the
         library is called; an id outside its table IndexError."""
         what = "VBPR.step"
-        mask = self._train(what, train)
-        l2_reg, l2_proj = self._coef(what, "l2_reg", l2_reg), self._coef(what, "l2_proj", l2_proj)
+        mask = _mask_arg(what, train, _VBPR_ROLES, self.b is not None) or 0
+        l2_reg, l2_proj = _coef_arg(what, "l2_reg", l2_reg), _coef_arg(what, "l2_proj", l2_proj)
         batch_chunk = int(batch_chunk)
         if batch_chunk < 0 or batch_chunk % 64:
             raise ValueError(f"{what}: batch_chunk = {batch_chunk}; 0 (the launcher's choice) or a positive multiple of 64")
@@ -2144,19 +2107,18 @@ class VBPR:
         self._fresh = False
         f = self.features
         check(self.ctx._lib.orx_vbpr_step(self.ctx._h, opt._h, self.U._h, self.V._h, _bias_h(self.b), self.E._h, f.device_ptr, f.rows, f.dim,
-                                          *ptrs, K, B, id_stride, l2_reg, l2_proj, batch_chunk, mask, _ffi.ORX_IDS_DEVICE if dev else 0,
-                                          lp, l2p))
+                                          *ptrs, K, B, id_stride, l2_reg, l2_proj, batch_chunk, mask, _flags(dev), lp, l2p))
         _keep_tables(opt, (self.U, self.V, self.b, self.E))
         return out
 
     def loss(self, uid, pid, nid, weights=None):
         """forward only: (loss, l2_loss) of one batch -- the step's own numbers bit for bit on the same tables; no table changes"""
         _, B, _, dev, ptrs, keep = self._args("VBPR.loss", uid, pid, nid, 1, None, None, weights)
-        out = np.empty(1, np.float32), np.empty(1, np.float32)
+        out, lp, l2p = _loss_outputs(1, True)
         f = self.features
         check(self.ctx._lib.orx_vbpr_loss(self.ctx._h, self.U._h, self.V._h, _bias_h(self.b), self.E._h, f.device_ptr, f.rows, f.dim,
-                                          *ptrs, B, _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
-        return float(out[0][0]), float(out[1][0])
+                                          *ptrs, B, _flags(dev), lp, l2p))
+        return _loss_pair(out)
 
     def invalidate(self):
         """V, E or the features were changed by anything but this object's own `step` (another train step, Table.write, a
@@ -2279,12 +2241,11 @@ def _seqrec_check_tables(what, H, V, b):
         raise ValueError(f"{what}: the history table and the item table are the same table (tied tables are not offered)")
     if H.ctx is not V.ctx or (b is not None and b.ctx is not H.ctx):
         raise ValueError(f"{what}: the tables live on different contexts")
-    if (H.rows, H.dim) != (V.rows, V.dim):
+    if (H.rows, H.dim) != (V.rows, V.dim):          # (rows too: the history table is indexed by item)
         raise ValueError(f"{what}: history table [{H.rows}, {H.dim}] and item table [{V.rows}, {V.dim}] differ in shape")
     if H.dim > 256:
         raise ValueError(f"{what}: dim {H.dim} above 256")
-    if b is not None and (b.rows, b.dim) != (V.rows, 1):
-        raise ValueError(f"{what}: bias must be [{V.rows}, 1], got [{b.rows}, {b.dim}]")
+    _dot_tables(what, H.dim, V.dim, V.rows, b)
 
 
 def bag_pool(H, bags, out, pool="mean", rows=None):
@@ -2332,54 +2293,22 @@ class SeqRec:
         self.H, self.V, self.b, self.ctx, self.pool = H, V, b, H.ctx, pool
         self._Q = None
 
-    def _train(self, what, train):
-        if train is None:
-            return 0
-        roles = [train] if isinstance(train, str) else list(train)
-        unknown = [r for r in roles if r not in _SEQ_ROLES]
-        if unknown:
-            raise ValueError(f"{what}: train: unknown table name(s) {unknown!r}; expected a subset of {sorted(_SEQ_ROLES)}")
-        if not roles:
-            raise ValueError(f"{what}: train: empty set (no table would be trained); pass None to train every table")
-        if "bias" in roles and self.b is None:
-            raise ValueError(f'{what}: train: "bias" named, but the model has no item-bias table (bias=None)')
-        mask = 0
-        for r in roles:
-            mask |= _SEQ_ROLES[r]
-        return mask
-
     def _args(self, what, loss, bags, pid, nid, weights, neg_offset):
-        if loss not in _MN_KIND:
-            raise ValueError(f"{what}: unknown loss {loss!r}; expected one of {sorted(_MN_KIND)}")
-        shape = tuple(getattr(nid, "shape", ()))
-        if isinstance(nid, DevicePtr) or len(shape) != 2:
-            raise ValueError(f"{what}: nid must be an array shaped [B, N] (N is taken from its last axis)")
-        N = int(shape[-1])
-        if not 1 <= N <= 64:
-            raise ValueError(f"{what}: N = {N} negatives per positive; N must be in [1, 64]")
-        pp, pi, B, n, dev, keep = _bags_arg(what, bags)
-        ppid, npid, dpid, k1 = _ids_arg(pid)
-        pnid, nnid, dnid, k2 = _ids_arg(nid)
-        if not (dev == dpid == dnid):
-            raise ValueError(f"{what}: bags and ids must be all on the host or all on the device")
+        kind, N = _negatives_arg(what, loss, nid, exact=True)
+        pp, pi, B, n, dev, kb = _bags_arg(what, bags)
+        (ppid, pnid), (npid, nnid), _, keep = _id_lists(what, (pid, nid), dev)          # (on the side the bags are on)
         if npid != B or nnid != B * N:
             raise ValueError(f"{what}: {B} bags, {npid} positive ids and {nnid} negative ids for N = {N} "
                              "(one positive per bag, nid N times as long)")
         if B * (1 + N) >= 2 ** 31:
             raise ValueError(f"{what}: B * (1 + N) = {B * (1 + N)} must be below 2^31")
-        pw = po = None
-        keep = [keep, k1, k2]
-        if weights is not None:
-            pw, kw = _weights_arg(weights, dev, B, what)
-            keep.append(kw)
-        if neg_offset is not None:
-            po, ko = _offsets_arg(what, "neg_offset", neg_offset, dev, nnid, "nid")
-            keep.append(ko)
-        self.ctx.after_torch(*keep[0][2:], pid, nid, weights, neg_offset)
+        pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
+        po, ko = _floats_arg(what, "neg_offset", neg_offset, dev, nnid, "nid")
+        self.ctx.after_torch(*kb, *keep, kw, ko)
         for t in (self.H, self.V, self.b):
             if t is not None:
                 t._sync_pending()
-        return _MN_KIND[loss], N, B, n, dev, (pp, pi, ppid, pnid, pw, po), keep
+        return kind, N, B, n, dev, (pp, pi, ppid, pnid, pw, po), (kb, keep, kw, ko)
 
     def step(self, opt, bags, pid, nid, loss="softmax", weights=None, neg_offset=None, l2_reg=0.0, train=None, want_loss=True):
         """One train step (orx_seqrec_step) on B histories: bag i against its positive pid[i] and the N negatives nid[i]
@@ -2389,24 +2318,22 @@ class SeqRec:
         unscaled l2_loss, when want_loss, else None (ragged lists on the device: no host synchronisation).  Bad arguments raise
         ValueError before the library is called; a malformed device list or an id outside its table IndexError."""
         what = "SeqRec.step"
-        mask = self._train(what, train)
-        l2c = float(l2_reg)
-        if not (np.isfinite(l2c) and l2c >= 0.0):
-            raise ValueError(f"{what}: l2_reg must be finite and >= 0 (got {l2c})")
+        mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
+        l2c = _coef_arg(what, "l2_reg", l2_reg)
         kind, N, B, n, dev, ptrs, keep = self._args(what, loss, bags, pid, nid, weights, neg_offset)
         out, lp, l2p = _loss_outputs(1, want_loss)
         check(self.ctx._lib.orx_seqrec_step(self.ctx._h, kind, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, N,
-                                            self._mode, self._denom, l2c, mask, _ffi.ORX_IDS_DEVICE if dev else 0, lp, l2p))
+                                            self._mode, self._denom, l2c, mask, _flags(dev), lp, l2p))
         _keep_tables(opt, (self.H, self.V, self.b))
         return out
 
     def loss(self, bags, pid, nid, loss="softmax", weights=None, neg_offset=None):
         """forward only: (loss, l2_loss) of one batch -- the step's own numbers bit for bit on the same tables; no table changes"""
         kind, N, B, n, dev, ptrs, keep = self._args("SeqRec.loss", loss, bags, pid, nid, weights, neg_offset)
-        out = np.empty(1, np.float32), np.empty(1, np.float32)
+        out, lp, l2p = _loss_outputs(1, True)
         check(self.ctx._lib.orx_seqrec_loss(self.ctx._h, kind, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, N, self._mode,
-                                            self._denom, _ffi.ORX_IDS_DEVICE if dev else 0, out[0].ctypes.data, out[1].ctypes.data))
-        return float(out[0][0]), float(out[1][0])
+                                            self._denom, _flags(dev), lp, l2p))
+        return _loss_pair(out)
 
     def user_table(self, bags, out=None):
         """-> a Table [B, D] of the pooled rows q_i of `bags` (out: a Table of that shape to write; None: one owned by this

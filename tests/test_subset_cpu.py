@@ -41,11 +41,7 @@ def test_mask_constants():
     assert vals == {"ORX_TRAIN_USER": 1, "ORX_TRAIN_ITEM": 2, "ORX_TRAIN_BIAS": 4}
 
 
-class _NoDevice:
-    """stands where a table / optimizer would: any use of it is a device call the check should have come before"""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"the runtime reached for .{name} before it refused the `train` argument")
+from runtime_standin import NoDevice as _NoDevice          # (any use of it is a device call the check should have come before)
 
 
 @pytest.mark.parametrize("train,bias,word", [(("users",), "t", "unknown"), ((), "t", "empty"), (("user", "bias"), None, "bias"), ("all", "t", "unknown")])
