@@ -1172,8 +1172,8 @@ int orx_vbpr_geometry(int64_t B, int32_t Fd, int32_t Dc, int32_t batch_chunk, in
  * as an address, a bag that holds one pools to +0 and its sample is dropped, and the context stays usable; the tables are then
  * only guaranteed to be in bounds and finite.
  * Not offered: tied tables (hist == item); per-occurrence weights (recency decay); the reference's hidden Dense(D) layer and
- * dropout; the full softmax over all items; in-batch negatives; K-step calls (a step at realistic sizes is hundreds of
- * microseconds); the sharded engines. */
+ * dropout; in-batch negatives; K-step calls (a step at realistic sizes is hundreds of microseconds); the sharded engines.
+ * (The full softmax over all items is orx_seqrec_full_step, below.) */
 enum orx_bag_mode { ORX_BAG_MEAN = 0, ORX_BAG_FIXED = 1 };
 int orx_bag_pool(orx_ctx* ctx, orx_table* H, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode,
                  float denom, orx_table* out, int64_t out_row0, int flags);
@@ -1188,6 +1188,81 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */, const int32_t* nid /* [B][N] */,
                     const float* weight /* NULL ok */, const float* neg_offset /* NULL ok */,
                     int64_t B, int64_t n, int32_t N, int mode, float denom, int flags, float* loss_out, float* l2_out);
+
+/* ---- THE FULL SOFTMAX OVER ALL ITEMS (api_fullsoftmax.hip, api_seqrec.hip, kernels_fullsoftmax.hip): one train step of a
+ * dot-product model under sparse_softmax_cross_entropy over EVERY row of the item table -- the objective of the reference's
+ * mlp_softmax / rnn_softmax interactions and of GRU4Rec / SASRec / Mult-VAE style models.  No B x NI matrix is stored.
+ * Sample i has a query vector u_i and a label item pid[i].  u_i = U[uid[i]] (orx_fullsoftmax_*: the user-table form) or the
+ * pooled q_i of bag i, pooled exactly as orx_bag_pool does (orx_seqrec_full_*: the SeqRec form; hist, item, bias, the bags, mode
+ * and denom as in the block above).  The columns are all NI rows of the item table, each once.
+ *   s_ij    = scale * (u_i . V[j] + b[j]) + off[j]        j in [0, NI);  no "+ b" with bias == NULL
+ *   lse_i   = logsumexp_j s_ij                            evaluated with the maximum subtracted: |s| of 200 stays finite
+ *   l_i     = lse_i - s_{i,pid[i]}
+ *   loss    = (1/B) sum_i w_i l_i                         w_i = weight[i], 1 when weight == NULL
+ *   l2_loss = 1/2 (sum_i |u_i|^2 + sum_i |V[pid[i]]|^2)   the 2B looked-up rows, as orx_inbatch_step: no biases, never weighted
+ *   J       = loss + l2_reg * l2_loss
+ * scale is finite and > 0.  off = item_offset[NI] is one float per ITEM (a log-prior), 0 when NULL; -inf removes the item from
+ * every row's softmax (a padding id, a retired item).  It lives where the ids live and is not validated; a label whose own offset
+ * is -inf is the caller's error.  loss_out is the loss, l2_out the UNSCALED l2_loss.
+ * Gradients, on the pre-step tables, with c_i = w_i / B, pi_ij = exp(s_ij - lse_i) and n_j = the number of live samples whose
+ * label is j:
+ *   A_i    = sum over j != pid[i] of pi_ij               (the pi themselves, never 1 - pi_label)
+ *   a_ij   = c_i pi_ij  (j != pid[i]),   a_{i,pid[i]} = -c_i A_i
+ *   g_u[i] = scale * sum_j a_ij V[j] + l2_reg u_i                       B rows
+ *   G_V[j] = scale * sum_i a_ij u_i  + l2_reg n_j V[j]                  ALL NI rows: a dense gradient
+ *   G_b[j] = scale * sum_i a_ij
+ * The apply.  User side: orx_apply_rows(user, NULL, uid, ...) in the user-table form; orx_seqrec_step's history route in the SeqRec
+ * form (occurrence e of bag i has the row c_i * g_q[i]; the n x D occurrence rows never exist).  The item table and the bias take
+ * the Keras DENSE rule of the optimizer on every row (as orx_table_apply_dense, as TensorFlow treats a Dense(total_items) kernel).
+ * Adam: item and bias are read in full, so lazily applied rows of theirs are finished before the forward and the two leave the
+ * lazy set; the user / history table stays lazy, and exactly the rows read are touched; the counter advances once per step,
+ * after the reads and before the applies.  One step per call.  loss_out == l2_out == NULL with ORX_IDS_DEVICE: no host
+ * synchronisation.  train_mask: ORX_TRAIN_USER (the user / history table) | _ITEM | _BIAS, 0 = every table given; a table outside
+ * the mask is read and never written, its optimizer slots are untouched; with neither item nor bias in the mask the item-side
+ * gradient pass is not launched.
+ * No float atomics anywhere: every sum has a fixed order that depends on (B, NI, D) and the chunking alone, so loss_out, l2_out,
+ * the row losses and all tables are bit-repeatable from run to run.  The forward-only calls give the step's loss_out / l2_out
+ * bit for bit and, if row_loss_out is not NULL, l_i of every sample ([B], where the ids live; 0 for a dropped sample).
+ * chunk_items / chunk_samples: items per chunk of the walks that own samples / samples per chunk of the walk that owns items; 0 --
+ * the launcher's own choice, a function of (B, NI, D) alone -- or a positive multiple of the tile width 64.
+ * flags: ORX_IDS_DEVICE, ORX_NO_L2 (the steps).  B == 0: ORX_OK, nothing is launched.
+ * ORX_ERR_ARG before any device work: what orx_inbatch_step and orx_seqrec_step refuse for the same arguments (dims unequal or
+ * above 256; a bias that is not [NI, 1]; scale; l2_reg; ORX_NO_L2 with l2_reg != 0; ORX_HOGWILD, ORX_CENSOR; another context; a
+ * bad host bag_ptr; hist == item; what orx_apply_rows refuses); a chunk argument that is negative or no multiple of 64, or so
+ * small that a walk would have more than 65535 chunks; B or NI outside 31 bits; a train mask with unknown bits, or
+ * ORX_TRAIN_BIAS without a bias.
+ * An id outside its table (uid, pid, an id in a bag) or a malformed device bag_ptr: ORX_ERR_INDEX, reported as orx_inbatch_step /
+ * orx_seqrec_step report it.  The id is never an address; its sample has c_i = 0 and contributes no loss, no l2, no gradient and
+ * no n_j; the context stays usable.
+ *   orx_fullsoftmax_geometry   no device: out = { own rows per workgroup, rows per tile, item chunks, sample chunks, padded dim,
+ *                              scratch bytes of a step of the user-table form with every table trained }
+ * Not offered: hidden layers or dropout between the query and the item table; K-step calls; UCML / L2 scoring; hit masking (every
+ * item is one column); a sampled or sharded item axis. */
+int orx_fullsoftmax_step(orx_ctx* ctx, orx_opt* opt,
+                         orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                         const int32_t* uid, const int32_t* pid,
+                         const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                         int64_t B, float scale, float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,
+                         float* loss_out, float* l2_out);
+int orx_fullsoftmax_loss(orx_ctx* ctx,
+                         orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                         const int32_t* uid, const int32_t* pid,
+                         const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                         int64_t B, float scale, int32_t chunk_items, int flags,
+                         float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+int orx_fullsoftmax_geometry(int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, int64_t out[6]);
+int orx_seqrec_full_step(orx_ctx* ctx, orx_opt* opt,
+                         orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                         const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */,
+                         const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                         int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
+                         int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_seqrec_full_loss(orx_ctx* ctx,
+                         orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                         const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */,
+                         const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                         int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                         float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
 
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,

@@ -118,6 +118,14 @@ SIGNATURES = {
                                 c_float, c_int, c_int, _fp, _fp]),
     "orx_seqrec_loss": (c_int, [_p, c_int, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int32, c_int, c_float,
                                 c_int, _fp, _fp]),
+    "orx_fullsoftmax_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _fp, _fp, c_int64, c_float, c_float, c_int32, c_int32, c_int, c_int,
+                                     _fp, _fp]),
+    "orx_fullsoftmax_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _fp, _fp, c_int64, c_float, c_int32, c_int, _fp, _fp, _fp]),
+    "orx_fullsoftmax_geometry": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "orx_seqrec_full_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int, c_float, c_float, c_float,
+                                     c_int32, c_int32, c_int, c_int, _fp, _fp]),
+    "orx_seqrec_full_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int, c_float, c_float, c_int32, c_int,
+                                     _fp, _fp, _fp]),
     "orx_lightgcn_create": (c_int, [_p, _p, _p, _p, _ip, _p, _ip, _fp, _fp, c_int64, c_int64, c_int32, _fp, _pp]),
     "orx_lightgcn_destroy": (c_int, [_p]),
     "orx_lightgcn_tables": (c_int, [_p, _pp, _pp]),

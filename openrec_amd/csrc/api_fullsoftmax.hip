@@ -1,0 +1,188 @@
+// C-ABI entry points of the softmax over all items with a user table: orx_fullsoftmax_step, orx_fullsoftmax_loss and
+// orx_fullsoftmax_geometry (include/openrec_hip.h has the semantics, kernels_fullsoftmax.hip the kernels; the SeqRec form,
+// orx_seqrec_full_step / orx_seqrec_full_loss, is in api_seqrec.hip and shares the checks and the scratch layout below).
+//
+// Per step: the item table and the bias are read in full, so a lazily applied Adam on them is finished first and they leave the
+// lazy set; the user rows are touched; the forward (prepare, item copy, LSE pass, finalize), the gradient passes (a walk and a
+// finishing pass per side), [Adam: the counter advances], then orx_apply_rows of the user table with uid and the DENSE rule of the
+// optimizer on the item table and the bias (orx_table_apply_dense_at: every row has a gradient).  No kernel of the forward or the
+// gradient passes writes a table, so every gradient is taken on the pre-step tables.  The scratch of a step --
+// O((B nci + NI ncs) Dp) floats, no B x NI buffer -- is carved from the context's grow-only d_tmp and reused by every step.
+#include <cmath>
+#include <cstring>
+
+#include "orx_graph.h"
+#include "orx_internal.h"
+
+namespace {
+
+constexpr int FS_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_HOGWILD | ORX_CENSOR;      // (the last two are named to be refused by name)
+
+}  // namespace
+
+int orx_fullsoftmax_check(const char* fn, int64_t B, int64_t NI, int32_t D, float scale, int32_t chunk_items, int32_t chunk_samples) {
+    ORX_ARG(D >= 1 && D <= 256, "%s: dim %d outside [1, 256]", fn, D);
+    ORX_ARG(std::isfinite(scale) && scale > 0.f, "%s: scale must be finite and > 0 (got %g)", fn, (double)scale);
+    ORX_ARG(chunk_items >= 0 && chunk_items % 64 == 0, "%s: chunk_items must be 0 or a positive multiple of the tile width 64 (got %d)", fn, chunk_items);
+    ORX_ARG(chunk_samples >= 0 && chunk_samples % 64 == 0, "%s: chunk_samples must be 0 or a positive multiple of the tile width 64 (got %d)", fn, chunk_samples);
+    ORX_ARG(B >= 0 && B <= 0x7fffff00LL, "%s: B = %lld (B must fit 31 bits)", fn, (long long)B);
+    ORX_ARG(NI >= 1 && NI <= 0x7fffff00LL, "%s: %lld items (the item count must fit 31 bits)", fn, (long long)NI);
+    FullSoftmaxPlan p;
+    orx_fullsoftmax_plan(B, NI, D, chunk_items, chunk_samples, &p);
+    ORX_ARG(p.nci <= 65535 && p.ncs <= 65535, "%s: %lld item chunks and %lld sample chunks (at most 65535 each: raise the chunk size)", fn,
+            (long long)p.nci, (long long)p.ncs);
+    ORX_ARG(p.NIp * p.Dp < 0xffffff00LL, "%s: %lld items of padded dim %lld: the padded copy of the item table is indexed by 32 bits", fn,
+            (long long)NI, (long long)p.Dp);
+    return ORX_OK;
+}
+
+void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, bool grads, bool query_side,
+                            bool item_side, bool host_off, FullSoftmaxLayout* l) {
+    memset(l, 0, sizeof(*l));
+    FullSoftmaxPlan& p = l->plan;
+    orx_fullsoftmax_plan(B, NI, D, chunk_items, chunk_samples, &p);
+    const int gs = (D + 1 + 3) & ~3;
+    const size_t row = (size_t)p.Bp * sizeof(float), rows = (size_t)p.Bp * p.Dp * sizeof(float);
+    const size_t irow = (size_t)p.NIp * sizeof(float), irows = (size_t)p.NIp * p.Dp * sizeof(float);
+    l->xq = cv->take(rows); l->xv = cv->take(irows);
+    l->key = cv->take(row); l->cw = cv->take(row); l->sq = cv->take(row);
+    l->ib = cv->take(irow); l->io = cv->take(irow);
+    l->pm = cv->take(row * p.nci); l->pe = cv->take(row * p.nci); l->psd = cv->take(row * p.nci);
+    l->rmax = cv->take(row); l->cn = cv->take(row); l->dcoef = cv->take(row); l->rowloss = cv->take(row);
+    l->off = host_off ? cv->take((size_t)NI * sizeof(float)) : 0;
+    l->host_off = host_off;
+    if (grads && query_side) { l->gpq = cv->take(rows * p.nci); l->gu = cv->take((size_t)B * gs * sizeof(float)); }
+    if (grads && item_side) {
+        l->gpv = cv->take(irows * p.ncs); l->bpart = cv->take(irow * p.ncs); l->npart = cv->take(irow * p.ncs);
+        l->GV = cv->take((size_t)NI * D * sizeof(float)); l->Gb = cv->take((size_t)NI * sizeof(float));
+    }
+}
+
+int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q, int64_t NQ, orx_table* V, orx_table* b, const float* item_offset,
+                         int64_t B, float scale, float l2w, FullSoftmaxArgs* out) {
+    FullSoftmaxArgs a;
+    memset(&a, 0, sizeof(a));
+    const FullSoftmaxPlan& p = l.plan;
+    a.Q = Q; a.V = V->w; a.b = b ? b->w : nullptr;
+    a.B = B; a.Bp = p.Bp; a.NQ = NQ; a.NI = V->rows; a.NIp = p.NIp;
+    a.D = V->dim; a.Dp = (int)p.Dp; a.gs = (a.D + 1 + 3) & ~3;
+    a.nci = (int)p.nci; a.tpi = (int)p.tpi; a.ncs = (int)p.ncs; a.tps = (int)p.tps;
+    a.scale = scale; a.invB = 1.0f / (float)B; a.l2w = l2w; a.err = c->d_err;
+    char* base = reinterpret_cast<char*>(c->d_tmp);
+    auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
+    a.xq = f(l.xq); a.xv = f(l.xv);
+    a.key = reinterpret_cast<int32_t*>(base + l.key); a.cw = f(l.cw); a.sq = f(l.sq); a.ib = f(l.ib); a.io = f(l.io);
+    a.pm = f(l.pm); a.pe = f(l.pe); a.psd = f(l.psd); a.rmax = f(l.rmax); a.cn = f(l.cn); a.dcoef = f(l.dcoef); a.rowloss = f(l.rowloss);
+    a.gpq = f(l.gpq); a.gu = f(l.gu);
+    a.gpv = f(l.gpv); a.bpart = f(l.bpart); a.npart = reinterpret_cast<int32_t*>(base + l.npart); a.GV = f(l.GV); a.Gb = f(l.Gb);
+    a.off = item_offset;
+    if (item_offset && l.host_off) {          // one float per ITEM: it lives where the ids live, and is not among the per-sample lists
+        ORX_HIP(hipMemcpyAsync(f(l.off), item_offset, (size_t)a.NI * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        a.off = f(l.off);
+    }
+    *out = a;
+    return ORX_OK;
+}
+
+int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask) {
+    const int every = ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS;
+    ORX_ARG((*train_mask & ~every) == 0, "%s: train mask 0x%x has bits outside ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS", fn, *train_mask);
+    ORX_ARG(b != nullptr || !(*train_mask & ORX_TRAIN_BIAS), "%s: ORX_TRAIN_BIAS without a bias table (bias is NULL)", fn);
+    if (*train_mask == 0) *train_mask = ORX_TRAIN_USER | ORX_TRAIN_ITEM | (b ? ORX_TRAIN_BIAS : 0);
+    return ORX_OK;
+}
+
+int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a) {
+    if (tV) CHECK(orx_table_apply_dense_at(c, opt, V, a.GV));
+    if (tb) CHECK(orx_table_apply_dense_at(c, opt, b, a.Gb));
+    return ORX_OK;
+}
+
+extern "C" int orx_fullsoftmax_geometry(int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, int64_t out[6]) {
+    static const char* fn = "orx_fullsoftmax_geometry";
+    ORX_ARG(out, "%s: NULL out", fn);
+    CHECK(orx_fullsoftmax_check(fn, B, NI, D, 1.0f, chunk_items, chunk_samples));
+    Carve cv;
+    FullSoftmaxLayout l;
+    orx_fullsoftmax_layout(&cv, B, NI, D, chunk_items, chunk_samples, true, true, true, false, &l);
+    out[0] = 64; out[1] = 64; out[2] = l.plan.nci; out[3] = l.plan.ncs; out[4] = l.plan.Dp; out[5] = (int64_t)cv.off;
+    return ORX_OK;
+}
+
+extern "C" int orx_fullsoftmax_step(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                                    const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
+                                    int64_t B, float scale, float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,
+                                    float* loss_out, float* l2_out) {
+    static const char* fn = "orx_fullsoftmax_step";
+    CHECK(orx_check_dot_step(fn, c, opt, U, V, b, 0, 1, B, B, l2_reg, flags, FS_FLAGS));
+    CHECK(orx_fullsoftmax_check(fn, B, V->rows, U->dim, scale, chunk_items, chunk_samples));
+    CHECK(orx_fullsoftmax_mask(fn, b, &train_mask));
+    CHECK(orx_check_apply_rows_opt(opt, U, nullptr));
+    if (B == 0) return ORX_OK;
+    ORX_ARG(uid && pid, "%s: NULL id pointer", fn);
+    ORX_HIP(hipSetDevice(c->device));
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    const bool tU = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
+
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}}, {{weight, 1}}, &in));
+    Carve cv;
+    FullSoftmaxLayout lay;
+    orx_fullsoftmax_layout(&cv, B, V->rows, U->dim, chunk_items, chunk_samples, true, tU, tV || tb, host && item_offset, &lay);
+    ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
+    FullSoftmaxArgs a;
+    CHECK(orx_fullsoftmax_bind(c, lay, U->w, U->rows, V, b, item_offset, B, scale, l2_reg, &a));
+    a.qid = in.id[0]; a.pid = in.id[1]; a.wt = in.f[0];
+    // the item table and the bias are read in full: every row current, and they leave the lazy set; a user table outside the mask
+    // is finished under the old counter as well, then only read
+    orx_table* keep[3]; int n_keep = 0;
+    if (tU) keep[n_keep++] = U; else CHECK(orx_table_sync(U));
+    CHECK(orx_table_sync(V)); CHECK(orx_table_sync(b));
+    if (tV) keep[n_keep++] = V;
+    if (b && tb) keep[n_keep++] = b;
+
+    return orx_run_steps(c, 1, orx_fullsoftmax_npartials(B), flags, loss_out, l2_out, nullptr, [&](int64_t, int64_t, float* partial) -> int {
+        a.partial = partial;
+        CHECK(orx_table_touch(U, a.qid, B));
+        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        CHECK(orx_launch_fullsoftmax_grads(c, a, tU, tV || tb));
+        if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
+        if (tU) CHECK(orx_apply_rows(c, opt, U, nullptr, a.qid, B, a.gu, a.gs));
+        return orx_fullsoftmax_apply_items(c, opt, V, b, tV, tb, a);
+    });
+}
+
+extern "C" int orx_fullsoftmax_loss(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b,
+                                    const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
+                                    int64_t B, float scale, int32_t chunk_items, int flags, float* loss_out, float* l2_out, float* row_loss_out) {
+    static const char* fn = "orx_fullsoftmax_loss";
+    CHECK(orx_check_dot_model(fn, c, U, V, b, 0, flags, FS_FLAGS));
+    CHECK(orx_fullsoftmax_check(fn, B, V->rows, U->dim, scale, chunk_items, 0));
+    ORX_ARG(!(flags & ORX_NO_L2), "%s: ORX_NO_L2 belongs to the step (the forward has no objective)", fn);
+    if (B == 0) {
+        if (loss_out) *loss_out = 0.f;
+        if (l2_out) *l2_out = 0.f;
+        return ORX_OK;
+    }
+    ORX_ARG(uid && pid, "%s: NULL id pointer", fn);
+    ORX_HIP(hipSetDevice(c->device));
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}}, {{weight, 1}}, &in));
+    Carve cv;
+    FullSoftmaxLayout lay;
+    orx_fullsoftmax_layout(&cv, B, V->rows, U->dim, chunk_items, 0, false, false, false, host && item_offset, &lay);
+    ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
+    FullSoftmaxArgs a;
+    CHECK(orx_fullsoftmax_bind(c, lay, U->w, U->rows, V, b, item_offset, B, scale, 0.f, &a));
+    a.qid = in.id[0]; a.pid = in.id[1]; a.wt = in.f[0];
+    return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
+        a.partial = partial;
+        CHECK(orx_table_sync(V)); CHECK(orx_table_sync(b));
+        CHECK(orx_table_touch(U, a.qid, B));
+        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        if (row_loss_out)
+            ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+        return ORX_OK;
+    });
+}

@@ -1,5 +1,6 @@
 // C-ABI entry points of the history-pooled sequence recommender: orx_bag_pool, orx_seqrec_step and orx_seqrec_loss
-// (include/openrec_hip.h has the semantics, kernels_bag.hip the kernels).
+// (include/openrec_hip.h has the semantics, kernels_bag.hip the kernels), and at the end of the file orx_seqrec_full_step and
+// orx_seqrec_full_loss, the softmax over all items with the pooled vector as the query (kernels_fullsoftmax.hip).
 //
 // The step is orx_multineg_step with the user row replaced by a pooled vector.  Per step: bag_items is sorted by row
 // (orx_rows_sort) and the lazy history rows are touched on the sorted list; pid and nid are touched as orx_multineg_step does;
@@ -250,5 +251,134 @@ extern "C" int orx_seqrec_loss(orx_ctx* c, int kind, orx_table* hist, orx_table*
         CHECK(orx_touch_step(nullptr, item, b, nullptr, 0, a.pid, B, a.nid, B * N));
         CHECK(orx_launch_bag_pool(c, s.bag));
         return orx_launch_multineg(c, kind, false, a);
+    });
+}
+
+// ---- the softmax over ALL items with the pooled vector as the query (kernels_fullsoftmax.hip; api_fullsoftmax.hip has the
+// user-table form and the shared checks and scratch layout).  The pool writes Q [B][D] and uid'[i] = i into scratch; the kernels
+// take Q as their query table with NQ = B.  The history side is orx_seqrec_step's route; the item table and the bias are read in
+// full -- finished first, out of the lazy set -- and take the dense rule.
+namespace {
+
+struct FullScratch { BagArgs bag; FullSoftmaxArgs fs; uint2* pairs; };
+
+int make_full_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b, const int32_t* bag_ptr, const int32_t* bag_items,
+                      const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2w, int32_t chunk_items,
+                      int32_t chunk_samples, bool host, bool grads, bool query_side, bool item_side, FullScratch* out) {
+    const int D = hist->dim;
+    Carve cv;
+    const size_t o_q = cv.take((size_t)B * D * sizeof(float));
+    const size_t o_uid = cv.take((size_t)B * sizeof(int32_t));
+    const size_t o_ptr = host ? cv.take((size_t)(B + 1) * sizeof(int32_t)) : 0, o_items = host ? cv.take((size_t)n * sizeof(int32_t)) : 0;
+    size_t o_coef = 0, o_owner = 0, o_pairs = 0;
+    if (grads) { o_coef = cv.take((size_t)B * sizeof(float)); o_owner = cv.take((size_t)n * sizeof(int32_t)); o_pairs = cv.take((size_t)n * sizeof(uint2)); }
+    FullSoftmaxLayout lay;
+    orx_fullsoftmax_layout(&cv, B, item->rows, D, chunk_items, chunk_samples, grads, query_side, item_side, host && item_offset, &lay);
+    ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
+    char* base = reinterpret_cast<char*>(c->d_tmp);
+    auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
+    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
+    FullScratch s;
+    memset(&s, 0, sizeof(s));
+    s.bag = bag_args(c, hist, B, n, mode, denom);
+    CHECK(stage_bags(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
+    s.bag.out = f(o_q); s.bag.uid = i32(o_uid);
+    if (grads) { s.bag.coef = f(o_coef); s.bag.owner = i32(o_owner); s.pairs = reinterpret_cast<uint2*>(base + o_pairs); }
+    CHECK(orx_fullsoftmax_bind(c, lay, f(o_q), B, item, b, item_offset, B, scale, l2w, &s.fs));
+    s.fs.qid = i32(o_uid);
+    *out = s;
+    return ORX_OK;
+}
+
+}  // namespace
+
+extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
+                                    const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
+                                    int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
+    static const char* fn = "orx_seqrec_full_step";
+    CHECK(check_model(fn, hist, item));
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS));
+    CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, chunk_samples));
+    CHECK(orx_fullsoftmax_mask(fn, b, &train_mask));
+    CHECK(orx_check_apply_rows_opt(opt, hist, nullptr));
+    if (B == 0) return ORX_OK;
+    ORX_ARG(pid, "%s: NULL id pointer", fn);
+    ORX_HIP(hipSetDevice(c->device));
+    const bool tH = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
+
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
+    FullScratch s;
+    CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, l2_reg, chunk_items, chunk_samples, host,
+                            true, tH && n > 0, tV || tb, &s));
+    FullSoftmaxArgs& a = s.fs;
+    a.pid = in.id[0]; a.wt = in.f[0];
+    const int gs = a.gs, D = a.D;
+    // the item table and the bias are read in full: every row current, out of the lazy set; a history table outside the mask is
+    // finished under the old counter (whatever optimizer it is lazy under), then only read
+    orx_table* keep[3]; int n_keep = 0;
+    if (tH) keep[n_keep++] = hist; else CHECK(orx_table_sync(hist));
+    CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
+    if (tV) keep[n_keep++] = item;
+    if (b && tb) keep[n_keep++] = b;
+
+    const int rc = orx_run_steps(c, 1, orx_fullsoftmax_npartials(B), flags, loss_out, l2_out, nullptr, [&](int64_t, int64_t, float* partial) -> int {
+        a.partial = partial;
+        // ONE sort of bag_items serves the touch of the history rows and, its positions rewritten to their owners right after the
+        // pool (before anything else may sort), the apply -- as orx_seqrec_step has it
+        const uint2* sorted = nullptr;
+        CHECK(touch_bags(c, hist, s.bag.items, n, tH, &sorted));
+        CHECK(orx_launch_bag_pool(c, s.bag));
+        if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, s.bag.owner, n, B, s.pairs));
+        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        CHECK(orx_launch_fullsoftmax_grads(c, a, tH && n > 0, tV || tb));
+        if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
+        if (tH && n > 0) {
+            CHECK(orx_launch_bag_scale_rows(c, a.gu, s.bag.coef, B, D, gs));
+            CHECK(orx_apply_rows_sorted(c, opt, hist, s.pairs, n, a.gu, gs));
+        }
+        return orx_fullsoftmax_apply_items(c, opt, item, b, tV, tb, a);
+    });
+    CHECK(rc);
+    // device lists whose caller took the losses: the call has synchronised, so the index flag is looked at here as well
+    if (!host && (loss_out || l2_out)) return orx_check_index_error(c);
+    return ORX_OK;
+}
+
+extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
+                                    const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items,
+                                    int flags, float* loss_out, float* l2_out, float* row_loss_out) {
+    static const char* fn = "orx_seqrec_full_loss";
+    CHECK(check_model(fn, hist, item));
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR));
+    CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, 0));
+    if (B == 0) {
+        if (loss_out) *loss_out = 0.f;
+        if (l2_out) *l2_out = 0.f;
+        return ORX_OK;
+    }
+    ORX_ARG(pid, "%s: NULL id pointer", fn);
+    ORX_HIP(hipSetDevice(c->device));
+    StepInputs in;
+    CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
+    FullScratch s;
+    CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, 0.f, chunk_items, 0, host, false, false, false, &s));
+    FullSoftmaxArgs& a = s.fs;
+    a.pid = in.id[0]; a.wt = in.f[0];
+    return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
+        a.partial = partial;
+        CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
+        CHECK(touch_bags(c, hist, s.bag.items, n, false, nullptr));
+        CHECK(orx_launch_bag_pool(c, s.bag));
+        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        if (row_loss_out)
+            ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
+        return ORX_OK;
     });
 }

@@ -1033,6 +1033,47 @@ void orx_inbatch_plan(int64_t B, int32_t D, int32_t chunk_cols, int32_t out[4], 
 int orx_launch_inbatch_forward(orx_ctx* ctx, const InBatchArgs& a);     // gather, LSE pass, finalize
 int orx_launch_inbatch_grads(orx_ctx* ctx, const InBatchArgs& a);       // the two gradient walks, the finishing pass
 
+// kernels_fullsoftmax.hip (orx_fullsoftmax_step / orx_seqrec_full_step and their forwards): one step of the softmax over all
+// items.  Bp = B and NIp = NI rounded up to 64, Dp = D rounded up to 16; every [Bp] / [NIp] / [..][Dp] / [chunks][..] array is
+// scratch carved from the context's d_tmp
+struct FullSoftmaxArgs {
+    const float* Q; const float* V; const float* b;       // read only; Q [NQ][D]: the user table, or the pooled rows; b NULL: no item bias
+    const int32_t* qid; const int32_t* pid;               // this step's [B] rows of Q (SeqRec form: i, -1 for a dead bag) and labels
+    const float* wt; const float* off;                    // [B] weights (NULL: all ones), DEVICE [NI] item offsets (NULL: 0)
+    int64_t B; int64_t Bp; int64_t NQ; int64_t NI; int64_t NIp;
+    int D; int Dp; int gs; int nci; int tpi; int ncs; int tps;    // nci item chunks of tpi tiles of 64; ncs sample chunks of tps tiles
+    float scale; float invB; float l2w;
+    float* xq; float* xv;                                 // [Bp][Dp] the query rows, [NIp][Dp] the zero-padded item table
+    int32_t* key; float* cw; float* sq;                   // [Bp] pid or -1, w / B, |u|^2 + |V[pid]|^2
+    float* ib; float* io;                                 // [NIp] bias, offset (0 beyond NI)
+    float* pm; float* pe; float* psd;                     // [nci][Bp] the chunks' running maximum, sum without the label, label score
+    float* rmax; float* cn; float* dcoef; float* rowloss; // [Bp] the row maximum m_i (+inf: a dead row), c_i / tot_i, -c_i A_i, l_i
+    float* gpq; float* gpv; float* bpart; int32_t* npart; // [nci][Bp][Dp], [ncs][NIp][Dp] partial gradient tiles; [ncs][NIp] of the bias, of n_j
+    float* gu; float* GV; float* Gb;                      // [B][gs] query gradient rows; [NI][D] and [NI]: the dense gradients
+    float* partial;                                       // [orx_fullsoftmax_npartials(B)][2] loss / l2 partials of this step
+    int* err;
+};
+struct FullSoftmaxPlan { int64_t Bp, NIp, Dp, tpi, nci, tps, ncs; };
+inline int orx_fullsoftmax_npartials(int64_t B) { return (int)((((B + 63) & ~(int64_t)63) + 255) / 256); }
+void orx_fullsoftmax_plan(int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, FullSoftmaxPlan* p);
+int orx_launch_fullsoftmax_forward(orx_ctx* ctx, const FullSoftmaxArgs& a);     // prepare, item copy, LSE pass, finalize
+int orx_launch_fullsoftmax_grads(orx_ctx* ctx, const FullSoftmaxArgs& a, bool query_side, bool item_side);      // a walk and its finishing pass per side
+// what the user-table form (api_fullsoftmax.hip) and the SeqRec form (api_seqrec.hip) share: the checks of (B, NI, D, scale, the
+// chunk arguments); the scratch of a step as offsets carved behind whatever the caller has carved (host_off: a piece for a host
+// item_offset); the kernels' arguments on the context's d_tmp once it is grown (qid / pid / wt / partial are the caller's to set);
+// the train mask; the dense rule on the item table and the bias
+struct FullSoftmaxLayout {
+    FullSoftmaxPlan plan; bool host_off;
+    size_t xq, xv, key, cw, sq, ib, io, pm, pe, psd, rmax, cn, dcoef, rowloss, off, gpq, gu, gpv, bpart, npart, GV, Gb;
+};
+int orx_fullsoftmax_check(const char* fn, int64_t B, int64_t NI, int32_t D, float scale, int32_t chunk_items, int32_t chunk_samples);
+void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, bool grads, bool query_side,
+                            bool item_side, bool host_off, FullSoftmaxLayout* l);
+int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q, int64_t NQ, orx_table* V, orx_table* b, const float* item_offset,
+                         int64_t B, float scale, float l2w, FullSoftmaxArgs* out);
+int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask);
+int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a);
+
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {
     SamplerArgs s;

@@ -611,6 +611,99 @@ def inbatch_geometry(B, D, chunk=0):
     return dict(rows=int(out[0]), tile=int(out[1]), chunks=int(out[2]), dim=int(out[3]))
 
 
+# ---- the full softmax over all items (orx_fullsoftmax_step / orx_fullsoftmax_loss; SeqRec.step_full is the pooled-query form) ----
+def _chunk_arg(what, name, x):
+    """chunk_items / chunk_samples -> an int that is 0 (the launcher's choice) or a positive multiple of the tile width 64"""
+    x = int(x)
+    if x < 0 or x % 64:
+        raise ValueError(f"{what}: {name} = {x}; 0 (the launcher's choice) or a multiple of the tile width 64")
+    return x
+
+
+def _scale_arg(what, scale):
+    scale = float(scale)
+    if not (np.isfinite(scale) and scale > 0.0):
+        raise ValueError(f"{what}: scale must be finite and > 0 (got {scale})")
+    return scale
+
+
+def _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, scale, chunk_items, chunk_samples):
+    """the checks and the pointers fullsoftmax_step and fullsoftmax_loss share; every bad argument is a ValueError raised
+    here, before the library is called"""
+    _dot_tables(what, user.shape[1], item.shape[1], item.shape[0], bias)
+    if user.shape[1] > 256:
+        raise ValueError(f"{what}: dim {user.shape[1]} above 256")
+    scale = _scale_arg(what, scale)
+    ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
+    _, B, _, dev, (pu, pp, pw), keep = _list_args(what, ("uid", "pid"), (uid, pid), (("weights", weights, 0),))
+    if B >= 2 ** 31 - 256 or item.shape[0] >= 2 ** 31 - 256:
+        raise ValueError(f"{what}: B = {B} samples, {item.shape[0]} items; both must fit 31 bits")
+    po, ko = _floats_arg(what, "item_offset", item_offset, dev, item.shape[0], "the item table's rows")      # one float per ITEM
+    user.ctx.after_torch(*keep, ko)
+    return B, dev, (pu, pp, pw, po), scale, ci, cs, (keep, ko)
+
+
+def fullsoftmax_step(opt, user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None,
+                     chunk_items=0, chunk_samples=0, want_loss=True):
+    """One train step on the softmax over ALL items (orx_fullsoftmax_step): sample i's label pid[i] against every row of the
+    item table, s_ij = scale (u_i . V[j] + b[j]) + off[j] with u_i = user[uid[i]] -- the reference's
+    sparse_softmax_cross_entropy_with_logits over a Dense(total_items) -- without a B x items matrix.  bias=None: no item bias.
+    weights: per-sample weights shaped like the ids; item_offset: one float per ITEM ([items]; a log-prior, -inf removes the
+    item from every softmax); both live where the ids live.  The objective is loss + l2_reg * l2_loss, l2_loss over the 2B
+    looked-up rows.  The user table takes the sparse rule on uid, the item table and the bias the optimizer's dense rule on
+    every row.  train: None, or a subset of ("user", "item", "bias") -- every other table is read, never written.
+    chunk_items / chunk_samples: 0 for the launcher's choice, or multiples of 64.  Returns (loss[1], l2[1]) as numpy float32
+    -- l2 the unscaled l2_loss -- when want_loss, else None (device ids: no host synchronisation).  Bad arguments raise
+    ValueError before the library is called; an id outside its table IndexError."""
+    what = "fullsoftmax_step"
+    mask = _train_mask(train, bias, what) or 0
+    l2c = _coef_arg(what, "l2_reg", l2_reg)
+    B, dev, ptrs, scale, ci, cs, keep = _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, scale,
+                                                           chunk_items, chunk_samples)
+    out, lp, l2p = _loss_outputs(1, want_loss)
+    check(user.ctx._lib.orx_fullsoftmax_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, l2c, ci, cs,
+                                             mask, _flags(dev), lp, l2p))
+    _keep_tables(opt, (user, item, bias))
+    return out
+
+
+def _row_loss_buffer(ctx, B, dev, per_row):
+    """the [B] output of a forward's row losses where the ids live -> (array or tensor or None, pointer or None)"""
+    if not per_row:
+        return None, None
+    if dev:
+        import torch
+        rows = torch.empty(B, dtype=torch.float32, device=torch.device("cuda", ctx.device))
+        ctx.after_torch(rows)
+        return rows, rows.data_ptr()
+    rows = np.empty(B, np.float32)
+    return rows, rows.ctypes.data
+
+
+def fullsoftmax_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
+    """forward only: (loss, l2_loss) of one batch of fullsoftmax_step -- the step's own numbers bit for bit on the same tables;
+    no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+    what = "fullsoftmax_loss"
+    B, dev, ptrs, scale, ci, _, keep = _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, scale, chunk_items, 0)
+    out, lp, l2p = _loss_outputs(1, True)
+    rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
+    check(user.ctx._lib.orx_fullsoftmax_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, ci, _flags(dev), lp, l2p, rp))
+    if not per_row:
+        return _loss_pair(out)
+    if dev:
+        rows = rows.cpu().numpy()          # (the call has synchronised the context's stream for the two sums)
+    return (*_loss_pair(out), rows)
+
+
+def fullsoftmax_geometry(B, items, D, chunk_items=0, chunk_samples=0):
+    """what the launcher of fullsoftmax_step does for (B, items, D) and the chunk arguments: a dict of own rows per workgroup,
+    rows per tile, item chunks, sample chunks, the padded dim and the scratch bytes of a step.  No device is needed."""
+    out = (c_int64 * 6)()
+    check(_ffi.load().orx_fullsoftmax_geometry(int(B), int(items), int(D), int(chunk_items), int(chunk_samples), out))
+    return dict(rows=int(out[0]), tile=int(out[1]), item_chunks=int(out[2]), sample_chunks=int(out[3]), dim=int(out[4]),
+                scratch_bytes=int(out[5]))
+
+
 _POINT = {"gmf": _ffi.ORX_GMF, "wrmf": _ffi.ORX_WRMF}
 
 
@@ -2282,7 +2375,8 @@ class SeqRec:
         q = pool(H[history]);   s(q, i) = q . V[i] + b[i]
     (the depth-0 YouTube retrieval tower, FISM, item2vec).  H, V [items, D] are two Tables (never the same one), b [items, 1] or
     None.  pool: "mean", "sum" or ("fixed", denom).  `step` trains on one positive against N negatives per history
-    (rt.multineg_step's objective with the user row replaced by q); `user_table(bags)` gives the pooled rows as a Table that
+    (rt.multineg_step's objective with the user row replaced by q), `step_full` on the softmax over ALL items
+    (rt.fullsoftmax_step's objective, the reference's); `user_table(bags)` gives the pooled rows as a Table that
     recommend_topk, rank_metrics_matrixfree, score_candidates and the samplers take with V and b as they stand, uid = the row
     number -- so a user never trained on is served from a history alone."""
 
@@ -2334,6 +2428,54 @@ class SeqRec:
         check(self.ctx._lib.orx_seqrec_loss(self.ctx._h, kind, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, N, self._mode,
                                             self._denom, _flags(dev), lp, l2p))
         return _loss_pair(out)
+
+    def _args_full(self, what, bags, pid, weights, item_offset, scale, chunk_items, chunk_samples):
+        scale = _scale_arg(what, scale)
+        ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
+        pp, pi, B, n, dev, kb = _bags_arg(what, bags)
+        (ppid,), (npid,), _, keep = _id_lists(what, (pid,), dev)          # (on the side the bags are on)
+        if npid != B:
+            raise ValueError(f"{what}: {B} bags and {npid} label ids (one label per bag)")
+        pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
+        po, ko = _floats_arg(what, "item_offset", item_offset, dev, self.V.rows, "the item table's rows")
+        self.ctx.after_torch(*kb, *keep, kw, ko)
+        for t in (self.H, self.V, self.b):
+            if t is not None:
+                t._sync_pending()
+        return B, n, dev, (pp, pi, ppid, pw, po), scale, ci, cs, (kb, keep, kw, ko)
+
+    def step_full(self, opt, bags, pid, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None, chunk_items=0,
+                  chunk_samples=0, want_loss=True):
+        """One train step on the softmax over ALL items (orx_seqrec_full_step): bag i's pooled vector against every row of the
+        item table, the label pid[i] -- rt.fullsoftmax_step's objective with the user row replaced by q.  weights [B];
+        item_offset [items], one float per item (-inf removes an item); both live where the bags live.  The history table goes
+        `step`'s route, the item table and the bias take the optimizer's dense rule on every row.  train: None, or a subset
+        of ("history", "item", "bias").  -> (loss[1], l2[1]) as numpy float32 when want_loss, else None.  Bad arguments raise
+        ValueError before the library is called; a malformed device list or an id outside its table IndexError."""
+        what = "SeqRec.step_full"
+        mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
+        l2c = _coef_arg(what, "l2_reg", l2_reg)
+        B, n, dev, ptrs, scale, ci, cs, keep = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items, chunk_samples)
+        out, lp, l2p = _loss_outputs(1, want_loss)
+        check(self.ctx._lib.orx_seqrec_full_step(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
+                                                 self._denom, scale, l2c, ci, cs, mask, _flags(dev), lp, l2p))
+        _keep_tables(opt, (self.H, self.V, self.b))
+        return out
+
+    def loss_full(self, bags, pid, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
+        """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
+        table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
+        what = "SeqRec.loss_full"
+        B, n, dev, ptrs, scale, ci, _, keep = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items, 0)
+        out, lp, l2p = _loss_outputs(1, True)
+        rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
+        check(self.ctx._lib.orx_seqrec_full_loss(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
+                                                 self._denom, scale, ci, _flags(dev), lp, l2p, rp))
+        if not per_row:
+            return _loss_pair(out)
+        if dev:
+            rows = rows.cpu().numpy()
+        return (*_loss_pair(out), rows)
 
     def user_table(self, bags, out=None):
         """-> a Table [B, D] of the pooled rows q_i of `bags` (out: a Table of that shape to write; None: one owned by this

@@ -377,3 +377,22 @@ class PairwiseRecommender(Recommender):
         off = _ids(item_offset) if item_offset is not None else None
         return rt.inbatch_step(opt, U, V, b, uid, pid, K=K, weights=wts, item_offset=off, scale=scale, mask_hits=mask_hits,
                                l2_reg=self.l2_reg, want_loss=want_loss)
+
+    def train_steps_full(self, optimizer, user_id, p_item_id, want_loss=True, sample_weight=None, item_offset=None, scale=1.0,
+                         train=None):
+        """Beyond the reference API: one step on the softmax over ALL items in one device call (rt.fullsoftmax_step): every
+        sample's positive is the label among every row of the item table -- no sampler, no B x items matrix.  user_id /
+        p_item_id shaped [B].  sample_weight: per-sample weights shaped like the ids; item_offset [total_items]: added to an
+        item's logit in every row (a log-prior; -inf removes the item).  scale = 1 / temperature.  The user table takes the
+        sparse rule, the item table and the bias the optimizer's dense rule on every row.  train: None, or a subset of
+        ("user", "item", "bias").  The objective is loss + l2_reg * l2_loss with the model's l2_reg; the returned l2 is the
+        unscaled l2_loss.  Dot-product models only: it goes through no tape, and UCML raises NotImplementedError."""
+        if self._model != "bpr":
+            raise NotImplementedError(f"{type(self).__name__}.train_steps_full: the full-softmax step scores by dot products "
+                                      "(u.v + b); UCML's squared-distance scores are not supported by it")
+        U, V, b = self._tables()
+        opt = optimizer.native(U.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(item_offset) if item_offset is not None else None
+        return rt.fullsoftmax_step(opt, U, V, b, _ids(user_id), _ids(p_item_id), weights=wts, item_offset=off, scale=scale,
+                                   l2_reg=self.l2_reg, train=train, want_loss=want_loss)

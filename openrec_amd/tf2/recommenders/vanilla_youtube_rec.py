@@ -5,8 +5,8 @@ plus a bias (rt.SeqRec),
 There is no user table: a history never trained on is served like any other.  Three deviations from the reference:
   * no hidden layer -- the reference puts Dense(dim_item_embed) layers (and dropout) between the pooled vector and the softmax;
     this is the depth-0 tower, the pooled vector itself meets the item table;
-  * a sampled softmax (or the log-sigmoid pair loss) over the label and N negatives the caller draws, instead of the full
-    softmax over all items;
+  * `train_steps` trains on a sampled softmax (or the log-sigmoid pair loss) over the label and N negatives the caller draws --
+    the default, and the cheap one; the reference's full softmax over all items is `train_steps_full` / `loss_full`;
   * the l2 term sits on the POOLED vector and the looked-up rows of the item table; the reference's l2_reg_embed sits on every
     looked-up row of the sequence embedding.
 The default pooling divides by max_seq_len, which is the reference's reduce_mean over the zero-masked padded axis;
@@ -72,6 +72,24 @@ class VanillaYouTubeRec(Recommender):
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(neg_offset) if neg_offset is not None else None
         return self._net.loss(self._bags(seq_item_id, seq_len), _ids(label), _ids(n_item_id), loss=loss, weights=wts, neg_offset=off)
+
+    def train_steps_full(self, optimizer, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, want_loss=True,
+                         train=None):
+        """One train step on the reference's objective (rt.SeqRec.step_full): the softmax of the label over ALL items, no
+        negatives to draw.  item_offset [total_items]: a per-item constant added to every row's logits (-inf removes an item,
+        a padding id for one).  The item table and the bias take the optimizer's dense rule on every row.
+        -> (loss[1], l2[1]) as float32 arrays when want_loss, else None"""
+        opt = optimizer.native(self._net.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(item_offset) if item_offset is not None else None
+        return self._net.step_full(opt, self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off,
+                                   l2_reg=self.l2_reg, train=train, want_loss=want_loss)
+
+    def loss_full(self, seq_item_id, seq_len, label, sample_weight=None, item_offset=None):
+        """the forward of train_steps_full alone -> (loss, l2)"""
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(item_offset) if item_offset is not None else None
+        return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off)
 
     def _tables(self, flush=True):
         """what the scoring paths see: (the pooled rows of the histories last handed over, V, b)"""
