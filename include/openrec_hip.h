@@ -1236,7 +1236,7 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
  * no n_j; the context stays usable.
  *   orx_fullsoftmax_geometry   no device: out = { own rows per workgroup, rows per tile, item chunks, sample chunks, padded dim,
  *                              scratch bytes of a step of the user-table form with every table trained }
- * Not offered: hidden layers or dropout between the query and the item table; K-step calls; UCML / L2 scoring; hit masking (every
+ * Not offered: dropout between the query and the item table (hidden layers: orx_tower_step, below); K-step calls; UCML / L2 scoring; hit masking (every
  * item is one column); a sampled or sharded item axis. */
 int orx_fullsoftmax_step(orx_ctx* ctx, orx_opt* opt,
                          orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
@@ -1263,6 +1263,61 @@ int orx_seqrec_full_loss(orx_ctx* ctx,
                          const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
                          int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
                          float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+
+/* ---- THE HISTORY-POOLED RECOMMENDER WITH A DENSE TOWER (api_tower.hip, kernels_tower.hip): the reference's YouTubeRec /
+ * VanillaYouTubeRec -- user-feature embeddings beside the pooled history, hidden layers, the softmax over all items.  Sample i:
+ *   x0_i    = [ S_1[f_1[i]] | ... | S_m[f_m[i]] | pool(H[bag_i]) ]         the side rows first, then the pool of orx_bag_pool (its bits)
+ *   x_{l+1} = act_l(x_l W_l + c_l),  l = 0 .. L-1                          act = relu (relu'(0) = 0); the last layer's only if relu_last
+ *   q_i     = x_L;  s_ij, lse_i, l_i and loss as orx_seqrec_full_step has them on q_i
+ *   l2_loss = 1/2 (sum_i |x0_i|^2 + sum_i |V[pid[i]]|^2)                   on the embedding outputs; the layers' part is not in l2_out
+ *   J       = loss + l2_reg * l2_loss + l2_mlp * 1/2 sum_l (|W_l|^2 + |c_l|^2)
+ * hist [items, Dh]; item [items, Dq], bias [items, 1] or NULL; side[j] [n_j, d_j], n_side in 0 .. 4, side_ids[j] an id list [B]
+ * that lives where the bags live; W[l] [in_l, out_l] and c[l] [1, out_l] (c NULL, or an entry NULL: no bias), n_layers in 1 .. 4,
+ * in_0 = sum d_j + Dh, in_{l+1} = out_l, out_{L-1} = Dq; every width, in_0 included, in 1 .. 256.  bags, mode, denom, pid, weight,
+ * item_offset, scale and the chunk arguments as in orx_seqrec_full_step.
+ * An EMPTY bag pools to zeros and stays a live sample (as in orx_seqrec_full_step, where its query is then 0): here its query comes
+ * from the side rows and the biases, and the layers take its gradient.  A sample with a bad id -- in its bag or in a side list --
+ * is dropped as a whole (x0 = 0, no loss, no l2, no gradient) and the call reports ORX_ERR_INDEX as orx_seqrec_full_step does.
+ * The step's order: every check; the lists staged; the lazy rows of every side table and of hist touched; item, bias and every
+ * layer finished and out of the lazy set; input, tower forward, full-softmax forward and gradients, tower backward (one pass over
+ * g_{l+1} per layer: g_l, and per-batch-chunk partials of dW_l and dc_l), one finishing launch; the Adam counter once; the applies:
+ * hist by the sorted route (occurrence e of bag i takes c_i * g_0[i][sum d_j ..]), side[j] by orx_apply_rows with side_ids[j]
+ * (rows outside the batch stay as they are), item, bias, W_l and c_l by the optimizer's dense rule.  No float atomics: all results
+ * are bit-repeatable; a row of the tower's output has the same bits in any batch.
+ * train_mask: ORX_TRAIN_USER (hist) | _ITEM | _BIAS | ORX_TRAIN_SIDE (every side table) | ORX_TRAIN_TOWER (every W_l and c_l);
+ * 0 = every table given.  flags: ORX_IDS_DEVICE, ORX_NO_L2 (then l2_reg == l2_mlp == 0).
+ * ORX_ERR_ARG before any device work, beyond what orx_seqrec_full_step refuses: n_layers outside 1 .. 4, n_side outside 0 .. 4; a
+ * width outside 1 .. 256; a layer whose inputs do not chain, a last layer that is not the item table's dim wide; c_l not
+ * [1, out_l]; a table passed twice; l2_mlp negative or not finite; ORX_TRAIN_SIDE without a side table; an optimizer that
+ * orx_apply_rows refuses for hist or a side table.
+ *   orx_tower_loss       forward only: the step's loss_out / l2_out bit for bit, and l_i per sample if row_loss_out is not NULL
+ *   orx_tower_query      q_i of B bags into rows [out_row0, out_row0 + B) of `out` [.., out_{L-1}]: the queries the step uses, bit for bit
+ *   orx_tower_geometry   no device: out = { rows per tile, batch chunks of the backward, tiles per chunk, scratch bytes of a step with
+ *                        every table trained beyond the lists' and the full softmax's } for B samples and widths[n_layers + 1]
+ * Not offered: the sampled-negatives form (orx_seqrec_step with a tower), dropout, batch norm, K-step calls. */
+enum orx_tower_train_mask { ORX_TRAIN_SIDE = 16, ORX_TRAIN_TOWER = 32 };      /* beside orx_train_mask's three (8 is ORX_TRAIN_PROJ) */
+int orx_tower_step(orx_ctx* ctx, orx_opt* opt,
+                   orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                   int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                   int32_t n_layers, orx_table* const* W, orx_table* const* c /* NULL ok */, int relu_last,
+                   const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */,
+                   const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                   int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg, float l2_mlp,
+                   int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_tower_loss(orx_ctx* ctx,
+                   orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                   int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                   int32_t n_layers, orx_table* const* W, orx_table* const* c /* NULL ok */, int relu_last,
+                   const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */,
+                   const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                   int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                   float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+int orx_tower_query(orx_ctx* ctx, orx_table* hist,
+                    int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                    int32_t n_layers, orx_table* const* W, orx_table* const* c /* NULL ok */, int relu_last,
+                    const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom,
+                    orx_table* out, int64_t out_row0, int flags);
+int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* widths /* [n_layers + 1] */, int64_t out[4]);
 
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,

@@ -17,6 +17,7 @@ ORX_GMF, ORX_WRMF = 0, 1
 ORX_IDS_DEVICE, ORX_HOGWILD, ORX_NO_L2, ORX_CENSOR, ORX_POINT_SIGMOID, ORX_OUT_DEVICE = 1, 2, 4, 8, 16, 32
 ORX_TRAIN_USER, ORX_TRAIN_ITEM, ORX_TRAIN_BIAS = 1, 2, 4      # enum orx_train_mask
 ORX_TRAIN_PROJ = 8                                            # (orx_vbpr_step: the projection)
+ORX_TRAIN_SIDE, ORX_TRAIN_TOWER = 16, 32                      # enum orx_tower_train_mask (orx_tower_step: the side tables, the layers)
 ORX_MN_SOFTMAX, ORX_MN_LOGSIG = 0, 1                          # enum orx_multineg_kind
 ORX_BAG_MEAN, ORX_BAG_FIXED = 0, 1                            # enum orx_bag_mode
 ORX_IB_MASK_HITS = 0x1000                                     # enum orx_inbatch_flags
@@ -126,6 +127,13 @@ SIGNATURES = {
                                      c_int32, c_int32, c_int, c_int, _fp, _fp]),
     "orx_seqrec_full_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int, c_float, c_float, c_int32, c_int,
                                      _fp, _fp, _fp]),
+    "orx_tower_step": (c_int, [_p, _p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64,
+                               c_int, c_float, c_float, c_float, c_float, c_int32, c_int32, c_int, c_int, _fp, _fp]),
+    "orx_tower_loss": (c_int, [_p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64,
+                               c_int, c_float, c_float, c_int32, c_int, _fp, _fp, _fp]),
+    "orx_tower_query": (c_int, [_p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, c_int64, c_int64, c_int, c_float,
+                                _p, c_int64, c_int]),
+    "orx_tower_geometry": (c_int, [c_int64, c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "orx_lightgcn_create": (c_int, [_p, _p, _p, _p, _ip, _p, _ip, _fp, _fp, c_int64, c_int64, c_int32, _fp, _pp]),
     "orx_lightgcn_destroy": (c_int, [_p]),
     "orx_lightgcn_tables": (c_int, [_p, _pp, _pp]),

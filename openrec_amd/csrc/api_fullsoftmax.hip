@@ -67,7 +67,7 @@ int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q,
     a.B = B; a.Bp = p.Bp; a.NQ = NQ; a.NI = V->rows; a.NIp = p.NIp;
     a.D = V->dim; a.Dp = (int)p.Dp; a.gs = (a.D + 1 + 3) & ~3;
     a.nci = (int)p.nci; a.tpi = (int)p.tpi; a.ncs = (int)p.ncs; a.tps = (int)p.tps;
-    a.scale = scale; a.invB = 1.0f / (float)B; a.l2w = l2w; a.err = c->d_err;
+    a.scale = scale; a.invB = 1.0f / (float)B; a.l2w = l2w; a.l2q = l2w; a.err = c->d_err;
     char* base = reinterpret_cast<char*>(c->d_tmp);
     auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
     a.xq = f(l.xq); a.xv = f(l.xv);

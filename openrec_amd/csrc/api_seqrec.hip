@@ -22,8 +22,10 @@ namespace {
 constexpr int SQ_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_HOGWILD | ORX_CENSOR;      // (the last two are named to be refused by name)
 constexpr int SQ_TRAIN_ALL = ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS;
 
-// what the three calls check of their lists before any device work; host lists are walked here
-int check_bags(const char* fn, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom, bool host) {
+}  // namespace
+
+// what the calls over bags (here and api_tower.hip) check of their lists before any device work; host lists are walked here
+int orx_bag_check(const char* fn, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom, bool host) {
     ORX_ARG(mode == ORX_BAG_MEAN || mode == ORX_BAG_FIXED, "%s: unknown pooling mode %d (ORX_BAG_MEAN, ORX_BAG_FIXED)", fn, mode);
     ORX_ARG(mode != ORX_BAG_FIXED || (std::isfinite(denom) && denom > 0.f), "%s: denom must be finite and > 0 (got %g)", fn, (double)denom);
     ORX_ARG(B >= 0 && B < 0x7fffffffLL, "%s: B = %lld (0 <= B < 2^31 - 1)", fn, (long long)B);
@@ -38,7 +40,7 @@ int check_bags(const char* fn, const int32_t* bag_ptr, const int32_t* bag_items,
     return ORX_OK;
 }
 
-int check_model(const char* fn, orx_table* hist, orx_table* item) {
+static int check_model(const char* fn, orx_table* hist, orx_table* item) {
     ORX_ARG(hist && item, "%s: NULL context/table", fn);
     ORX_ARG(hist != item && hist->w != item->w, "%s: the history table and the item table are the same table (tied tables are not offered)", fn);
     ORX_ARG(hist->rows == item->rows, "%s: %lld history rows for %lld items", fn, (long long)hist->rows, (long long)item->rows);
@@ -46,7 +48,7 @@ int check_model(const char* fn, orx_table* hist, orx_table* item) {
     return ORX_OK;
 }
 
-int check_kind(const char* fn, int kind, int32_t N, int64_t B) {
+static int check_kind(const char* fn, int kind, int32_t N, int64_t B) {
     ORX_ARG(kind == ORX_MN_SOFTMAX || kind == ORX_MN_LOGSIG, "%s: unknown loss kind %d (ORX_MN_SOFTMAX, ORX_MN_LOGSIG)", fn, kind);
     ORX_ARG(N >= 1 && N <= 64, "%s: N must be in [1, 64], got %d", fn, N);
     ORX_ARG((B * (1 + (int64_t)N)) <= 0x7fffffffLL, "%s: B * (1 + N) must fit 31 bits", fn);
@@ -54,7 +56,7 @@ int check_kind(const char* fn, int kind, int32_t N, int64_t B) {
 }
 
 // the call's lists on the device: device lists pass through, host lists are copied into the two pieces of scratch
-int stage_bags(orx_ctx* c, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, bool host, int32_t* d_ptr, int32_t* d_items,
+int orx_bag_stage(orx_ctx* c, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, bool host, int32_t* d_ptr, int32_t* d_items,
                BagArgs* a) {
     a->ptr = bag_ptr; a->items = bag_items;
     if (!host) return ORX_OK;
@@ -64,7 +66,7 @@ int stage_bags(orx_ctx* c, const int32_t* bag_ptr, const int32_t* bag_items, int
     return ORX_OK;
 }
 
-BagArgs bag_args(orx_ctx* c, orx_table* H, int64_t B, int64_t n, int mode, float denom) {
+BagArgs orx_bag_args(orx_ctx* c, orx_table* H, int64_t B, int64_t n, int mode, float denom) {
     BagArgs a;
     memset(&a, 0, sizeof(a));
     a.H = H->w; a.rows = H->rows; a.D = H->dim; a.B = B; a.n = n; a.mode = mode;
@@ -76,7 +78,7 @@ BagArgs bag_args(orx_ctx* c, orx_table* H, int64_t B, int64_t n, int mode, float
 // The rows of H the bags read, brought up to date where H is lazily applied under Adam: on the sorted list -- a radix sort of the n
 // ids and one launch -- and not by orx_table_touch, whose duplicate analysis takes 1 ms at n = 1.3M.  *sorted (may be NULL): the
 // pairs, valid until the context's next sort, for a caller that applies with them; always sorted when `always`.
-int touch_bags(orx_ctx* c, orx_table* H, const int32_t* items, int64_t n, bool always, const uint2** sorted) {
+int orx_bag_touch(orx_ctx* c, orx_table* H, const int32_t* items, int64_t n, bool always, const uint2** sorted) {
     if (sorted) *sorted = nullptr;
     if (n == 0 || (!always && !H->lazy)) return ORX_OK;
     const uint2* s = nullptr;
@@ -85,6 +87,8 @@ int touch_bags(orx_ctx* c, orx_table* H, const int32_t* items, int64_t n, bool a
     if (H->lazy) CHECK(orx_adam_rows_sorted(c, H->lazy, H, s, n, nullptr, 0, false));
     return ORX_OK;
 }
+
+namespace {
 
 // scratch of the step and of the forward (grads == false: the pooled rows and the lists alone)
 struct Scratch { BagArgs bag; MultiNegArgs mn; uint2* pairs; uint2* isorted; };
@@ -109,8 +113,8 @@ int make_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b, con
     auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
     Scratch s;
     memset(&s, 0, sizeof(s));
-    s.bag = bag_args(c, hist, B, n, mode, denom);
-    CHECK(stage_bags(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
+    s.bag = orx_bag_args(c, hist, B, n, mode, denom);
+    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
     s.bag.out = f(o_q); s.bag.uid = i32(o_uid);
     MultiNegArgs& a = s.mn;
     a.U = f(o_q); a.V = item->w; a.b = b ? b->w : nullptr; a.uid = i32(o_uid);
@@ -138,7 +142,7 @@ extern "C" int orx_bag_pool(orx_ctx* c, orx_table* H, const int32_t* bag_ptr, co
     ORX_ARG(out->dim == H->dim, "%s: output dim %d != table dim %d", fn, out->dim, H->dim);
     ORX_ARG(H->dim <= 256, "%s: dim %d above 256", fn, H->dim);
     const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     ORX_ARG(out_row0 >= 0 && out_row0 + B <= out->rows, "%s: rows [%lld, %lld) outside the %lld output rows", fn, (long long)out_row0,
             (long long)(out_row0 + B), (long long)out->rows);
     if (B == 0) return ORX_OK;
@@ -148,10 +152,10 @@ extern "C" int orx_bag_pool(orx_ctx* c, orx_table* H, const int32_t* bag_ptr, co
     const size_t o_ptr = cv.take((size_t)(B + 1) * sizeof(int32_t)), o_items = cv.take((size_t)n * sizeof(int32_t));
     if (host) ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     char* base = reinterpret_cast<char*>(c->d_tmp);
-    BagArgs a = bag_args(c, H, B, n, mode, denom);
-    CHECK(stage_bags(c, bag_ptr, bag_items, B, n, host, reinterpret_cast<int32_t*>(base + o_ptr), reinterpret_cast<int32_t*>(base + o_items), &a));
+    BagArgs a = orx_bag_args(c, H, B, n, mode, denom);
+    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, reinterpret_cast<int32_t*>(base + o_ptr), reinterpret_cast<int32_t*>(base + o_items), &a));
     a.out = out->w + (size_t)out_row0 * out->dim;
-    CHECK(touch_bags(c, H, a.items, n, false, nullptr));
+    CHECK(orx_bag_touch(c, H, a.items, n, false, nullptr));
     CHECK(orx_launch_bag_pool(c, a));
     out->version++;
     if (host) return orx_check_index_error(c);
@@ -165,7 +169,7 @@ extern "C" int orx_seqrec_step(orx_ctx* c, int kind, orx_opt* opt, orx_table* hi
     static const char* fn = "orx_seqrec_step";
     CHECK(check_model(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     CHECK(orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS));
     CHECK(check_kind(fn, kind, N, B));
     ORX_ARG((train_mask & ~SQ_TRAIN_ALL) == 0, "%s: train mask 0x%x has bits outside ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS", fn, train_mask);
@@ -198,7 +202,7 @@ extern "C" int orx_seqrec_step(orx_ctx* c, int kind, orx_opt* opt, orx_table* hi
         // ONE sort of bag_items serves the touch of the history rows and, its positions rewritten to their owners right after the
         // pool (before anything else may sort), the apply.  A history table outside the mask is current: no touch, no sort
         const uint2* sorted = nullptr;
-        CHECK(touch_bags(c, hist, s.bag.items, n, tH, &sorted));
+        CHECK(orx_bag_touch(c, hist, s.bag.items, n, tH, &sorted));
         CHECK(orx_launch_bag_pool(c, s.bag));
         if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, s.bag.owner, n, B, s.pairs));
         CHECK(orx_touch_step(nullptr, item, b, nullptr, 0, a.pid, B, a.nid, B * N));
@@ -229,7 +233,7 @@ extern "C" int orx_seqrec_loss(orx_ctx* c, int kind, orx_table* hist, orx_table*
     static const char* fn = "orx_seqrec_loss";
     CHECK(check_model(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     CHECK(orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR));
     CHECK(check_kind(fn, kind, N, B));
     if (B == 0) {
@@ -247,7 +251,7 @@ extern "C" int orx_seqrec_loss(orx_ctx* c, int kind, orx_table* hist, orx_table*
     a.pid = in.id[0]; a.nid = in.id[1]; a.wt = in.f[0]; a.off = in.f[1];
     return orx_run_forward(c, orx_multineg_nwaves(c, a.D, B), loss_out, l2_out, [&](float* partial) -> int {
         a.partial = partial;
-        CHECK(touch_bags(c, hist, s.bag.items, n, false, nullptr));
+        CHECK(orx_bag_touch(c, hist, s.bag.items, n, false, nullptr));
         CHECK(orx_touch_step(nullptr, item, b, nullptr, 0, a.pid, B, a.nid, B * N));
         CHECK(orx_launch_bag_pool(c, s.bag));
         return orx_launch_multineg(c, kind, false, a);
@@ -280,8 +284,8 @@ int make_full_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b
     auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
     FullScratch s;
     memset(&s, 0, sizeof(s));
-    s.bag = bag_args(c, hist, B, n, mode, denom);
-    CHECK(stage_bags(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
+    s.bag = orx_bag_args(c, hist, B, n, mode, denom);
+    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
     s.bag.out = f(o_q); s.bag.uid = i32(o_uid);
     if (grads) { s.bag.coef = f(o_coef); s.bag.owner = i32(o_owner); s.pairs = reinterpret_cast<uint2*>(base + o_pairs); }
     CHECK(orx_fullsoftmax_bind(c, lay, f(o_q), B, item, b, item_offset, B, scale, l2w, &s.fs));
@@ -299,7 +303,7 @@ extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, o
     static const char* fn = "orx_seqrec_full_step";
     CHECK(check_model(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     CHECK(orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS));
     CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, chunk_samples));
     CHECK(orx_fullsoftmax_mask(fn, b, &train_mask));
@@ -330,7 +334,7 @@ extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, o
         // ONE sort of bag_items serves the touch of the history rows and, its positions rewritten to their owners right after the
         // pool (before anything else may sort), the apply -- as orx_seqrec_step has it
         const uint2* sorted = nullptr;
-        CHECK(touch_bags(c, hist, s.bag.items, n, tH, &sorted));
+        CHECK(orx_bag_touch(c, hist, s.bag.items, n, tH, &sorted));
         CHECK(orx_launch_bag_pool(c, s.bag));
         if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, s.bag.owner, n, B, s.pairs));
         CHECK(orx_launch_fullsoftmax_forward(c, a));
@@ -355,7 +359,7 @@ extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item
     static const char* fn = "orx_seqrec_full_loss";
     CHECK(check_model(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(check_bags(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     CHECK(orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR));
     CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, 0));
     if (B == 0) {
@@ -374,7 +378,7 @@ extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item
     return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
         a.partial = partial;
         CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
-        CHECK(touch_bags(c, hist, s.bag.items, n, false, nullptr));
+        CHECK(orx_bag_touch(c, hist, s.bag.items, n, false, nullptr));
         CHECK(orx_launch_bag_pool(c, s.bag));
         CHECK(orx_launch_fullsoftmax_forward(c, a));
         if (row_loss_out)

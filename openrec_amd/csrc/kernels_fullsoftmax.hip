@@ -69,11 +69,14 @@ __global__ __launch_bounds__(256) void fs_prepare_kernel(FullSoftmaxArgs a) {
     const float* ur = a.Q + (size_t)(ok ? u : 0) * a.D;
     const float* vr = a.V + (size_t)(ok ? p : 0) * a.D;
     float sq = 0.0f;
-    for (int c = lane; c < a.Dp; c += 64) {
+    const int cend = a.X0 && a.x0w > a.Dp ? a.x0w : a.Dp;
+    for (int c = lane; c < cend; c += 64) {
         const bool in = ok && c < a.D;
         const float x = in ? ur[c] : 0.0f, y = in ? vr[c] : 0.0f;
-        a.xq[(size_t)t * a.Dp + c] = x;
-        sq = fmaf(x, x, fmaf(y, y, sq));
+        if (c < a.Dp) a.xq[(size_t)t * a.Dp + c] = x;
+        // (X0: the rows whose squares are the query side's l2 term, in the place of the query's own)
+        const float xs = a.X0 ? ((ok && c < a.x0w) ? a.X0[(size_t)t * a.x0ld + c] : 0.0f) : x;
+        sq = fmaf(xs, xs, fmaf(y, y, sq));
     }
     sq = wave_sum(sq);
     if (lane == 0) {
@@ -329,7 +332,7 @@ __global__ __launch_bounds__(256) void fs_finish_kernel(FullSoftmaxArgs a) {
         if (d < a.D) {
             float s = 0.0f;
             for (int ch = 0; ch < a.nci; ++ch) s += a.gpq[((size_t)ch * a.Bp + o) * a.Dp + d];
-            g = fmaf(a.scale, s, a.l2w * a.xq[(size_t)o * a.Dp + d]);
+            g = fmaf(a.scale, s, a.l2q * a.xq[(size_t)o * a.Dp + d]);
         }
         a.gu[idx] = g;
     } else {

@@ -1009,6 +1009,14 @@ struct BagArgs {
 int orx_launch_bag_pool(orx_ctx* ctx, const BagArgs& a);
 int orx_launch_bag_scale_rows(orx_ctx* ctx, float* g, const float* coef, int64_t B, int D, int gs);           // g[i][0 .. D) *= coef[i]
 int orx_launch_bag_owner_pairs(orx_ctx* ctx, const uint2* sorted, const int32_t* owner, int64_t n, int64_t B, uint2* out);   // (row, position) -> (row, owner[position])
+// what the calls over bags share (api_seqrec.hip; api_tower.hip): the checks of the lists before any device work (host lists are
+// walked); the lists on the device (host lists copied into the two pieces of scratch); the kernels' arguments; the touch of the
+// lazy rows of H on the sorted list, *sorted the pairs for a caller that applies with them
+int orx_bag_check(const char* fn, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom, bool host);
+int orx_bag_stage(orx_ctx* c, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, bool host, int32_t* d_ptr, int32_t* d_items,
+                  BagArgs* a);
+BagArgs orx_bag_args(orx_ctx* c, orx_table* H, int64_t B, int64_t n, int mode, float denom);
+int orx_bag_touch(orx_ctx* c, orx_table* H, const int32_t* items, int64_t n, bool always, const uint2** sorted);
 
 // kernels_inbatch.hip (orx_inbatch_step / orx_inbatch_loss): one step of the in-batch softmax.  Bp = B rounded up to 64, Dp = D
 // rounded up to 16; every [Bp] / [Bp][Dp] / [nch][..] array is scratch carved from the context's d_tmp
@@ -1043,6 +1051,8 @@ struct FullSoftmaxArgs {
     int64_t B; int64_t Bp; int64_t NQ; int64_t NI; int64_t NIp;
     int D; int Dp; int gs; int nci; int tpi; int ncs; int tps;    // nci item chunks of tpi tiles of 64; ncs sample chunks of tps tiles
     float scale; float invB; float l2w;
+    float l2q; const float* X0; int x0w; int x0ld;        // the query side's own l2: g_u takes l2q * u_i (orx_fullsoftmax_bind: l2w), and the l2 sum
+                                                          // |u_i|^2 -- or, X0 not NULL, |X0[i][0 .. x0w)|^2 in its place (the tower: x0, with l2q = 0)
     float* xq; float* xv;                                 // [Bp][Dp] the query rows, [NIp][Dp] the zero-padded item table
     int32_t* key; float* cw; float* sq;                   // [Bp] pid or -1, w / B, |u|^2 + |V[pid]|^2
     float* ib; float* io;                                 // [NIp] bias, offset (0 beyond NI)
@@ -1073,6 +1083,30 @@ int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q,
                          int64_t B, float scale, float l2w, FullSoftmaxArgs* out);
 int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask);
 int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a);
+
+// kernels_tower.hip (orx_tower_step / orx_tower_loss / orx_tower_query): the dense tower between the pooled history and the full
+// softmax's query.  Layer l maps x[l] [B][w[l]] to x[l + 1] [B][w[l + 1]]; every buffer has its own row stride, so that x[L] is
+// the full softmax's Q (stride w[L]) and g[L] its gu (stride gs).  Everything but the tables is scratch carved from d_tmp
+constexpr int ORX_TOWER_LAYERS = 4, ORX_TOWER_SIDE = 4, ORX_TOWER_WIDTH = 256;
+struct TowerArgs {
+    int L; int m; int relu_last; int so;                  // layers, side tables, relu on the last layer, so = sum d_j: the pool's first column of x[0]
+    int64_t B;
+    int w[ORX_TOWER_LAYERS + 1];                          // w[0] = in_0 ... w[L] = the item table's dim
+    const float* W[ORX_TOWER_LAYERS]; const float* c[ORX_TOWER_LAYERS];      // [w[l]][w[l + 1]]; [w[l + 1]] or NULL
+    float* x[ORX_TOWER_LAYERS + 1]; int ldx[ORX_TOWER_LAYERS + 1];           // activations (all stored: the backward's inputs and relu masks)
+    float* g[ORX_TOWER_LAYERS + 1]; int ldg[ORX_TOWER_LAYERS + 1];           // gradients; g[0] NULL: nobody takes it
+    float* pw[ORX_TOWER_LAYERS]; float* pc[ORX_TOWER_LAYERS];                // [nch][w[l] w[l + 1]], [nch][w[l + 1]] per-batch-chunk partials; NULL: the tower is not trained
+    float* GW[ORX_TOWER_LAYERS]; float* Gc[ORX_TOWER_LAYERS];                // the dense gradients
+    int nch; int tpc;                                     // batch chunks of tpc tiles of 64 rows
+    float l2x; float l2m;                                 // the coefficient on x[0] (g[0] += l2x x[0]) and on the layers
+    const float* S[ORX_TOWER_SIDE]; int64_t srows[ORX_TOWER_SIDE]; int sd[ORX_TOWER_SIDE]; const int32_t* f[ORX_TOWER_SIDE];      // side tables, DEVICE [B] ids
+    BagArgs bag;                                          // the history lists (out unused: the pooled row goes to columns [so, w[0]) of x[0])
+};
+void orx_tower_plan(int64_t B, int* nch, int* tpc);       // a function of B alone
+int orx_launch_tower_input(orx_ctx* ctx, const TowerArgs& a);
+int orx_launch_tower_forward(orx_ctx* ctx, const TowerArgs& a);                 // one launch per layer
+int orx_launch_tower_backward(orx_ctx* ctx, const TowerArgs& a);                // one launch per layer, last to first
+int orx_launch_tower_finish(orx_ctx* ctx, const TowerArgs& a);                  // one launch: the partials of all layers in chunk order, + l2m * (W, c)
 
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {

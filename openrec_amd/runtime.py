@@ -2497,3 +2497,172 @@ class SeqRec:
         user_table(bags); excl: a SparseMask or a dense bool mask [B, items] of items never returned (the history itself, say)"""
         Q = self.user_table(bags)
         return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl)
+
+
+# ---- history-pooled recommender with a dense tower (orx_tower_step / orx_tower_loss / orx_tower_query) -------------------------------
+_DEEP_ROLES = {**_SEQ_ROLES, "side": _ffi.ORX_TRAIN_SIDE, "tower": _ffi.ORX_TRAIN_TOWER}
+_TOWER_LAYERS, _TOWER_SIDE, _TOWER_WIDTH = 4, 4, 256
+
+
+def _handles(tables):
+    """tables (None entries allowed) -> a C array of their handles"""
+    return (c_void_p * max(len(tables), 1))(*[None if t is None else t._h for t in tables])
+
+
+def tower_geometry(B, widths):
+    """what the launcher of DeepSeqRec's tower does for B samples and the widths (in_0, out_0, ..., out_{L-1}): a dict of the rows
+    per tile, the batch chunks of the backward, the tiles per chunk and the scratch bytes of a step with every table trained
+    (beyond the lists' and the full softmax's).  No device is needed."""
+    widths = [int(x) for x in widths]
+    if not 2 <= len(widths) <= _TOWER_LAYERS + 1:
+        raise ValueError(f"tower_geometry: {len(widths) - 1} layers (1 .. {_TOWER_LAYERS})")
+    out = (c_int64 * 4)()
+    check(_ffi.load().orx_tower_geometry(int(B), len(widths) - 1, (c_int32 * len(widths))(*widths), out))
+    return dict(tile=int(out[0]), batch_chunks=int(out[1]), tiles_per_chunk=int(out[2]), scratch_bytes=int(out[3]))
+
+
+class DeepSeqRec:
+    """SeqRec with user-feature embeddings and hidden layers between the pool and the query (the reference's YouTubeRec):
+        x0 = [ S_1[f_1] | ... | S_m[f_m] | pool(H[history]) ];   x_{l+1} = relu(x_l W_l + c_l);   q = x_L;   s(q, i) = q . V[i] + b[i]
+    H [items, Dh], V [items, Dq], b [items, 1] or None.  layers: 1 .. 4 pairs (W_l [in_l, out_l], c_l [1, out_l] or None), or bare
+    tables for layers without a bias; in_0 = sum d_j + Dh, out_{L-1} = Dq, every width in 1 .. 256.  side: 0 .. 4 Tables
+    S_j [n_j, d_j], each indexed by one id list per call.  relu_last=False: the last layer is linear.  No table may be passed
+    twice.  An EMPTY history pools to zeros and stays a live sample: in SeqRec its query is then 0 and only the item side takes a
+    gradient; here the query comes from the side rows and the biases, and the layers and side rows take its gradient too."""
+
+    def __init__(self, H, V, b, layers, side=(), pool="mean", relu_last=True):
+        what = "DeepSeqRec"
+        self._mode, self._denom = _pool_arg(what, pool)
+        layers = [tuple(l) if isinstance(l, (tuple, list)) else (l, None) for l in layers]
+        side = list(side)
+        if not 1 <= len(layers) <= _TOWER_LAYERS:
+            raise ValueError(f"{what}: {len(layers)} layers (1 .. {_TOWER_LAYERS})")
+        if len(side) > _TOWER_SIDE:
+            raise ValueError(f"{what}: {len(side)} side tables (0 .. {_TOWER_SIDE})")
+        if any(len(l) != 2 or l[0] is None for l in layers):
+            raise ValueError(f"{what}: a layer is (W, c) with c a Table or None")
+        every = [H, V, b] + side + [t for l in layers for t in l]
+        live = [t for t in every if t is not None]
+        if len({id(t) for t in live}) != len(live):
+            raise ValueError(f"{what}: a table is passed twice (tied tables are not offered)")
+        if any(t.ctx is not H.ctx for t in live):
+            raise ValueError(f"{what}: the tables live on different contexts")
+        if H.rows != V.rows:
+            raise ValueError(f"{what}: {H.rows} history rows for {V.rows} items")
+        if b is not None and tuple(b.shape) != (V.rows, 1):
+            raise ValueError(f"{what}: bias must be [{V.rows}, 1], got {list(b.shape)}")
+        widths = [sum(s.dim for s in side) + H.dim]
+        for l, (W, c) in enumerate(layers):
+            if W.rows != widths[-1]:
+                raise ValueError(f"{what}: layer {l} takes {W.rows} inputs where {widths[-1]} arrive (the widths do not chain)")
+            if c is not None and tuple(c.shape) != (1, W.dim):
+                raise ValueError(f"{what}: the bias of layer {l} is {list(c.shape)}, not [1, {W.dim}]")
+            widths.append(W.dim)
+        if widths[-1] != V.dim:
+            raise ValueError(f"{what}: the last layer is {widths[-1]} wide, the item table has dim {V.dim}")
+        bad = [w for w in widths + [s.dim for s in side] + [H.dim] if not 1 <= w <= _TOWER_WIDTH]
+        if bad:
+            raise ValueError(f"{what}: width {bad[0]} outside [1, {_TOWER_WIDTH}]")
+        self.H, self.V, self.b, self.ctx, self.pool = H, V, b, H.ctx, pool
+        self.layers, self.side, self.widths, self.relu_last = layers, side, widths, bool(relu_last)
+        self._tables = live
+        self._Q = None
+
+    def _model_args(self, side_ptrs):
+        """the side tables, their id pointers and the layers as the C arrays the three calls take"""
+        m, L = len(self.side), len(self.layers)
+        ids = (c_void_p * max(m, 1))(*side_ptrs)
+        arrays = (_handles(self.side), ids, _handles([W for W, _ in self.layers]), _handles([c for _, c in self.layers]))
+        return (m, arrays[0], arrays[1], L, arrays[2], arrays[3], int(self.relu_last)), arrays
+
+    def _lists(self, what, bags, side_ids):
+        pp, pi, B, n, dev, kb = _bags_arg(what, bags)
+        side_ids = tuple(side_ids)
+        if len(side_ids) != len(self.side):
+            raise ValueError(f"{what}: {len(side_ids)} side id lists for {len(self.side)} side tables")
+        ps, ns, _, ks = _id_lists(what, side_ids, dev)                  # (on the side the bags are on)
+        if any(x != B for x in ns):
+            raise ValueError(f"{what}: {B} bags and side id lists of {ns} ids (one id per bag and side table)")
+        return pp, pi, B, n, dev, ps, (kb, ks)
+
+    def _args_full(self, what, bags, pid, side_ids, weights, item_offset, scale, chunk_items, chunk_samples):
+        scale = _scale_arg(what, scale)
+        ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
+        pp, pi, B, n, dev, ps, (kb, ks) = self._lists(what, bags, side_ids)
+        (ppid,), (npid,), _, keep = _id_lists(what, (pid,), dev)
+        if npid != B:
+            raise ValueError(f"{what}: {B} bags and {npid} label ids (one label per bag)")
+        pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
+        po, ko = _floats_arg(what, "item_offset", item_offset, dev, self.V.rows, "the item table's rows")
+        self.ctx.after_torch(*kb, *ks, *keep, kw, ko)
+        for t in self._tables:
+            t._sync_pending()
+        model, arrays = self._model_args(ps)
+        return B, n, dev, model, (pp, pi, ppid, pw, po), scale, ci, cs, (kb, ks, keep, kw, ko, arrays)
+
+    def step_full(self, opt, bags, pid, side_ids=(), weights=None, item_offset=None, scale=1.0, l2_reg=0.0, l2_mlp=0.0, train=None,
+                  chunk_items=0, chunk_samples=0, want_loss=True):
+        """One train step on the softmax over ALL items (orx_tower_step): SeqRec.step_full's objective with the query computed by
+        the tower.  side_ids: one id list [B] per side table, where the bags live.  J = loss + l2_reg * l2_loss + l2_mlp * 1/2
+        sum_l (|W_l|^2 + |c_l|^2), l2_loss = 1/2 (sum |x0_i|^2 + sum |V[pid_i]|^2) on the embedding outputs.  The history table
+        goes SeqRec's sorted route, a side table takes the sparse rule on its id list, V, b and every W_l, c_l the optimizer's
+        dense rule.  train: None, or a subset of ("history", "item", "bias", "side", "tower").  -> (loss[1], l2[1]) as numpy
+        float32, l2 the unscaled l2_loss, when want_loss, else None.  Bad arguments raise ValueError before the library is
+        called; a malformed device list or an id outside its table IndexError."""
+        what = "DeepSeqRec.step_full"
+        mask = _mask_arg(what, train, _DEEP_ROLES, self.b is not None) or 0
+        if mask & _ffi.ORX_TRAIN_SIDE and not self.side:
+            raise ValueError(f'{what}: train: "side" named, but the model has no side table')
+        l2c, l2m = _coef_arg(what, "l2_reg", l2_reg), _coef_arg(what, "l2_mlp", l2_mlp)
+        B, n, dev, model, ptrs, scale, ci, cs, keep = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale,
+                                                                       chunk_items, chunk_samples)
+        out, lp, l2p = _loss_outputs(1, want_loss)
+        check(self.ctx._lib.orx_tower_step(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n,
+                                           self._mode, self._denom, scale, l2c, l2m, ci, cs, mask, _flags(dev), lp, l2p))
+        _keep_tables(opt, self._tables)
+        return out
+
+    def loss_full(self, bags, pid, side_ids=(), weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
+        """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
+        table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
+        what = "DeepSeqRec.loss_full"
+        B, n, dev, model, ptrs, scale, ci, _, keep = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale, chunk_items, 0)
+        out, lp, l2p = _loss_outputs(1, True)
+        rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
+        check(self.ctx._lib.orx_tower_loss(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n, self._mode,
+                                           self._denom, scale, ci, _flags(dev), lp, l2p, rp))
+        if not per_row:
+            return _loss_pair(out)
+        if dev:
+            rows = rows.cpu().numpy()
+        return (*_loss_pair(out), rows)
+
+    def user_table(self, bags, side_ids=(), out=None):
+        """-> a Table [B, Dq] of the queries q_i (orx_tower_query) -- the rows the step scores with, bit for bit, and a row's bits
+        do not depend on the batch around it.  out: a Table of that shape to write; None: one owned by this object, valid until
+        the next call with another B.  With (V, b) it goes wherever a user table goes, uid = the row number."""
+        what = "DeepSeqRec.user_table"
+        pp, pi, B, n, dev, ps, keep = self._lists(what, bags, side_ids)
+        if B < 1:
+            raise ValueError(f"{what}: no bags")
+        if out is None:
+            if self._Q is None or self._Q.rows != B:
+                self._Q = Table(B, self.V.dim, self.ctx)
+            out = self._Q
+        elif (out.rows, out.dim) != (B, self.V.dim):
+            raise ValueError(f"{what}: out is [{out.rows}, {out.dim}] for {B} bags and queries of dim {self.V.dim}")
+        if any(out is t for t in self._tables):
+            raise ValueError(f"{what}: the output is one of the model's tables")
+        self.ctx.after_torch(*keep[0], *keep[1])
+        for t in self._tables:
+            t._sync_pending()
+        out._sync_pending()
+        model, arrays = self._model_args(ps)
+        check(self.ctx._lib.orx_tower_query(self.ctx._h, self.H._h, *model, pp, pi, B, n, self._mode, self._denom, out._h, 0, _flags(dev)))
+        return out
+
+    def recommend(self, bags, side_ids, k, excl=None):
+        """the k best items for each history -> (item ids int32 [B, k], scores float32 [B, k]): recommend_topk("dot", ...) on
+        user_table(bags, side_ids); excl: a SparseMask or a dense bool mask [B, items] of items never returned"""
+        Q = self.user_table(bags, side_ids)
+        return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl)
