@@ -1191,7 +1191,8 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
 
 /* ---- THE FULL SOFTMAX OVER ALL ITEMS (api_fullsoftmax.hip, api_seqrec.hip, kernels_fullsoftmax.hip): one train step of a
  * dot-product model under sparse_softmax_cross_entropy over EVERY row of the item table -- the objective of the reference's
- * mlp_softmax / rnn_softmax interactions and of GRU4Rec / SASRec / Mult-VAE style models.  No B x NI matrix is stored.
+ * mlp_softmax / rnn_softmax interactions and of GRU4Rec / SASRec / Mult-VAE style models (a label SET per sample, the
+ * multinomial likelihood of Mult-VAE / Mult-DAE: orx_seqrec_full_sets_step, below).  No B x NI matrix is stored.
  * Sample i has a query vector u_i and a label item pid[i].  u_i = U[uid[i]] (orx_fullsoftmax_*: the user-table form) or the
  * pooled q_i of bag i, pooled exactly as orx_bag_pool does (orx_seqrec_full_*: the SeqRec form; hist, item, bias, the bags, mode
  * and denom as in the block above).  The columns are all NI rows of the item table, each once.
@@ -1237,7 +1238,8 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
  *   orx_fullsoftmax_geometry   no device: out = { own rows per workgroup, rows per tile, item chunks, sample chunks, padded dim,
  *                              scratch bytes of a step of the user-table form with every table trained }
  * Not offered: dropout between the query and the item table (hidden layers: orx_tower_step, below); K-step calls; UCML / L2 scoring; hit masking (every
- * item is one column); a sampled or sharded item axis. */
+ * item is one column); a sampled or sharded item axis; label sets in the user-table form (orx_seqrec_full_sets_step and
+ * orx_tower_sets_step have them). */
 int orx_fullsoftmax_step(orx_ctx* ctx, orx_opt* opt,
                          orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
                          const int32_t* uid, const int32_t* pid,
@@ -1318,6 +1320,73 @@ int orx_tower_query(orx_ctx* ctx, orx_table* hist,
                     const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom,
                     orx_table* out, int64_t out_row0, int flags);
 int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* widths /* [n_layers + 1] */, int64_t out[4]);
+
+/* ---- LABEL SETS UNDER THE FULL SOFTMAX (api_fullsoftmax.hip, api_seqrec.hip, api_tower.hip, kernels_labelsets.hip): the
+ * multinomial likelihood of Mult-DAE / Mult-VAE (Liang et al. 2018) -- a sample's query against every item, scored on the
+ * sample's WHOLE SET of items in one walk.  orx_seqrec_full_sets_* and orx_tower_sets_* are orx_seqrec_full_* and orx_tower_*
+ * with pid replaced by ragged label lists.  Sample i has the query q_i of its form (the pooled history; the tower's output)
+ * and the entries e in [lab_ptr[i], lab_ptr[i + 1]), each an item j_e = lab_items[e] with a weight t_e = lab_weight[e], 1 when
+ * lab_weight == NULL.  A duplicate in a set is two entries.  T_i = sum_e t_e.  s_ij, lse_i, scale, item_offset, weight,
+ * c_i = w_i / B and pi_ij as in orx_seqrec_full_step.
+ *   l_i     = T_i lse_i - sum_e t_e s_{i,j_e}
+ *   loss    = (1/B) sum_i w_i l_i
+ *   l2_loss = 1/2 (sum_i |the query side's rows as in the single-label call|^2 + sum over live entries e of |V[j_e]|^2)
+ *   a_ij    = c_i (T_i pi_ij - sum over e of set i with j_e = j of t_e)
+ *   g_q[i]  = scale * sum_j a_ij V[j] + (the single-label call's l2 term)
+ *   G_V[j]  = scale * sum_i a_ij q_i  + l2_reg n_j V[j]       n_j = the number of live label entries with item j, not weighted by t
+ *   G_b[j]  = scale * sum_i a_ij
+ * An EMPTY set: the sample stays live with T_i = 0; it contributes its query side's l2 part and nothing else.  Sets of one with
+ * t = 1 are the single-label objective, equal to fp32 rounding and NOT bit for bit: here the label is one of the items summed
+ * into the softmax's denominator and its coefficient is formed by a subtraction on the finished gradient, where the
+ * single-label walks keep the label out of the sum.  The single-label calls' results are unchanged in every bit.
+ * An id outside the item table in a label set, a bad id in the bag or in a side list, or a malformed device lab_ptr (negative,
+ * decreasing, beyond n_lab, lab_ptr[0] != 0, lab_ptr[B] != n_lab) drops the sample as a whole and reports ORX_ERR_INDEX as the bag
+ * lists do; the id is never an address; the context stays usable.  A bad HOST lab_ptr is ORX_ERR_ARG before any device work.
+ * lab_weight lives where the ids live and is not validated, like item_offset.
+ * The apply rules, the lazy-Adam order, the train masks, the flags, the refusals and B == 0 are the single-label calls'.
+ * The dense part c_i T_i pi_ij is the single-label walks on rows no item is the label of; the sparse part: one wavefront per
+ * sample over its entries (64 ids per load) for the scores, T_i, sum_e t_e V[j_e] and the |V|^2; the label entries sorted by
+ * item (the stable sort of orx_apply_rows) and one wavefront per run of equal items, in position order, for G_V, G_b and n_j.
+ * No float atomics: every sum has a fixed order that depends on the lists and the shapes alone; losses, row losses and all tables
+ * are bit-repeatable from run to run.  The forward-only calls give the step's loss_out / l2_out bit for bit.
+ * Not offered: label sets in the user-table form (orx_fullsoftmax_step); the VAE's sampling and KL term; tanh; a 1 / sqrt(len)
+ * pool; dropout inside the tower; the sampled-negatives form with sets; K-step calls. */
+int orx_seqrec_full_sets_step(orx_ctx* ctx, orx_opt* opt,
+                              orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                              const int32_t* bag_ptr, const int32_t* bag_items,
+                              const int32_t* lab_ptr /* [B + 1] */, const int32_t* lab_items /* [n_lab] */,
+                              const float* lab_weight /* [n_lab], NULL ok */, int64_t n_lab,
+                              const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                              int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
+                              int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_seqrec_full_sets_loss(orx_ctx* ctx,
+                              orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                              const int32_t* bag_ptr, const int32_t* bag_items,
+                              const int32_t* lab_ptr /* [B + 1] */, const int32_t* lab_items /* [n_lab] */,
+                              const float* lab_weight /* [n_lab], NULL ok */, int64_t n_lab,
+                              const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                              int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                              float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+int orx_tower_sets_step(orx_ctx* ctx, orx_opt* opt,
+                        orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                        int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                        int32_t n_layers, orx_table* const* W, orx_table* const* c /* NULL ok */, int relu_last,
+                        const int32_t* bag_ptr, const int32_t* bag_items,
+                        const int32_t* lab_ptr /* [B + 1] */, const int32_t* lab_items /* [n_lab] */,
+                        const float* lab_weight /* [n_lab], NULL ok */, int64_t n_lab,
+                        const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                        int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg, float l2_mlp,
+                        int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_tower_sets_loss(orx_ctx* ctx,
+                        orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                        int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                        int32_t n_layers, orx_table* const* W, orx_table* const* c /* NULL ok */, int relu_last,
+                        const int32_t* bag_ptr, const int32_t* bag_items,
+                        const int32_t* lab_ptr /* [B + 1] */, const int32_t* lab_items /* [n_lab] */,
+                        const float* lab_weight /* [n_lab], NULL ok */, int64_t n_lab,
+                        const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
+                        int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                        float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
 
 /* Diagnostics of the duplicate plan of the exact steps (api_plan.hip; DESIGN.md "The duplicate plan as tested").
  *   orx_plan_geometry   host only, no device: out[16] = {nru, nri, lgu, lgi, shift, W (32-bit words per range bitmap), PL_UN, PL_LCNT,

@@ -131,6 +131,14 @@ SIGNATURES = {
                                c_int, c_float, c_float, c_float, c_float, c_int32, c_int32, c_int, c_int, _fp, _fp]),
     "orx_tower_loss": (c_int, [_p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64,
                                c_int, c_float, c_float, c_int32, c_int, _fp, _fp, _fp]),
+    "orx_seqrec_full_sets_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, c_int64, _fp, _fp, c_int64, c_int64, c_int, c_float,
+                                          c_float, c_float, c_int32, c_int32, c_int, c_int, _fp, _fp]),
+    "orx_seqrec_full_sets_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, c_int64, _fp, _fp, c_int64, c_int64, c_int, c_float,
+                                          c_float, c_int32, c_int, _fp, _fp, _fp]),
+    "orx_tower_sets_step": (c_int, [_p, _p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _ip, _fp, c_int64, _fp, _fp,
+                                    c_int64, c_int64, c_int, c_float, c_float, c_float, c_float, c_int32, c_int32, c_int, c_int, _fp, _fp]),
+    "orx_tower_sets_loss": (c_int, [_p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _ip, _fp, c_int64, _fp, _fp,
+                                    c_int64, c_int64, c_int, c_float, c_float, c_int32, c_int, _fp, _fp, _fp]),
     "orx_tower_query": (c_int, [_p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, c_int64, c_int64, c_int, c_float,
                                 _p, c_int64, c_int]),
     "orx_tower_geometry": (c_int, [c_int64, c_int32, POINTER(c_int32), POINTER(c_int64)]),

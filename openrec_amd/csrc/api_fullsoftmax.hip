@@ -1,6 +1,7 @@
 // C-ABI entry points of the softmax over all items with a user table: orx_fullsoftmax_step, orx_fullsoftmax_loss and
 // orx_fullsoftmax_geometry (include/openrec_hip.h has the semantics, kernels_fullsoftmax.hip the kernels; the SeqRec form,
-// orx_seqrec_full_step / orx_seqrec_full_loss, is in api_seqrec.hip and shares the checks and the scratch layout below).
+// orx_seqrec_full_step / orx_seqrec_full_loss, is in api_seqrec.hip and shares the checks and the scratch layout below; so do the
+// label-set entry points of api_seqrec.hip and api_tower.hip, whose own checks, layout and bind are here as well).
 //
 // Per step: the item table and the bias are read in full, so a lazily applied Adam on them is finished first and they leave the
 // lazy set; the user rows are touched; the forward (prepare, item copy, LSE pass, finalize), the gradient passes (a walk and a
@@ -95,6 +96,46 @@ int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask) {
 int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a) {
     if (tV) CHECK(orx_table_apply_dense_at(c, opt, V, a.GV));
     if (tb) CHECK(orx_table_apply_dense_at(c, opt, b, a.Gb));
+    return ORX_OK;
+}
+
+// ---- label sets (orx_seqrec_full_sets_step / orx_tower_sets_step and their forwards; kernels_labelsets.hip): what the two forms share
+int orx_labelsets_check(const char* fn, const int32_t* lab_ptr, const int32_t* lab_items, int64_t B, int64_t n_lab, bool host) {
+    ORX_ARG(n_lab >= 0 && n_lab < 0x80000000LL, "%s: n_lab = %lld (0 <= n_lab < 2^31)", fn, (long long)n_lab);
+    if (B == 0) return ORX_OK;
+    ORX_ARG(lab_ptr && (n_lab == 0 || lab_items), "%s: NULL label list", fn);
+    if (!host) return ORX_OK;
+    ORX_ARG(lab_ptr[0] == 0, "%s: lab_ptr[0] = %d, not 0", fn, lab_ptr[0]);
+    for (int64_t i = 0; i < B; ++i)
+        ORX_ARG(lab_ptr[i + 1] >= lab_ptr[i], "%s: lab_ptr decreases at sample %lld (%d after %d)", fn, (long long)i, lab_ptr[i + 1], lab_ptr[i]);
+    ORX_ARG(lab_ptr[B] == n_lab, "%s: lab_ptr[B] = %d for n_lab = %lld label entries", fn, lab_ptr[B], (long long)n_lab);
+    return ORX_OK;
+}
+
+void orx_labelsets_layout(Carve* cv, int64_t B, int32_t D, int64_t n_lab, bool host, bool host_tw, bool grads, LabelSetLayout* l) {
+    memset(l, 0, sizeof(*l));
+    if (host) { l->ptr = cv->take((size_t)(B + 1) * sizeof(int32_t)); l->items = cv->take((size_t)n_lab * sizeof(int32_t)); }
+    if (host_tw) l->tw = cv->take((size_t)n_lab * sizeof(float));
+    if (grads) { l->owner = cv->take((size_t)n_lab * sizeof(int32_t)); l->lp = cv->take((size_t)B * D * sizeof(float)); }
+}
+
+int orx_labelsets_bind(orx_ctx* c, const LabelSetLayout& l, const FullSoftmaxArgs& fs, const int32_t* lab_ptr, const int32_t* lab_items,
+                       const float* lab_weight, int64_t n_lab, bool host, bool grads, LabelSetArgs* out) {
+    LabelSetArgs a;
+    memset(&a, 0, sizeof(a));
+    char* base = reinterpret_cast<char*>(c->d_tmp);
+    a.fs = fs; a.n = n_lab;
+    BagArgs lists;                              // the label lists are staged as the bag lists are
+    memset(&lists, 0, sizeof(lists));
+    CHECK(orx_bag_stage(c, lab_ptr, lab_items, fs.B, n_lab, host, reinterpret_cast<int32_t*>(base + l.ptr), reinterpret_cast<int32_t*>(base + l.items), &lists));
+    a.ptr = lists.ptr; a.items = lists.items;
+    a.tw = lab_weight;
+    if (lab_weight && host && n_lab) {          // one float per ENTRY: it lives where the ids live
+        ORX_HIP(hipMemcpyAsync(base + l.tw, lab_weight, (size_t)n_lab * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        a.tw = reinterpret_cast<float*>(base + l.tw);
+    }
+    if (grads) { a.owner = reinterpret_cast<int32_t*>(base + l.owner); a.lp = reinterpret_cast<float*>(base + l.lp); }
+    *out = a;
     return ORX_OK;
 }
 

@@ -1,6 +1,7 @@
 // C-ABI entry points of the history-pooled sequence recommender: orx_bag_pool, orx_seqrec_step and orx_seqrec_loss
 // (include/openrec_hip.h has the semantics, kernels_bag.hip the kernels), and at the end of the file orx_seqrec_full_step and
-// orx_seqrec_full_loss, the softmax over all items with the pooled vector as the query (kernels_fullsoftmax.hip).
+// orx_seqrec_full_loss, the softmax over all items with the pooled vector as the query (kernels_fullsoftmax.hip), with
+// orx_seqrec_full_sets_step / orx_seqrec_full_sets_loss, the same with a label set per sample (kernels_labelsets.hip).
 //
 // The step is orx_multineg_step with the user row replaced by a pooled vector.  Per step: bag_items is sorted by row
 // (orx_rows_sort) and the lazy history rows are touched on the sorted list; pid and nid are touched as orx_multineg_step does;
@@ -264,11 +265,11 @@ extern "C" int orx_seqrec_loss(orx_ctx* c, int kind, orx_table* hist, orx_table*
 // full -- finished first, out of the lazy set -- and take the dense rule.
 namespace {
 
-struct FullScratch { BagArgs bag; FullSoftmaxArgs fs; uint2* pairs; };
+struct FullScratch { BagArgs bag; FullSoftmaxArgs fs; uint2* pairs; LabelSetArgs ls; };
 
 int make_full_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b, const int32_t* bag_ptr, const int32_t* bag_items,
                       const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2w, int32_t chunk_items,
-                      int32_t chunk_samples, bool host, bool grads, bool query_side, bool item_side, FullScratch* out) {
+                      int32_t chunk_samples, bool host, bool grads, bool query_side, bool item_side, const LabelLists* sets, FullScratch* out) {
     const int D = hist->dim;
     Carve cv;
     const size_t o_q = cv.take((size_t)B * D * sizeof(float));
@@ -278,6 +279,8 @@ int make_full_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b
     if (grads) { o_coef = cv.take((size_t)B * sizeof(float)); o_owner = cv.take((size_t)n * sizeof(int32_t)); o_pairs = cv.take((size_t)n * sizeof(uint2)); }
     FullSoftmaxLayout lay;
     orx_fullsoftmax_layout(&cv, B, item->rows, D, chunk_items, chunk_samples, grads, query_side, item_side, host && item_offset, &lay);
+    LabelSetLayout llay;
+    if (sets) orx_labelsets_layout(&cv, B, D, sets->n, host, host && sets->weight, grads, &llay);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     char* base = reinterpret_cast<char*>(c->d_tmp);
     auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
@@ -290,17 +293,18 @@ int make_full_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b
     if (grads) { s.bag.coef = f(o_coef); s.bag.owner = i32(o_owner); s.pairs = reinterpret_cast<uint2*>(base + o_pairs); }
     CHECK(orx_fullsoftmax_bind(c, lay, f(o_q), B, item, b, item_offset, B, scale, l2w, &s.fs));
     s.fs.qid = i32(o_uid);
+    if (sets) CHECK(orx_labelsets_bind(c, llay, s.fs, sets->ptr, sets->items, sets->weight, sets->n, host, grads, &s.ls));
     *out = s;
     return ORX_OK;
 }
 
 }  // namespace
 
-extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
-                                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
-                                    const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
-                                    int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
-    static const char* fn = "orx_seqrec_full_step";
+// the step with one label per sample (sets NULL) or a label set per sample (pid NULL)
+static int full_step(const char* fn, orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const LabelLists* sets, const float* weight,
+                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
+                     int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
     CHECK(check_model(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
     CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
@@ -308,8 +312,9 @@ extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, o
     CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, chunk_samples));
     CHECK(orx_fullsoftmax_mask(fn, b, &train_mask));
     CHECK(orx_check_apply_rows_opt(opt, hist, nullptr));
+    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
     if (B == 0) return ORX_OK;
-    ORX_ARG(pid, "%s: NULL id pointer", fn);
+    ORX_ARG(sets || pid, "%s: NULL id pointer", fn);
     ORX_HIP(hipSetDevice(c->device));
     const bool tH = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
 
@@ -317,7 +322,7 @@ extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, o
     CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
     FullScratch s;
     CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, l2_reg, chunk_items, chunk_samples, host,
-                            true, tH && n > 0, tV || tb, &s));
+                            true, tH && n > 0, tV || tb, sets, &s));
     FullSoftmaxArgs& a = s.fs;
     a.pid = in.id[0]; a.wt = in.f[0];
     const int gs = a.gs, D = a.D;
@@ -337,8 +342,14 @@ extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, o
         CHECK(orx_bag_touch(c, hist, s.bag.items, n, tH, &sorted));
         CHECK(orx_launch_bag_pool(c, s.bag));
         if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, s.bag.owner, n, B, s.pairs));
-        CHECK(orx_launch_fullsoftmax_forward(c, a));
-        CHECK(orx_launch_fullsoftmax_grads(c, a, tH && n > 0, tV || tb));
+        if (sets) {                         // (after the pairs are taken: the label entries are sorted by item on the same buffers)
+            s.ls.fs = a;
+            CHECK(orx_launch_labelsets_forward(c, s.ls));
+            CHECK(orx_launch_labelsets_grads(c, s.ls, tH && n > 0, tV || tb));
+        } else {
+            CHECK(orx_launch_fullsoftmax_forward(c, a));
+            CHECK(orx_launch_fullsoftmax_grads(c, a, tH && n > 0, tV || tb));
+        }
         if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
         if (tH && n > 0) {
             CHECK(orx_launch_bag_scale_rows(c, a.gu, s.bag.coef, B, D, gs));
@@ -352,27 +363,28 @@ extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, o
     return ORX_OK;
 }
 
-extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
-                                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
-                                    const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items,
-                                    int flags, float* loss_out, float* l2_out, float* row_loss_out) {
-    static const char* fn = "orx_seqrec_full_loss";
+static int full_loss(const char* fn, orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const LabelLists* sets, const float* weight,
+                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items,
+                     int flags, float* loss_out, float* l2_out, float* row_loss_out) {
     CHECK(check_model(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
     CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     CHECK(orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR));
     CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, 0));
+    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
     if (B == 0) {
         if (loss_out) *loss_out = 0.f;
         if (l2_out) *l2_out = 0.f;
         return ORX_OK;
     }
-    ORX_ARG(pid, "%s: NULL id pointer", fn);
+    ORX_ARG(sets || pid, "%s: NULL id pointer", fn);
     ORX_HIP(hipSetDevice(c->device));
     StepInputs in;
     CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
     FullScratch s;
-    CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, 0.f, chunk_items, 0, host, false, false, false, &s));
+    CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, 0.f, chunk_items, 0, host, false, false, false,
+                            sets, &s));
     FullSoftmaxArgs& a = s.fs;
     a.pid = in.id[0]; a.wt = in.f[0];
     return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
@@ -380,9 +392,48 @@ extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item
         CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
         CHECK(orx_bag_touch(c, hist, s.bag.items, n, false, nullptr));
         CHECK(orx_launch_bag_pool(c, s.bag));
-        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        if (sets) { s.ls.fs = a; CHECK(orx_launch_labelsets_forward(c, s.ls)); }
+        else CHECK(orx_launch_fullsoftmax_forward(c, a));
         if (row_loss_out)
             ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
         return ORX_OK;
     });
+}
+
+extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
+                                    const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
+                                    int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
+    return full_step("orx_seqrec_full_step", c, opt, hist, item, b, bag_ptr, bag_items, pid, nullptr, weight, item_offset, B, n, mode, denom, scale,
+                     l2_reg, chunk_items, chunk_samples, train_mask, flags, loss_out, l2_out);
+}
+
+extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                                    const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
+                                    const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items,
+                                    int flags, float* loss_out, float* l2_out, float* row_loss_out) {
+    return full_loss("orx_seqrec_full_loss", c, hist, item, b, bag_ptr, bag_items, pid, nullptr, weight, item_offset, B, n, mode, denom, scale,
+                     chunk_items, flags, loss_out, l2_out, row_loss_out);
+}
+
+// the same with a label set per sample (kernels_labelsets.hip)
+extern "C" int orx_seqrec_full_sets_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                                         const int32_t* bag_ptr, const int32_t* bag_items,
+                                         const int32_t* lab_ptr, const int32_t* lab_items, const float* lab_weight, int64_t n_lab,
+                                         const float* weight, const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale,
+                                         float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,
+                                         float* loss_out, float* l2_out) {
+    const LabelLists sets{lab_ptr, lab_items, lab_weight, n_lab};
+    return full_step("orx_seqrec_full_sets_step", c, opt, hist, item, b, bag_ptr, bag_items, nullptr, &sets, weight, item_offset, B, n, mode, denom,
+                     scale, l2_reg, chunk_items, chunk_samples, train_mask, flags, loss_out, l2_out);
+}
+
+extern "C" int orx_seqrec_full_sets_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                                         const int32_t* bag_ptr, const int32_t* bag_items,
+                                         const int32_t* lab_ptr, const int32_t* lab_items, const float* lab_weight, int64_t n_lab,
+                                         const float* weight, const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale,
+                                         int32_t chunk_items, int flags, float* loss_out, float* l2_out, float* row_loss_out) {
+    const LabelLists sets{lab_ptr, lab_items, lab_weight, n_lab};
+    return full_loss("orx_seqrec_full_sets_loss", c, hist, item, b, bag_ptr, bag_items, nullptr, &sets, weight, item_offset, B, n, mode, denom, scale,
+                     chunk_items, flags, loss_out, l2_out, row_loss_out);
 }

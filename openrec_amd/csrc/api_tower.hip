@@ -1,5 +1,6 @@
 // C-ABI entry points of the history-pooled recommender with a dense tower: orx_tower_step, orx_tower_loss, orx_tower_query and
-// orx_tower_geometry (include/openrec_hip.h has the semantics, kernels_tower.hip the kernels).
+// orx_tower_geometry (include/openrec_hip.h has the semantics, kernels_tower.hip the kernels), and orx_tower_sets_step /
+// orx_tower_sets_loss, the step and the forward with a label set per sample (kernels_labelsets.hip).
 //
 // The step is orx_seqrec_full_step with the tower between the pool and the query.  Per step: everything is checked; the lists are
 // staged; the lazy rows of every side table are touched with its id list, then bag_items is sorted and the lazy history rows are
@@ -176,13 +177,13 @@ extern "C" int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* wi
     return ORX_OK;
 }
 
-extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
-                              int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
-                              int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
-                              const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight, const float* item_offset,
-                              int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg, float l2_mlp,
-                              int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
-    static const char* fn = "orx_tower_step";
+// the step with one label per sample (sets NULL) or a label set per sample (pid NULL)
+static int tower_step(const char* fn, orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                      int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                      int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
+                      const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const LabelLists* sets, const float* weight,
+                      const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg, float l2_mlp,
+                      int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
     CHECK(check_item(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
     CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
@@ -200,8 +201,9 @@ extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_tab
     if (train_mask == 0) train_mask = ORX_TRAIN_USER | ORX_TRAIN_ITEM | (b ? ORX_TRAIN_BIAS : 0) | (md.m ? ORX_TRAIN_SIDE : 0) | ORX_TRAIN_TOWER;
     CHECK(orx_check_apply_rows_opt(opt, hist, nullptr));
     for (int j = 0; j < md.m; ++j) CHECK(orx_check_apply_rows_opt(opt, md.S[j], nullptr));
+    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
     if (B == 0) return ORX_OK;
-    ORX_ARG(pid, "%s: NULL id pointer", fn);
+    ORX_ARG(sets || pid, "%s: NULL id pointer", fn);
     ORX_HIP(hipSetDevice(c->device));
     const bool tH = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
     const bool tS = (train_mask & ORX_TRAIN_SIDE) != 0, tT = (train_mask & ORX_TRAIN_TOWER) != 0;
@@ -214,6 +216,8 @@ extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_tab
     tower_layout(&cv, md.w, md.L, md.m, B, n, host, true, true, below, want_g0, tT, &tl);
     FullSoftmaxLayout lay;
     orx_fullsoftmax_layout(&cv, B, item->rows, item->dim, chunk_items, chunk_samples, true, below, tV || tb, host && item_offset, &lay);
+    LabelSetLayout llay;
+    if (sets) orx_labelsets_layout(&cv, B, item->dim, sets->n, host, host && sets->weight, true, &llay);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     TowerArgs t;
     CHECK(tower_bind(c, md, tl, bag_ptr, bag_items, B, n, mode, denom, host, true, true, below, want_g0, tT, &t));
@@ -223,6 +227,8 @@ extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_tab
     a.qid = t.bag.uid; a.pid = in.id[0]; a.wt = in.f[0];
     a.l2q = 0.f; a.X0 = t.x[0]; a.x0w = md.w[0]; a.x0ld = t.ldx[0];              // the l2 term sits on x0, not on the query
     t.g[md.L] = a.gu; t.ldg[md.L] = a.gs;
+    LabelSetArgs ls;
+    if (sets) CHECK(orx_labelsets_bind(c, llay, a, sets->ptr, sets->items, sets->weight, sets->n, host, true, &ls));
     uint2* pairs = reinterpret_cast<uint2*>(reinterpret_cast<char*>(c->d_tmp) + tl.pairs);
     // V, b and the layers are read in full: every row current, out of the lazy set; a table outside the mask is finished under the
     // old counter (whatever optimizer it is lazy under), then only read
@@ -246,8 +252,14 @@ extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_tab
         CHECK(orx_launch_tower_input(c, t));
         if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, t.bag.owner, n, B, pairs));
         CHECK(orx_launch_tower_forward(c, t));
-        CHECK(orx_launch_fullsoftmax_forward(c, a));
-        CHECK(orx_launch_fullsoftmax_grads(c, a, below, tV || tb));
+        if (sets) {                         // (after the pairs are taken: the label entries are sorted by item on the same buffers)
+            ls.fs = a;
+            CHECK(orx_launch_labelsets_forward(c, ls));
+            CHECK(orx_launch_labelsets_grads(c, ls, below, tV || tb));
+        } else {
+            CHECK(orx_launch_fullsoftmax_forward(c, a));
+            CHECK(orx_launch_fullsoftmax_grads(c, a, below, tV || tb));
+        }
         if (below) CHECK(orx_launch_tower_backward(c, t));
         if (tT) CHECK(orx_launch_tower_finish(c, t));
         if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
@@ -275,13 +287,12 @@ extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_tab
     return ORX_OK;
 }
 
-extern "C" int orx_tower_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
-                              int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
-                              int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
-                              const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight, const float* item_offset,
-                              int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
-                              float* loss_out, float* l2_out, float* row_loss_out) {
-    static const char* fn = "orx_tower_loss";
+static int tower_loss(const char* fn, orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                      int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                      int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
+                      const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const LabelLists* sets, const float* weight,
+                      const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                      float* loss_out, float* l2_out, float* row_loss_out) {
     CHECK(check_item(fn, hist, item));
     const bool host = !(flags & ORX_IDS_DEVICE);
     CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
@@ -289,12 +300,13 @@ extern "C" int orx_tower_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_
     TowerModel md;
     CHECK(check_tower(fn, c, hist, n_side, side, side_ids, n_layers, W, cs, relu_last, item->dim, "the item table", {item, b}, B, &md));
     CHECK(orx_fullsoftmax_check(fn, B, item->rows, item->dim, scale, chunk_items, 0));
+    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
     if (B == 0) {
         if (loss_out) *loss_out = 0.f;
         if (l2_out) *l2_out = 0.f;
         return ORX_OK;
     }
-    ORX_ARG(pid, "%s: NULL id pointer", fn);
+    ORX_ARG(sets || pid, "%s: NULL id pointer", fn);
     ORX_HIP(hipSetDevice(c->device));
     StepInputs in;
     CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
@@ -303,6 +315,8 @@ extern "C" int orx_tower_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_
     tower_layout(&cv, md.w, md.L, md.m, B, n, host, true, false, false, false, false, &tl);
     FullSoftmaxLayout lay;
     orx_fullsoftmax_layout(&cv, B, item->rows, item->dim, chunk_items, 0, false, false, false, host && item_offset, &lay);
+    LabelSetLayout llay;
+    if (sets) orx_labelsets_layout(&cv, B, item->dim, sets->n, host, host && sets->weight, false, &llay);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     TowerArgs t;
     CHECK(tower_bind(c, md, tl, bag_ptr, bag_items, B, n, mode, denom, host, true, false, false, false, false, &t));
@@ -310,6 +324,8 @@ extern "C" int orx_tower_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_
     CHECK(orx_fullsoftmax_bind(c, lay, t.x[md.L], B, item, b, item_offset, B, scale, 0.f, &a));
     a.qid = t.bag.uid; a.pid = in.id[0]; a.wt = in.f[0];
     a.l2q = 0.f; a.X0 = t.x[0]; a.x0w = md.w[0]; a.x0ld = t.ldx[0];
+    LabelSetArgs ls;
+    if (sets) CHECK(orx_labelsets_bind(c, llay, a, sets->ptr, sets->items, sets->weight, sets->n, host, false, &ls));
     return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
         a.partial = partial;
         CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
@@ -317,11 +333,60 @@ extern "C" int orx_tower_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_
         CHECK(touch_inputs(c, md, t, B, n, false, nullptr));
         CHECK(orx_launch_tower_input(c, t));
         CHECK(orx_launch_tower_forward(c, t));
-        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        if (sets) { ls.fs = a; CHECK(orx_launch_labelsets_forward(c, ls)); }
+        else CHECK(orx_launch_fullsoftmax_forward(c, a));
         if (row_loss_out)
             ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
         return ORX_OK;
     });
+}
+
+extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                              int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                              int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
+                              const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight, const float* item_offset,
+                              int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg, float l2_mlp,
+                              int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
+    return tower_step("orx_tower_step", c, opt, hist, item, b, n_side, side, side_ids, n_layers, W, cs, relu_last, bag_ptr, bag_items, pid, nullptr,
+                      weight, item_offset, B, n, mode, denom, scale, l2_reg, l2_mlp, chunk_items, chunk_samples, train_mask, flags, loss_out, l2_out);
+}
+
+extern "C" int orx_tower_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                              int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                              int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
+                              const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight, const float* item_offset,
+                              int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                              float* loss_out, float* l2_out, float* row_loss_out) {
+    return tower_loss("orx_tower_loss", c, hist, item, b, n_side, side, side_ids, n_layers, W, cs, relu_last, bag_ptr, bag_items, pid, nullptr, weight,
+                      item_offset, B, n, mode, denom, scale, chunk_items, flags, loss_out, l2_out, row_loss_out);
+}
+
+// the same with a label set per sample (kernels_labelsets.hip)
+extern "C" int orx_tower_sets_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
+                                   int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                                   int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
+                                   const int32_t* bag_ptr, const int32_t* bag_items,
+                                   const int32_t* lab_ptr, const int32_t* lab_items, const float* lab_weight, int64_t n_lab,
+                                   const float* weight, const float* item_offset,
+                                   int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg, float l2_mlp,
+                                   int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
+    const LabelLists sets{lab_ptr, lab_items, lab_weight, n_lab};
+    return tower_step("orx_tower_sets_step", c, opt, hist, item, b, n_side, side, side_ids, n_layers, W, cs, relu_last, bag_ptr, bag_items, nullptr,
+                      &sets, weight, item_offset, B, n, mode, denom, scale, l2_reg, l2_mlp, chunk_items, chunk_samples, train_mask, flags, loss_out,
+                      l2_out);
+}
+
+extern "C" int orx_tower_sets_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
+                                   int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,
+                                   int32_t n_layers, orx_table* const* W, orx_table* const* cs, int relu_last,
+                                   const int32_t* bag_ptr, const int32_t* bag_items,
+                                   const int32_t* lab_ptr, const int32_t* lab_items, const float* lab_weight, int64_t n_lab,
+                                   const float* weight, const float* item_offset,
+                                   int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
+                                   float* loss_out, float* l2_out, float* row_loss_out) {
+    const LabelLists sets{lab_ptr, lab_items, lab_weight, n_lab};
+    return tower_loss("orx_tower_sets_loss", c, hist, item, b, n_side, side, side_ids, n_layers, W, cs, relu_last, bag_ptr, bag_items, nullptr, &sets,
+                      weight, item_offset, B, n, mode, denom, scale, chunk_items, flags, loss_out, l2_out, row_loss_out);
 }
 
 extern "C" int orx_tower_query(orx_ctx* c, orx_table* hist, int32_t n_side, orx_table* const* side, const int32_t* const* side_ids,

@@ -401,21 +401,25 @@ void orx_fullsoftmax_plan(int64_t B, int64_t NI, int32_t D, int32_t chunk_items,
     cut(p->Bp >> 6, p->NIp >> 6, chunk_samples, &p->tps, &p->ncs);
 }
 
+// the item copy and the LSE pass: what the forward does between its prepare and its finalize (the label-set form,
+// kernels_labelsets.hip, has a prepare and a finalize of its own around the same two launches)
+int orx_launch_fullsoftmax_lse(orx_ctx* ctx, const FullSoftmaxArgs& a) {
+    {
+        ProfScope ps(ctx, ORX_K_FUSED);
+        ORX_LAUNCH(ctx, fs_items_kernel, dim3((unsigned)((a.NIp * a.Dp + 255) / 256)), dim3(256), 0, a);
+        ORX_HIP(hipGetLastError());
+    }
+    ProfScope ps(ctx, ORX_K_GEMM);
+    return fs_walk<0>(ctx, a);
+}
+
 int orx_launch_fullsoftmax_forward(orx_ctx* ctx, const FullSoftmaxArgs& a) {
     {
         ProfScope ps(ctx, ORX_K_FUSED);
         ORX_LAUNCH(ctx, fs_prepare_kernel, dim3((unsigned)((a.Bp + 3) / 4)), dim3(256), 0, a);
         ORX_HIP(hipGetLastError());
     }
-    {
-        ProfScope ps(ctx, ORX_K_FUSED);
-        ORX_LAUNCH(ctx, fs_items_kernel, dim3((unsigned)((a.NIp * a.Dp + 255) / 256)), dim3(256), 0, a);
-        ORX_HIP(hipGetLastError());
-    }
-    {
-        ProfScope ps(ctx, ORX_K_GEMM);
-        CHECK(fs_walk<0>(ctx, a));
-    }
+    CHECK(orx_launch_fullsoftmax_lse(ctx, a));
     ProfScope ps(ctx, ORX_K_FUSED);
     ORX_LAUNCH(ctx, fs_finalize_kernel, dim3((unsigned)orx_fullsoftmax_npartials(a.B)), dim3(256), 0, a);
     ORX_HIP(hipGetLastError());

@@ -1083,6 +1083,32 @@ int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q,
                          int64_t B, float scale, float l2w, FullSoftmaxArgs* out);
 int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask);
 int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a);
+int orx_launch_fullsoftmax_lse(orx_ctx* ctx, const FullSoftmaxArgs& a);         // the item copy and the LSE pass alone
+
+// kernels_labelsets.hip (orx_seqrec_full_sets_step / orx_tower_sets_step and their forwards): the full softmax with a label SET
+// per sample.  The dense part is the three walks of kernels_fullsoftmax.hip on rows whose key no walked item equals
+// (ORX_LS_KEY); the sparse part -- the labels' scores, their sum of item rows, the item side's subtraction -- is here
+constexpr int32_t ORX_LS_KEY = 0x7fffffff;                // a live sample's key: above every item of a table of at most 2^31 - 256 rows
+struct LabelSetArgs {
+    FullSoftmaxArgs fs;                                   // pid unused; key[i] is ORX_LS_KEY or -1
+    const int32_t* ptr; const int32_t* items;             // DEVICE [B + 1] offsets, [n] label items
+    const float* tw;                                      // DEVICE [n] entry weights (NULL: all ones)
+    int64_t n;
+    int32_t* owner;                                       // [n] the sample of a list position (-1: no well-formed set covers it)
+    float* lp;                                            // [B][D] c_i sum_e t_e V[j_e]; NULL: the forward alone
+};
+struct LabelSetLayout { size_t ptr, items, tw, owner, lp; };
+struct LabelLists { const int32_t* ptr; const int32_t* items; const float* weight; int64_t n; };       // a call's label sets as the caller passed them
+// what the SeqRec form and the tower form share (api_fullsoftmax.hip): the checks of the lists before any device work; the
+// scratch behind whatever the caller has carved; the lists on the device and the kernels' arguments once d_tmp is grown
+// (orx_bag_stage copies host lists); the forward (prepare, item copy, LSE pass, rows, loss partials) and the gradient passes
+// (the dense walks, then the labels' part of g_q, the sort of the label entries by item and the item side's runs)
+int orx_labelsets_check(const char* fn, const int32_t* lab_ptr, const int32_t* lab_items, int64_t B, int64_t n_lab, bool host);
+void orx_labelsets_layout(Carve* cv, int64_t B, int32_t D, int64_t n_lab, bool host, bool host_tw, bool grads, LabelSetLayout* l);
+int orx_labelsets_bind(orx_ctx* c, const LabelSetLayout& l, const FullSoftmaxArgs& fs, const int32_t* lab_ptr, const int32_t* lab_items,
+                       const float* lab_weight, int64_t n_lab, bool host, bool grads, LabelSetArgs* out);
+int orx_launch_labelsets_forward(orx_ctx* ctx, const LabelSetArgs& a);
+int orx_launch_labelsets_grads(orx_ctx* ctx, const LabelSetArgs& a, bool query_side, bool item_side);
 
 // kernels_tower.hip (orx_tower_step / orx_tower_loss / orx_tower_query): the dense tower between the pooled history and the full
 // softmax's query.  Layer l maps x[l] [B][w[l]] to x[l + 1] [B][w[l + 1]]; every buffer has its own row stride, so that x[L] is

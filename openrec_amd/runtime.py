@@ -2297,6 +2297,17 @@ def bags_to_ragged(seq, seq_len):
     return ptr, items
 
 
+def _flat_keep(keep):
+    """the arrays of a (possibly nested) keepalive tuple, for Context.after_torch"""
+    out = []
+    for k in keep:
+        if isinstance(k, (tuple, list)):
+            out.extend(_flat_keep(k))
+        else:
+            out.append(k)
+    return out
+
+
 def _host_array(x):
     return x.numpy() if hasattr(x, "numpy") and not isinstance(x, np.ndarray) else x
 
@@ -2339,6 +2350,45 @@ def _seqrec_check_tables(what, H, V, b):
     if H.dim > 256:
         raise ValueError(f"{what}: dim {H.dim} above 256")
     _dot_tables(what, H.dim, V.dim, V.rows, b)
+
+
+def _labels_arg(what, pid, labels, label_weights, dev, B):
+    """the label part of a full-softmax call: one label per bag (pid) or a label set per bag (labels: (ptr, items) or the padded
+    pair (seq, seq_len), as _bags_arg takes bags; label_weights: one float per ragged entry, or [B, L] beside a padded pair).
+    -> (the C arguments between the bags and the weights, sets?, keepalive)"""
+    if (pid is None) == (labels is None):
+        raise ValueError(f"{what}: pass either pid (one label per bag) or labels (a label set per bag), "
+                         f"{'not both' if pid is not None else 'one of them'}")
+    if labels is None:
+        if label_weights is not None:
+            raise ValueError(f"{what}: label_weights without labels")
+        (ppid,), (npid,), _, keep = _id_lists(what, (pid,), dev)          # (on the side the bags are on)
+        if npid != B:
+            raise ValueError(f"{what}: {B} bags and {npid} label ids (one label per bag)")
+        return (ppid,), False, keep
+    if not isinstance(labels, (tuple, list)) or len(labels) != 2:
+        raise ValueError(f"{what}: labels must be (ptr, items) or the padded pair (seq [B, L], seq_len [B])")
+    shape = tuple(getattr(labels[0], "shape", ())) if not isinstance(labels[0], DevicePtr) else ()
+    if len(shape) == 2 and label_weights is not None:                   # padded weights follow their padded ids
+        if tuple(getattr(label_weights, "shape", ())) != shape:
+            raise ValueError(f"{what}: label_weights {list(getattr(label_weights, 'shape', ()))} beside padded labels {list(shape)}")
+        if _is_device_tensor(labels[0]):
+            import torch
+            if not _is_device_tensor(label_weights):
+                raise ValueError(f"{what}: label_weights on the host with labels on the device (label_weights lives where the ids live)")
+            ln = labels[1].to(torch.int64).clamp(0, shape[1])
+            label_weights = label_weights[torch.arange(shape[1], device=labels[0].device)[None, :] < ln[:, None]].float().contiguous()
+        else:
+            ln = np.asarray(_host_array(labels[1])).astype(np.int64).reshape(-1)
+            lw = np.asarray(_host_array(label_weights), dtype=np.float32)
+            label_weights = np.ascontiguousarray(lw[np.arange(shape[1])[None, :] < ln[:, None]])
+    lp, li, LB, n_lab, ldev, kl = _bags_arg(what + " labels", labels)
+    if ldev != dev:
+        raise ValueError(f"{what}: the label sets must live where the bags live")
+    if LB != B:
+        raise ValueError(f"{what}: {B} bags and {LB} label sets (one set per bag)")
+    ptw, ktw = _floats_arg(what, "label_weights", label_weights, dev, n_lab, "the label entries")
+    return (lp, li, ptw, n_lab), True, (kl, ktw)
 
 
 def bag_pool(H, bags, out, pool="mean", rows=None):
@@ -2429,48 +2479,56 @@ class SeqRec:
                                             self._denom, _flags(dev), lp, l2p))
         return _loss_pair(out)
 
-    def _args_full(self, what, bags, pid, weights, item_offset, scale, chunk_items, chunk_samples):
+    def _args_full(self, what, bags, pid, weights, item_offset, scale, chunk_items, chunk_samples, labels=None, label_weights=None):
         scale = _scale_arg(what, scale)
         ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
         pp, pi, B, n, dev, kb = _bags_arg(what, bags)
-        (ppid,), (npid,), _, keep = _id_lists(what, (pid,), dev)          # (on the side the bags are on)
-        if npid != B:
-            raise ValueError(f"{what}: {B} bags and {npid} label ids (one label per bag)")
+        plab, sets, keep = _labels_arg(what, pid, labels, label_weights, dev, B)
         pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
         po, ko = _floats_arg(what, "item_offset", item_offset, dev, self.V.rows, "the item table's rows")
-        self.ctx.after_torch(*kb, *keep, kw, ko)
+        self.ctx.after_torch(*kb, *_flat_keep(keep), kw, ko)
         for t in (self.H, self.V, self.b):
             if t is not None:
                 t._sync_pending()
-        return B, n, dev, (pp, pi, ppid, pw, po), scale, ci, cs, (kb, keep, kw, ko)
+        return B, n, dev, (pp, pi, *plab, pw, po), scale, ci, cs, (kb, keep, kw, ko), sets
 
-    def step_full(self, opt, bags, pid, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None, chunk_items=0,
-                  chunk_samples=0, want_loss=True):
+    def step_full(self, opt, bags, pid=None, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None, chunk_items=0,
+                  chunk_samples=0, want_loss=True, labels=None, label_weights=None):
         """One train step on the softmax over ALL items (orx_seqrec_full_step): bag i's pooled vector against every row of the
         item table, the label pid[i] -- rt.fullsoftmax_step's objective with the user row replaced by q.  weights [B];
         item_offset [items], one float per item (-inf removes an item); both live where the bags live.  The history table goes
         `step`'s route, the item table and the bias take the optimizer's dense rule on every row.  train: None, or a subset
         of ("history", "item", "bias").  -> (loss[1], l2[1]) as numpy float32 when want_loss, else None.  Bad arguments raise
-        ValueError before the library is called; a malformed device list or an id outside its table IndexError."""
+        ValueError before the library is called; a malformed device list or an id outside its table IndexError.
+        labels= with pid=None (orx_seqrec_full_sets_step): a label SET per bag under the multinomial likelihood,
+        l_i = T_i lse_i - sum_e t_e s_{i,j_e} -- Mult-DAE's objective.  labels is (ptr, items), ragged, no host synchronisation
+        wherever it lives, or the padded pair (seq, seq_len); label_weights: t_e per entry (None: 1).  An empty set keeps the
+        sample live with its l2 part alone; passing both pid and labels, or neither, raises."""
         what = "SeqRec.step_full"
         mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
         l2c = _coef_arg(what, "l2_reg", l2_reg)
-        B, n, dev, ptrs, scale, ci, cs, keep = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items, chunk_samples)
+        B, n, dev, ptrs, scale, ci, cs, keep, sets = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items,
+                                                                      chunk_samples, labels, label_weights)
         out, lp, l2p = _loss_outputs(1, want_loss)
-        check(self.ctx._lib.orx_seqrec_full_step(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
-                                                 self._denom, scale, l2c, ci, cs, mask, _flags(dev), lp, l2p))
+        fn = self.ctx._lib.orx_seqrec_full_sets_step if sets else self.ctx._lib.orx_seqrec_full_step
+        check(fn(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
+                 self._denom, scale, l2c, ci, cs, mask, _flags(dev), lp, l2p))
         _keep_tables(opt, (self.H, self.V, self.b))
         return out
 
-    def loss_full(self, bags, pid, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
+    def loss_full(self, bags, pid=None, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False, labels=None,
+                  label_weights=None):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
-        table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
+        table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
+        label_weights= as step_full takes them"""
         what = "SeqRec.loss_full"
-        B, n, dev, ptrs, scale, ci, _, keep = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items, 0)
+        B, n, dev, ptrs, scale, ci, _, keep, sets = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items, 0,
+                                                                     labels, label_weights)
         out, lp, l2p = _loss_outputs(1, True)
         rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
-        check(self.ctx._lib.orx_seqrec_full_loss(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
-                                                 self._denom, scale, ci, _flags(dev), lp, l2p, rp))
+        fn = self.ctx._lib.orx_seqrec_full_sets_loss if sets else self.ctx._lib.orx_seqrec_full_loss
+        check(fn(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
+                 self._denom, scale, ci, _flags(dev), lp, l2p, rp))
         if not per_row:
             return _loss_pair(out)
         if dev:
@@ -2585,52 +2643,57 @@ class DeepSeqRec:
             raise ValueError(f"{what}: {B} bags and side id lists of {ns} ids (one id per bag and side table)")
         return pp, pi, B, n, dev, ps, (kb, ks)
 
-    def _args_full(self, what, bags, pid, side_ids, weights, item_offset, scale, chunk_items, chunk_samples):
+    def _args_full(self, what, bags, pid, side_ids, weights, item_offset, scale, chunk_items, chunk_samples, labels=None,
+                   label_weights=None):
         scale = _scale_arg(what, scale)
         ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
         pp, pi, B, n, dev, ps, (kb, ks) = self._lists(what, bags, side_ids)
-        (ppid,), (npid,), _, keep = _id_lists(what, (pid,), dev)
-        if npid != B:
-            raise ValueError(f"{what}: {B} bags and {npid} label ids (one label per bag)")
+        plab, sets, keep = _labels_arg(what, pid, labels, label_weights, dev, B)
         pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
         po, ko = _floats_arg(what, "item_offset", item_offset, dev, self.V.rows, "the item table's rows")
-        self.ctx.after_torch(*kb, *ks, *keep, kw, ko)
+        self.ctx.after_torch(*kb, *ks, *_flat_keep(keep), kw, ko)
         for t in self._tables:
             t._sync_pending()
         model, arrays = self._model_args(ps)
-        return B, n, dev, model, (pp, pi, ppid, pw, po), scale, ci, cs, (kb, ks, keep, kw, ko, arrays)
+        return B, n, dev, model, (pp, pi, *plab, pw, po), scale, ci, cs, (kb, ks, keep, kw, ko, arrays), sets
 
-    def step_full(self, opt, bags, pid, side_ids=(), weights=None, item_offset=None, scale=1.0, l2_reg=0.0, l2_mlp=0.0, train=None,
-                  chunk_items=0, chunk_samples=0, want_loss=True):
+    def step_full(self, opt, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, l2_reg=0.0, l2_mlp=0.0, train=None,
+                  chunk_items=0, chunk_samples=0, want_loss=True, labels=None, label_weights=None):
         """One train step on the softmax over ALL items (orx_tower_step): SeqRec.step_full's objective with the query computed by
         the tower.  side_ids: one id list [B] per side table, where the bags live.  J = loss + l2_reg * l2_loss + l2_mlp * 1/2
         sum_l (|W_l|^2 + |c_l|^2), l2_loss = 1/2 (sum |x0_i|^2 + sum |V[pid_i]|^2) on the embedding outputs.  The history table
         goes SeqRec's sorted route, a side table takes the sparse rule on its id list, V, b and every W_l, c_l the optimizer's
         dense rule.  train: None, or a subset of ("history", "item", "bias", "side", "tower").  -> (loss[1], l2[1]) as numpy
         float32, l2 the unscaled l2_loss, when want_loss, else None.  Bad arguments raise ValueError before the library is
-        called; a malformed device list or an id outside its table IndexError."""
+        called; a malformed device list or an id outside its table IndexError.  labels= / label_weights= with pid=None
+        (orx_tower_sets_step): a label set per bag, as SeqRec.step_full takes them -- Mult-DAE with hidden layers."""
         what = "DeepSeqRec.step_full"
         mask = _mask_arg(what, train, _DEEP_ROLES, self.b is not None) or 0
         if mask & _ffi.ORX_TRAIN_SIDE and not self.side:
             raise ValueError(f'{what}: train: "side" named, but the model has no side table')
         l2c, l2m = _coef_arg(what, "l2_reg", l2_reg), _coef_arg(what, "l2_mlp", l2_mlp)
-        B, n, dev, model, ptrs, scale, ci, cs, keep = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale,
-                                                                       chunk_items, chunk_samples)
+        B, n, dev, model, ptrs, scale, ci, cs, keep, sets = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale,
+                                                                             chunk_items, chunk_samples, labels, label_weights)
         out, lp, l2p = _loss_outputs(1, want_loss)
-        check(self.ctx._lib.orx_tower_step(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n,
-                                           self._mode, self._denom, scale, l2c, l2m, ci, cs, mask, _flags(dev), lp, l2p))
+        fn = self.ctx._lib.orx_tower_sets_step if sets else self.ctx._lib.orx_tower_step
+        check(fn(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n,
+                 self._mode, self._denom, scale, l2c, l2m, ci, cs, mask, _flags(dev), lp, l2p))
         _keep_tables(opt, self._tables)
         return out
 
-    def loss_full(self, bags, pid, side_ids=(), weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
+    def loss_full(self, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False,
+                  labels=None, label_weights=None):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
-        table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
+        table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
+        label_weights= as step_full takes them"""
         what = "DeepSeqRec.loss_full"
-        B, n, dev, model, ptrs, scale, ci, _, keep = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale, chunk_items, 0)
+        B, n, dev, model, ptrs, scale, ci, _, keep, sets = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale,
+                                                                            chunk_items, 0, labels, label_weights)
         out, lp, l2p = _loss_outputs(1, True)
         rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
-        check(self.ctx._lib.orx_tower_loss(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n, self._mode,
-                                           self._denom, scale, ci, _flags(dev), lp, l2p, rp))
+        fn = self.ctx._lib.orx_tower_sets_loss if sets else self.ctx._lib.orx_tower_loss
+        check(fn(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n, self._mode,
+                 self._denom, scale, ci, _flags(dev), lp, l2p, rp))
         if not per_row:
             return _loss_pair(out)
         if dev:

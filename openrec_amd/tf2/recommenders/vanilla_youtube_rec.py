@@ -144,6 +144,44 @@ class VanillaYouTubeRec(Recommender):
         self._side(user_features)
         return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off)
 
+    def _label_sets(self, label_item_id, label_len, label_weight):
+        lab, ln = _ids(label_item_id), _ids(label_len)
+        shape = tuple(getattr(lab, "shape", ()))
+        if len(shape) != 2:
+            raise ValueError(f"{type(self).__name__}: label_item_id shaped {shape}; expected the padded [B, L] beside label_len [B]")
+        return (lab, ln), (_ids(label_weight) if label_weight is not None else None)
+
+    def train_steps_sets(self, optimizer, seq_item_id, seq_len, label_item_id, label_len, label_weight=None, sample_weight=None,
+                         item_offset=None, want_loss=True, train=None, **user_features):
+        """train_steps_full with a label SET per history (rt.SeqRec.step_full(labels=...) / rt.DeepSeqRec.step_full(labels=...)):
+        the multinomial likelihood of the history's whole set of items over ALL items, in one walk of the item table -- the
+        objective of Mult-DAE.  label_item_id [B, Ll] of which label_len [B] entries count (an empty set keeps only its l2
+        part); label_weight [B, Ll]: per-entry weights (None: 1).  Everything else as train_steps_full.
+        -> (loss[1], l2[1]) as float32 arrays when want_loss, else None"""
+        opt = optimizer.native(self._net.ctx) if hasattr(optimizer, "native") else optimizer
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(item_offset) if item_offset is not None else None
+        labels, lw = self._label_sets(label_item_id, label_len, label_weight)
+        if self._deep:
+            return self._net.step_full(opt, self._bags(seq_item_id, seq_len), None, self._side(user_features), weights=wts,
+                                       item_offset=off, l2_reg=self.l2_reg, l2_mlp=self.l2_reg_mlp, train=train, want_loss=want_loss,
+                                       labels=labels, label_weights=lw)
+        self._side(user_features)
+        return self._net.step_full(opt, self._bags(seq_item_id, seq_len), None, weights=wts, item_offset=off, l2_reg=self.l2_reg,
+                                   train=train, want_loss=want_loss, labels=labels, label_weights=lw)
+
+    def loss_sets(self, seq_item_id, seq_len, label_item_id, label_len, label_weight=None, sample_weight=None, item_offset=None,
+                  **user_features):
+        """the forward of train_steps_sets alone -> (loss, l2)"""
+        wts = _ids(sample_weight) if sample_weight is not None else None
+        off = _ids(item_offset) if item_offset is not None else None
+        labels, lw = self._label_sets(label_item_id, label_len, label_weight)
+        if self._deep:
+            return self._net.loss_full(self._bags(seq_item_id, seq_len), None, self._side(user_features), weights=wts, item_offset=off,
+                                       labels=labels, label_weights=lw)
+        self._side(user_features)
+        return self._net.loss_full(self._bags(seq_item_id, seq_len), None, weights=wts, item_offset=off, labels=labels, label_weights=lw)
+
     def _tables(self, flush=True):
         """what the scoring paths see: (the pooled rows of the histories last handed over, V, b)"""
         if self._history is None:
