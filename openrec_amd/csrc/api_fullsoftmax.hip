@@ -1,14 +1,14 @@
-// C-ABI entry points of the softmax over all items with a user table: orx_fullsoftmax_step, orx_fullsoftmax_loss and
-// orx_fullsoftmax_geometry (include/openrec_hip.h has the semantics, kernels_fullsoftmax.hip the kernels; the SeqRec form,
-// orx_seqrec_full_step / orx_seqrec_full_loss, is in api_seqrec.hip and shares the checks and the scratch layout below; so do the
-// label-set entry points of api_seqrec.hip and api_tower.hip, whose own checks, layout and bind are here as well).
+// The softmax over all items: the two host drivers every call on this objective goes through (orx_fullsoftmax_drive_step /
+// orx_fullsoftmax_drive_loss; orx_internal.h has the query form they take), the checks, scratch layout and bind of the objective
+// and of the label sets, and the C-ABI entry points of the user-table form: orx_fullsoftmax_step, orx_fullsoftmax_loss and
+// orx_fullsoftmax_geometry (include/openrec_hip.h has the semantics, kernels_fullsoftmax.hip and kernels_labelsets.hip the
+// kernels; the bag form is in api_seqrec.hip, the tower form in api_tower.hip).
 //
-// Per step: the item table and the bias are read in full, so a lazily applied Adam on them is finished first and they leave the
-// lazy set; the user rows are touched; the forward (prepare, item copy, LSE pass, finalize), the gradient passes (a walk and a
-// finishing pass per side), [Adam: the counter advances], then orx_apply_rows of the user table with uid and the DENSE rule of the
-// optimizer on the item table and the bias (orx_table_apply_dense_at: every row has a gradient).  No kernel of the forward or the
-// gradient passes writes a table, so every gradient is taken on the pre-step tables.  The scratch of a step --
-// O((B nci + NI ncs) Dp) floats, no B x NI buffer -- is carved from the context's grow-only d_tmp and reused by every step.
+// Per step: the item table, the bias and the form's dense tables are read in full, so a lazily applied Adam on them is finished
+// first and they leave the lazy set; the form touches its rows and writes Q; the forward and the gradient passes; the form's
+// backward; [Adam: the counter advances]; the form's applies, then the DENSE rule of the optimizer on the item table and the bias
+// (orx_table_apply_dense_at: every row has a gradient).  No kernel before the applies writes a table, so every gradient is taken
+// on the pre-step tables.  The scratch of a step is carved from the context's grow-only d_tmp and reused by every step.
 #include <cmath>
 #include <cstring>
 
@@ -59,16 +59,17 @@ void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t
     }
 }
 
-int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q, int64_t NQ, orx_table* V, orx_table* b, const float* item_offset,
+int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const FullSoftmaxQuery& q, orx_table* V, orx_table* b, const float* item_offset,
                          int64_t B, float scale, float l2w, FullSoftmaxArgs* out) {
     FullSoftmaxArgs a;
     memset(&a, 0, sizeof(a));
     const FullSoftmaxPlan& p = l.plan;
-    a.Q = Q; a.V = V->w; a.b = b ? b->w : nullptr;
-    a.B = B; a.Bp = p.Bp; a.NQ = NQ; a.NI = V->rows; a.NIp = p.NIp;
+    a.Q = q.Q; a.qid = q.qid; a.V = V->w; a.b = b ? b->w : nullptr;
+    a.B = B; a.Bp = p.Bp; a.NQ = q.NQ; a.NI = V->rows; a.NIp = p.NIp;
     a.D = V->dim; a.Dp = (int)p.Dp; a.gs = (a.D + 1 + 3) & ~3;
     a.nci = (int)p.nci; a.tpi = (int)p.tpi; a.ncs = (int)p.ncs; a.tps = (int)p.tps;
     a.scale = scale; a.invB = 1.0f / (float)B; a.l2w = l2w; a.l2q = l2w; a.err = c->d_err;
+    if (q.X0) { a.l2q = 0.f; a.X0 = q.X0; a.x0w = q.x0w; a.x0ld = q.x0ld; }          // the l2 term sits on x0, not on the query
     char* base = reinterpret_cast<char*>(c->d_tmp);
     auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
     a.xq = f(l.xq); a.xv = f(l.xv);
@@ -90,12 +91,6 @@ int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask) {
     ORX_ARG((*train_mask & ~every) == 0, "%s: train mask 0x%x has bits outside ORX_TRAIN_USER | ORX_TRAIN_ITEM | ORX_TRAIN_BIAS", fn, *train_mask);
     ORX_ARG(b != nullptr || !(*train_mask & ORX_TRAIN_BIAS), "%s: ORX_TRAIN_BIAS without a bias table (bias is NULL)", fn);
     if (*train_mask == 0) *train_mask = ORX_TRAIN_USER | ORX_TRAIN_ITEM | (b ? ORX_TRAIN_BIAS : 0);
-    return ORX_OK;
-}
-
-int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a) {
-    if (tV) CHECK(orx_table_apply_dense_at(c, opt, V, a.GV));
-    if (tb) CHECK(orx_table_apply_dense_at(c, opt, b, a.Gb));
     return ORX_OK;
 }
 
@@ -150,80 +145,161 @@ extern "C" int orx_fullsoftmax_geometry(int64_t B, int64_t NI, int32_t D, int32_
     return ORX_OK;
 }
 
-extern "C" int orx_fullsoftmax_step(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
-                                    const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
-                                    int64_t B, float scale, float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,
-                                    float* loss_out, float* l2_out) {
-    static const char* fn = "orx_fullsoftmax_step";
-    CHECK(orx_check_dot_step(fn, c, opt, U, V, b, 0, 1, B, B, l2_reg, flags, FS_FLAGS));
-    CHECK(orx_fullsoftmax_check(fn, B, V->rows, U->dim, scale, chunk_items, chunk_samples));
-    CHECK(orx_fullsoftmax_mask(fn, b, &train_mask));
-    CHECK(orx_check_apply_rows_opt(opt, U, nullptr));
-    if (B == 0) return ORX_OK;
-    ORX_ARG(uid && pid, "%s: NULL id pointer", fn);
+// ---- the drivers
+namespace {
+
+// what a step and a forward share once their checks have passed: the NULL-id refusal, the lists on the device, the scratch of the
+// form, of the full softmax and of the label sets in d_tmp, and the kernels' arguments (partial is the caller's to set per call)
+int prepare(orx_ctx* c, FullSoftmaxForm& f, orx_table* V, orx_table* b, const int32_t* pid, const LabelLists* sets, const float* weight,
+            const float* item_offset, int64_t B, float scale, float l2w, int32_t chunk_items, int32_t chunk_samples, bool grads, bool item_side, int flags,
+            FullSoftmaxArgs* a, LabelSetArgs* ls) {
+    ORX_ARG((sets || pid) && (!f.has_ids || f.ids), "%s: NULL id pointer", f.fn);
     ORX_HIP(hipSetDevice(c->device));
     const bool host = !(flags & ORX_IDS_DEVICE);
-    const bool tU = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
-
     StepInputs in;
-    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}}, {{weight, 1}}, &in));
+    if (f.has_ids) CHECK(orx_stage_steps(c, 1, B, B, flags, {{f.ids, 1}, {pid, 1}}, {{weight, 1}}, &in));
+    else CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
     Carve cv;
+    f.carve(&cv, grads);
     FullSoftmaxLayout lay;
-    orx_fullsoftmax_layout(&cv, B, V->rows, U->dim, chunk_items, chunk_samples, true, tU, tV || tb, host && item_offset, &lay);
+    orx_fullsoftmax_layout(&cv, B, V->rows, V->dim, chunk_items, chunk_samples, grads, grads && f.query_side, item_side, host && item_offset, &lay);
+    LabelSetLayout llay;
+    if (sets) orx_labelsets_layout(&cv, B, V->dim, sets->n, host, host && sets->weight, grads, &llay);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
+    FullSoftmaxQuery q;
+    memset(&q, 0, sizeof(q));
+    q.qid = f.has_ids ? in.id[0] : nullptr;
+    CHECK(f.bind(grads, &q));
+    CHECK(orx_fullsoftmax_bind(c, lay, q, V, b, item_offset, B, scale, l2w, a));
+    a->pid = in.id[f.has_ids ? 1 : 0]; a->wt = in.f[0];
+    if (sets) CHECK(orx_labelsets_bind(c, llay, *a, sets->ptr, sets->items, sets->weight, sets->n, host, grads, ls));
+    return ORX_OK;
+}
+
+}  // namespace
+
+int orx_fullsoftmax_drive_step(orx_ctx* c, orx_opt* opt, FullSoftmaxForm& f, orx_table* V, orx_table* b, const int32_t* pid, const LabelLists* sets,
+                               const float* weight, const float* item_offset, int64_t B, float scale, float l2_reg, int32_t chunk_items,
+                               int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
+    const char* fn = f.fn;
+    CHECK(f.check());
+    CHECK(orx_fullsoftmax_check(fn, B, V->rows, V->dim, scale, chunk_items, chunk_samples));
+    CHECK(f.train(&train_mask));
+    for (int i = 0; i < f.n_tab; ++i)
+        if (!f.tab[i].dense) CHECK(orx_check_apply_rows_opt(opt, f.tab[i].t, nullptr));
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
+    if (B == 0) return ORX_OK;
+    const bool tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
     FullSoftmaxArgs a;
-    CHECK(orx_fullsoftmax_bind(c, lay, U->w, U->rows, V, b, item_offset, B, scale, l2_reg, &a));
-    a.qid = in.id[0]; a.pid = in.id[1]; a.wt = in.f[0];
-    // the item table and the bias are read in full: every row current, and they leave the lazy set; a user table outside the mask
-    // is finished under the old counter as well, then only read
-    orx_table* keep[3]; int n_keep = 0;
-    if (tU) keep[n_keep++] = U; else CHECK(orx_table_sync(U));
+    LabelSetArgs ls;
+    CHECK(prepare(c, f, V, b, pid, sets, weight, item_offset, B, scale, l2_reg, chunk_items, chunk_samples, true, tV || tb, flags, &a, &ls));
+    // One rule for every table: V, b and the form's dense tables are read in full -- every row current, out of the lazy set; a table
+    // outside the mask is finished under the old counter (whatever optimizer it is lazy under), then only read
+    orx_table* keep[2 + sizeof(f.tab) / sizeof(f.tab[0])]; int n_keep = 0;
+    for (int i = 0; i < f.n_tab; ++i)
+        if (!f.tab[i].dense) { if (f.tab[i].trained) keep[n_keep++] = f.tab[i].t; else CHECK(orx_table_sync(f.tab[i].t)); }
     CHECK(orx_table_sync(V)); CHECK(orx_table_sync(b));
     if (tV) keep[n_keep++] = V;
     if (b && tb) keep[n_keep++] = b;
+    for (int i = 0; i < f.n_tab; ++i)
+        if (f.tab[i].dense) { CHECK(orx_table_sync(f.tab[i].t)); if (f.tab[i].t && f.tab[i].trained) keep[n_keep++] = f.tab[i].t; }
 
-    return orx_run_steps(c, 1, orx_fullsoftmax_npartials(B), flags, loss_out, l2_out, nullptr, [&](int64_t, int64_t, float* partial) -> int {
+    const int rc = orx_run_steps(c, 1, orx_fullsoftmax_npartials(B), flags, loss_out, l2_out, nullptr, [&](int64_t, int64_t, float* partial) -> int {
         a.partial = partial;
-        CHECK(orx_table_touch(U, a.qid, B));
-        CHECK(orx_launch_fullsoftmax_forward(c, a));
-        CHECK(orx_launch_fullsoftmax_grads(c, a, tU, tV || tb));
+        CHECK(f.produce(a, true));
+        if (sets) {                         // (after the form has taken its pairs: the label entries are sorted by item on the same buffers)
+            ls.fs = a;
+            CHECK(orx_launch_labelsets_forward(c, ls));
+            CHECK(orx_launch_labelsets_grads(c, ls, f.query_side, tV || tb));
+        } else {
+            CHECK(orx_launch_fullsoftmax_forward(c, a));
+            CHECK(orx_launch_fullsoftmax_grads(c, a, f.query_side, tV || tb));
+        }
+        if (f.backward) CHECK(f.backward());
         if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
-        if (tU) CHECK(orx_apply_rows(c, opt, U, nullptr, a.qid, B, a.gu, a.gs));
-        return orx_fullsoftmax_apply_items(c, opt, V, b, tV, tb, a);
+        CHECK(f.apply(a));
+        if (tV) CHECK(orx_table_apply_dense_at(c, opt, V, a.GV));
+        if (tb) CHECK(orx_table_apply_dense_at(c, opt, b, a.Gb));
+        return ORX_OK;
     });
+    CHECK(rc);
+    // device lists whose caller took the losses: the call has synchronised, so the index flag is looked at here as well
+    if (f.index_flag && !host && (loss_out || l2_out)) return orx_check_index_error(c);
+    return ORX_OK;
 }
 
-extern "C" int orx_fullsoftmax_loss(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b,
-                                    const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
-                                    int64_t B, float scale, int32_t chunk_items, int flags, float* loss_out, float* l2_out, float* row_loss_out) {
-    static const char* fn = "orx_fullsoftmax_loss";
-    CHECK(orx_check_dot_model(fn, c, U, V, b, 0, flags, FS_FLAGS));
-    CHECK(orx_fullsoftmax_check(fn, B, V->rows, U->dim, scale, chunk_items, 0));
-    ORX_ARG(!(flags & ORX_NO_L2), "%s: ORX_NO_L2 belongs to the step (the forward has no objective)", fn);
+int orx_fullsoftmax_drive_loss(orx_ctx* c, FullSoftmaxForm& f, orx_table* V, orx_table* b, const int32_t* pid, const LabelLists* sets,
+                               const float* weight, const float* item_offset, int64_t B, float scale, int32_t chunk_items, int flags,
+                               float* loss_out, float* l2_out, float* row_loss_out) {
+    const char* fn = f.fn;
+    CHECK(f.check());
+    CHECK(orx_fullsoftmax_check(fn, B, V->rows, V->dim, scale, chunk_items, 0));
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
     if (B == 0) {
         if (loss_out) *loss_out = 0.f;
         if (l2_out) *l2_out = 0.f;
         return ORX_OK;
     }
-    ORX_ARG(uid && pid, "%s: NULL id pointer", fn);
-    ORX_HIP(hipSetDevice(c->device));
-    const bool host = !(flags & ORX_IDS_DEVICE);
-    StepInputs in;
-    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}}, {{weight, 1}}, &in));
-    Carve cv;
-    FullSoftmaxLayout lay;
-    orx_fullsoftmax_layout(&cv, B, V->rows, U->dim, chunk_items, 0, false, false, false, host && item_offset, &lay);
-    ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     FullSoftmaxArgs a;
-    CHECK(orx_fullsoftmax_bind(c, lay, U->w, U->rows, V, b, item_offset, B, scale, 0.f, &a));
-    a.qid = in.id[0]; a.pid = in.id[1]; a.wt = in.f[0];
+    LabelSetArgs ls;
+    CHECK(prepare(c, f, V, b, pid, sets, weight, item_offset, B, scale, 0.f, chunk_items, 0, false, false, flags, &a, &ls));
     return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
         a.partial = partial;
-        CHECK(orx_table_sync(V)); CHECK(orx_table_sync(b));
-        CHECK(orx_table_touch(U, a.qid, B));
-        CHECK(orx_launch_fullsoftmax_forward(c, a));
+        CHECK(orx_table_sync(V)); CHECK(orx_table_sync(b));         // what is read in full: every row current
+        for (int i = 0; i < f.n_tab; ++i)
+            if (f.tab[i].dense) CHECK(orx_table_sync(f.tab[i].t));
+        CHECK(f.produce(a, false));
+        if (sets) { ls.fs = a; CHECK(orx_launch_labelsets_forward(c, ls)); }
+        else CHECK(orx_launch_fullsoftmax_forward(c, a));
         if (row_loss_out)
             ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
         return ORX_OK;
     });
+}
+
+// ---- the user-table form: Q is the user table itself, qid the staged uid
+namespace {
+
+// is_step: the step's checks (opt among them); otherwise the forward's
+void user_form(FullSoftmaxForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, const int32_t* uid,
+               int64_t B, float l2_reg, int flags) {
+    f->fn = fn; f->has_ids = true; f->ids = uid; f->index_flag = false; f->query_side = false;
+    f->n_tab = 1; f->tab[0] = {U, false, false};
+    f->check = [=]() -> int {
+        if (is_step) return orx_check_dot_step(fn, c, opt, U, V, b, 0, 1, B, B, l2_reg, flags, FS_FLAGS);
+        CHECK(orx_check_dot_model(fn, c, U, V, b, 0, flags, FS_FLAGS));
+        ORX_ARG(!(flags & ORX_NO_L2), "%s: ORX_NO_L2 belongs to the step (the forward has no objective)", fn);
+        return ORX_OK;
+    };
+    f->train = [=](int* mask) -> int {
+        CHECK(orx_fullsoftmax_mask(fn, b, mask));
+        f->tab[0].trained = f->query_side = (*mask & ORX_TRAIN_USER) != 0;
+        return ORX_OK;
+    };
+    f->carve = [](Carve*, bool) {};
+    f->bind = [=](bool, FullSoftmaxQuery* q) -> int { q->Q = U->w; q->NQ = U->rows; return ORX_OK; };
+    f->produce = [=](const FullSoftmaxArgs& a, bool) -> int { return orx_table_touch(U, a.qid, B); };
+    f->apply = [=](const FullSoftmaxArgs& a) -> int { return f->query_side ? orx_apply_rows(c, opt, U, nullptr, a.qid, B, a.gu, a.gs) : ORX_OK; };
+}
+
+}  // namespace
+
+extern "C" int orx_fullsoftmax_step(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
+                                    const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
+                                    int64_t B, float scale, float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,
+                                    float* loss_out, float* l2_out) {
+    FullSoftmaxForm f;
+    user_form(&f, "orx_fullsoftmax_step", true, c, opt, U, V, b, uid, B, l2_reg, flags);
+    return orx_fullsoftmax_drive_step(c, opt, f, V, b, pid, nullptr, weight, item_offset, B, scale, l2_reg, chunk_items, chunk_samples, train_mask, flags,
+                                      loss_out, l2_out);
+}
+
+extern "C" int orx_fullsoftmax_loss(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b,
+                                    const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
+                                    int64_t B, float scale, int32_t chunk_items, int flags, float* loss_out, float* l2_out, float* row_loss_out) {
+    FullSoftmaxForm f;
+    user_form(&f, "orx_fullsoftmax_loss", false, c, nullptr, U, V, b, uid, B, 0.f, flags);
+    return orx_fullsoftmax_drive_loss(c, f, V, b, pid, nullptr, weight, item_offset, B, scale, chunk_items, flags, loss_out, l2_out, row_loss_out);
 }

@@ -1,18 +1,19 @@
 // C-ABI entry points of the history-pooled sequence recommender: orx_bag_pool, orx_seqrec_step and orx_seqrec_loss
-// (include/openrec_hip.h has the semantics, kernels_bag.hip the kernels), and at the end of the file orx_seqrec_full_step and
-// orx_seqrec_full_loss, the softmax over all items with the pooled vector as the query (kernels_fullsoftmax.hip), with
-// orx_seqrec_full_sets_step / orx_seqrec_full_sets_loss, the same with a label set per sample (kernels_labelsets.hip).
+// (include/openrec_hip.h has the semantics, kernels_bag.hip the kernels); what every call over bags shares -- the checks, the
+// scratch layout and bind of the lists (BagLayout), the two halves of a step's history side (orx_bag_produce, orx_bag_apply);
+// and at the end of the file the bag form of the softmax over all items: orx_seqrec_full_step / orx_seqrec_full_loss and, with
+// a label set per sample, orx_seqrec_full_sets_step / orx_seqrec_full_sets_loss (the drivers are in api_fullsoftmax.hip).
 //
-// The step is orx_multineg_step with the user row replaced by a pooled vector.  Per step: bag_items is sorted by row
-// (orx_rows_sort) and the lazy history rows are touched on the sorted list; pid and nid are touched as orx_multineg_step does;
-// the pool writes Q [B][D] into scratch, an id list uid'[i] = i (-1: a dead bag), c_i and the owner of every list position; ONE
-// gradient launch (orx_launch_multineg with U = Q, NU = B, uid = uid') writes per-occurrence gradient rows and pid | nid;
-// [Adam: the counter advances]; g_q[i] is scaled by c_i in place; every sorted pair's position is replaced by its owner, and
-// orx_apply_rows_sorted sums a history row's occurrences in list order out of the B rows
-// of g_q -- the n x D occurrence rows never exist; then orx_apply_rows of the item table and the bias with pid | nid, as
-// orx_multineg_step applies them.  No kernel before the applies writes a table, so every gradient is taken on the pre-step tables.
-// With a train mask that leaves the item table or the bias out, the two are applied as tables of their own on one sort of the
-// list (as orx_vbpr_step does).  Scratch is carved from the context's grow-only d_tmp: O(n) words and O(B (1 + N) D).
+// orx_seqrec_step is orx_multineg_step with the user row replaced by a pooled vector.  Per step: bag_items is sorted by row
+// (orx_rows_sort) and the lazy history rows are touched on the sorted list; the pool writes Q [B][D] into scratch, an id list
+// uid'[i] = i (-1: a dead bag), c_i and the owner of every list position; every sorted pair's position is replaced by its owner;
+// pid and nid are touched as orx_multineg_step does; ONE gradient launch (orx_launch_multineg with U = Q, NU = B, uid = uid')
+// writes per-occurrence gradient rows and pid | nid; [Adam: the counter advances]; g_q[i] is scaled by c_i in place and
+// orx_apply_rows_sorted sums a history row's occurrences in list order out of the B rows of g_q -- the n x D occurrence rows
+// never exist; then orx_apply_rows of the item table and the bias with pid | nid, as orx_multineg_step applies them.  No kernel
+// before the applies writes a table, so every gradient is taken on the pre-step tables.  With a train mask that leaves the item
+// table or the bias out, the two are applied as tables of their own on one sort of the list (as orx_vbpr_step does).  Scratch is
+// carved from the context's grow-only d_tmp: O(n) words and O(B (1 + N) D).
 #include <cmath>
 #include <cstring>
 
@@ -67,13 +68,29 @@ int orx_bag_stage(orx_ctx* c, const int32_t* bag_ptr, const int32_t* bag_items, 
     return ORX_OK;
 }
 
-BagArgs orx_bag_args(orx_ctx* c, orx_table* H, int64_t B, int64_t n, int mode, float denom) {
+void orx_bag_layout(Carve* cv, int64_t B, int64_t n, bool host, int keep, BagLayout* l) {
+    memset(l, 0, sizeof(*l));
+    l->keep = keep;
+    if (keep >= ORX_BAG_FORWARD) l->uid = cv->take((size_t)B * sizeof(int32_t));
+    if (host) { l->ptr = cv->take((size_t)(B + 1) * sizeof(int32_t)); l->items = cv->take((size_t)n * sizeof(int32_t)); }
+    if (keep >= ORX_BAG_STEP) { l->coef = cv->take((size_t)B * sizeof(float)); l->owner = cv->take((size_t)n * sizeof(int32_t)); l->pairs = cv->take((size_t)n * sizeof(uint2)); }
+}
+
+int orx_bag_bind(orx_ctx* c, const BagLayout& l, orx_table* H, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode,
+                 float denom, bool host, BagArgs* out, uint2** pairs) {
+    char* base = reinterpret_cast<char*>(c->d_tmp);
+    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
     BagArgs a;
     memset(&a, 0, sizeof(a));
     a.H = H->w; a.rows = H->rows; a.D = H->dim; a.B = B; a.n = n; a.mode = mode;
     a.inv_denom = mode == ORX_BAG_FIXED ? 1.0f / denom : 0.f;
     a.err = c->d_err;
-    return a;
+    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, i32(l.ptr), i32(l.items), &a));
+    if (l.keep >= ORX_BAG_FORWARD) a.uid = i32(l.uid);
+    if (l.keep >= ORX_BAG_STEP) { a.coef = reinterpret_cast<float*>(base + l.coef); a.owner = i32(l.owner); }
+    if (pairs) *pairs = l.keep >= ORX_BAG_STEP ? reinterpret_cast<uint2*>(base + l.pairs) : nullptr;
+    *out = a;
+    return ORX_OK;
 }
 
 // The rows of H the bags read, brought up to date where H is lazily applied under Adam: on the sorted list -- a radix sort of the n
@@ -89,6 +106,21 @@ int orx_bag_touch(orx_ctx* c, orx_table* H, const int32_t* items, int64_t n, boo
     return ORX_OK;
 }
 
+// ONE sort of bag_items serves the touch of the history rows and, its positions rewritten to their owners right after the producing
+// launch (before anything else may sort), the apply.  A history table outside the mask is current: no touch, no sort
+int orx_bag_produce(orx_ctx* c, orx_table* H, const BagArgs& bag, uint2* pairs, const std::function<int()>& launch) {
+    const uint2* sorted = nullptr;
+    CHECK(orx_bag_touch(c, H, bag.items, bag.n, pairs != nullptr, pairs ? &sorted : nullptr));
+    CHECK(launch());
+    if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, bag.owner, bag.n, bag.B, pairs));
+    return ORX_OK;
+}
+
+int orx_bag_apply(orx_ctx* c, orx_opt* opt, orx_table* H, const BagArgs& bag, const uint2* pairs, float* g, int col0, int ld) {
+    CHECK(orx_launch_bag_scale_rows(c, g + col0, bag.coef, bag.B, bag.D, ld));
+    return orx_apply_rows_sorted(c, opt, H, pairs, bag.n, g + col0, ld);
+}
+
 namespace {
 
 // scratch of the step and of the forward (grads == false: the pooled rows and the lists alone)
@@ -100,31 +132,26 @@ int make_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b, con
     const int64_t nI = B * (1 + (int64_t)N);
     Carve cv;
     const size_t o_q = cv.take((size_t)B * D * sizeof(float));
-    const size_t o_uid = cv.take((size_t)B * sizeof(int32_t));
-    const size_t o_ptr = host ? cv.take((size_t)(B + 1) * sizeof(int32_t)) : 0, o_items = host ? cv.take((size_t)n * sizeof(int32_t)) : 0;
-    size_t o_coef = 0, o_owner = 0, o_pairs = 0, o_list = 0, o_gu = 0, o_gi = 0, o_isorted = 0;
+    BagLayout bl;
+    orx_bag_layout(&cv, B, n, host, grads ? ORX_BAG_STEP : ORX_BAG_FORWARD, &bl);
+    size_t o_list = 0, o_gu = 0, o_gi = 0, o_isorted = 0;
     if (grads) {
-        o_coef = cv.take((size_t)B * sizeof(float)); o_owner = cv.take((size_t)n * sizeof(int32_t)); o_pairs = cv.take((size_t)n * sizeof(uint2));
         o_list = cv.take((size_t)nI * sizeof(int32_t)); o_gu = cv.take((size_t)B * gs * sizeof(float)); o_gi = cv.take((size_t)nI * gs * sizeof(float));
         if (item_sorted) o_isorted = cv.take((size_t)nI * sizeof(uint2));
     }
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     char* base = reinterpret_cast<char*>(c->d_tmp);
     auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
     Scratch s;
     memset(&s, 0, sizeof(s));
-    s.bag = orx_bag_args(c, hist, B, n, mode, denom);
-    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
-    s.bag.out = f(o_q); s.bag.uid = i32(o_uid);
+    CHECK(orx_bag_bind(c, bl, hist, bag_ptr, bag_items, B, n, mode, denom, host, &s.bag, &s.pairs));
+    s.bag.out = f(o_q);
     MultiNegArgs& a = s.mn;
-    a.U = f(o_q); a.V = item->w; a.b = b ? b->w : nullptr; a.uid = i32(o_uid);
+    a.U = f(o_q); a.V = item->w; a.b = b ? b->w : nullptr; a.uid = s.bag.uid;
     a.B = B; a.NU = B; a.NI = item->rows; a.N = N; a.D = D; a.gs = gs;
     a.invB = 1.0f / (float)B; a.l2w = l2w; a.err = c->d_err;
     if (grads) {
-        s.bag.coef = f(o_coef); s.bag.owner = i32(o_owner);
-        s.pairs = reinterpret_cast<uint2*>(base + o_pairs);
-        a.list = i32(o_list); a.gu = f(o_gu); a.gi = f(o_gi);
+        a.list = reinterpret_cast<int32_t*>(base + o_list); a.gu = f(o_gu); a.gi = f(o_gi);
         if (item_sorted) s.isorted = reinterpret_cast<uint2*>(base + o_isorted);
     }
     *out = s;
@@ -150,11 +177,11 @@ extern "C" int orx_bag_pool(orx_ctx* c, orx_table* H, const int32_t* bag_ptr, co
     ORX_HIP(hipSetDevice(c->device));
     CHECK(orx_table_sync(out));
     Carve cv;
-    const size_t o_ptr = cv.take((size_t)(B + 1) * sizeof(int32_t)), o_items = cv.take((size_t)n * sizeof(int32_t));
-    if (host) ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
-    char* base = reinterpret_cast<char*>(c->d_tmp);
-    BagArgs a = orx_bag_args(c, H, B, n, mode, denom);
-    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, reinterpret_cast<int32_t*>(base + o_ptr), reinterpret_cast<int32_t*>(base + o_items), &a));
+    BagLayout bl;
+    orx_bag_layout(&cv, B, n, host, ORX_BAG_STAGED, &bl);
+    if (host) ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);          // (device lists pass through: no scratch, and d_tmp is not touched)
+    BagArgs a;
+    CHECK(orx_bag_bind(c, bl, H, bag_ptr, bag_items, B, n, mode, denom, host, &a, nullptr));
     a.out = out->w + (size_t)out_row0 * out->dim;
     CHECK(orx_bag_touch(c, H, a.items, n, false, nullptr));
     CHECK(orx_launch_bag_pool(c, a));
@@ -200,19 +227,11 @@ extern "C" int orx_seqrec_step(orx_ctx* c, int kind, orx_opt* opt, orx_table* hi
 
     const int rc = orx_run_steps(c, 1, orx_multineg_nwaves(c, D, B), flags, loss_out, l2_out, nullptr, [&](int64_t, int64_t, float* partial) -> int {
         a.partial = partial;
-        // ONE sort of bag_items serves the touch of the history rows and, its positions rewritten to their owners right after the
-        // pool (before anything else may sort), the apply.  A history table outside the mask is current: no touch, no sort
-        const uint2* sorted = nullptr;
-        CHECK(orx_bag_touch(c, hist, s.bag.items, n, tH, &sorted));
-        CHECK(orx_launch_bag_pool(c, s.bag));
-        if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, s.bag.owner, n, B, s.pairs));
+        CHECK(orx_bag_produce(c, hist, s.bag, tH ? s.pairs : nullptr, [&]() { return orx_launch_bag_pool(c, s.bag); }));
         CHECK(orx_touch_step(nullptr, item, b, nullptr, 0, a.pid, B, a.nid, B * N));
         CHECK(orx_launch_multineg(c, kind, true, a));
         if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
-        if (tH && n > 0) {
-            CHECK(orx_launch_bag_scale_rows(c, a.gu, s.bag.coef, B, D, gs));
-            CHECK(orx_apply_rows_sorted(c, opt, hist, s.pairs, n, a.gu, gs));
-        }
+        if (tH && n > 0) CHECK(orx_bag_apply(c, opt, hist, s.bag, s.pairs, a.gu, 0, gs));
         if (item_joint) return orx_apply_rows(c, opt, item, b, a.list, nI, a.gi, gs);
         if (tV || tb) {                     // one sort of pid | nid, each table on its own
             CHECK(orx_rows_sort_keep(c, a.list, 1, nI, nI, item->rows, s.isorted));
@@ -259,161 +278,66 @@ extern "C" int orx_seqrec_loss(orx_ctx* c, int kind, orx_table* hist, orx_table*
     });
 }
 
-// ---- the softmax over ALL items with the pooled vector as the query (kernels_fullsoftmax.hip; api_fullsoftmax.hip has the
-// user-table form and the shared checks and scratch layout).  The pool writes Q [B][D] and uid'[i] = i into scratch; the kernels
-// take Q as their query table with NQ = B.  The history side is orx_seqrec_step's route; the item table and the bias are read in
-// full -- finished first, out of the lazy set -- and take the dense rule.
+// ---- the softmax over ALL items with the pooled vector as the query: the bag form of api_fullsoftmax.hip's drivers.  The pool
+// writes Q [B][D] and uid'[i] = i into scratch; the kernels take Q as their query table with NQ = B.  The history side is
+// orx_seqrec_step's route
 namespace {
 
-struct FullScratch { BagArgs bag; FullSoftmaxArgs fs; uint2* pairs; LabelSetArgs ls; };
+struct BagForm : FullSoftmaxForm { BagLayout bl; size_t o_q; BagArgs bag; uint2* pairs; bool tH; };
 
-int make_full_scratch(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b, const int32_t* bag_ptr, const int32_t* bag_items,
-                      const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2w, int32_t chunk_items,
-                      int32_t chunk_samples, bool host, bool grads, bool query_side, bool item_side, const LabelLists* sets, FullScratch* out) {
-    const int D = hist->dim;
-    Carve cv;
-    const size_t o_q = cv.take((size_t)B * D * sizeof(float));
-    const size_t o_uid = cv.take((size_t)B * sizeof(int32_t));
-    const size_t o_ptr = host ? cv.take((size_t)(B + 1) * sizeof(int32_t)) : 0, o_items = host ? cv.take((size_t)n * sizeof(int32_t)) : 0;
-    size_t o_coef = 0, o_owner = 0, o_pairs = 0;
-    if (grads) { o_coef = cv.take((size_t)B * sizeof(float)); o_owner = cv.take((size_t)n * sizeof(int32_t)); o_pairs = cv.take((size_t)n * sizeof(uint2)); }
-    FullSoftmaxLayout lay;
-    orx_fullsoftmax_layout(&cv, B, item->rows, D, chunk_items, chunk_samples, grads, query_side, item_side, host && item_offset, &lay);
-    LabelSetLayout llay;
-    if (sets) orx_labelsets_layout(&cv, B, D, sets->n, host, host && sets->weight, grads, &llay);
-    ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
-    char* base = reinterpret_cast<char*>(c->d_tmp);
-    auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
-    auto i32 = [&](size_t o) { return reinterpret_cast<int32_t*>(base + o); };
-    FullScratch s;
-    memset(&s, 0, sizeof(s));
-    s.bag = orx_bag_args(c, hist, B, n, mode, denom);
-    CHECK(orx_bag_stage(c, bag_ptr, bag_items, B, n, host, i32(o_ptr), i32(o_items), &s.bag));
-    s.bag.out = f(o_q); s.bag.uid = i32(o_uid);
-    if (grads) { s.bag.coef = f(o_coef); s.bag.owner = i32(o_owner); s.pairs = reinterpret_cast<uint2*>(base + o_pairs); }
-    CHECK(orx_fullsoftmax_bind(c, lay, f(o_q), B, item, b, item_offset, B, scale, l2w, &s.fs));
-    s.fs.qid = i32(o_uid);
-    if (sets) CHECK(orx_labelsets_bind(c, llay, s.fs, sets->ptr, sets->items, sets->weight, sets->n, host, grads, &s.ls));
-    *out = s;
-    return ORX_OK;
+// is_step: the step's checks (opt among them); otherwise the forward's
+void bag_form(BagForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b, const int32_t* bag_ptr,
+              const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom, float l2_reg, int flags) {
+    const bool host = !(flags & ORX_IDS_DEVICE);
+    f->fn = fn; f->has_ids = false; f->ids = nullptr; f->index_flag = true; f->query_side = f->tH = false;
+    f->n_tab = 1; f->tab[0] = {hist, false, false};
+    f->check = [=]() -> int {
+        CHECK(check_model(fn, hist, item));
+        CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
+        if (is_step) return orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS);
+        return orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR);
+    };
+    f->train = [=](int* mask) -> int {
+        CHECK(orx_fullsoftmax_mask(fn, b, mask));
+        f->tab[0].trained = f->tH = (*mask & ORX_TRAIN_USER) != 0;
+        f->query_side = f->tH && n > 0;
+        return ORX_OK;
+    };
+    f->carve = [=](Carve* cv, bool grads) {
+        f->o_q = cv->take((size_t)B * hist->dim * sizeof(float));
+        orx_bag_layout(cv, B, n, host, grads ? ORX_BAG_STEP : ORX_BAG_FORWARD, &f->bl);
+    };
+    f->bind = [=](bool, FullSoftmaxQuery* q) -> int {
+        CHECK(orx_bag_bind(c, f->bl, hist, bag_ptr, bag_items, B, n, mode, denom, host, &f->bag, &f->pairs));
+        f->bag.out = reinterpret_cast<float*>(reinterpret_cast<char*>(c->d_tmp) + f->o_q);
+        q->Q = f->bag.out; q->NQ = B; q->qid = f->bag.uid;
+        return ORX_OK;
+    };
+    f->produce = [=](const FullSoftmaxArgs&, bool step) -> int {
+        return orx_bag_produce(c, hist, f->bag, step && f->tH ? f->pairs : nullptr, [=]() { return orx_launch_bag_pool(c, f->bag); });
+    };
+    f->apply = [=](const FullSoftmaxArgs& a) -> int { return f->query_side ? orx_bag_apply(c, opt, hist, f->bag, f->pairs, a.gu, 0, a.gs) : ORX_OK; };
 }
 
 }  // namespace
-
-// the step with one label per sample (sets NULL) or a label set per sample (pid NULL)
-static int full_step(const char* fn, orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
-                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const LabelLists* sets, const float* weight,
-                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
-                     int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
-    CHECK(check_model(fn, hist, item));
-    const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
-    CHECK(orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS));
-    CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, chunk_samples));
-    CHECK(orx_fullsoftmax_mask(fn, b, &train_mask));
-    CHECK(orx_check_apply_rows_opt(opt, hist, nullptr));
-    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
-    if (B == 0) return ORX_OK;
-    ORX_ARG(sets || pid, "%s: NULL id pointer", fn);
-    ORX_HIP(hipSetDevice(c->device));
-    const bool tH = (train_mask & ORX_TRAIN_USER) != 0, tV = (train_mask & ORX_TRAIN_ITEM) != 0, tb = (train_mask & ORX_TRAIN_BIAS) != 0;
-
-    StepInputs in;
-    CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
-    FullScratch s;
-    CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, l2_reg, chunk_items, chunk_samples, host,
-                            true, tH && n > 0, tV || tb, sets, &s));
-    FullSoftmaxArgs& a = s.fs;
-    a.pid = in.id[0]; a.wt = in.f[0];
-    const int gs = a.gs, D = a.D;
-    // the item table and the bias are read in full: every row current, out of the lazy set; a history table outside the mask is
-    // finished under the old counter (whatever optimizer it is lazy under), then only read
-    orx_table* keep[3]; int n_keep = 0;
-    if (tH) keep[n_keep++] = hist; else CHECK(orx_table_sync(hist));
-    CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
-    if (tV) keep[n_keep++] = item;
-    if (b && tb) keep[n_keep++] = b;
-
-    const int rc = orx_run_steps(c, 1, orx_fullsoftmax_npartials(B), flags, loss_out, l2_out, nullptr, [&](int64_t, int64_t, float* partial) -> int {
-        a.partial = partial;
-        // ONE sort of bag_items serves the touch of the history rows and, its positions rewritten to their owners right after the
-        // pool (before anything else may sort), the apply -- as orx_seqrec_step has it
-        const uint2* sorted = nullptr;
-        CHECK(orx_bag_touch(c, hist, s.bag.items, n, tH, &sorted));
-        CHECK(orx_launch_bag_pool(c, s.bag));
-        if (sorted) CHECK(orx_launch_bag_owner_pairs(c, sorted, s.bag.owner, n, B, s.pairs));
-        if (sets) {                         // (after the pairs are taken: the label entries are sorted by item on the same buffers)
-            s.ls.fs = a;
-            CHECK(orx_launch_labelsets_forward(c, s.ls));
-            CHECK(orx_launch_labelsets_grads(c, s.ls, tH && n > 0, tV || tb));
-        } else {
-            CHECK(orx_launch_fullsoftmax_forward(c, a));
-            CHECK(orx_launch_fullsoftmax_grads(c, a, tH && n > 0, tV || tb));
-        }
-        if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
-        if (tH && n > 0) {
-            CHECK(orx_launch_bag_scale_rows(c, a.gu, s.bag.coef, B, D, gs));
-            CHECK(orx_apply_rows_sorted(c, opt, hist, s.pairs, n, a.gu, gs));
-        }
-        return orx_fullsoftmax_apply_items(c, opt, item, b, tV, tb, a);
-    });
-    CHECK(rc);
-    // device lists whose caller took the losses: the call has synchronised, so the index flag is looked at here as well
-    if (!host && (loss_out || l2_out)) return orx_check_index_error(c);
-    return ORX_OK;
-}
-
-static int full_loss(const char* fn, orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
-                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const LabelLists* sets, const float* weight,
-                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items,
-                     int flags, float* loss_out, float* l2_out, float* row_loss_out) {
-    CHECK(check_model(fn, hist, item));
-    const bool host = !(flags & ORX_IDS_DEVICE);
-    CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
-    CHECK(orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR));
-    CHECK(orx_fullsoftmax_check(fn, B, item->rows, hist->dim, scale, chunk_items, 0));
-    if (sets) CHECK(orx_labelsets_check(fn, sets->ptr, sets->items, B, sets->n, host));
-    if (B == 0) {
-        if (loss_out) *loss_out = 0.f;
-        if (l2_out) *l2_out = 0.f;
-        return ORX_OK;
-    }
-    ORX_ARG(sets || pid, "%s: NULL id pointer", fn);
-    ORX_HIP(hipSetDevice(c->device));
-    StepInputs in;
-    CHECK(orx_stage_steps(c, 1, B, B, flags, {{pid, 1}}, {{weight, 1}}, &in));
-    FullScratch s;
-    CHECK(make_full_scratch(c, hist, item, b, bag_ptr, bag_items, item_offset, B, n, mode, denom, scale, 0.f, chunk_items, 0, host, false, false, false,
-                            sets, &s));
-    FullSoftmaxArgs& a = s.fs;
-    a.pid = in.id[0]; a.wt = in.f[0];
-    return orx_run_forward(c, orx_fullsoftmax_npartials(B), loss_out, l2_out, [&](float* partial) -> int {
-        a.partial = partial;
-        CHECK(orx_table_sync(item)); CHECK(orx_table_sync(b));
-        CHECK(orx_bag_touch(c, hist, s.bag.items, n, false, nullptr));
-        CHECK(orx_launch_bag_pool(c, s.bag));
-        if (sets) { s.ls.fs = a; CHECK(orx_launch_labelsets_forward(c, s.ls)); }
-        else CHECK(orx_launch_fullsoftmax_forward(c, a));
-        if (row_loss_out)
-            ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
-        return ORX_OK;
-    });
-}
 
 extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
                                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
                                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,
                                     int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
-    return full_step("orx_seqrec_full_step", c, opt, hist, item, b, bag_ptr, bag_items, pid, nullptr, weight, item_offset, B, n, mode, denom, scale,
-                     l2_reg, chunk_items, chunk_samples, train_mask, flags, loss_out, l2_out);
+    BagForm f;
+    bag_form(&f, "orx_seqrec_full_step", true, c, opt, hist, item, b, bag_ptr, bag_items, B, n, mode, denom, l2_reg, flags);
+    return orx_fullsoftmax_drive_step(c, opt, f, item, b, pid, nullptr, weight, item_offset, B, scale, l2_reg, chunk_items, chunk_samples, train_mask,
+                                      flags, loss_out, l2_out);
 }
 
 extern "C" int orx_seqrec_full_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
                                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
                                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items,
                                     int flags, float* loss_out, float* l2_out, float* row_loss_out) {
-    return full_loss("orx_seqrec_full_loss", c, hist, item, b, bag_ptr, bag_items, pid, nullptr, weight, item_offset, B, n, mode, denom, scale,
-                     chunk_items, flags, loss_out, l2_out, row_loss_out);
+    BagForm f;
+    bag_form(&f, "orx_seqrec_full_loss", false, c, nullptr, hist, item, b, bag_ptr, bag_items, B, n, mode, denom, 0.f, flags);
+    return orx_fullsoftmax_drive_loss(c, f, item, b, pid, nullptr, weight, item_offset, B, scale, chunk_items, flags, loss_out, l2_out, row_loss_out);
 }
 
 // the same with a label set per sample (kernels_labelsets.hip)
@@ -424,8 +348,10 @@ extern "C" int orx_seqrec_full_sets_step(orx_ctx* c, orx_opt* opt, orx_table* hi
                                          float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,
                                          float* loss_out, float* l2_out) {
     const LabelLists sets{lab_ptr, lab_items, lab_weight, n_lab};
-    return full_step("orx_seqrec_full_sets_step", c, opt, hist, item, b, bag_ptr, bag_items, nullptr, &sets, weight, item_offset, B, n, mode, denom,
-                     scale, l2_reg, chunk_items, chunk_samples, train_mask, flags, loss_out, l2_out);
+    BagForm f;
+    bag_form(&f, "orx_seqrec_full_sets_step", true, c, opt, hist, item, b, bag_ptr, bag_items, B, n, mode, denom, l2_reg, flags);
+    return orx_fullsoftmax_drive_step(c, opt, f, item, b, nullptr, &sets, weight, item_offset, B, scale, l2_reg, chunk_items, chunk_samples, train_mask,
+                                      flags, loss_out, l2_out);
 }
 
 extern "C" int orx_seqrec_full_sets_loss(orx_ctx* c, orx_table* hist, orx_table* item, orx_table* b,
@@ -434,6 +360,7 @@ extern "C" int orx_seqrec_full_sets_loss(orx_ctx* c, orx_table* hist, orx_table*
                                          const float* weight, const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale,
                                          int32_t chunk_items, int flags, float* loss_out, float* l2_out, float* row_loss_out) {
     const LabelLists sets{lab_ptr, lab_items, lab_weight, n_lab};
-    return full_loss("orx_seqrec_full_sets_loss", c, hist, item, b, bag_ptr, bag_items, nullptr, &sets, weight, item_offset, B, n, mode, denom, scale,
-                     chunk_items, flags, loss_out, l2_out, row_loss_out);
+    BagForm f;
+    bag_form(&f, "orx_seqrec_full_sets_loss", false, c, nullptr, hist, item, b, bag_ptr, bag_items, B, n, mode, denom, 0.f, flags);
+    return orx_fullsoftmax_drive_loss(c, f, item, b, nullptr, &sets, weight, item_offset, B, scale, chunk_items, flags, loss_out, l2_out, row_loss_out);
 }

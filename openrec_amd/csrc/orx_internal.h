@@ -1010,13 +1010,26 @@ int orx_launch_bag_pool(orx_ctx* ctx, const BagArgs& a);
 int orx_launch_bag_scale_rows(orx_ctx* ctx, float* g, const float* coef, int64_t B, int D, int gs);           // g[i][0 .. D) *= coef[i]
 int orx_launch_bag_owner_pairs(orx_ctx* ctx, const uint2* sorted, const int32_t* owner, int64_t n, int64_t B, uint2* out);   // (row, position) -> (row, owner[position])
 // what the calls over bags share (api_seqrec.hip; api_tower.hip): the checks of the lists before any device work (host lists are
-// walked); the lists on the device (host lists copied into the two pieces of scratch); the kernels' arguments; the touch of the
-// lazy rows of H on the sorted list, *sorted the pairs for a caller that applies with them
+// walked); the scratch of the lists behind whatever the caller has carved -- ORX_BAG_STAGED: the pieces host lists are copied
+// into, nothing else; ORX_BAG_FORWARD: + uid'; ORX_BAG_STEP: + c_i, the owners and the pairs the apply takes --; the kernels'
+// arguments on d_tmp once it is grown (host lists are copied here; `out` is the caller's to set); the touch of the lazy rows of H
+// on the sorted list, *sorted the pairs for a caller that applies with them
+enum { ORX_BAG_STAGED = 0, ORX_BAG_FORWARD = 1, ORX_BAG_STEP = 2 };
+struct BagLayout { size_t uid, ptr, items, coef, owner, pairs; int keep; };
 int orx_bag_check(const char* fn, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom, bool host);
+void orx_bag_layout(Carve* cv, int64_t B, int64_t n, bool host, int keep, BagLayout* l);
+int orx_bag_bind(orx_ctx* c, const BagLayout& l, orx_table* H, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode,
+                 float denom, bool host, BagArgs* a, uint2** pairs);
 int orx_bag_stage(orx_ctx* c, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, bool host, int32_t* d_ptr, int32_t* d_items,
                   BagArgs* a);
-BagArgs orx_bag_args(orx_ctx* c, orx_table* H, int64_t B, int64_t n, int mode, float denom);
 int orx_bag_touch(orx_ctx* c, orx_table* H, const int32_t* items, int64_t n, bool always, const uint2** sorted);
+// The history side of a step, in its two halves.  First: the lazy rows of H are touched on the sorted list, `launch` produces what
+// the bags pool into (orx_launch_bag_pool, orx_launch_tower_input), and -- pairs not NULL: H is trained -- the sorted pairs'
+// positions are replaced by their owners right away, before anything else may sort.  pairs NULL (a forward, or H outside the
+// mask and so current): the touch alone, no sort unless H is lazy.  Second, after the counter has advanced: columns
+// [col0, col0 + D) of the gradient rows g [B][ld] are scaled by c_i in place and orx_apply_rows_sorted sums a row's occurrences
+int orx_bag_produce(orx_ctx* c, orx_table* H, const BagArgs& bag, uint2* pairs, const std::function<int()>& launch);
+int orx_bag_apply(orx_ctx* c, orx_opt* opt, orx_table* H, const BagArgs& bag, const uint2* pairs, float* g, int col0, int ld);
 
 // kernels_inbatch.hip (orx_inbatch_step / orx_inbatch_loss): one step of the in-batch softmax.  Bp = B rounded up to 64, Dp = D
 // rounded up to 16; every [Bp] / [Bp][Dp] / [nch][..] array is scratch carved from the context's d_tmp
@@ -1068,10 +1081,9 @@ inline int orx_fullsoftmax_npartials(int64_t B) { return (int)((((B + 63) & ~(in
 void orx_fullsoftmax_plan(int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, FullSoftmaxPlan* p);
 int orx_launch_fullsoftmax_forward(orx_ctx* ctx, const FullSoftmaxArgs& a);     // prepare, item copy, LSE pass, finalize
 int orx_launch_fullsoftmax_grads(orx_ctx* ctx, const FullSoftmaxArgs& a, bool query_side, bool item_side);      // a walk and its finishing pass per side
-// what the user-table form (api_fullsoftmax.hip) and the SeqRec form (api_seqrec.hip) share: the checks of (B, NI, D, scale, the
-// chunk arguments); the scratch of a step as offsets carved behind whatever the caller has carved (host_off: a piece for a host
-// item_offset); the kernels' arguments on the context's d_tmp once it is grown (qid / pid / wt / partial are the caller's to set);
-// the train mask; the dense rule on the item table and the bias
+// what the drivers (below, after the tower's declarations) build a call from: the checks of (B, NI, D, scale, the chunk
+// arguments); the scratch of a step as offsets carved behind whatever the form has carved (host_off: a piece for a host
+// item_offset); the train mask of a form with the three usual tables
 struct FullSoftmaxLayout {
     FullSoftmaxPlan plan; bool host_off;
     size_t xq, xv, key, cw, sq, ib, io, pm, pe, psd, rmax, cn, dcoef, rowloss, off, gpq, gu, gpv, bpart, npart, GV, Gb;
@@ -1079,10 +1091,7 @@ struct FullSoftmaxLayout {
 int orx_fullsoftmax_check(const char* fn, int64_t B, int64_t NI, int32_t D, float scale, int32_t chunk_items, int32_t chunk_samples);
 void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, bool grads, bool query_side,
                             bool item_side, bool host_off, FullSoftmaxLayout* l);
-int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const float* Q, int64_t NQ, orx_table* V, orx_table* b, const float* item_offset,
-                         int64_t B, float scale, float l2w, FullSoftmaxArgs* out);
 int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask);
-int orx_fullsoftmax_apply_items(orx_ctx* c, orx_opt* opt, orx_table* V, orx_table* b, bool tV, bool tb, const FullSoftmaxArgs& a);
 int orx_launch_fullsoftmax_lse(orx_ctx* ctx, const FullSoftmaxArgs& a);         // the item copy and the LSE pass alone
 
 // kernels_labelsets.hip (orx_seqrec_full_sets_step / orx_tower_sets_step and their forwards): the full softmax with a label SET
@@ -1133,6 +1142,43 @@ int orx_launch_tower_input(orx_ctx* ctx, const TowerArgs& a);
 int orx_launch_tower_forward(orx_ctx* ctx, const TowerArgs& a);                 // one launch per layer
 int orx_launch_tower_backward(orx_ctx* ctx, const TowerArgs& a);                // one launch per layer, last to first
 int orx_launch_tower_finish(orx_ctx* ctx, const TowerArgs& a);                  // one launch: the partials of all layers in chunk order, + l2m * (W, c)
+
+// ---------------------------------- the host driver of the calls on the softmax over all items (api_fullsoftmax.hip) ---
+// A model on this objective is a QUERY FORM: what produces the query matrix Q [NQ][D] and what takes its gradient.  The entry
+// point fills one in and calls a driver; the drivers hold everything else once -- the checks of the objective, the lists, the
+// scratch of the full softmax and of the label sets, which tables are finished and which stay lazy, the forward and the gradient
+// passes (one label per sample, or sets != NULL a label set), the counter, the dense rule on V and b, the losses.
+struct FullSoftmaxTable { orx_table* t; bool dense; bool trained; };        // dense: read in full (a layer), so always finished first; else touched by produce
+struct FullSoftmaxQuery {                                   // what bind yields
+    const float* Q; int64_t NQ; const int32_t* qid;         // the rows the kernels score with; qid arrives as the staged `ids` of the form, if it has any
+    const float* X0; int x0w; int x0ld;                     // not NULL: the l2 term sits on these rows and not on the query (FullSoftmaxArgs::l2q = 0)
+};
+// The drivers call the members in this order, each once per call and `produce` once per step: check, [a step: train], carve, bind,
+// then produce, [backward], [apply].  A member may rely on what the earlier ones left in the form (check fills tab[], train sets what
+// carve sizes by); a forward never calls train, so the builder leaves every trained / gradient flag false.
+struct FullSoftmaxForm {
+    const char* fn;
+    bool has_ids; const int32_t* ids;                       // a [B] id list of the form's own beside pid (the user table's uid), staged with it
+    bool index_flag;                                        // a synchronising step over device lists looks at the index flag at its end
+    FullSoftmaxTable tab[1 + ORX_TOWER_SIDE + 2 * ORX_TOWER_LAYERS]; int n_tab;       // the form's tables, in the order they are finished and kept
+    bool query_side;                                        // set by train: the gradient passes take the query side
+    std::function<int()> check;                             // the form's own checks, before the objective's
+    std::function<int(int*)> train;                         // the step's mask: its own bits refused, 0 replaced by every table, tab[].trained and query_side set
+    std::function<void(Carve*, bool)> carve;                // its part of d_tmp (grads?)
+    std::function<int(bool, FullSoftmaxQuery*)> bind;       // its kernels' arguments once d_tmp is grown; host lists are copied here
+    std::function<int(const FullSoftmaxArgs&, bool)> produce;       // per call (step?): touch the rows it reads, launch what writes Q
+    std::function<int()> backward;                          // after the gradient passes, before the counter advances (may be empty)
+    std::function<int(const FullSoftmaxArgs&)> apply;       // after the counter has advanced: its tables' applies
+};
+// the kernels' arguments on the context's d_tmp once it is grown, the query's part from q (pid / wt / partial are the drivers' to set)
+int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const FullSoftmaxQuery& q, orx_table* V, orx_table* b, const float* item_offset,
+                         int64_t B, float scale, float l2w, FullSoftmaxArgs* out);
+int orx_fullsoftmax_drive_step(orx_ctx* c, orx_opt* opt, FullSoftmaxForm& f, orx_table* V, orx_table* b, const int32_t* pid, const LabelLists* sets,
+                               const float* weight, const float* item_offset, int64_t B, float scale, float l2_reg, int32_t chunk_items,
+                               int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_fullsoftmax_drive_loss(orx_ctx* c, FullSoftmaxForm& f, orx_table* V, orx_table* b, const int32_t* pid, const LabelLists* sets,
+                               const float* weight, const float* item_offset, int64_t B, float scale, int32_t chunk_items, int flags,
+                               float* loss_out, float* l2_out, float* row_loss_out);
 
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {

@@ -584,23 +584,10 @@ def inbatch_loss(user, item, bias, uid, pid, weights=None, item_offset=None, sca
     _, B, _, dev, ptrs, scale, chunk, keep = _inbatch_args("inbatch_loss", user, item, bias, uid, pid, 1, None, None, weights,
                                                            item_offset, scale, chunk)
     out, lp, l2p = _loss_outputs(1, True)
-    rows = rp = None
-    if per_row:
-        if dev:
-            import torch
-            rows = torch.empty(B, dtype=torch.float32, device=torch.device("cuda", user.ctx.device))
-            user.ctx.after_torch(rows)
-            rp = rows.data_ptr()
-        else:
-            rows = np.empty(B, np.float32)
-            rp = rows.ctypes.data
+    rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
     flags = _flags(dev, _ffi.ORX_IB_MASK_HITS if mask_hits else 0)
     check(user.ctx._lib.orx_inbatch_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, chunk, flags, lp, l2p, rp))
-    if not per_row:
-        return _loss_pair(out)
-    if dev:
-        rows = rows.cpu().numpy()          # (the call has synchronised the context's stream for the two sums)
-    return (*_loss_pair(out), rows)
+    return _forward_result(out, rows, dev)
 
 
 def inbatch_geometry(B, D, chunk=0):
@@ -680,6 +667,15 @@ def _row_loss_buffer(ctx, B, dev, per_row):
     return rows, rows.ctypes.data
 
 
+def _forward_result(out, rows, dev):
+    """what a forward-only call returns: (loss, l2_loss), and with _row_loss_buffer's rows (loss, l2_loss, l) as numpy"""
+    if rows is None:
+        return _loss_pair(out)
+    if dev:
+        rows = rows.cpu().numpy()          # (the call has synchronised the context's stream for the two sums)
+    return (*_loss_pair(out), rows)
+
+
 def fullsoftmax_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
     """forward only: (loss, l2_loss) of one batch of fullsoftmax_step -- the step's own numbers bit for bit on the same tables;
     no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
@@ -688,11 +684,7 @@ def fullsoftmax_loss(user, item, bias, uid, pid, weights=None, item_offset=None,
     out, lp, l2p = _loss_outputs(1, True)
     rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
     check(user.ctx._lib.orx_fullsoftmax_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, ci, _flags(dev), lp, l2p, rp))
-    if not per_row:
-        return _loss_pair(out)
-    if dev:
-        rows = rows.cpu().numpy()          # (the call has synchronised the context's stream for the two sums)
-    return (*_loss_pair(out), rows)
+    return _forward_result(out, rows, dev)
 
 
 def fullsoftmax_geometry(B, items, D, chunk_items=0, chunk_samples=0):
@@ -2391,6 +2383,59 @@ def _labels_arg(what, pid, labels, label_weights, dev, B):
     return (lp, li, ptw, n_lab), True, (kl, ktw)
 
 
+# What SeqRec.step_full / loss_full and DeepSeqRec.step_full / loss_full share (4.5z has the C side).  m: the model
+# (H, V, b, ctx, _mode, _denom); lists(what) reads the model's own lists -> (bag ptr, bag items, B, n, on_device, a callable that
+# makes the model's C arguments between the bias and the bags -- called last, after every refusal --, keepalives); tables: what
+# the call flushes and the optimizer keeps; fns: the C functions' names (one label per bag, a label set per bag); coefs:
+# l2_reg [, l2_mlp] as checked by the caller.
+def _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, chunk_samples, labels, label_weights):
+    scale = _scale_arg(what, scale)
+    ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
+    pp, pi, B, n, dev, model, kl = lists(what)
+    plab, sets, keep = _labels_arg(what, pid, labels, label_weights, dev, B)
+    pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
+    po, ko = _floats_arg(what, "item_offset", item_offset, dev, m.V.rows, "the item table's rows")
+    m.ctx.after_torch(*_flat_keep(kl), *_flat_keep(keep), kw, ko)
+    for t in tables:
+        if t is not None:
+            t._sync_pending()
+    return B, n, dev, sets, (*model(), pp, pi, *plab, pw, po), scale, ci, cs, (kl, keep, kw, ko)
+
+
+def _full_step(what, m, fns, lists, tables, opt, coefs, mask, pid, weights, item_offset, scale, chunk_items, chunk_samples, want_loss, labels,
+               label_weights):
+    B, n, dev, sets, ptrs, scale, ci, cs, keep = _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, chunk_samples,
+                                                            labels, label_weights)
+    out, lp, l2p = _loss_outputs(1, want_loss)
+    check(getattr(m.ctx._lib, fns[sets])(m.ctx._h, opt._h, m.H._h, m.V._h, _bias_h(m.b), *ptrs, B, n, m._mode, m._denom, scale, *coefs, ci, cs,
+                                         mask, _flags(dev), lp, l2p))
+    _keep_tables(opt, tables)
+    return out
+
+
+def _full_loss(what, m, fns, lists, tables, pid, weights, item_offset, scale, chunk_items, per_row, labels, label_weights):
+    B, n, dev, sets, ptrs, scale, ci, _, keep = _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, 0, labels,
+                                                           label_weights)
+    out, lp, l2p = _loss_outputs(1, True)
+    rows, rp = _row_loss_buffer(m.ctx, B, dev, per_row)
+    check(getattr(m.ctx._lib, fns[sets])(m.ctx._h, m.H._h, m.V._h, _bias_h(m.b), *ptrs, B, n, m._mode, m._denom, scale, ci, _flags(dev), lp, l2p, rp))
+    return _forward_result(out, rows, dev)
+
+
+def _owned_output(what, m, B, dim, out, rows_are="bags"):
+    """the output table of a user_table call: `out` once its shape is checked, or the one the model owns -- valid until the
+    next call with another B"""
+    if B < 1:
+        raise ValueError(f"{what}: no bags")
+    if out is None:
+        if m._Q is None or m._Q.rows != B:
+            m._Q = Table(B, dim, m.ctx)
+        return m._Q
+    if (out.rows, out.dim) != (B, dim):
+        raise ValueError(f"{what}: out is [{out.rows}, {out.dim}] for {B} {rows_are} of dim {dim}")
+    return out
+
+
 def bag_pool(H, bags, out, pool="mean", rows=None):
     """out[row0 + i] = c_i * sum of H[items of bag i] in list order (orx_bag_pool): an EmbeddingBag over per-call ragged lists.
     bags: (ptr, items) or the padded pair (seq, seq_len) -- see _bags_arg; pool: "mean" (c_i = 1 / len_i), "sum", or
@@ -2479,18 +2524,13 @@ class SeqRec:
                                             self._denom, _flags(dev), lp, l2p))
         return _loss_pair(out)
 
-    def _args_full(self, what, bags, pid, weights, item_offset, scale, chunk_items, chunk_samples, labels=None, label_weights=None):
-        scale = _scale_arg(what, scale)
-        ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
-        pp, pi, B, n, dev, kb = _bags_arg(what, bags)
-        plab, sets, keep = _labels_arg(what, pid, labels, label_weights, dev, B)
-        pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
-        po, ko = _floats_arg(what, "item_offset", item_offset, dev, self.V.rows, "the item table's rows")
-        self.ctx.after_torch(*kb, *_flat_keep(keep), kw, ko)
-        for t in (self.H, self.V, self.b):
-            if t is not None:
-                t._sync_pending()
-        return B, n, dev, (pp, pi, *plab, pw, po), scale, ci, cs, (kb, keep, kw, ko), sets
+    _FULL_STEP, _FULL_LOSS = ("orx_seqrec_full_step", "orx_seqrec_full_sets_step"), ("orx_seqrec_full_loss", "orx_seqrec_full_sets_loss")
+
+    def _full_lists(self, bags):
+        def lists(what):
+            pp, pi, B, n, dev, kb = _bags_arg(what, bags)
+            return pp, pi, B, n, dev, lambda: (), kb          # (no C arguments of the model's own)
+        return lists
 
     def step_full(self, opt, bags, pid=None, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None, chunk_items=0,
                   chunk_samples=0, want_loss=True, labels=None, label_weights=None):
@@ -2507,47 +2547,23 @@ class SeqRec:
         what = "SeqRec.step_full"
         mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
         l2c = _coef_arg(what, "l2_reg", l2_reg)
-        B, n, dev, ptrs, scale, ci, cs, keep, sets = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items,
-                                                                      chunk_samples, labels, label_weights)
-        out, lp, l2p = _loss_outputs(1, want_loss)
-        fn = self.ctx._lib.orx_seqrec_full_sets_step if sets else self.ctx._lib.orx_seqrec_full_step
-        check(fn(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
-                 self._denom, scale, l2c, ci, cs, mask, _flags(dev), lp, l2p))
-        _keep_tables(opt, (self.H, self.V, self.b))
-        return out
+        return _full_step(what, self, self._FULL_STEP, self._full_lists(bags), (self.H, self.V, self.b), opt, (l2c,), mask, pid, weights,
+                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights)
 
     def loss_full(self, bags, pid=None, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False, labels=None,
                   label_weights=None):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
         table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
         label_weights= as step_full takes them"""
-        what = "SeqRec.loss_full"
-        B, n, dev, ptrs, scale, ci, _, keep, sets = self._args_full(what, bags, pid, weights, item_offset, scale, chunk_items, 0,
-                                                                     labels, label_weights)
-        out, lp, l2p = _loss_outputs(1, True)
-        rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
-        fn = self.ctx._lib.orx_seqrec_full_sets_loss if sets else self.ctx._lib.orx_seqrec_full_loss
-        check(fn(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, self._mode,
-                 self._denom, scale, ci, _flags(dev), lp, l2p, rp))
-        if not per_row:
-            return _loss_pair(out)
-        if dev:
-            rows = rows.cpu().numpy()
-        return (*_loss_pair(out), rows)
+        return _full_loss("SeqRec.loss_full", self, self._FULL_LOSS, self._full_lists(bags), (self.H, self.V, self.b), pid, weights, item_offset,
+                          scale, chunk_items, per_row, labels, label_weights)
 
     def user_table(self, bags, out=None):
         """-> a Table [B, D] of the pooled rows q_i of `bags` (out: a Table of that shape to write; None: one owned by this
         object, valid until the next call with another B).  With (V, b) it goes wherever a user table goes, uid = the row number."""
         what = "SeqRec.user_table"
         pp, pi, B, n, dev, keep = _bags_arg(what, bags)
-        if B < 1:
-            raise ValueError(f"{what}: no bags")
-        if out is None:
-            if self._Q is None or self._Q.rows != B:
-                self._Q = Table(B, self.H.dim, self.ctx)
-            out = self._Q
-        elif (out.rows, out.dim) != (B, self.H.dim):
-            raise ValueError(f"{what}: out is [{out.rows}, {out.dim}] for {B} bags of dim {self.H.dim}")
+        out = _owned_output(what, self, B, self.H.dim, out)
         return bag_pool(self.H, keep[2:], out, self.pool)           # (the ragged lists: a padded pair is converted once)
 
     def recommend(self, bags, k, excl=None):
@@ -2643,19 +2659,13 @@ class DeepSeqRec:
             raise ValueError(f"{what}: {B} bags and side id lists of {ns} ids (one id per bag and side table)")
         return pp, pi, B, n, dev, ps, (kb, ks)
 
-    def _args_full(self, what, bags, pid, side_ids, weights, item_offset, scale, chunk_items, chunk_samples, labels=None,
-                   label_weights=None):
-        scale = _scale_arg(what, scale)
-        ci, cs = _chunk_arg(what, "chunk_items", chunk_items), _chunk_arg(what, "chunk_samples", chunk_samples)
-        pp, pi, B, n, dev, ps, (kb, ks) = self._lists(what, bags, side_ids)
-        plab, sets, keep = _labels_arg(what, pid, labels, label_weights, dev, B)
-        pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
-        po, ko = _floats_arg(what, "item_offset", item_offset, dev, self.V.rows, "the item table's rows")
-        self.ctx.after_torch(*kb, *ks, *_flat_keep(keep), kw, ko)
-        for t in self._tables:
-            t._sync_pending()
-        model, arrays = self._model_args(ps)
-        return B, n, dev, model, (pp, pi, *plab, pw, po), scale, ci, cs, (kb, ks, keep, kw, ko, arrays), sets
+    _FULL_STEP, _FULL_LOSS = ("orx_tower_step", "orx_tower_sets_step"), ("orx_tower_loss", "orx_tower_sets_loss")
+
+    def _full_lists(self, bags, side_ids):
+        def lists(what):
+            pp, pi, B, n, dev, ps, keep = self._lists(what, bags, side_ids)
+            return pp, pi, B, n, dev, lambda: self._model_args(ps)[0], keep          # (the C arrays live as long as the tuple that holds them)
+        return lists
 
     def step_full(self, opt, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, l2_reg=0.0, l2_mlp=0.0, train=None,
                   chunk_items=0, chunk_samples=0, want_loss=True, labels=None, label_weights=None):
@@ -2672,33 +2682,16 @@ class DeepSeqRec:
         if mask & _ffi.ORX_TRAIN_SIDE and not self.side:
             raise ValueError(f'{what}: train: "side" named, but the model has no side table')
         l2c, l2m = _coef_arg(what, "l2_reg", l2_reg), _coef_arg(what, "l2_mlp", l2_mlp)
-        B, n, dev, model, ptrs, scale, ci, cs, keep, sets = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale,
-                                                                             chunk_items, chunk_samples, labels, label_weights)
-        out, lp, l2p = _loss_outputs(1, want_loss)
-        fn = self.ctx._lib.orx_tower_sets_step if sets else self.ctx._lib.orx_tower_step
-        check(fn(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n,
-                 self._mode, self._denom, scale, l2c, l2m, ci, cs, mask, _flags(dev), lp, l2p))
-        _keep_tables(opt, self._tables)
-        return out
+        return _full_step(what, self, self._FULL_STEP, self._full_lists(bags, side_ids), self._tables, opt, (l2c, l2m), mask, pid, weights,
+                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights)
 
     def loss_full(self, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False,
                   labels=None, label_weights=None):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
         table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
         label_weights= as step_full takes them"""
-        what = "DeepSeqRec.loss_full"
-        B, n, dev, model, ptrs, scale, ci, _, keep, sets = self._args_full(what, bags, pid, side_ids, weights, item_offset, scale,
-                                                                            chunk_items, 0, labels, label_weights)
-        out, lp, l2p = _loss_outputs(1, True)
-        rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
-        fn = self.ctx._lib.orx_tower_sets_loss if sets else self.ctx._lib.orx_tower_loss
-        check(fn(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *model, *ptrs, B, n, self._mode,
-                 self._denom, scale, ci, _flags(dev), lp, l2p, rp))
-        if not per_row:
-            return _loss_pair(out)
-        if dev:
-            rows = rows.cpu().numpy()
-        return (*_loss_pair(out), rows)
+        return _full_loss("DeepSeqRec.loss_full", self, self._FULL_LOSS, self._full_lists(bags, side_ids), self._tables, pid, weights,
+                          item_offset, scale, chunk_items, per_row, labels, label_weights)
 
     def user_table(self, bags, side_ids=(), out=None):
         """-> a Table [B, Dq] of the queries q_i (orx_tower_query) -- the rows the step scores with, bit for bit, and a row's bits
@@ -2706,14 +2699,7 @@ class DeepSeqRec:
         the next call with another B.  With (V, b) it goes wherever a user table goes, uid = the row number."""
         what = "DeepSeqRec.user_table"
         pp, pi, B, n, dev, ps, keep = self._lists(what, bags, side_ids)
-        if B < 1:
-            raise ValueError(f"{what}: no bags")
-        if out is None:
-            if self._Q is None or self._Q.rows != B:
-                self._Q = Table(B, self.V.dim, self.ctx)
-            out = self._Q
-        elif (out.rows, out.dim) != (B, self.V.dim):
-            raise ValueError(f"{what}: out is [{out.rows}, {out.dim}] for {B} bags and queries of dim {self.V.dim}")
+        out = _owned_output(what, self, B, self.V.dim, out, "bags and queries")
         if any(out is t for t in self._tables):
             raise ValueError(f"{what}: the output is one of the model's tables")
         self.ctx.after_torch(*keep[0], *keep[1])

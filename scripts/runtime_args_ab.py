@@ -43,7 +43,7 @@ def cases(si):
             add("no bias", e, dev, bias=False, **shape(e))
             add("mixed sides", e, dev, over={second(e): dict(dev=not dev)}, **shape(e))
             add("second list one longer", e, dev, over={second(e): dict(shape=(NEED + 1,))}, **shape(e))
-            third = "label" if e.startswith("pointwise") else "nid" if not e.startswith("inbatch") else None
+            third = "label" if e.startswith("pointwise") else "nid" if "nid" in [x[0] for x in si._LISTS[si.family(e)]] else None
             if third:
                 n_wide = si.family(e) in ("multineg", "SeqRec")
                 add("third list one longer", e, dev, over={third: dict(shape=(NEED + 1, N) if n_wide else (NEED + 1,))}, **shape(e))
@@ -74,7 +74,7 @@ def cases(si):
                 add(f"l2_reg = {bad}", e, dev, l2_reg=bad, **shape(e))
             add("l2_reg = 0.25", e, dev, l2_reg=0.25, **shape(e))
             if e.split("_")[0] not in ("multineg", "inbatch"):
-                role = "history" if e.startswith("SeqRec") else "user"
+                role = "history" if "SeqRec" in e else "user"
                 for label, kw in (("train unknown", dict(train=("users",))), ("train empty", dict(train=())), ("train bias without a bias", dict(train=("bias",), bias=False)),
                                   (f"train {role}", dict(train=role)), ("train item and bias", dict(train=("item", "bias")))):
                     if not (e.startswith("LightGCN") and "bias" in str(kw.get("train"))):
@@ -93,6 +93,45 @@ def cases(si):
             add("routing " + repr(kw), "pointwise_step", dev, **kw, **shape("pointwise_step"))
         add("scale, chunk, no mask_hits", "inbatch_step", dev, scale=2.0, chunk=128, mask_hits=False, **shape("inbatch_step"))
         add("scale = 0", "inbatch_loss", dev, scale=0.0)
+        for e in si.FULL:          # the calls on the softmax over all items
+            step, bags, deep = "step" in e, "SeqRec" in e, e.startswith("Deep")
+            add("scale, chunk_items", e, dev, scale=2.0, chunk_items=128)
+            for label, kw in (("scale = 0", dict(scale=0.0)), ("scale = nan", dict(scale=float("nan"))), ("chunk_items = 65", dict(chunk_items=65)),
+                              ("chunk_items = -64", dict(chunk_items=-64)), ("no bags", dict(n=0)), ("one bag", dict(n=1))):
+                add(label, e, dev, **kw)
+            if step:
+                add("chunk_samples, no loss", e, dev, chunk_samples=64, want_loss=False)
+                add("chunk_samples = 1", e, dev, chunk_samples=1)
+                add("every table by name", e, dev, train=("user" if not bags else "history", "item", "bias"))
+            if deep and step:
+                for label, kw in (("l2_mlp", dict(l2_mlp=0.25)), ("l2_mlp = -1", dict(l2_mlp=-1.0)), ("l2_mlp = nan, train unknown", dict(l2_mlp=float("nan"), train="x")),
+                                  ("train side and tower", dict(train=("side", "tower"))), ("train tower", dict(train="tower"))):
+                    add(label, e, dev, **kw)
+            if deep:
+                add("one side id list", e, dev, side_ids=(np.zeros(NEED, np.int32),))
+                add("a side id list on the other side", e, dev, over={"f1": dict(dev=not dev)})
+                add("a side id list one longer", e, dev, over={"f0": dict(shape=(NEED + 1,))})
+            if not bags:
+                continue
+            for lw in (False, True):
+                opt = ("label_weights",) if lw else ()
+                add(f"ragged label sets, label_weights {lw}", e, dev, labels="ragged", optional=opt)
+                add(f"ragged label sets, label_weights {lw}, every optional list, no bias", e, dev, labels="ragged", optional=si.OPTIONAL + opt, bias=False)
+                if not dev:
+                    add(f"padded label sets, label_weights {lw}", e, dev, labels="padded", optional=opt)
+            for label, kw in (("pid and labels", dict(labels="ragged", over={"pid": {}})), ("neither pid nor labels", dict(over={"pid": None})),
+                              ("label_weights without labels", dict(over={"label_weights": dict(shape=(NEED,))})),
+                              ("labels on the other side", dict(labels="ragged", over={"lab_ptr": dict(dev=not dev), "lab_items": dict(dev=not dev)})),
+                              ("one label set more", dict(labels="ragged", over={"lab_ptr": dict(shape=(NEED + 2,)), "lab_items": dict(shape=(2 * NEED + 2,))})),
+                              ("label_weights one short", dict(labels="ragged", over={"label_weights": dict(shape=(2 * NEED - 1,))})),
+                              ("label_weights on the other side", dict(labels="ragged", over={"label_weights": dict(dev=not dev)})),
+                              ("pid one short", dict(over={"pid": dict(shape=(NEED - 1,))})),
+                              ("padded label_weights of another shape", dict(labels="padded", over={"label_weights": dict(shape=(NEED, 2))}))):
+                if not (dev and kw.get("labels") == "padded"):
+                    add(label, e, dev, **kw)
+    for e in si.FULL:
+        if "loss" in e:
+            add("per_row", e, False, per_row=True)
     add("per_row", "inbatch_loss", False, per_row=True)
     rng = np.random.default_rng(20240607)
     for _ in range(80):

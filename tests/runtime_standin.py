@@ -1,6 +1,6 @@
 """A recording stand-in for everything openrec_amd.runtime's train-step and forward-loss calls touch: a library whose orx_*
 functions write down (name, args) and return 0, a context that writes down what after_torch was given, tables and an optimizer
-with handles only, and fake device tensors.  No library and no device is needed.  `run` makes one call of one of the fourteen
+with handles only, and fake device tensors.  No library and no device is needed.  `run` makes one call of one of the twenty
 entry points on a fresh set of these and returns what happened; tests/test_runtime_args_cpu.py and scripts/runtime_args_ab.py are
 built on it."""
 import numpy as np
@@ -10,8 +10,11 @@ NEED = (K - 1) * STRIDE + B                 # 9 ids a list needs
 USERS, ITEMS, FD, DC = 20, 30, 6, 3
 
 ENTRIES = ("pairwise_step", "pairwise_loss", "pointwise_step", "pointwise_loss", "multineg_step", "multineg_loss", "inbatch_step",
-           "inbatch_loss", "LightGCN.step", "LightGCN.loss", "VBPR.step", "VBPR.loss", "SeqRec.step", "SeqRec.loss")
-STEPS = tuple(e for e in ENTRIES if e.endswith("step"))
+           "inbatch_loss", "LightGCN.step", "LightGCN.loss", "VBPR.step", "VBPR.loss", "SeqRec.step", "SeqRec.loss", "fullsoftmax_step", "fullsoftmax_loss",
+           "SeqRec.step_full", "SeqRec.loss_full", "DeepSeqRec.step_full", "DeepSeqRec.loss_full")
+FULL = ENTRIES[14:]                         # the calls on the softmax over all items: item_offset is one float per ITEM
+STEPS = tuple(e for e in ENTRIES if "step" in e.split(".")[-1])
+SIDE, HID = ((5, 2), (7, 3)), 6             # DeepSeqRec: two side tables [rows, dim]; W0 [2 + 3 + D, HID] with a bias, W1 [HID, D] without one
 
 
 class NoDevice:
@@ -74,8 +77,9 @@ class RecordingContext:
 
 
 class StandinTable:
-    def __init__(self, ctx, name, rows, dim):
-        self.ctx, self._h, self.rows, self.dim, self.shape, self.flushes = ctx, "h:" + name, rows, dim, (rows, dim), 0
+    def __init__(self, ctx, name, rows, dim, handle=None):          # handle: an integer one, for a table that travels in a C array
+        self.ctx, self._h, self.rows, self.dim, self.shape, self.flushes = ctx, handle or "h:" + name, rows, dim, (rows, dim), 0
+        self.name = name
 
     def _sync_pending(self):
         self.flushes += 1
@@ -96,13 +100,16 @@ class World:
         T = lambda name, rows, dim: StandinTable(self.ctx, name, rows, dim)
         self.U, self.V, self.b, self.w = T("U", USERS, D), T("V", ITEMS, D), (T("b", ITEMS, 1) if bias else None), T("w", D, 1)
         self.H, self.E, self.Uv = T("H", ITEMS, D), T("E", FD, DC), T("Uv", USERS, D + DC)
+        A = lambda i, name, rows, dim: StandinTable(self.ctx, name, rows, dim, 0x1000 + i)
+        self.S = [A(j, f"S{j}", rows, dim) for j, (rows, dim) in enumerate(SIDE)]
+        self.W0, self.c0, self.W1 = A(4, "W0", sum(d for _, d in SIDE) + D, HID), A(5, "c0", 1, HID), A(6, "W1", HID, D)
 
     @property
     def calls(self):
         return self.ctx._lib.calls
 
     def tables(self):
-        return [t for t in (self.U, self.V, self.b, self.w, self.H, self.E, self.Uv) if t is not None]
+        return [t for t in (self.U, self.V, self.b, self.w, self.H, self.E, self.Uv, *self.S, self.W0, self.c0, self.W1) if t is not None]
 
     def lightgcn(self):
         m = self.rt.LightGCN.__new__(self.rt.LightGCN)
@@ -116,6 +123,9 @@ class World:
 
     def seqrec(self):
         return self.rt.SeqRec(self.H, self.V, self.b, pool=("fixed", 2.0))
+
+    def deepseqrec(self):
+        return self.rt.DeepSeqRec(self.H, self.V, self.b, [(self.W0, self.c0), self.W1], side=self.S, pool=("fixed", 2.0), relu_last=False)
 
 
 def make_list(shape, dev, dtype="int32", fill=1):
@@ -135,28 +145,46 @@ _LISTS = {
 }
 _LISTS["LightGCN"] = _LISTS["pairwise"][:3]
 _LISTS["VBPR"] = _LISTS["pairwise"]
+# the full softmax: item_offset has ITEMS entries; a bag form takes pid or -- labels="ragged" / "padded" -- a label set per bag
+_LABELS = (("lab_ptr", "int32", "ptr"), ("lab_items", "int32", "items"), ("lab_seq", "int32", "L"), ("lab_len", "int32", 1),
+           ("label_weights", "float32", "items"))
+_LISTS["fullsoftmax"] = (("uid", "int32", 1), ("pid", "int32", 1), ("weights", "float32", 1), ("item_offset", "float32", "I"))
+_LISTS["SeqRec.full"] = (("ptr", "int32", "ptr"), ("items", "int32", "items"), ("pid", "int32", 1), *_LABELS, ("weights", "float32", 1),
+                         ("item_offset", "float32", "I"))
+_LISTS["DeepSeqRec.full"] = (*_LISTS["SeqRec.full"][:2], ("f0", "int32", 1), ("f1", "int32", 1), *_LISTS["SeqRec.full"][2:])
 OPTIONAL = ("weights", "neg_offset", "item_offset")
+LABEL_LISTS = {None: ("pid",), "ragged": ("lab_ptr", "lab_items"), "padded": ("lab_seq", "lab_len")}
 
 
 def family(entry):
+    if entry.endswith("_full"):
+        return entry.split(".")[0] + ".full"
     return entry.split(".")[0].rsplit("_", 1)[0]
 
 
-def make_lists(entry, dev, n, optional=(), over=None):
+def make_lists(entry, dev, n, optional=(), over=None, labels=None):
     """the lists of one call: every required one and the `optional` ones named, n ids each on the side `dev`; over:
-    {name: dict(dev=, shape=) or an object to pass as it is} for the lists that break the rule"""
+    {name: dict(dev=, shape=) or an object to pass as it is} for the lists that break the rule; labels: None (pid), "ragged"
+    or "padded" (two label items per bag; padded: the pair [n, 3], [n]), with "label_weights" among `optional` or not"""
     out = {}
     for name, dtype, unit in _LISTS[family(entry)]:
         if name in OPTIONAL and name not in optional and name not in (over or {}):
             continue
-        shape = {1: (n,), "N": (n, N), "ptr": (n + 1,), "items": (2 * n,)}[unit]
+        if name in ("pid",) + tuple(x[0] for x in _LABELS) and family(entry).endswith(".full"):
+            if name not in LABEL_LISTS[labels] + (("label_weights",) if labels and "label_weights" in optional else ()) and name not in (over or {}):
+                continue
+        shape = {1: (n,), "N": (n, N), "ptr": (n + 1,), "items": (2 * n,), "I": (ITEMS,), "L": (n, 3)}[unit]
+        if name == "label_weights" and labels == "padded":
+            shape = (n, 3)
         spec = (over or {}).get(name, {})
         if not isinstance(spec, dict):
             out[name] = spec
             continue
         x = make_list(spec.get("shape", shape), spec.get("dev", dev), dtype)
-        if name == "ptr" and not spec.get("dev", dev):
+        if name in ("ptr", "lab_ptr") and not spec.get("dev", dev):
             x[:] = 2 * np.arange(x.size)          # n bags of two items each
+        if name == "lab_len" and not spec.get("dev", dev):
+            x[:] = 2
         out[name] = x
     return out
 
@@ -194,6 +222,19 @@ def call(w, entry, L, kw):
         return w.seqrec().step(w.opt, (L["ptr"], L["items"]), L["pid"], L["nid"], weights=L.get("weights"), neg_offset=L.get("neg_offset"), **kw)
     if entry == "SeqRec.loss":
         return w.seqrec().loss((L["ptr"], L["items"]), L["pid"], L["nid"], weights=L.get("weights"), neg_offset=L.get("neg_offset"), **kw)
+    if entry in ("fullsoftmax_step", "fullsoftmax_loss"):
+        head = (w.opt,) if entry.endswith("step") else ()
+        return getattr(rt, entry)(*head, w.U, w.V, w.b, L["uid"], L["pid"], weights=L.get("weights"), item_offset=L.get("item_offset"), **kw)
+    if entry in FULL:
+        model = w.seqrec() if entry.startswith("SeqRec") else w.deepseqrec()
+        head = (w.opt,) if entry.endswith("step_full") else ()
+        if "lab_ptr" in L or "lab_seq" in L:
+            kw.update(labels=(L["lab_ptr"], L["lab_items"]) if "lab_ptr" in L else (L["lab_seq"], L["lab_len"]))
+        kw.update(label_weights=L.get("label_weights"))
+        if entry.startswith("Deep"):
+            kw.setdefault("side_ids", (L["f0"], L["f1"]))
+        return getattr(model, entry.split(".")[1])(*head, (L["ptr"], L["items"]), L.get("pid"), weights=L.get("weights"),
+                                                   item_offset=L.get("item_offset"), **kw)
     raise KeyError(entry)
 
 
@@ -215,11 +256,11 @@ class Outcome:
         return calls[0]
 
 
-def run(rt, entry, dev=False, n=NEED, optional=(), over=None, bias=True, **kw):
+def run(rt, entry, dev=False, n=NEED, optional=(), over=None, bias=True, labels=None, **kw):
     """one call of `entry` on a fresh world; an exception is caught and kept"""
     o = Outcome()
     o.world = World(rt, bias)
-    o.lists = make_lists(entry, dev, n, optional, over)
+    o.lists = make_lists(entry, dev, n, optional, over, labels)
     o.result = o.error = None
     try:
         o.result = call(o.world, entry, o.lists, kw)
@@ -234,11 +275,14 @@ def describe(o):
     if o.error is not None:
         return type(o.error).__name__
     where = {o.pointer_of(k): k for k, x in o.lists.items() if isinstance(x, (FakeDeviceTensor, np.ndarray))}
+    named = {**where, **{t._h: t.name for t in o.world.tables() if isinstance(t._h, int)}}
     out = []
     for fn, args in o.calls:
         shown = []
         for a in args:
-            if isinstance(a, (int, np.integer)) and not isinstance(a, bool) and int(a) in where:
+            if hasattr(a, "_length_"):          # a C array of handles or pointers
+                shown.append("[" + ", ".join(named.get(v, repr(v)) for v in a) + "]")
+            elif isinstance(a, (int, np.integer)) and not isinstance(a, bool) and int(a) in where:
                 shown.append(where[int(a)] + "+0")
             elif isinstance(a, (int, np.integer)) and int(a) >= 1 << 32:
                 base = [k for p, k in where.items() if p < int(a) < p + 4 * max(o.lists[k].size if isinstance(o.lists[k], np.ndarray) else o.lists[k].numel(), 1)]
@@ -248,7 +292,7 @@ def describe(o):
             else:
                 shown.append(type(a).__name__)
         out.append(f"{fn}({', '.join(shown)})")
-    flushed = "".join(t._h[2:] for t in o.world.tables() if t.flushes)
+    flushed = "".join(t.name for t in o.world.tables() if t.flushes)
     ordered = sorted(o.ordered_lists())
     res ="None" if o.result is None else "floats" if isinstance(o.result[0], float) else f"arrays{[len(r) for r in o.result]}"
     return "; ".join(out) + f" | flushed: {flushed or '-'} | after_torch: {ordered} | -> {res}"

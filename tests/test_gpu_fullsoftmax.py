@@ -459,6 +459,87 @@ def test_seqrec_train_masks_and_bad_lists():
     assert np.array_equal(again.view(np.int32), good.view(np.int32))
 
 
+# ---- 10b. the drivers' two early-outs, on every entry point that goes through them ---------------------------------------------------------
+TEN = ("fullsoftmax_step", "fullsoftmax_loss", "seqrec_full_step", "seqrec_full_loss", "seqrec_full_sets_step", "seqrec_full_sets_loss",
+       "tower_step", "tower_loss", "tower_sets_step", "tower_sets_loss")
+
+
+def _tiny_model(rt, entry, seed=5):
+    """items = 65, D = 8: -> (the call of `entry` on (opt, bags, B), the tables by name)"""
+    rng = np.random.default_rng(seed)
+    T = lambda rows, dim: rt.Table(rows, dim).write(rng.uniform(-0.3, 0.3, (rows, dim)).astype(np.float32))
+    tabs = dict(V=T(65, 8), b=T(65, 1))
+    if entry.startswith("fullsoftmax"):
+        tabs["U"] = T(10, 8)
+    elif entry.startswith("seqrec"):
+        tabs["H"] = T(65, 8)
+        net = rt.SeqRec(tabs["H"], tabs["V"], tabs["b"])
+    else:
+        tabs.update(H=T(65, 6), S0=T(7, 3), W0=T(9, 12), c0=T(1, 12), W1=T(12, 8))
+        net = rt.DeepSeqRec(tabs["H"], tabs["V"], tabs["b"], [(tabs["W0"], tabs["c0"]), tabs["W1"]], side=[tabs["S0"]], relu_last=False)
+
+    def call(opt, bags, B):
+        ids = rng.integers(0, 7, B).astype(np.int32)
+        kw = dict(labels=(np.arange(B + 1, dtype=np.int32), ids)) if "sets" in entry else {}
+        if entry.startswith("tower"):
+            kw["side_ids"] = (ids,)
+        if entry.startswith("fullsoftmax"):
+            head = (tabs["U"], tabs["V"], tabs["b"], ids, ids)
+            return rt.fullsoftmax_step(opt, *head) if entry.endswith("step") else rt.fullsoftmax_loss(*head, per_row=True)
+        pid = None if "sets" in entry else ids
+        return net.step_full(opt, bags, pid, **kw) if entry.endswith("step") else net.loss_full(bags, pid, per_row=True, **kw)
+    return call, tabs
+
+
+@pytest.mark.parametrize("entry", TEN)
+def test_an_empty_batch_succeeds_and_changes_nothing(entry, monkeypatch):
+    rt = _rt()
+    call, tabs = _tiny_model(rt, entry)
+    before = _bits(*tabs.values())
+    made = []
+
+    def outputs(K, want_loss):          # the (loss, l2) pair the library is handed, holding 7 and not 0 beforehand
+        out = np.full(K, 7.0, np.float32), np.full(K, 7.0, np.float32)
+        made.append(out)
+        return out, out[0].ctypes.data, out[1].ctypes.data
+    monkeypatch.setattr(rt, "_loss_outputs", outputs)
+    got = call(_dev_opt(rt, "adam"), (np.zeros(1, np.int32), np.zeros(0, np.int32)), 0)
+    assert len(made) == 1
+    if entry.endswith("loss"):          # the forward's early-out writes its zeros
+        assert made[0][0][0] == 0.0 and made[0][1][0] == 0.0 and got[:2] == (0.0, 0.0) and got[2].shape == (0,)
+    assert _same(before, _bits(*tabs.values()))
+
+
+@pytest.mark.parametrize("entry", [e for e in TEN if e.endswith("step")])
+def test_a_step_without_an_optimizer_is_refused_by_name(entry):
+    """the raw C call with opt = NULL: the step's own checks refuse it, whatever else the call holds; no table changes"""
+    rt = _rt()
+    call, tabs = _tiny_model(rt, entry)
+    before = _bits(*tabs.values())
+
+    class NoOptimizer:
+        _h, _tables = None, []
+    with pytest.raises(ValueError, match="orx_" + entry + ": NULL optimizer"):
+        call(NoOptimizer(), (np.arange(6, dtype=np.int32), np.arange(5, dtype=np.int32)), 5)
+    assert _same(before, _bits(*tabs.values()))
+
+
+@pytest.mark.parametrize("opt", ["sgd", "adam"])
+@pytest.mark.parametrize("entry", [e for e in TEN if e.endswith("step") and not e.startswith("fullsoftmax")])
+def test_every_bag_empty_with_the_history_trained_moves_the_item_side_alone(entry, opt):
+    rt = _rt()
+    call, tabs = _tiny_model(rt, entry)
+    before = {k: t.read().view(np.int32) for k, t in tabs.items()}
+    losses = call(_dev_opt(rt, opt), (np.zeros(6, np.int32), np.zeros(0, np.int32)), 5)
+    after = {k: t.read().view(np.int32) for k, t in tabs.items()}
+    assert np.isfinite(losses[0]).all() and np.isfinite(losses[1]).all()
+    assert np.array_equal(before["H"], after["H"])
+    # the item side moves: the bias always; the item rows where the query is not 0 (SeqRec pools an empty bag to q = 0, so g_V = 0;
+    # the tower's query comes from the side rows and the layers' biases)
+    assert not np.array_equal(before["b"], after["b"])
+    assert np.array_equal(before["V"], after["V"]) == entry.startswith("seqrec")
+
+
 # ---- 11. refusals --------------------------------------------------------------------------------------------------------------------
 def _raw_step(ctx, opt, U, V, b, uid, pid, scale=1.0, l2_reg=0.0, ci=0, cs=0, mask=0, flags=0):
     from openrec_amd import _ffi

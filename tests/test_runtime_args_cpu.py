@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import runtime_standin as si
-from runtime_standin import B, ENTRIES, FD, ITEMS, K, N, NEED, STEPS, STRIDE, run
+from runtime_standin import B, ENTRIES, FD, FULL, ITEMS, K, N, NEED, STEPS, STRIDE, run
 
 from openrec_amd import _ffi
 from openrec_amd import runtime as rt
@@ -36,6 +36,8 @@ def assert_call(o, fn, want):
             assert type(a).__name__ == "CArgObject", (fn, i, a)
         elif isinstance(w, str) and w.startswith("@"):
             assert a == o.pointer_of(w[1:]), (fn, i, a, w)
+        elif isinstance(w, list):          # a C array: handles, or "@list" pointers
+            assert list(a) == [o.pointer_of(x[1:]) if isinstance(x, str) else x for x in w], (fn, i, list(a), w)
         else:
             assert a == w and (a is None) == (w is None) and isinstance(a, float) == isinstance(w, float), (fn, i, a, w)
 
@@ -44,6 +46,8 @@ def expected(entry, f):
     """the C function and its arguments for the plain call of `entry` with every optional list present (where it takes any),
     K = 2, B = 4, id_stride = 5 over 9 ids (a forward-only call: B = 9); f: ORX_IDS_DEVICE or 0"""
     tri, outs = ("@uid", "@pid", "@nid"), (OUT, OUT)
+    if entry in FULL:
+        return expected_full(entry, f)
     return {
         "pairwise_step": ("orx_pairwise_step_weighted", ("h:ctx", _ffi.ORX_BPR, "h:opt", "h:U", "h:V", "h:b", *tri, "@weights", 2, 4, 5, 0.5, 1.0,
                                                         f, 0, *outs)),
@@ -68,7 +72,34 @@ def expected(entry, f):
     }[entry]
 
 
-FLUSHED = {"LightGCN": "UV", "VBPR": "VbEUv", "SeqRec": "VbH"}          # the tables a family flushes, in World.tables() order
+FIXED = _ffi.ORX_BAG_FIXED
+TOWER = (2, [0x1000, 0x1001], ["@f0", "@f1"], 2, [0x1004, 0x1006], [0x1005, None], 0)          # the stand-in's DeepSeqRec as the C calls take it
+
+
+def expected_full(entry, f, labels=None, label_weights=True, optional=True, bias=True, l2=(0.0, 0.0), chunks=(0, 0), mask=0, scale=1.0, outs=(OUT, OUT),
+                  rows=None):
+    """the same for the six calls on the softmax over all items; labels: None (pid), or "ragged" (the label lists reach the
+    library as they came); the rest: what the call was given beyond the defaults"""
+    b, wt, off = "h:b" if bias else None, "@weights" if optional else None, "@item_offset" if optional else None
+    step = "step" in entry
+    if entry.startswith("fullsoftmax"):
+        tail = (9, scale, l2[0], *chunks, mask, f, *outs) if step else (9, scale, chunks[0], f, OUT, OUT, rows)
+        return "orx_" + entry, ("h:ctx", *(("h:opt",) if step else ()), "h:U", "h:V", b, "@uid", "@pid", wt, off, *tail)
+    deep = entry.startswith("Deep")
+    lab = ("@pid",) if labels is None else ("@lab_ptr", "@lab_items", "@label_weights" if label_weights else None, 18)
+    coef = (l2 if deep else l2[:1])
+    tail = (9, 18, FIXED, 2.0, scale, *coef, *chunks, mask, f, *outs) if step else (9, 18, FIXED, 2.0, scale, chunks[0], f, OUT, OUT, rows)
+    name = ("orx_tower" if deep else "orx_seqrec_full") + ("_sets" if labels else "") + ("_step" if step else "_loss")
+    return name, ("h:ctx", *(("h:opt",) if step else ()), "h:H", "h:V", b, *(TOWER if deep else ()), "@ptr", "@items", *lab, wt, off, *tail)
+
+
+DEEP_TABLES = "S0S1W0c0W1"
+FLUSHED = {"LightGCN": "UV", "VBPR": "VbEUv", "SeqRec": "VbH", "SeqRec.full": "VbH",          # the tables a family flushes, in World.tables() order
+           "DeepSeqRec.full": "VbH" + DEEP_TABLES}
+
+
+def flushed(o):
+    return "".join(t.name for t in o.world.tables() if t.flushes)
 
 
 # ---- 1. the C call ------------------------------------------------------------------------------------------------------------------------
@@ -79,8 +110,8 @@ def test_the_c_call_of_every_entry_point(entry, dev):
     assert_call(o, *expected(entry, DEV if dev else 0))
     # the library's stream is ordered behind torch for every device list, and the flushes are the family's own
     assert o.ordered_lists() == (set(o.lists) if dev else set())
-    assert "".join(t._h[2:] for t in o.world.tables() if t.flushes) == FLUSHED.get(si.family(entry), "")
-    if entry.endswith("loss") or entry == "LightGCN.step":
+    assert flushed(o) == FLUSHED.get(si.family(entry), "")
+    if "loss" in entry.split(".")[-1] or entry == "LightGCN.step":
         assert isinstance(o.result, tuple) and len(o.result) == 2 and all(isinstance(x, float) for x in o.result)
     else:
         k = K if entry in KSTEP else 1
@@ -214,11 +245,12 @@ def test_lists_one_short_of_what_the_steps_read_are_refused(entry, dev):
 def test_float_lists_on_the_wrong_side_or_of_the_wrong_length_are_refused(entry, name):
     kw = shape_kw(entry)
     like_nid = name == "neg_offset"
+    full = NEED * N if like_nid else ITEMS if name == "item_offset" and entry in FULL else NEED          # (the full softmax: one float per ITEM)
     assert f"{name} on the device with ids on the host" in refused(entry, False, over={name: dict(dev=True)}, **kw)
     assert f"{name} on the host with ids on the device" in refused(entry, True, over={name: dict(dev=False)}, **kw)
     for dev in (False, True):
-        msg = refused(entry, dev, over={name: dict(shape=(NEED, N - 1) if like_nid else (NEED - 1,))}, **kw)
-        assert f"{NEED * (N - 1) if like_nid else NEED - 1} {name} for {NEED * N if like_nid else NEED} ids" in msg
+        msg = refused(entry, dev, over={name: dict(shape=(NEED, N - 1) if like_nid else (full - 1,))}, **kw)
+        assert f"{NEED * (N - 1) if like_nid else full - 1} {name} for {full} ids" in msg
 
 
 @pytest.mark.parametrize("entry", ["pairwise_step", "pointwise_step", "LightGCN.step", "VBPR.step", "SeqRec.step"])
@@ -232,7 +264,7 @@ def test_a_bad_train_is_refused(entry):
 
 
 @pytest.mark.parametrize("bad", [-1.0, float("nan"), float("inf"), -float("inf")])
-@pytest.mark.parametrize("entry,name", [(e, "l2_reg") for e in STEPS + ("LightGCN.loss",)] + [("VBPR.step", "l2_proj")])
+@pytest.mark.parametrize("entry,name", [(e, "l2_reg") for e in STEPS + ("LightGCN.loss",)] + [("VBPR.step", "l2_proj"), ("DeepSeqRec.step_full", "l2_mlp")])
 def test_a_bad_coefficient_is_refused(entry, name, bad):
     assert f"{name} must be finite and >= 0" in refused(entry, **{name: bad}, **shape_kw(entry))
 
@@ -286,7 +318,8 @@ def test_train_and_l2_refusals_come_before_any_device_object():
     ids, lab = np.zeros(4, np.int32), np.zeros(4, np.float32)
     nid = np.zeros((4, N), np.int32)
     models = {}
-    for cls, names in ((rt.LightGCN, ("U", "V", "ctx", "_h")), (rt.VBPR, ("U", "V", "b", "E", "features", "ctx")), (rt.SeqRec, ("H", "V", "b", "ctx"))):
+    for cls, names in ((rt.LightGCN, ("U", "V", "ctx", "_h")), (rt.VBPR, ("U", "V", "b", "E", "features", "ctx")), (rt.SeqRec, ("H", "V", "b", "ctx")),
+                       (rt.DeepSeqRec, ("H", "V", "b", "ctx", "side", "layers", "_tables"))):
         m = models[cls.__name__] = cls.__new__(cls)
         for nm in names:
             setattr(m, nm, t)
@@ -298,6 +331,9 @@ def test_train_and_l2_refusals_come_before_any_device_object():
         "LightGCN.step": lambda **kw: models["LightGCN"].step(t, ids, ids, ids, **kw),
         "VBPR.step": lambda **kw: models["VBPR"].step(t, ids, ids, ids, **kw),
         "SeqRec.step": lambda **kw: models["SeqRec"].step(t, (np.arange(5, dtype=np.int32), ids), ids, nid, **kw),
+        "fullsoftmax_step": lambda **kw: rt.fullsoftmax_step(t, t, t, t, ids, ids, **kw),
+        "SeqRec.step_full": lambda **kw: models["SeqRec"].step_full(t, (np.arange(5, dtype=np.int32), ids), ids, **kw),
+        "DeepSeqRec.step_full": lambda **kw: models["DeepSeqRec"].step_full(t, (np.arange(5, dtype=np.int32), ids), ids, **kw),
     }
     assert set(steps) == set(STEPS)
     for entry, step in steps.items():
@@ -307,3 +343,97 @@ def test_train_and_l2_refusals_come_before_any_device_object():
     for entry in ("pairwise_step", "pointwise_step", "multineg_step", "inbatch_step"):
         with pytest.raises(ValueError, match="no_l2"):
             steps[entry](no_l2=True, l2_reg=0.01)
+    for bad in (-1.0, math.nan):
+        with pytest.raises(ValueError, match="DeepSeqRec.step_full: l2_mlp"):
+            steps["DeepSeqRec.step_full"](l2_mlp=bad)
+
+
+# ---- 6. the calls on the softmax over all items: label sets, the tower's arrays, the options --------------------------------------------------
+BAGS = ("SeqRec.step_full", "SeqRec.loss_full", "DeepSeqRec.step_full", "DeepSeqRec.loss_full")
+
+
+@pytest.mark.parametrize("dev,f", [(False, 0), (True, DEV)], ids=["host", "device"])
+@pytest.mark.parametrize("lw", [True, False], ids=["label_weights", "no_label_weights"])
+@pytest.mark.parametrize("entry", BAGS)
+def test_ragged_label_sets_reach_the_sets_call_as_they_came(entry, lw, dev, f):
+    o = run(rt, entry, dev, labels="ragged", optional=si.OPTIONAL + (("label_weights",) if lw else ()))
+    assert_call(o, *expected_full(entry, f, labels="ragged", label_weights=lw))
+    assert o.ordered_lists() == (set(o.lists) if dev else set())
+    assert flushed(o) == FLUSHED[si.family(entry)]
+
+
+@pytest.mark.parametrize("lw", [True, False], ids=["label_weights", "no_label_weights"])
+@pytest.mark.parametrize("entry", BAGS)
+def test_a_padded_pair_of_label_sets_is_made_ragged_on_the_host(entry, lw):
+    """(a padded pair on the device is converted with torch's own ops: the GPU tests have it)"""
+    o = run(rt, entry, False, labels="padded", optional=("label_weights",) if lw else ())
+    name, want = expected_full(entry, 0, labels="ragged", label_weights=lw, optional=False)
+    at = want.index("@lab_ptr")
+    assert_call(o, name, tuple(OUT if str(w).startswith("@lab") else w for w in want))          # (arrays of the wrapper's own, 18 entries)
+    got = o.only_call()[1]
+    assert not {got[at], got[at + 1], got[at + 2]} & {o.pointer_of(k) for k in o.lists} and got[at] != got[at + 1]
+    assert flushed(o) == FLUSHED[si.family(entry)]
+
+
+@pytest.mark.parametrize("dev,f", [(False, 0), (True, DEV)], ids=["host", "device"])
+@pytest.mark.parametrize("entry", FULL)
+def test_the_options_of_the_full_softmax_calls(entry, dev, f):
+    step, deep = "step" in entry, entry.startswith("Deep")
+    o = run(rt, entry, dev, bias=False, scale=2.0, chunk_items=128)
+    assert_call(o, *expected_full(entry, f, optional=False, bias=False, scale=2.0, chunks=(128, 0)))
+    if not step:
+        if not dev:          # (device lists: the rows are a torch tensor on the device -- the GPU tests have it)
+            o = run(rt, entry, dev, per_row=True)
+            name, args = o.only_call()
+            assert len(o.result) == 3 and all(isinstance(x, float) for x in o.result[:2])
+            assert args[-1] == o.result[2].ctypes.data and o.result[2].shape == (NEED,) and o.result[2].dtype == np.float32
+        return
+    role = "user" if entry.startswith("fullsoftmax") else "history"
+    o = run(rt, entry, dev, l2_reg=0.5, chunk_samples=64, train=(role, "bias"), want_loss=False, **(dict(l2_mlp=0.25) if deep else {}))
+    assert_call(o, *expected_full(entry, f, optional=False, l2=(0.5, 0.25), chunks=(0, 64), mask=5, outs=(None, None)))
+    assert o.result is None and [t.name for t in o.world.opt._tables] == [c for c in (["U", "V", "b"] if role == "user" else
+                                                                                       ["H", "V", "b"] + (["S0", "S1", "W0", "c0", "W1"] if deep else []))]
+    if deep:
+        assert _tail(run(rt, entry, dev, train=("side", "tower")), 4)[0] == _ffi.ORX_TRAIN_SIDE | _ffi.ORX_TRAIN_TOWER
+
+
+@pytest.mark.parametrize("dev", [False, True], ids=["host", "device"])
+@pytest.mark.parametrize("entry", BAGS)
+def test_what_the_label_and_side_lists_refuse(entry, dev):
+    deep = entry.startswith("Deep")
+    assert "either pid" in refused(entry, dev, labels="ragged", over={"pid": {}}) and "not both" in refused(entry, dev, labels="ragged", over={"pid": {}})
+    o = run(rt, entry, dev, over={"pid": None})
+    assert isinstance(o.error, ValueError) and "one of them" in str(o.error) and o.calls == []
+    assert "label_weights without labels" in refused(entry, dev, optional=("label_weights",), over={"label_weights": dict(shape=(NEED,))})
+    assert "must live where the bags live" in refused(entry, dev, labels="ragged", over={"lab_ptr": dict(dev=not dev), "lab_items": dict(dev=not dev)})
+    assert f"{NEED} bags and {NEED + 1} label sets" in refused(entry, dev, labels="ragged", over={"lab_ptr": dict(shape=(NEED + 2,)), "lab_items": dict(shape=(2 * NEED + 2,))})
+    assert f"{2 * NEED - 1} label_weights for {2 * NEED} ids" in refused(entry, dev, labels="ragged", optional=("label_weights",),
+                                                                         over={"label_weights": dict(shape=(2 * NEED - 1,))})
+    assert "label_weights on the" in refused(entry, dev, labels="ragged", optional=("label_weights",), over={"label_weights": dict(dev=not dev)})
+    assert f"{NEED} bags and {NEED - 1} label ids" in refused(entry, dev, over={"pid": dict(shape=(NEED - 1,))})
+    if not dev:
+        assert "label_weights [9, 2] beside padded labels [9, 3]" in refused(entry, dev, labels="padded", optional=("label_weights",),
+                                                                             over={"label_weights": dict(shape=(NEED, 2))})
+        bad = np.arange(NEED + 1, dtype=np.int32) * 2
+        bad[-1] -= 1
+        assert "bag offsets must start at 0" in refused(entry, dev, over={"ptr": bad})
+    if deep:
+        assert "1 side id lists for 2 side tables" in refused(entry, dev, side_ids=(np.zeros(NEED, np.int32),))
+        assert "ids must be all on the host or all on the device" in refused(entry, dev, over={"f1": dict(dev=not dev)})
+        assert "side id lists of" in refused(entry, dev, over={"f0": dict(shape=(NEED + 1,))})
+        if "step" in entry:
+            o = run(rt, entry, dev, train=("side",))
+            assert o.error is None
+
+
+def test_a_bad_train_of_the_full_softmax_steps_is_refused():
+    for entry in ("fullsoftmax_step", "SeqRec.step_full", "DeepSeqRec.step_full"):
+        assert "unknown" in refused(entry, train=("users",)) and "empty" in refused(entry, train=())
+        assert '"bias" named' in refused(entry, train=("item", "bias"), bias=False)
+        assert "unknown" in refused(entry, train=("item", "history" if entry == "fullsoftmax_step" else "user"))
+    assert "unknown" in refused("SeqRec.step_full", train=("tower",))
+    m = rt.DeepSeqRec.__new__(rt.DeepSeqRec)
+    m.H = m.V = m.ctx = si.NoDevice()
+    m.b, m.side = None, []
+    with pytest.raises(ValueError, match='DeepSeqRec.step_full: train: "side" named'):
+        m.step_full(si.NoDevice(), (np.arange(5, dtype=np.int32), np.zeros(4, np.int32)), np.zeros(4, np.int32), train=("side",))
