@@ -3,9 +3,9 @@
 (`VanillaYouTubeRec.train_steps_full`) -- no negatives are drawn, no B x items matrix exists.  Beside it, from the same start and
 on the same batches, the sampled-softmax run of that example (`train_steps`, N drawn negatives).  Both are trained on one half
 of the users and recommend for the OTHER half from their histories alone; the script prints Recall@K of the held-out users' last
-item for both.
+item for both.  --precision bf16 runs the full-softmax steps with bf16 operands on the matrix cores (fp32 sums and tables).
 
-    python examples/seqrec_full_softmax.py [--steps 300] [--k 20]
+    python examples/seqrec_full_softmax.py [--steps 300] [--k 20] [--precision fp32|bf16]
 """
 import argparse
 import os
@@ -28,6 +28,7 @@ def main():
     ap.add_argument("--negatives", type=int, default=16)
     ap.add_argument("--seq", type=int, default=5)
     ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     args = ap.parse_args()
     raw, NU, NI = planted()
     train_half = raw["user_id"] % 2 == 0
@@ -43,7 +44,7 @@ def main():
     rng = np.random.default_rng(1)
     geo = rt.fullsoftmax_geometry(args.batch, NI, 32)
     print(f"{train.size} training records of {NU // 2} users, {len(ev['label'])} held-out users, {NI} items, histories of up to {args.seq}, "
-          f"D = 32, B = {args.batch}, Adam(0.01)")
+          f"D = 32, B = {args.batch}, Adam(0.01), full softmax in {args.precision}")
     print(f"  full softmax: {geo['item_chunks']} item chunks, {geo['sample_chunks']} sample chunks, {geo['scratch_bytes'] / 2 ** 20:.1f} MiB of "
           f"scratch (a B x items logit matrix and its gradient: {2 * args.batch * NI * 4 / 2 ** 20:.1f} MiB)")
     print(f"  start     : recall@{args.k} for the held-out users {recall_at(full, ev, args.k):.4f}")
@@ -52,7 +53,8 @@ def main():
         bt = next(batches)
         nid = rng.integers(0, NI, (args.batch, args.negatives)).astype(np.int32)
         want = (step + 1) % 100 == 0
-        lf = full.train_steps_full(opt_full, bt["seq_item_id"], bt["seq_len"], bt["label"], want_loss=want)
+        lf = full.train_steps_full(opt_full, bt["seq_item_id"], bt["seq_len"], bt["label"], want_loss=want,
+                                   precision=args.precision)
         ls = sampled.train_steps(opt_sampled, bt["seq_item_id"], bt["seq_len"], bt["label"], nid, loss="softmax", want_loss=want)
         if want or step + 1 == args.steps:
             tail = f"loss {lf[0][0]:.4f} / {ls[0][0]:.4f}  " if lf is not None else ""

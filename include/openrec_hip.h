@@ -79,7 +79,9 @@ enum orx_flags {
     ORX_POINT_SIGMOID = 16, /* orx_pointwise_step / _loss with ORX_WRMF: PointwiseMSELoss(sigmoid=True),
                              the prediction goes through a sigmoid before the weighted squared
                              error (modules/pointwise_mse_loss.py:24-25)        */
-    ORX_OUT_DEVICE = 32   /* orx_recommend_topk, orx_score_candidates: the outputs are device pointers */
+    ORX_OUT_DEVICE = 32,  /* orx_recommend_topk, orx_score_candidates: the outputs are device pointers */
+    ORX_FS_BF16 = 0x2000  /* the single-label full-softmax calls: the query-against-items products take bf16 operands on the
+                             matrix cores; fp32 sums, tables and optimizer state (the block above orx_fullsoftmax_step)      */
 };
 
 /* kernels whose device time can be sampled with orx_prof_* */
@@ -1226,7 +1228,18 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
  * bit for bit and, if row_loss_out is not NULL, l_i of every sample ([B], where the ids live; 0 for a dropped sample).
  * chunk_items / chunk_samples: items per chunk of the walks that own samples / samples per chunk of the walk that owns items; 0 --
  * the launcher's own choice, a function of (B, NI, D) alone -- or a positive multiple of the tile width 64.
- * flags: ORX_IDS_DEVICE, ORX_NO_L2 (the steps).  B == 0: ORX_OK, nothing is launched.
+ * flags: ORX_IDS_DEVICE, ORX_NO_L2 (the steps), ORX_FS_BF16.  B == 0: ORX_OK, nothing is launched.
+ * ORX_FS_BF16 (mixed precision; the six single-label calls orx_fullsoftmax_*, orx_seqrec_full_step / _loss, orx_tower_step /
+ * _loss -- the tower's own layers stay fp32).  With bf(x) = x rounded to nearest even to bfloat16:
+ *   s_ij   = scale * (sum_d bf(u_id) bf(V_jd) + b_j) + off_j      the sum in fp32 on the matrix cores; bias, offset, scale fp32
+ *   lse_i, l_i, tot_i, A_i, c_i as above, in fp32, from these s; the label's score is the same rounded product
+ *   g_u[i] = scale * sum_j bf(a_ij) bf(V_jd) + l2_reg u_i
+ *   G_V[j] = scale * sum_i bf(a_ij) bf(u_id) + l2_reg n_j V_j
+ *   G_b[j] = scale * sum_i a_ij                                   the unrounded fp32 coefficients
+ * The l2 loss, the l2 gradient terms, the tables, the optimizer slots and every apply use the unrounded fp32 values.  Everything
+ * else is as without the flag: off = -inf gives exactly zero gradients, a dead sample has c = 0, no float atomics, bit-repeatable
+ * results, the forward gives the step's loss and l2 bit for bit.  The label-set calls refuse the flag by name with ORX_ERR_ARG
+ * before any device work.
  * ORX_ERR_ARG before any device work: what orx_inbatch_step and orx_seqrec_step refuse for the same arguments (dims unequal or
  * above 256; a bias that is not [NI, 1]; scale; l2_reg; ORX_NO_L2 with l2_reg != 0; ORX_HOGWILD, ORX_CENSOR; another context; a
  * bad host bag_ptr; hist == item; what orx_apply_rows refuses); a chunk argument that is negative or no multiple of 64, or so
@@ -1236,8 +1249,10 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
  * orx_seqrec_step report it.  The id is never an address; its sample has c_i = 0 and contributes no loss, no l2, no gradient and
  * no n_j; the context stays usable.
  *   orx_fullsoftmax_geometry   no device: out = { own rows per workgroup, rows per tile, item chunks, sample chunks, padded dim,
- *                              scratch bytes of a step of the user-table form with every table trained }
- * Not offered: dropout between the query and the item table (hidden layers: orx_tower_step, below); K-step calls; UCML / L2 scoring; hit masking (every
+ *                              scratch bytes of a step of the user-table form with every table trained }; it reports the fp32
+ *                              path (ORX_FS_BF16 adds two bf16 copies, (Bp + NIp) rows of D rounded up to 32, to the scratch)
+ * Not offered: ORX_FS_BF16 with label sets (their sparse part scores the label entries from the fp32 rows), fp16 or fp8 operands,
+ * bf16 tables or optimizer state; dropout between the query and the item table (hidden layers: orx_tower_step, below); K-step calls; UCML / L2 scoring; hit masking (every
  * item is one column); a sampled or sharded item axis; label sets in the user-table form (orx_seqrec_full_sets_step and
  * orx_tower_sets_step have them). */
 int orx_fullsoftmax_step(orx_ctx* ctx, orx_opt* opt,

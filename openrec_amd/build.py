@@ -22,6 +22,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
             "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value",
             "-Wno-bitwise-instead-of-logical"]
+# per source file: kernels_fullsoftmax16.hip is compiled without the packed fp32 VALU instructions (v_pk_add / mul / fma_f32), so
+# its fp32 epilogue is the scalar-per-lane code the fp32 walk's is
+EXTRA_FLAGS = {"kernels_fullsoftmax16.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _sources():
@@ -60,7 +63,7 @@ def _compile(src):
     hdr_t = max(os.path.getmtime(f) for f in _deps() if not f.endswith(".hip"))
     if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(src), hdr_t):
         return obj
-    cmd = [HIPCC] + CXXFLAGS + ["-c", src, "-o", obj]
+    cmd = [HIPCC] + CXXFLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError("hipcc failed:\n" + " ".join(cmd) + "\n" + r.stdout + r.stderr)

@@ -17,7 +17,7 @@
 
 namespace {
 
-constexpr int FS_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_HOGWILD | ORX_CENSOR;      // (the last two are named to be refused by name)
+constexpr int FS_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_FS_BF16 | ORX_HOGWILD | ORX_CENSOR;      // (the last two are named to be refused by name)
 
 }  // namespace
 
@@ -38,7 +38,7 @@ int orx_fullsoftmax_check(const char* fn, int64_t B, int64_t NI, int32_t D, floa
 }
 
 void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, bool grads, bool query_side,
-                            bool item_side, bool host_off, FullSoftmaxLayout* l) {
+                            bool item_side, bool host_off, bool bf16, FullSoftmaxLayout* l) {
     memset(l, 0, sizeof(*l));
     FullSoftmaxPlan& p = l->plan;
     orx_fullsoftmax_plan(B, NI, D, chunk_items, chunk_samples, &p);
@@ -56,6 +56,11 @@ void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t
     if (grads && item_side) {
         l->gpv = cv->take(irows * p.ncs); l->bpart = cv->take(irow * p.ncs); l->npart = cv->take(irow * p.ncs);
         l->GV = cv->take((size_t)NI * D * sizeof(float)); l->Gb = cv->take((size_t)NI * sizeof(float));
+    }
+    l->bf16 = bf16;
+    if (bf16) {                                 // ORX_FS_BF16 alone pays for its copies; every other piece keeps its place
+        const size_t Dk = (size_t)((D + 31) & ~31);
+        l->xq16 = cv->take((size_t)p.Bp * Dk * sizeof(unsigned short)); l->xv16 = cv->take((size_t)p.NIp * Dk * sizeof(unsigned short));
     }
 }
 
@@ -77,6 +82,10 @@ int orx_fullsoftmax_bind(orx_ctx* c, const FullSoftmaxLayout& l, const FullSoftm
     a.pm = f(l.pm); a.pe = f(l.pe); a.psd = f(l.psd); a.rmax = f(l.rmax); a.cn = f(l.cn); a.dcoef = f(l.dcoef); a.rowloss = f(l.rowloss);
     a.gpq = f(l.gpq); a.gu = f(l.gu);
     a.gpv = f(l.gpv); a.bpart = f(l.bpart); a.npart = reinterpret_cast<int32_t*>(base + l.npart); a.GV = f(l.GV); a.Gb = f(l.Gb);
+    if (l.bf16) {
+        a.xq16 = reinterpret_cast<unsigned short*>(base + l.xq16); a.xv16 = reinterpret_cast<unsigned short*>(base + l.xv16);
+        a.Dk = (a.D + 31) & ~31;
+    }
     a.off = item_offset;
     if (item_offset && l.host_off) {          // one float per ITEM: it lives where the ids live, and is not among the per-sample lists
         ORX_HIP(hipMemcpyAsync(f(l.off), item_offset, (size_t)a.NI * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -140,7 +149,7 @@ extern "C" int orx_fullsoftmax_geometry(int64_t B, int64_t NI, int32_t D, int32_
     CHECK(orx_fullsoftmax_check(fn, B, NI, D, 1.0f, chunk_items, chunk_samples));
     Carve cv;
     FullSoftmaxLayout l;
-    orx_fullsoftmax_layout(&cv, B, NI, D, chunk_items, chunk_samples, true, true, true, false, &l);
+    orx_fullsoftmax_layout(&cv, B, NI, D, chunk_items, chunk_samples, true, true, true, false, false, &l);
     out[0] = 64; out[1] = 64; out[2] = l.plan.nci; out[3] = l.plan.ncs; out[4] = l.plan.Dp; out[5] = (int64_t)cv.off;
     return ORX_OK;
 }
@@ -162,7 +171,8 @@ int prepare(orx_ctx* c, FullSoftmaxForm& f, orx_table* V, orx_table* b, const in
     Carve cv;
     f.carve(&cv, grads);
     FullSoftmaxLayout lay;
-    orx_fullsoftmax_layout(&cv, B, V->rows, V->dim, chunk_items, chunk_samples, grads, grads && f.query_side, item_side, host && item_offset, &lay);
+    orx_fullsoftmax_layout(&cv, B, V->rows, V->dim, chunk_items, chunk_samples, grads, grads && f.query_side, item_side, host && item_offset,
+                           (flags & ORX_FS_BF16) != 0, &lay);
     LabelSetLayout llay;
     if (sets) orx_labelsets_layout(&cv, B, V->dim, sets->n, host, host && sets->weight, grads, &llay);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
@@ -182,6 +192,7 @@ int orx_fullsoftmax_drive_step(orx_ctx* c, orx_opt* opt, FullSoftmaxForm& f, orx
                                const float* weight, const float* item_offset, int64_t B, float scale, float l2_reg, int32_t chunk_items,
                                int32_t chunk_samples, int train_mask, int flags, float* loss_out, float* l2_out) {
     const char* fn = f.fn;
+    ORX_ARG(!(sets && (flags & ORX_FS_BF16)), "%s: ORX_FS_BF16 is not offered with label sets (their label entries are scored from the fp32 rows)", fn);
     CHECK(f.check());
     CHECK(orx_fullsoftmax_check(fn, B, V->rows, V->dim, scale, chunk_items, chunk_samples));
     CHECK(f.train(&train_mask));
@@ -233,6 +244,7 @@ int orx_fullsoftmax_drive_loss(orx_ctx* c, FullSoftmaxForm& f, orx_table* V, orx
                                const float* weight, const float* item_offset, int64_t B, float scale, int32_t chunk_items, int flags,
                                float* loss_out, float* l2_out, float* row_loss_out) {
     const char* fn = f.fn;
+    ORX_ARG(!(sets && (flags & ORX_FS_BF16)), "%s: ORX_FS_BF16 is not offered with label sets (their label entries are scored from the fp32 rows)", fn);
     CHECK(f.check());
     CHECK(orx_fullsoftmax_check(fn, B, V->rows, V->dim, scale, chunk_items, 0));
     const bool host = !(flags & ORX_IDS_DEVICE);

@@ -294,8 +294,8 @@ void bag_form(BagForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt* opt
     f->check = [=]() -> int {
         CHECK(check_model(fn, hist, item));
         CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
-        if (is_step) return orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS);
-        return orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR);
+        if (is_step) return orx_check_dot_step(fn, c, opt, hist, item, b, 0, 1, B, B, l2_reg, flags, SQ_FLAGS | ORX_FS_BF16);
+        return orx_check_dot_model(fn, c, hist, item, b, 0, flags, ORX_IDS_DEVICE | ORX_FS_BF16 | ORX_HOGWILD | ORX_CENSOR);
     };
     f->train = [=](int* mask) -> int {
         CHECK(orx_fullsoftmax_mask(fn, b, mask));

@@ -169,11 +169,11 @@ void tower_form(TowerForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt*
         CHECK(check_item(fn, hist, item));
         CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
         if (is_step) {
-            CHECK(orx_check_dot_step(fn, c, opt, item, item, b, 0, 1, B, B, l2_reg, flags, TW_FLAGS));
+            CHECK(orx_check_dot_step(fn, c, opt, item, item, b, 0, 1, B, B, l2_reg, flags, TW_FLAGS | ORX_FS_BF16));
             ORX_ARG(std::isfinite(l2_mlp) && l2_mlp >= 0.f, "%s: l2_mlp must be finite and >= 0 (got %g)", fn, (double)l2_mlp);
             ORX_ARG(!(flags & ORX_NO_L2) || l2_mlp == 0.f, "%s: ORX_NO_L2 together with l2_mlp = %g (drop the flag, or pass l2_mlp = 0)", fn, (double)l2_mlp);
         } else {
-            CHECK(orx_check_dot_model(fn, c, item, item, b, 0, flags, ORX_IDS_DEVICE | ORX_HOGWILD | ORX_CENSOR));
+            CHECK(orx_check_dot_model(fn, c, item, item, b, 0, flags, ORX_IDS_DEVICE | ORX_FS_BF16 | ORX_HOGWILD | ORX_CENSOR));
         }
         TowerModel& md = f->md;
         CHECK(check_tower(fn, c, hist, n_side, side, side_ids, n_layers, W, cs, relu_last, item->dim, "the item table", {item, b}, B, &md));

@@ -408,9 +408,10 @@ int orx_launch_fullsoftmax_lse(orx_ctx* ctx, const FullSoftmaxArgs& a) {
         ProfScope ps(ctx, ORX_K_FUSED);
         ORX_LAUNCH(ctx, fs_items_kernel, dim3((unsigned)((a.NIp * a.Dp + 255) / 256)), dim3(256), 0, a);
         ORX_HIP(hipGetLastError());
+        if (a.xv16) CHECK(orx_launch_fullsoftmax16_copies(ctx, a));          // (both callers have written xq by now)
     }
     ProfScope ps(ctx, ORX_K_GEMM);
-    return fs_walk<0>(ctx, a);
+    return a.xv16 ? orx_launch_fullsoftmax16_walk(ctx, a, 0) : fs_walk<0>(ctx, a);
 }
 
 int orx_launch_fullsoftmax_forward(orx_ctx* ctx, const FullSoftmaxArgs& a) {
@@ -430,7 +431,7 @@ int orx_launch_fullsoftmax_grads(orx_ctx* ctx, const FullSoftmaxArgs& a, bool qu
     if (query_side) {
         {
             ProfScope ps(ctx, ORX_K_GEMM);
-            CHECK(fs_walk<1>(ctx, a));
+            CHECK(a.xv16 ? orx_launch_fullsoftmax16_walk(ctx, a, 1) : fs_walk<1>(ctx, a));
         }
         ProfScope ps(ctx, ORX_K_FUSED);
         ORX_LAUNCH(ctx, fs_finish_kernel<0>, dim3((unsigned)((a.B * a.gs + 255) / 256)), dim3(256), 0, a);
@@ -439,7 +440,7 @@ int orx_launch_fullsoftmax_grads(orx_ctx* ctx, const FullSoftmaxArgs& a, bool qu
     if (item_side) {
         {
             ProfScope ps(ctx, ORX_K_GEMM);
-            CHECK(fs_walk<2>(ctx, a));
+            CHECK(a.xv16 ? orx_launch_fullsoftmax16_walk(ctx, a, 2) : fs_walk<2>(ctx, a));
         }
         ProfScope ps(ctx, ORX_K_FUSED);
         ORX_LAUNCH(ctx, fs_finish_kernel<1>, dim3((unsigned)((a.NI * (a.D + 1) + 255) / 256)), dim3(256), 0, a);

@@ -1075,22 +1075,28 @@ struct FullSoftmaxArgs {
     float* gu; float* GV; float* Gb;                      // [B][gs] query gradient rows; [NI][D] and [NI]: the dense gradients
     float* partial;                                       // [orx_fullsoftmax_npartials(B)][2] loss / l2 partials of this step
     int* err;
+    unsigned short* xq16; unsigned short* xv16; int Dk;   // ORX_FS_BF16: [Bp][Dk], [NIp][Dk] bf16 copies of xq / xv, Dk = D rounded up to 32; else NULL
 };
 struct FullSoftmaxPlan { int64_t Bp, NIp, Dp, tpi, nci, tps, ncs; };
 inline int orx_fullsoftmax_npartials(int64_t B) { return (int)((((B + 63) & ~(int64_t)63) + 255) / 256); }
 void orx_fullsoftmax_plan(int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, FullSoftmaxPlan* p);
 int orx_launch_fullsoftmax_forward(orx_ctx* ctx, const FullSoftmaxArgs& a);     // prepare, item copy, LSE pass, finalize
 int orx_launch_fullsoftmax_grads(orx_ctx* ctx, const FullSoftmaxArgs& a, bool query_side, bool item_side);      // a walk and its finishing pass per side
+// kernels_fullsoftmax16.hip: what the three launchers above run in the place of a walk when a.xv16 is set (ORX_FS_BF16) -- the bf16
+// copies once xq and xv are written, and walk `mode` (0 the LSE pass, 1 the query side, 2 the item side) on the matrix cores in bf16
+int orx_launch_fullsoftmax16_copies(orx_ctx* ctx, const FullSoftmaxArgs& a);
+int orx_launch_fullsoftmax16_walk(orx_ctx* ctx, const FullSoftmaxArgs& a, int mode);
 // what the drivers (below, after the tower's declarations) build a call from: the checks of (B, NI, D, scale, the chunk
 // arguments); the scratch of a step as offsets carved behind whatever the form has carved (host_off: a piece for a host
-// item_offset); the train mask of a form with the three usual tables
+// item_offset; bf16: the two bf16 copies of ORX_FS_BF16, behind everything else); the train mask of a form with the three usual tables
 struct FullSoftmaxLayout {
-    FullSoftmaxPlan plan; bool host_off;
+    FullSoftmaxPlan plan; bool host_off; bool bf16;
+    size_t xq16, xv16;
     size_t xq, xv, key, cw, sq, ib, io, pm, pe, psd, rmax, cn, dcoef, rowloss, off, gpq, gu, gpv, bpart, npart, GV, Gb;
 };
 int orx_fullsoftmax_check(const char* fn, int64_t B, int64_t NI, int32_t D, float scale, int32_t chunk_items, int32_t chunk_samples);
 void orx_fullsoftmax_layout(Carve* cv, int64_t B, int64_t NI, int32_t D, int32_t chunk_items, int32_t chunk_samples, bool grads, bool query_side,
-                            bool item_side, bool host_off, FullSoftmaxLayout* l);
+                            bool item_side, bool host_off, bool bf16, FullSoftmaxLayout* l);
 int orx_fullsoftmax_mask(const char* fn, orx_table* b, int* train_mask);
 int orx_launch_fullsoftmax_lse(orx_ctx* ctx, const FullSoftmaxArgs& a);         // the item copy and the LSE pass alone
 

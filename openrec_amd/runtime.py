@@ -614,6 +614,16 @@ def _scale_arg(what, scale):
     return scale
 
 
+def _precision_bits(what, precision, labels=None):
+    """precision= of the full-softmax calls -> the call's flag bits: "fp32", or "bf16" (ORX_FS_BF16: bf16 operands on the matrix
+    cores, fp32 sums and tables), which the label-set forms do not offer"""
+    if precision not in ("fp32", "bf16"):
+        raise ValueError(f"{what}: precision = {precision!r}; 'fp32' or 'bf16'")
+    if precision == "bf16" and labels is not None:
+        raise ValueError(f"{what}: precision='bf16' is not offered with labels= (a label set per bag)")
+    return _ffi.ORX_FS_BF16 if precision == "bf16" else 0
+
+
 def _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, scale, chunk_items, chunk_samples):
     """the checks and the pointers fullsoftmax_step and fullsoftmax_loss share; every bad argument is a ValueError raised
     here, before the library is called"""
@@ -631,7 +641,7 @@ def _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, sc
 
 
 def fullsoftmax_step(opt, user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None,
-                     chunk_items=0, chunk_samples=0, want_loss=True):
+                     chunk_items=0, chunk_samples=0, want_loss=True, precision="fp32"):
     """One train step on the softmax over ALL items (orx_fullsoftmax_step): sample i's label pid[i] against every row of the
     item table, s_ij = scale (u_i . V[j] + b[j]) + off[j] with u_i = user[uid[i]] -- the reference's
     sparse_softmax_cross_entropy_with_logits over a Dense(total_items) -- without a B x items matrix.  bias=None: no item bias.
@@ -640,16 +650,18 @@ def fullsoftmax_step(opt, user, item, bias, uid, pid, weights=None, item_offset=
     looked-up rows.  The user table takes the sparse rule on uid, the item table and the bias the optimizer's dense rule on
     every row.  train: None, or a subset of ("user", "item", "bias") -- every other table is read, never written.
     chunk_items / chunk_samples: 0 for the launcher's choice, or multiples of 64.  Returns (loss[1], l2[1]) as numpy float32
-    -- l2 the unscaled l2_loss -- when want_loss, else None (device ids: no host synchronisation).  Bad arguments raise
-    ValueError before the library is called; an id outside its table IndexError."""
+    -- l2 the unscaled l2_loss -- when want_loss, else None (device ids: no host synchronisation).  precision="bf16": the
+    products of the query rows with the item table take bf16 operands on the matrix cores (ORX_FS_BF16); sums, tables and
+    optimizer state stay fp32.  Bad arguments raise ValueError before the library is called; an id outside its table IndexError."""
     what = "fullsoftmax_step"
+    bits = _precision_bits(what, precision)
     mask = _train_mask(train, bias, what) or 0
     l2c = _coef_arg(what, "l2_reg", l2_reg)
     B, dev, ptrs, scale, ci, cs, keep = _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, scale,
                                                            chunk_items, chunk_samples)
     out, lp, l2p = _loss_outputs(1, want_loss)
     check(user.ctx._lib.orx_fullsoftmax_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, l2c, ci, cs,
-                                             mask, _flags(dev), lp, l2p))
+                                             mask, _flags(dev, bits), lp, l2p))
     _keep_tables(opt, (user, item, bias))
     return out
 
@@ -676,14 +688,16 @@ def _forward_result(out, rows, dev):
     return (*_loss_pair(out), rows)
 
 
-def fullsoftmax_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False):
-    """forward only: (loss, l2_loss) of one batch of fullsoftmax_step -- the step's own numbers bit for bit on the same tables;
-    no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+def fullsoftmax_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False,
+                     precision="fp32"):
+    """forward only: (loss, l2_loss) of one batch of fullsoftmax_step at the same precision -- the step's own numbers bit for
+    bit on the same tables; no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
     what = "fullsoftmax_loss"
+    bits = _precision_bits(what, precision)
     B, dev, ptrs, scale, ci, _, keep = _fullsoftmax_args(what, user, item, bias, uid, pid, weights, item_offset, scale, chunk_items, 0)
     out, lp, l2p = _loss_outputs(1, True)
     rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
-    check(user.ctx._lib.orx_fullsoftmax_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, ci, _flags(dev), lp, l2p, rp))
+    check(user.ctx._lib.orx_fullsoftmax_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, ci, _flags(dev, bits), lp, l2p, rp))
     return _forward_result(out, rows, dev)
 
 
@@ -2403,22 +2417,24 @@ def _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_i
 
 
 def _full_step(what, m, fns, lists, tables, opt, coefs, mask, pid, weights, item_offset, scale, chunk_items, chunk_samples, want_loss, labels,
-               label_weights):
+               label_weights, precision="fp32"):
+    bits = _precision_bits(what, precision, labels)
     B, n, dev, sets, ptrs, scale, ci, cs, keep = _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, chunk_samples,
                                                             labels, label_weights)
     out, lp, l2p = _loss_outputs(1, want_loss)
     check(getattr(m.ctx._lib, fns[sets])(m.ctx._h, opt._h, m.H._h, m.V._h, _bias_h(m.b), *ptrs, B, n, m._mode, m._denom, scale, *coefs, ci, cs,
-                                         mask, _flags(dev), lp, l2p))
+                                         mask, _flags(dev, bits), lp, l2p))
     _keep_tables(opt, tables)
     return out
 
 
-def _full_loss(what, m, fns, lists, tables, pid, weights, item_offset, scale, chunk_items, per_row, labels, label_weights):
+def _full_loss(what, m, fns, lists, tables, pid, weights, item_offset, scale, chunk_items, per_row, labels, label_weights, precision="fp32"):
+    bits = _precision_bits(what, precision, labels)
     B, n, dev, sets, ptrs, scale, ci, _, keep = _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, 0, labels,
                                                            label_weights)
     out, lp, l2p = _loss_outputs(1, True)
     rows, rp = _row_loss_buffer(m.ctx, B, dev, per_row)
-    check(getattr(m.ctx._lib, fns[sets])(m.ctx._h, m.H._h, m.V._h, _bias_h(m.b), *ptrs, B, n, m._mode, m._denom, scale, ci, _flags(dev), lp, l2p, rp))
+    check(getattr(m.ctx._lib, fns[sets])(m.ctx._h, m.H._h, m.V._h, _bias_h(m.b), *ptrs, B, n, m._mode, m._denom, scale, ci, _flags(dev, bits), lp, l2p, rp))
     return _forward_result(out, rows, dev)
 
 
@@ -2533,7 +2549,7 @@ class SeqRec:
         return lists
 
     def step_full(self, opt, bags, pid=None, weights=None, item_offset=None, scale=1.0, l2_reg=0.0, train=None, chunk_items=0,
-                  chunk_samples=0, want_loss=True, labels=None, label_weights=None):
+                  chunk_samples=0, want_loss=True, labels=None, label_weights=None, precision="fp32"):
         """One train step on the softmax over ALL items (orx_seqrec_full_step): bag i's pooled vector against every row of the
         item table, the label pid[i] -- rt.fullsoftmax_step's objective with the user row replaced by q.  weights [B];
         item_offset [items], one float per item (-inf removes an item); both live where the bags live.  The history table goes
@@ -2543,20 +2559,21 @@ class SeqRec:
         labels= with pid=None (orx_seqrec_full_sets_step): a label SET per bag under the multinomial likelihood,
         l_i = T_i lse_i - sum_e t_e s_{i,j_e} -- Mult-DAE's objective.  labels is (ptr, items), ragged, no host synchronisation
         wherever it lives, or the padded pair (seq, seq_len); label_weights: t_e per entry (None: 1).  An empty set keeps the
-        sample live with its l2 part alone; passing both pid and labels, or neither, raises."""
+        sample live with its l2 part alone; passing both pid and labels, or neither, raises.  precision="bf16": as in
+        rt.fullsoftmax_step (one label per bag only)."""
         what = "SeqRec.step_full"
         mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
         l2c = _coef_arg(what, "l2_reg", l2_reg)
         return _full_step(what, self, self._FULL_STEP, self._full_lists(bags), (self.H, self.V, self.b), opt, (l2c,), mask, pid, weights,
-                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights)
+                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights, precision)
 
     def loss_full(self, bags, pid=None, weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False, labels=None,
-                  label_weights=None):
+                  label_weights=None, precision="fp32"):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
         table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
         label_weights= as step_full takes them"""
         return _full_loss("SeqRec.loss_full", self, self._FULL_LOSS, self._full_lists(bags), (self.H, self.V, self.b), pid, weights, item_offset,
-                          scale, chunk_items, per_row, labels, label_weights)
+                          scale, chunk_items, per_row, labels, label_weights, precision)
 
     def user_table(self, bags, out=None):
         """-> a Table [B, D] of the pooled rows q_i of `bags` (out: a Table of that shape to write; None: one owned by this
@@ -2668,7 +2685,7 @@ class DeepSeqRec:
         return lists
 
     def step_full(self, opt, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, l2_reg=0.0, l2_mlp=0.0, train=None,
-                  chunk_items=0, chunk_samples=0, want_loss=True, labels=None, label_weights=None):
+                  chunk_items=0, chunk_samples=0, want_loss=True, labels=None, label_weights=None, precision="fp32"):
         """One train step on the softmax over ALL items (orx_tower_step): SeqRec.step_full's objective with the query computed by
         the tower.  side_ids: one id list [B] per side table, where the bags live.  J = loss + l2_reg * l2_loss + l2_mlp * 1/2
         sum_l (|W_l|^2 + |c_l|^2), l2_loss = 1/2 (sum |x0_i|^2 + sum |V[pid_i]|^2) on the embedding outputs.  The history table
@@ -2683,15 +2700,15 @@ class DeepSeqRec:
             raise ValueError(f'{what}: train: "side" named, but the model has no side table')
         l2c, l2m = _coef_arg(what, "l2_reg", l2_reg), _coef_arg(what, "l2_mlp", l2_mlp)
         return _full_step(what, self, self._FULL_STEP, self._full_lists(bags, side_ids), self._tables, opt, (l2c, l2m), mask, pid, weights,
-                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights)
+                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights, precision)
 
     def loss_full(self, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False,
-                  labels=None, label_weights=None):
+                  labels=None, label_weights=None, precision="fp32"):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
         table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
         label_weights= as step_full takes them"""
         return _full_loss("DeepSeqRec.loss_full", self, self._FULL_LOSS, self._full_lists(bags, side_ids), self._tables, pid, weights,
-                          item_offset, scale, chunk_items, per_row, labels, label_weights)
+                          item_offset, scale, chunk_items, per_row, labels, label_weights, precision)
 
     def user_table(self, bags, side_ids=(), out=None):
         """-> a Table [B, Dq] of the queries q_i (orx_tower_query) -- the rows the step scores with, bit for bit, and a row's bits

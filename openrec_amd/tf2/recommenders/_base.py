@@ -379,7 +379,7 @@ class PairwiseRecommender(Recommender):
                                l2_reg=self.l2_reg, want_loss=want_loss)
 
     def train_steps_full(self, optimizer, user_id, p_item_id, want_loss=True, sample_weight=None, item_offset=None, scale=1.0,
-                         train=None):
+                         train=None, precision="fp32"):
         """Beyond the reference API: one step on the softmax over ALL items in one device call (rt.fullsoftmax_step): every
         sample's positive is the label among every row of the item table -- no sampler, no B x items matrix.  user_id /
         p_item_id shaped [B].  sample_weight: per-sample weights shaped like the ids; item_offset [total_items]: added to an
@@ -395,4 +395,4 @@ class PairwiseRecommender(Recommender):
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(item_offset) if item_offset is not None else None
         return rt.fullsoftmax_step(opt, U, V, b, _ids(user_id), _ids(p_item_id), weights=wts, item_offset=off, scale=scale,
-                                   l2_reg=self.l2_reg, train=train, want_loss=want_loss)
+                                   l2_reg=self.l2_reg, train=train, want_loss=want_loss, precision=precision)

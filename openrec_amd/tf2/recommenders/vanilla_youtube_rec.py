@@ -118,7 +118,7 @@ class VanillaYouTubeRec(Recommender):
         return self._net.loss(self._bags(seq_item_id, seq_len), _ids(label), _ids(n_item_id), loss=loss, weights=wts, neg_offset=off)
 
     def train_steps_full(self, optimizer, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, want_loss=True,
-                         train=None, **user_features):
+                         train=None, precision="fp32", **user_features):
         """One train step on the reference's objective (rt.SeqRec.step_full): the softmax of the label over ALL items, no
         negatives to draw.  item_offset [total_items]: a per-item constant added to every row's logits (-inf removes an item,
         a padding id for one).  The item table and the bias take the optimizer's dense rule on every row.  With hidden layers
@@ -130,19 +130,21 @@ class VanillaYouTubeRec(Recommender):
         off = _ids(item_offset) if item_offset is not None else None
         if self._deep:
             return self._net.step_full(opt, self._bags(seq_item_id, seq_len), _ids(label), self._side(user_features), weights=wts,
-                                       item_offset=off, l2_reg=self.l2_reg, l2_mlp=self.l2_reg_mlp, train=train, want_loss=want_loss)
+                                       item_offset=off, l2_reg=self.l2_reg, l2_mlp=self.l2_reg_mlp, train=train, want_loss=want_loss,
+                                       precision=precision)
         self._side(user_features)
         return self._net.step_full(opt, self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off,
-                                   l2_reg=self.l2_reg, train=train, want_loss=want_loss)
+                                   l2_reg=self.l2_reg, train=train, want_loss=want_loss, precision=precision)
 
-    def loss_full(self, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, **user_features):
+    def loss_full(self, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, precision="fp32", **user_features):
         """the forward of train_steps_full alone -> (loss, l2)"""
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(item_offset) if item_offset is not None else None
         if self._deep:
-            return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), self._side(user_features), weights=wts, item_offset=off)
+            return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), self._side(user_features), weights=wts, item_offset=off,
+                                       precision=precision)
         self._side(user_features)
-        return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off)
+        return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off, precision=precision)
 
     def _label_sets(self, label_item_id, label_len, label_weight):
         lab, ln = _ids(label_item_id), _ids(label_len)
