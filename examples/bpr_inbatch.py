@@ -4,9 +4,10 @@ its negative is not used --, and `rt.inbatch_step` scores every positive against
 softmax with the log-Q correction: an item that is popular shows up as an in-batch negative in proportion to its count, so
 -log Q(item) is added to its column (Yi et al. 2019).  The counts are taken from the interactions with NumPy once.  The run
 prints the train loss and recall@20 of some users' training positives among all items (`rt.recommend_topk`), with and without
-the correction.
+the correction.  --precision bf16 trains every configuration a second time with bf16 operands on the matrix cores
+(`precision="bf16"`: fp32 sums, tables and optimizer state) and prints its final recall@20 beside the fp32 run's.
 
-    python examples/bpr_inbatch.py [--steps 300] [--batch 4096] [--temperature 0.5]
+    python examples/bpr_inbatch.py [--steps 300] [--batch 4096] [--temperature 0.5] [--precision bf16]
 """
 import argparse
 import os
@@ -40,7 +41,7 @@ def recall_at(U, V, b, users, positives, k=20):
     return hits / sum(min(k, len(positives[u])) for u in users)
 
 
-def train(sampler, NU, NI, steps, B, scale, neg_log_q, users, positives, log):
+def train(sampler, NU, NI, steps, B, scale, neg_log_q, users, positives, log, precision):
     import torch
     dev = torch.device("cuda", 0)
     U = rt.Table(NU, 64).init_uniform(seed=1); V = rt.Table(NI, 64).init_uniform(seed=2)
@@ -51,9 +52,11 @@ def train(sampler, NU, NI, steps, B, scale, neg_log_q, users, positives, log):
         sampler.pairwise(1, step * B, B, uid, pid, unused)
         sampler.ctx.synchronize()                                     # (the gather below runs on torch's stream)
         off = neg_log_q[pid.long()].contiguous() if neg_log_q is not None else None
-        out = rt.inbatch_step(opt, U, V, None, uid, pid, K=1, B=B, item_offset=off, scale=scale, l2_reg=1e-6, want_loss=want)
+        out = rt.inbatch_step(opt, U, V, None, uid, pid, K=1, B=B, item_offset=off, scale=scale, l2_reg=1e-6, want_loss=want,
+                              precision=precision)
         if want:
             print(f"  step {step + 1:4d}  train loss {out[0][0]:.4f}  recall@20 {recall_at(U, V, None, users, positives):.4f}")
+    return recall_at(U, V, None, users, positives)
 
 
 def main():
@@ -61,6 +64,7 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--temperature", type=float, default=0.5)
+    ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
     args = ap.parse_args()
     import torch
     raw, NU, NI = synthetic()
@@ -74,8 +78,12 @@ def main():
         if int(u) in positives:
             positives[int(u)].add(int(i))
     for name, off in (("in-batch softmax, no correction", None), ("in-batch softmax with the log-Q correction", neg_log_q)):
-        print(name)
-        train(sampler, NU, NI, args.steps, args.batch, 1.0 / args.temperature, off, users, positives, max(1, args.steps // 6))
+        final = {}
+        for precision in ("fp32", "bf16") if args.precision == "bf16" else ("fp32",):
+            print(f"{name} ({precision})")
+            final[precision] = train(sampler, NU, NI, args.steps, args.batch, 1.0 / args.temperature, off, users, positives,
+                                     max(1, args.steps // 6), precision)
+        print("  final recall@20  " + "  ".join(f"{k} {v:.4f}" for k, v in final.items()))
 
 
 if __name__ == "__main__":

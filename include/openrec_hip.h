@@ -320,15 +320,31 @@ int orx_multineg_loss(orx_ctx* ctx, int loss_kind,
  * call fully asynchronous.  weight and item_offset live where the ids live.  No float atomics in the step's own kernels or the
  * loss sums: loss_out, l2_out and the row losses are bit-repeatable, and so are the tables when bias == NULL (the sorted apply).
  * chunk_cols: 0 -- the launcher splits the columns of a row block into chunks as it sees fit, from (B, D) alone --, or a multiple
- * of the tile width 64: that many columns per chunk.  flags: ORX_IDS_DEVICE, ORX_NO_L2, ORX_IB_MASK_HITS.
+ * of the tile width 64: that many columns per chunk.  flags: ORX_IDS_DEVICE, ORX_NO_L2, ORX_IB_MASK_HITS, ORX_IB_BF16.
+ * ORX_IB_BF16 (mixed precision; orx_inbatch_step and orx_inbatch_loss).  With bf(x) = x rounded to nearest even to bfloat16:
+ *   s_ij   = scale * (sum_d bf(u_id) bf(v_jd) + b_j) + off_j      every score, the diagonal included; the sum in fp32 on the
+ *                                                                 matrix cores; bias, offset, scale fp32
+ *   lse_i, l_i, pi_ij, A_i, c_i and the hit masking as above, in fp32, from these s
+ *   g_u[i] = scale * sum_j bf(a_ij) bf(v_jd) + l2_reg u_id        the diagonal's a_ii = -c_i A_i is rounded like the others
+ *   g_v[j] = scale * sum_i bf(a_ij) bf(u_id) + l2_reg v_jd        (the coefficients span bf16's exponent range, not fp16's)
+ *   g_b[j] = scale * sum_i a_ij                                   the unrounded fp32 coefficients
+ * The l2 loss, the l2 gradient terms, the tables, the optimizer slots and orx_apply_rows use the unrounded fp32 values.  Everything
+ * else is as without the flag: a K-step call is K one-step calls bit for bit, lazy Adam touches exactly the rows read, a bad id
+ * gives ORX_ERR_INDEX and zeroes only its own sample, no float atomics, the losses are bit-repeatable and so are the tables when
+ * bias == NULL, the forward gives the step's loss and l2 bit for bit.  The flag adds two bf16 copies of the gathered rows, Bp rows
+ * of D rounded up to 32 each, to the scratch.
  * B == 1: l = 0, only the l2 gradient moves the rows.  K == 0 or B == 0: ORX_OK, nothing is launched.
  * ORX_ERR_ARG before any device work: scale not finite or <= 0; l2_reg negative or not finite; ORX_NO_L2 with l2_reg != 0;
  * ORX_HOGWILD or ORX_CENSOR; user dim != item dim, or a dim above 256; a bias that is not [item rows, 1]; tables or optimizer on
  * another context; chunk_cols negative or no multiple of 64; what orx_apply_rows refuses (ORX_ADAM_DENSE with a bias).
  * An id outside its table: ORX_ERR_INDEX as orx_multineg_step reports it.  The bad id is never used as an address; its sample
  * contributes no loss, no l2 and no gradient and leaves every other row's softmax as a column; the context stays usable.
- * Not offered: UCML / L2 scoring, train masks, the sharded engines, a symmetric (item -> user) loss. */
-enum orx_inbatch_flags { ORX_IB_MASK_HITS = 0x1000 };
+ * Not offered: UCML / L2 scoring, train masks, the sharded engines, a symmetric (item -> user) loss; fp16 or fp8 operands, bf16
+ * tables or optimizer state. */
+enum orx_inbatch_flags {
+    ORX_IB_MASK_HITS = 0x1000,
+    ORX_IB_BF16 = 0x2000      /* the value of ORX_FS_BF16: bf16 operands on the matrix cores, fp32 sums, tables and optimizer state */
+};
 int orx_inbatch_step(orx_ctx* ctx, orx_opt* opt,
                      orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
                      const int32_t* uid, const int32_t* pid,
@@ -337,7 +353,7 @@ int orx_inbatch_step(orx_ctx* ctx, orx_opt* opt,
                      float* loss_out, float* l2_out);
 /* Forward only, by the same kernels: (loss, l2_loss) of one batch -- the step's loss_out / l2_out bit for bit on the same tables
  * -- and, if row_loss_out is not NULL, l_i of every sample ([B], where the ids live; 0 for a sample with an id out of range).
- * No table changes.  flags: ORX_IDS_DEVICE, ORX_IB_MASK_HITS. */
+ * No table changes.  flags: ORX_IDS_DEVICE, ORX_IB_MASK_HITS, ORX_IB_BF16 (the forward of the step with the same flag). */
 int orx_inbatch_loss(orx_ctx* ctx,
                      orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
                      const int32_t* uid, const int32_t* pid,
@@ -345,7 +361,8 @@ int orx_inbatch_loss(orx_ctx* ctx,
                      int64_t B, float scale, int32_t chunk_cols, int flags,
                      float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
 /* What the launcher does for (B, D, chunk_cols): out = { own rows per workgroup, columns per tile, column chunks per row block,
- * padded dim }.  No device is needed. */
+ * padded dim }.  No device is needed.  It reports the fp32 path: under ORX_IB_BF16 the rows, the tile and the chunks are the same,
+ * the walks' k dimension is D rounded up to 32. */
 int orx_inbatch_geometry(int64_t B, int32_t D, int32_t chunk_cols, int32_t out[4]);
 
 /* K train steps of GMF.call / WRMF.call (gmf.py:22-34, wrmf.py:21-34,

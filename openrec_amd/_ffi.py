@@ -22,6 +22,7 @@ ORX_MN_SOFTMAX, ORX_MN_LOGSIG = 0, 1                          # enum orx_multine
 ORX_BAG_MEAN, ORX_BAG_FIXED = 0, 1                            # enum orx_bag_mode
 ORX_IB_MASK_HITS = 0x1000                                     # enum orx_inbatch_flags
 ORX_FS_BF16 = 0x2000                                          # enum orx_flags: the single-label full-softmax calls
+ORX_IB_BF16 = 0x2000                                          # enum orx_inbatch_flags: the same bit on the in-batch calls
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
 ORX_DLRM_FP16_MLP = 32

@@ -12,7 +12,7 @@
 
 namespace {
 
-constexpr int IB_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_IB_MASK_HITS | ORX_HOGWILD | ORX_CENSOR;
+constexpr int IB_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_IB_MASK_HITS | ORX_IB_BF16 | ORX_HOGWILD | ORX_CENSOR;
 
 // what the step and the forward check beyond the shared checks
 int check_own(const char* fn, orx_table* U, float scale, int32_t chunk_cols) {
@@ -47,6 +47,11 @@ int make_args(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b, int64_t B, f
         o_gpu = cv.take(rows * a.nch); o_gpv = cv.take(rows * a.nch); o_bp = cv.take(row * a.nch);
         o_gu = cv.take((size_t)B * a.gs * sizeof(float)); o_gi = cv.take((size_t)B * a.gs * sizeof(float));
     }
+    // ORX_IB_BF16: the bf16 copies of xu / xv, behind everything else; their pointers are what the launchers branch on
+    const bool bf16 = (flags & ORX_IB_BF16) != 0;
+    const int Dk = (a.D + 31) & ~31;
+    size_t o_xu16 = 0, o_xv16 = 0;
+    if (bf16) { o_xu16 = cv.take((size_t)a.Bp * Dk * sizeof(unsigned short)); o_xv16 = cv.take((size_t)a.Bp * Dk * sizeof(unsigned short)); }
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     char* base = reinterpret_cast<char*>(c->d_tmp);
     auto f = [&](size_t o) { return reinterpret_cast<float*>(base + o); };
@@ -54,6 +59,7 @@ int make_args(orx_ctx* c, orx_table* U, orx_table* V, orx_table* b, int64_t B, f
     a.key = reinterpret_cast<int32_t*>(base + o_key); a.cb = f(o_cb); a.co = f(o_co); a.cw = f(o_cw); a.sq = f(o_sq);
     a.pm = f(o_pm); a.pe = f(o_pe); a.psd = f(o_psd); a.rmax = f(o_rm); a.cn = f(o_cn); a.dcoef = f(o_dc); a.rowloss = f(o_rl);
     if (grads) { a.gpu = f(o_gpu); a.gpv = f(o_gpv); a.bpart = f(o_bp); a.gu = f(o_gu); a.gi = f(o_gi); }
+    if (bf16) { a.xu16 = reinterpret_cast<unsigned short*>(base + o_xu16); a.xv16 = reinterpret_cast<unsigned short*>(base + o_xv16); a.Dk = Dk; }
     *out = a;
     return ORX_OK;
 }

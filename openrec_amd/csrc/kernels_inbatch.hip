@@ -31,6 +31,8 @@
 // Masking is a compare of keys: a column whose key is < 0 is in nobody's softmax; with mask_hits, neither is a column j != i with
 // key[j] == key[i].  A row with key < 0 has c = 0, m = +inf (every exp(s - m) is 0) and a diagonal coefficient of 0.
 // No atomics anywhere: every sum has a fixed order.
+// ORX_IB_BF16 (a.xv16 set): the launchers at the end run kernels_inbatch16.hip's gather and walks in the place of this file's;
+// finalize, finish and the loss reduction are the ones here.
 #include <algorithm>
 
 #include "orx_device.h"
@@ -375,12 +377,15 @@ void orx_inbatch_plan(int64_t B, int32_t D, int32_t chunk_cols, int32_t out[4], 
 int orx_launch_inbatch_forward(orx_ctx* ctx, const InBatchArgs& a) {
     {
         ProfScope ps(ctx, ORX_K_FUSED);
-        ORX_LAUNCH(ctx, inbatch_gather_kernel, dim3((unsigned)((a.Bp + 3) / 4)), dim3(256), 0, a);
-        ORX_HIP(hipGetLastError());
+        if (a.xv16) CHECK(orx_launch_inbatch16_gather(ctx, a));
+        else {
+            ORX_LAUNCH(ctx, inbatch_gather_kernel, dim3((unsigned)((a.Bp + 3) / 4)), dim3(256), 0, a);
+            ORX_HIP(hipGetLastError());
+        }
     }
     {
         ProfScope ps(ctx, ORX_K_GEMM);
-        CHECK(ib_walk<0>(ctx, a));
+        CHECK(a.xv16 ? orx_launch_inbatch16_walk(ctx, a, 0) : ib_walk<0>(ctx, a));
     }
     ProfScope ps(ctx, ORX_K_FUSED);
     ORX_LAUNCH(ctx, inbatch_finalize_kernel, dim3((unsigned)orx_inbatch_npartials(a.B)), dim3(256), 0, a);
@@ -391,11 +396,11 @@ int orx_launch_inbatch_forward(orx_ctx* ctx, const InBatchArgs& a) {
 int orx_launch_inbatch_grads(orx_ctx* ctx, const InBatchArgs& a) {
     {
         ProfScope ps(ctx, ORX_K_GEMM);
-        CHECK(ib_walk<1>(ctx, a));
+        CHECK(a.xv16 ? orx_launch_inbatch16_walk(ctx, a, 1) : ib_walk<1>(ctx, a));
     }
     {
         ProfScope ps(ctx, ORX_K_GEMM);
-        CHECK(ib_walk<2>(ctx, a));
+        CHECK(a.xv16 ? orx_launch_inbatch16_walk(ctx, a, 2) : ib_walk<2>(ctx, a));
     }
     ProfScope ps(ctx, ORX_K_FUSED);
     ORX_LAUNCH(ctx, inbatch_finish_kernel, dim3((unsigned)((a.B * a.gs + 255) / 256)), dim3(256), 0, a);

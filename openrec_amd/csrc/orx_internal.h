@@ -1048,11 +1048,17 @@ struct InBatchArgs {
     float* gu; float* gi;                                 // [B][gs] gradient rows, the bias gradient in column D of gi
     float* partial;                                       // [orx_inbatch_npartials(B)][2] loss / l2 partials of this step
     int* err;
+    unsigned short* xu16; unsigned short* xv16; int Dk;   // ORX_IB_BF16: [Bp][Dk] bf16 copies of xu / xv, Dk = D rounded up to 32; else NULL
 };
 inline int orx_inbatch_npartials(int64_t B) { return (int)((((B + 63) & ~(int64_t)63) + 255) / 256); }
 void orx_inbatch_plan(int64_t B, int32_t D, int32_t chunk_cols, int32_t out[4], int* tiles_per_chunk = nullptr);
 int orx_launch_inbatch_forward(orx_ctx* ctx, const InBatchArgs& a);     // gather, LSE pass, finalize
 int orx_launch_inbatch_grads(orx_ctx* ctx, const InBatchArgs& a);       // the two gradient walks, the finishing pass
+// kernels_inbatch16.hip: what the two launchers above run in the place of the gather and of a walk when a.xv16 is set (ORX_IB_BF16)
+// -- the gather that also writes the bf16 copies, and walk `mode` (0 the LSE pass, 1 the user side, 2 the item side) on the matrix
+// cores in bf16
+int orx_launch_inbatch16_gather(orx_ctx* ctx, const InBatchArgs& a);
+int orx_launch_inbatch16_walk(orx_ctx* ctx, const InBatchArgs& a, int mode);
 
 // kernels_fullsoftmax.hip (orx_fullsoftmax_step / orx_seqrec_full_step and their forwards): one step of the softmax over all
 // items.  Bp = B and NIp = NI rounded up to 64, Dp = D rounded up to 16; every [Bp] / [NIp] / [..][Dp] / [chunks][..] array is

@@ -557,35 +557,40 @@ def _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights, it
 
 
 def inbatch_step(opt, user, item, bias, uid, pid, K=1, B=None, id_stride=None, weights=None, item_offset=None, scale=1.0,
-                 mask_hits=True, l2_reg=1.0, no_l2=False, want_loss=True, chunk=0):
+                 mask_hits=True, l2_reg=1.0, no_l2=False, want_loss=True, chunk=0, precision="fp32"):
     """K train steps on in-batch negatives (orx_inbatch_step): the positive of every sample is scored against the positives of
     all B samples of its step, s_ij = scale (u_i . v_j + b_j) + off_j, and the loss is the softmax over the row -- no sampler, no
     B x B matrix.  uid / pid as in pairwise_step; bias=None: no item bias.  weights: per-sample weights; item_offset: added to
     column j in every row (-log Q(pid[j]) is the log-Q correction); both shaped like the ids and living where they live.
     scale = 1 / temperature.  mask_hits: a column with the row's own positive item (other than the diagonal) is no negative.
     The objective is loss + l2_reg * l2_loss (no_l2=True: l2_reg = 0).  chunk: columns per chunk of a row block, 0 for the
-    launcher's choice.  Returns (loss[K], l2[K]) as numpy float32 -- l2 the unscaled l2_loss -- when want_loss, else None
-    (fully asynchronous).  Bad arguments raise ValueError before the library is called; an id outside its table IndexError."""
+    launcher's choice.  precision="bf16": the two products over the gathered rows take bf16 operands on the matrix cores
+    (ORX_IB_BF16); sums, tables and optimizer state stay fp32.  Returns (loss[K], l2[K]) as numpy float32 -- l2 the unscaled
+    l2_loss -- when want_loss, else None (fully asynchronous).  Bad arguments raise ValueError before the library is called; an
+    id outside its table IndexError."""
     what = "inbatch_step"
+    bits = _precision_bits(what, precision)
     l2c = _l2_arg(what, l2_reg, no_l2, default_is_one=True)
     K, B, id_stride, dev, ptrs, scale, chunk, keep = _inbatch_args(what, user, item, bias, uid, pid, K, B, id_stride, weights,
                                                                    item_offset, scale, chunk)
     out, lp, l2p = _loss_outputs(K, want_loss)
-    flags = _flags(dev, (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0))
+    flags = _flags(dev, (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | (_ffi.ORX_NO_L2 if no_l2 else 0) | bits)
     check(user.ctx._lib.orx_inbatch_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, K, B, id_stride, scale, l2c,
                                          chunk, flags, lp, l2p))
     _keep_tables(opt, (user, item, bias))
     return out
 
 
-def inbatch_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, mask_hits=True, chunk=0, per_row=False):
-    """forward only: (loss, l2_loss) of one batch of inbatch_step -- the step's own numbers bit for bit on the same tables; no
-    table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+def inbatch_loss(user, item, bias, uid, pid, weights=None, item_offset=None, scale=1.0, mask_hits=True, chunk=0, per_row=False,
+                 precision="fp32"):
+    """forward only: (loss, l2_loss) of one batch of inbatch_step at the same precision -- the step's own numbers bit for bit on
+    the same tables; no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+    bits = _precision_bits("inbatch_loss", precision)
     _, B, _, dev, ptrs, scale, chunk, keep = _inbatch_args("inbatch_loss", user, item, bias, uid, pid, 1, None, None, weights,
                                                            item_offset, scale, chunk)
     out, lp, l2p = _loss_outputs(1, True)
     rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
-    flags = _flags(dev, _ffi.ORX_IB_MASK_HITS if mask_hits else 0)
+    flags = _flags(dev, (_ffi.ORX_IB_MASK_HITS if mask_hits else 0) | bits)
     check(user.ctx._lib.orx_inbatch_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, scale, chunk, flags, lp, l2p, rp))
     return _forward_result(out, rows, dev)
 
@@ -615,8 +620,8 @@ def _scale_arg(what, scale):
 
 
 def _precision_bits(what, precision, labels=None):
-    """precision= of the full-softmax calls -> the call's flag bits: "fp32", or "bf16" (ORX_FS_BF16: bf16 operands on the matrix
-    cores, fp32 sums and tables), which the label-set forms do not offer"""
+    """precision= of the full-softmax and in-batch calls -> the call's flag bits: "fp32", or "bf16" (ORX_FS_BF16 == ORX_IB_BF16: bf16
+    operands on the matrix cores, fp32 sums and tables), which the label-set forms do not offer"""
     if precision not in ("fp32", "bf16"):
         raise ValueError(f"{what}: precision = {precision!r}; 'fp32' or 'bf16'")
     if precision == "bf16" and labels is not None:
