@@ -80,8 +80,9 @@ enum orx_flags {
                              the prediction goes through a sigmoid before the weighted squared
                              error (modules/pointwise_mse_loss.py:24-25)        */
     ORX_OUT_DEVICE = 32,  /* orx_recommend_topk, orx_score_candidates: the outputs are device pointers */
-    ORX_FS_BF16 = 0x2000  /* the single-label full-softmax calls: the query-against-items products take bf16 operands on the
+    ORX_FS_BF16 = 0x2000, /* the single-label full-softmax calls: the query-against-items products take bf16 operands on the
                              matrix cores; fp32 sums, tables and optimizer state (the block above orx_fullsoftmax_step)      */
+    ORX_TOPK_BF16_PREFILTER = 0x2000  /* orx_recommend_topk: the same bit; a speed option that changes no output bit (see there) */
 };
 
 /* kernels whose device time can be sampled with orx_prof_* */
@@ -506,10 +507,28 @@ int orx_rank_metrics_candidates_check(int64_t n, int64_t items, const int64_t* p
  *             form; either may be NULL for none)
  * 1 <= k <= 1024 (else ORX_ERR_ARG); a uid outside [0, user rows) or an excluded id outside [0, item rows) is ORX_ERR_INDEX.
  * Outputs out_items int32[n * k], out_scores float[n * k]: host memory, device memory with flags = ORX_OUT_DEVICE.
- * The result does not depend on launch shapes or atomics: a repeated call gives the same bits.  Lazy tables are synced. */
+ * The result does not depend on launch shapes or atomics: a repeated call gives the same bits.  Lazy tables are synced.
+ *
+ * flags | ORX_TOPK_BF16_PREFILTER: a pure speed option.  With or without it the outputs are the same bits (order, ties, NaN and
+ * -inf, padding included).  With it, where the fused route exists -- kinds dot, L2 and GMF, with or without bias, dim <= 256,
+ * more items than the threshold sample, no ORX_SCORE_SIMPLE -- every user x item product is first taken with bf16 operands on the
+ * matrix cores and compared against the exact fp32 threshold LOWERED by a proven bound of |bf16 score - fp32 score|; only the
+ * pairs that pass (a superset of the fp32 route's candidates, NaN and inf scores included) are re-scored with the scorer's own
+ * fp32 bits and selected as without the flag.  Users whose candidates overflow take the dense fallback as before.  L2 has no fused
+ * route without the flag and gets one with it.  Where the route does not exist the call takes the route it takes without the flag;
+ * without the flag none of this code runs.  The bf16 copy of the item table (items rounded up to 64, x dim rounded up to 32, x 2
+ * bytes, plus 8 bytes per item) is context scratch written once per call and never reused by a later one.
+ * orx_ctx_stat 4 / 5 / 6: of the most recent call, the users answered from prefiltered candidates, the users answered densely,
+ * and the candidates the prefilter kept for the former. */
 int orx_recommend_topk(orx_ctx* ctx, int kind, orx_table* user, orx_table* item, orx_table* bias, orx_table* w,
                        const int32_t* uid, int64_t n, const int64_t* excl_ptr, const int32_t* excl_items, int32_t k, int flags,
                        int32_t* out_items, float* out_scores);
+
+/* Host only: what orx_recommend_topk does for n users, `items` item rows of dim D, k, kind and flags (the process' ORX_SCORE_SIMPLE
+ * applies).  out = {route: 0 dense / 1 the fp32 fused route / 2 the bf16 prefilter, threshold sample P, candidate capacity C, users
+ * per batch, users per filter workgroup, items per filter tile, items per filter workgroup, bytes of the bf16 item copy}; the last
+ * four are 0 where there is no such thing. */
+int orx_topk_geometry(int64_t n, int64_t items, int32_t D, int32_t k, int kind, int flags, int64_t out[8]);
 
 /* The same selection and rules over scores that exist already: scores float[n * m] row-major, in device memory when
  * scores_on_device != 0 (e.g. what orx_score_all_items_device wrote), else on the host.  excl_ptr / excl_items as in

@@ -22,6 +22,7 @@ ORX_MN_SOFTMAX, ORX_MN_LOGSIG = 0, 1                          # enum orx_multine
 ORX_BAG_MEAN, ORX_BAG_FIXED = 0, 1                            # enum orx_bag_mode
 ORX_IB_MASK_HITS = 0x1000                                     # enum orx_inbatch_flags
 ORX_FS_BF16 = 0x2000                                          # enum orx_flags: the single-label full-softmax calls
+ORX_TOPK_BF16_PREFILTER = 0x2000                              # orx_recommend_topk: the same bit, a speed option that changes no output bit
 ORX_IB_BF16 = 0x2000                                          # enum orx_inbatch_flags: the same bit on the in-batch calls
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
@@ -150,6 +151,7 @@ SIGNATURES = {
     "orx_lightgcn_propagate": (c_int, [_p]),
     "orx_lightgcn_step": (c_int, [_p, _p, _ip, _ip, _ip, c_int64, c_float, c_int, c_int, POINTER(c_float), POINTER(c_float)]),
     "orx_lightgcn_loss": (c_int, [_p, _ip, _ip, _ip, c_int64, c_float, c_int, POINTER(c_float), POINTER(c_float)]),
+    "orx_topk_geometry": (c_int, [c_int64, c_int64, c_int32, c_int32, c_int, c_int, POINTER(c_int64)]),
     "orx_topk_rows": (c_int, [_p, _fp, c_int32, c_int64, c_int64, _p, _ip, c_int32, _ip, _fp]),
     "orx_sampler_create": (c_int, [_p, _ip, _ip, c_int64, _p, _ip, c_int64, c_int64, _pp]),
     "orx_sampler_destroy": (c_int, [_p]),

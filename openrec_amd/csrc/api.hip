@@ -127,7 +127,7 @@ extern "C" int orx_ctx_destroy(orx_ctx* c) {
     hipStreamSynchronize(c->stream);
     prof_collect(c);
     hipFree(c->d_err); hipFree(c->d_ids); hipFree(c->d_lab); hipFree(c->d_dflag); hipFree(c->d_evalbits); hipFree(c->d_ids2); hipFree(c->d_roles); hipFree(c->d_cflag); hipFree(c->d_dupbits); hipFree(c->d_dlist);
-    hipFree(c->d_dcount); hipFree(c->d_refinfo); hipFree(c->d_tricnt); hipFree(c->d_segstart); hipFree(c->d_alloc); hipFree(c->d_dseg); hipFree(c->d_dcnt); hipFree(c->d_chunks); hipFree(c->d_part); hipFree(c->d_partb); hipFree(c->d_stage); hipFree(c->d_stageb); hipFree(c->d_partial); hipFree(c->d_loss); hipFree(c->d_tmp); hipFree(c->d_topk);
+    hipFree(c->d_dcount); hipFree(c->d_refinfo); hipFree(c->d_tricnt); hipFree(c->d_segstart); hipFree(c->d_alloc); hipFree(c->d_dseg); hipFree(c->d_dcnt); hipFree(c->d_chunks); hipFree(c->d_part); hipFree(c->d_partb); hipFree(c->d_stage); hipFree(c->d_stageb); hipFree(c->d_partial); hipFree(c->d_loss); hipFree(c->d_tmp); hipFree(c->d_topk); hipFree(c->d_topk16);
     hipFree(c->d_wpart); hipFree(c->d_pl_cnt); hipFree(c->d_pl_list);
     hipFree(c->d_partner); hipFree(c->d_pslot); hipFree(c->d_ids4);
     hipFree(c->d_sort[0]); hipFree(c->d_sort[1]); hipFree(c->d_sort_hist); hipFree(c->d_csr_part[0]); hipFree(c->d_csr_part[1]); hipFree(c->d_splitk);
@@ -846,7 +846,8 @@ static int plan_stats_poll(orx_ctx* c) {
     return ORX_OK;
 }
 extern "C" int orx_ctx_stat(orx_ctx* c, int what, int64_t* out) {
-    ORX_ARG(c && out && what >= 0 && what <= 3, "orx_ctx_stat: bad argument");
+    ORX_ARG(c && out && what >= 0 && what <= 6, "orx_ctx_stat: bad argument");
+    if (what >= 4) { *out = what == 4 ? c->stat_topk_pref : what == 5 ? c->stat_topk_dense : c->stat_topk_cand; return ORX_OK; }
     ORX_HIP(hipSetDevice(c->device));
     if (c->stats_pending) { c->stats_age = 1 << 20; CHECK(plan_stats_poll(c)); }      // (wait for the counters the last call left behind)
     *out = what == 0 ? c->stat_pairs : what == 1 ? c->stat_max_dup : what == 2 ? c->stat_nowait_calls : (int64_t)(c->plan_stats.valid && c->plan_stats.quiet);

@@ -17,20 +17,21 @@ struct TopkScratch {
     int64_t* eptr; int32_t* eitems; int32_t* rowmap; int32_t* uidsub;
     int32_t* oi; float* os;
     int2* pool_iu; float* pool_s;           // the filter's per-workgroup candidate pools (fused route only)
+    unsigned long long* total;              // the bf16 prefilter's candidate counter
 };
 
 static int topk_scratch(orx_ctx* c, int64_t nb, int C, int64_t max_excl, int k, TopkScratch* s) {
     const size_t pool = C ? (size_t)TOPK_FILTER_BLOCKS * TOPK_POOL : 0;
-    const size_t sizes[12] = {(size_t)nb * 4, (size_t)nb * 4, (size_t)nb * C * 4, (size_t)nb * C * 4, (size_t)(nb + 1) * 8,
+    const size_t sizes[13] = {(size_t)nb * 4, (size_t)nb * 4, (size_t)nb * C * 4, (size_t)nb * C * 4, (size_t)(nb + 1) * 8,
                               (size_t)max_excl * 4, (size_t)nb * 4, (size_t)nb * 4, (size_t)nb * k * 4, (size_t)nb * k * 4,
-                              pool * 8, pool * 4};
-    size_t off[12];
-    ENSURE(c->d_topk, c->d_topk_cap, orx_layout(sizes, 12, off));
+                              pool * 8, pool * 4, 8};
+    size_t off[13];
+    ENSURE(c->d_topk, c->d_topk_cap, orx_layout(sizes, 13, off));
     unsigned char* p = c->d_topk;
     s->theta = (float*)(p + off[0]); s->cnt = (int*)(p + off[1]); s->cs = (float*)(p + off[2]); s->ci = (int32_t*)(p + off[3]);
     s->eptr = (int64_t*)(p + off[4]); s->eitems = (int32_t*)(p + off[5]); s->rowmap = (int32_t*)(p + off[6]);
     s->uidsub = (int32_t*)(p + off[7]); s->oi = (int32_t*)(p + off[8]); s->os = (float*)(p + off[9]);
-    s->pool_iu = (int2*)(p + off[10]); s->pool_s = (float*)(p + off[11]);
+    s->pool_iu = (int2*)(p + off[10]); s->pool_s = (float*)(p + off[11]); s->total = (unsigned long long*)(p + off[12]);
     return ORX_OK;
 }
 
@@ -75,6 +76,57 @@ static int topk_dense_users(orx_ctx* c, int kind, orx_table* U, orx_table* V, or
     return ORX_OK;
 }
 
+// the route of a call and its shapes: what orx_recommend_topk launches and what orx_topk_geometry reports
+struct TopkPlan {
+    int route;                  // 0 dense, 1 the fp32 fused route, 2 the bf16 prefilter
+    int C; int64_t P;           // candidate capacity and sample size
+    int64_t nb;                 // users per batch
+    int user_tile, item_tile; int64_t chunk;    // of the filter launch of a full batch (0: no filter)
+    int Dk; int64_t NIp; size_t copy_bytes;     // route 2: the item copy
+};
+
+static TopkPlan topk_plan(int64_t n, int64_t NI, int D, int k, int kind, int flags) {
+    TopkPlan p;
+    memset(&p, 0, sizeof(p));
+    // candidate capacity C and sample size P: the sample's k-th best leaves about k NI / P candidates, an eighth of C
+    p.C = 8192;
+    while (p.C < 160 * k && p.C < 65536) p.C <<= 1;
+    p.P = std::max<int64_t>(8192, (8 * (int64_t)k * NI + p.C - 1) / p.C);
+    p.P = (p.P + 63) / 64 * 64;
+    const bool tiles = D <= 256 && getenv("ORX_SCORE_SIMPLE") == nullptr && p.P < NI;
+    p.route = !tiles ? 0 : ((flags & ORX_TOPK_BF16_PREFILTER) ? 2 : (kind != 1 ? 1 : 0));    // (kernels_topk.hip: why no fp32 route for L2)
+    const size_t per_user = p.route ? (size_t)p.P * 4 + (size_t)p.C * 8 + 16 + (size_t)k * 8 : 16 + (size_t)k * 8;
+    const int64_t nbmax = p.route ? std::max<int64_t>(64, std::min<int64_t>(4096, (int64_t)(ORX_TOPK_BATCH_BYTES / per_user))) : 4096;
+    const int64_t nbatch = std::max<int64_t>(1, (n + nbmax - 1) / nbmax);
+    p.nb = (n + nbatch - 1) / nbatch;
+    if (p.route == 2) {
+        int UW, KBMAX;
+        orx_topk16_tile(p.nb, D, &UW, &KBMAX);
+        p.Dk = (D + 31) / 32 * 32; p.NIp = (NI + 63) / 64 * 64;
+        p.user_tile = 64 * UW; p.item_tile = 64; p.chunk = orx_topk16_chunk(p.nb, p.NIp, UW);
+        p.copy_bytes = (size_t)p.NIp * p.Dk * 2 + (size_t)p.NIp * 8;
+    } else if (p.route == 1) {             // orx_launch_topk_filter's shapes
+        int KB = 1;
+        while (16 * KB < D) KB *= 2;
+        const int UW = KB == 16 ? 1 : (p.nb > 64 ? 2 : 1), TI = KB == 16 ? 32 : 64;
+        const int64_t nqt = (p.nb + 64 * UW - 1) / (64 * UW);
+        int64_t chunk = ((NI * nqt + 1023) / 1024 + TI - 1) / TI * TI;
+        chunk = std::min<int64_t>(4096, std::max<int64_t>(chunk, 4 * TI));
+        const int64_t gx_max = std::max<int64_t>(1, TOPK_FILTER_BLOCKS / nqt);
+        if ((NI + chunk - 1) / chunk > gx_max) chunk = ((NI + gx_max - 1) / gx_max + TI - 1) / TI * TI;
+        p.user_tile = 64 * UW; p.item_tile = TI; p.chunk = chunk;
+    }
+    return p;
+}
+
+extern "C" int orx_topk_geometry(int64_t n, int64_t items, int32_t D, int32_t k, int kind, int flags, int64_t out[8]) {
+    ORX_ARG(out && n >= 1 && items >= 1 && D >= 1 && k >= 1 && k <= ORX_TOPK_MAX_K && kind >= 0 && kind <= 2, "orx_topk_geometry: bad argument");
+    const TopkPlan p = topk_plan(n, items, D, k, kind, flags);
+    out[0] = p.route; out[1] = p.P; out[2] = p.C; out[3] = p.nb; out[4] = p.user_tile; out[5] = p.item_tile; out[6] = p.chunk;
+    out[7] = (int64_t)p.copy_bytes;
+    return ORX_OK;
+}
+
 extern "C" int orx_recommend_topk(orx_ctx* c, int kind, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
                                   const int32_t* uid, int64_t n, const int64_t* excl_ptr, const int32_t* excl_items, int32_t k,
                                   int flags, int32_t* out_items, float* out_scores) {
@@ -82,27 +134,37 @@ extern "C" int orx_recommend_topk(orx_ctx* c, int kind, orx_table* U, orx_table*
     CHECK(orx_sync_tables({U, V, b, w}));
     ORX_ARG(c && U && V && n >= 0 && (n == 0 || (uid && out_items && out_scores)), "%s: NULL argument", fn);
     ORX_ARG(k >= 1 && k <= ORX_TOPK_MAX_K, "%s: k = %d outside [1, %d]", fn, k, ORX_TOPK_MAX_K);
-    ORX_ARG((flags & ~ORX_OUT_DEVICE) == 0, "%s: unknown flags 0x%x", fn, flags);
+    ORX_ARG((flags & ~(ORX_OUT_DEVICE | ORX_TOPK_BF16_PREFILTER)) == 0, "%s: unknown flags 0x%x", fn, flags);
     CHECK(orx_check_scorer(fn, c, kind, U, V, b, w, uid, n, true));
     if (excl_ptr) CHECK(orx_check_lists(fn, "exclusion", excl_ptr, excl_items, n, V->rows, false, nullptr));
+    c->stat_topk_pref = c->stat_topk_dense = c->stat_topk_cand = 0;
     if (n == 0) return ORX_OK;
     ORX_HIP(hipSetDevice(c->device));
     const int64_t NI = V->rows;
     const int D = U->dim;
     const bool dev_out = (flags & ORX_OUT_DEVICE) != 0;
-    // candidate capacity C and sample size P: the sample's k-th best leaves about k NI / P candidates, an eighth of C
-    int C = 8192;
-    while (C < 160 * k && C < 65536) C <<= 1;
-    int64_t P = std::max<int64_t>(8192, (8 * (int64_t)k * NI + C - 1) / C);
-    P = (P + 63) / 64 * 64;
-    const bool fused = kind != 1 && D <= 256 && getenv("ORX_SCORE_SIMPLE") == nullptr && P < NI;     // (kernels_topk.hip: why not L2)
-    const size_t per_user = fused ? (size_t)P * 4 + (size_t)C * 8 + 16 + (size_t)k * 8 : 16 + (size_t)k * 8;
-    const int64_t nbmax = fused ? std::max<int64_t>(64, std::min<int64_t>(4096, (int64_t)(ORX_TOPK_BATCH_BYTES / per_user))) : 4096;
-    const int64_t nbatch = (n + nbmax - 1) / nbmax, nb = (n + nbatch - 1) / nbatch;
+    const TopkPlan plan = topk_plan(n, NI, D, k, kind, flags);
+    const int C = plan.C;
+    const int64_t P = plan.P, nb = plan.nb;
+    const bool fused = plan.route != 0, pre16 = plan.route == 2;
     TopkScratch s;
     CHECK(topk_scratch(c, nb, fused ? C : 0, topk_max_excl(excl_ptr, n, nb), k, &s));
     ENSURE(c->d_ids, c->d_ids_cap, (size_t)nb * sizeof(int32_t));
     if (fused) ENSURE(c->d_tmp, c->d_tmp_cap, (size_t)nb * P * sizeof(float));
+    // the bf16 item copy, once per call and never kept: the tables change under training
+    unsigned short* V16 = nullptr;
+    float *nrm = nullptr, *hg = nullptr;
+    if (pre16) {
+        ENSURE(c->d_topk16, c->d_topk16_cap, plan.copy_bytes);
+        V16 = reinterpret_cast<unsigned short*>(c->d_topk16);
+        nrm = reinterpret_cast<float*>(c->d_topk16 + (size_t)plan.NIp * plan.Dk * 2);
+        hg = nrm + plan.NIp;
+        Topk16ItemArgs ia;
+        ia.V = V->w; ia.b = b ? b->w : nullptr; ia.NI = NI; ia.NIp = plan.NIp; ia.D = D; ia.Dk = plan.Dk; ia.l2 = kind == 1;
+        ia.V16 = V16; ia.nrm = nrm; ia.hg = hg;
+        CHECK(orx_launch_topk16_items(c, ia));
+        ORX_HIP(hipMemsetAsync(s.total, 0, 8, c->stream));
+    }
     static thread_local std::vector<int64_t> hp;
     static thread_local std::vector<int32_t> hi, local, huid_sub;
     static thread_local std::vector<int> hcnt;
@@ -122,10 +184,25 @@ extern "C" int orx_recommend_topk(orx_ctx* c, int kind, orx_table* U, orx_table*
             a.theta = s.theta; a.cnt = s.cnt; a.C = C;
             CHECK(orx_launch_topk_select(c, a, nq));
             // 2. every item scored, the candidates kept
-            bool launched = false;
-            CHECK(orx_launch_topk_filter(c, U->w, V->w, b ? b->w : nullptr, w ? w->w : nullptr, c->d_ids, nq, U->rows, NI, D, kind,
-                                         s.theta, s.cnt, s.cs, s.ci, C, s.pool_iu, s.pool_s, &launched));
-            ORX_ARG(launched, "orx_recommend_topk: no MFMA tile for dim %d", D);
+            if (pre16) {                   // a superset of them through the bf16 cores, then the scorer's own bits and its test
+                Topk16FilterArgs fa;
+                memset(&fa, 0, sizeof(fa));
+                fa.U = U->w; fa.w = w ? w->w : nullptr; fa.uid = c->d_ids; fa.nq = nq; fa.NU = U->rows; fa.NI = NI; fa.NIp = plan.NIp;
+                fa.D = D; fa.Dk = plan.Dk; fa.gmf = kind == 2; fa.V16 = V16; fa.nrm = nrm; fa.hg = hg;
+                fa.theta = s.theta; fa.cnt = s.cnt; fa.ci = s.ci; fa.C = C; fa.pool_iu = s.pool_iu;
+                CHECK(orx_launch_topk16_filter(c, fa, kind == 1));
+                Topk16RescoreArgs ra;
+                memset(&ra, 0, sizeof(ra));
+                ra.U = U->w; ra.V = V->w; ra.b = b ? b->w : nullptr; ra.w = w ? w->w : nullptr; ra.uid = c->d_ids; ra.NU = U->rows;
+                ra.NI = NI; ra.D = D; ra.kind = kind; ra.nrm = nrm; ra.theta = s.theta; ra.cnt = s.cnt; ra.cs = s.cs; ra.ci = s.ci;
+                ra.C = C; ra.total = s.total;
+                CHECK(orx_launch_topk16_rescore(c, ra, nq));
+            } else {
+                bool launched = false;
+                CHECK(orx_launch_topk_filter(c, U->w, V->w, b ? b->w : nullptr, w ? w->w : nullptr, c->d_ids, nq, U->rows, NI, D, kind,
+                                             s.theta, s.cnt, s.cs, s.ci, C, s.pool_iu, s.pool_s, &launched));
+                ORX_ARG(launched, "orx_recommend_topk: no MFMA tile for dim %d", D);
+            }
             // 3. selection over the candidates, the excluded ones left out
             memset(&a, 0, sizeof(a));
             a.cs = s.cs; a.ci = s.ci; a.cnt = s.cnt; a.C = C; a.k = k; a.out_items = oi; a.out_scores = os;
@@ -139,12 +216,20 @@ extern "C" int orx_recommend_topk(orx_ctx* c, int kind, orx_table* U, orx_table*
         } else {
             for (int64_t q = 0; q < nq; ++q) local.push_back((int32_t)q);
         }
+        c->stat_topk_dense += (int64_t)local.size();
+        if (pre16) c->stat_topk_pref += nq - (int64_t)local.size();
         CHECK(topk_dense_users(c, kind, U, V, b, w, uid + q0, local, s, excl_ptr != nullptr, n > 64, k, oi, os, huid_sub));
         if (!dev_out) {
             ORX_HIP(hipMemcpyAsync(out_items + q0 * k, oi, (size_t)nq * k * 4, hipMemcpyDeviceToHost, c->stream));
             ORX_HIP(hipMemcpyAsync(out_scores + q0 * k, os, (size_t)nq * k * 4, hipMemcpyDeviceToHost, c->stream));
         }
         ORX_HIP(hipStreamSynchronize(c->stream));          // (the host staging vectors are refilled by the next batch)
+    }
+    if (pre16) {
+        unsigned long long total = 0;
+        ORX_HIP(hipMemcpyAsync(&total, s.total, 8, hipMemcpyDeviceToHost, c->stream));
+        ORX_HIP(hipStreamSynchronize(c->stream));
+        c->stat_topk_cand = (int64_t)total;
     }
     return orx_check_index_error(c);
 }

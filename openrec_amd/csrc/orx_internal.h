@@ -115,6 +115,8 @@ struct orx_ctx {
     double* d_loss = nullptr;  size_t d_loss_cap = 0;       // [K][2] step results
     float* d_tmp = nullptr;    size_t d_tmp_cap = 0;        // misc fp32 scratch
     unsigned char* d_topk = nullptr; size_t d_topk_cap = 0;  // top-K: thresholds, candidate lists, exclusion rows, staged outputs
+    unsigned char* d_topk16 = nullptr; size_t d_topk16_cap = 0;      // top-K bf16 prefilter: the item copy of one call (never cached)
+    int64_t stat_topk_pref = 0, stat_topk_dense = 0, stat_topk_cand = 0;     // orx_ctx_stat 4 / 5 / 6: the last orx_recommend_topk call
     float* d_wpart = nullptr;  size_t d_wpart_cap = 0;      // [nwaves][D] dense-kernel gradient partials
     // deterministic row apply (kernels_rowsort.hip): ping-pong buffers of the radix sort, its histograms, partial sums of runs
     // that cross a 64-entry block
@@ -584,6 +586,31 @@ constexpr int TOPK_POOL = 2048;            // pending candidates per workgroup (
 int orx_launch_topk_filter(orx_ctx* ctx, const float* U, const float* V, const float* b, const float* w, const int32_t* uid,
                            int64_t nq, int64_t NU, int64_t NI, int D, int kind, const float* theta, int* cnt, float* cs,
                            int32_t* ci, int C, int2* pool_iu, float* pool_s, bool* launched);
+
+// the bf16 prefilter of the top-K (kernels_topk16.hip)
+struct Topk16ItemArgs {
+    const float* V; const float* b; int64_t NI; int64_t NIp; int D; int Dk; int l2;       // NIp: NI rounded up to 64; Dk: D to 32
+    unsigned short* V16; float* nrm; float* hg;      // [NIp][Dk] bf16 rows; [NIp] |v| bound (L2: the scorer's |v|^2); [NIp] the test's item side
+};
+struct Topk16FilterArgs {
+    const float* U; const float* w; const int32_t* uid; int64_t nq; int64_t NU; int64_t NI; int64_t NIp;
+    int D; int Dk; int gmf;
+    const unsigned short* V16; const float* nrm; const float* hg;
+    const float* theta; int* cnt; int32_t* ci; int C;
+    int2* pool_iu; int pool_cap; int64_t chunk; float cmul; int* err;         // (the last four are the launcher's)
+};
+struct Topk16RescoreArgs {
+    const float* U; const float* V; const float* b; const float* w; const int32_t* uid; int64_t NU; int64_t NI;
+    int D; int KB; int kind; const float* nrm;       // nrm: the scorer's |v|^2 per item (L2)
+    const float* theta; int* cnt; float* cs; int32_t* ci; int C;
+    unsigned long long* total;                       // += the candidates the filter kept for the users rescored
+    int* err;
+};
+int orx_launch_topk16_items(orx_ctx* ctx, const Topk16ItemArgs& a);
+void orx_topk16_tile(int64_t nq, int D, int* UW, int* KBMAX);
+int64_t orx_topk16_chunk(int64_t nq, int64_t NIp, int UW);
+int orx_launch_topk16_filter(orx_ctx* ctx, Topk16FilterArgs a, bool l2);
+int orx_launch_topk16_rescore(orx_ctx* ctx, Topk16RescoreArgs a, int64_t nq);
 
 // launchers implemented in kernels_pairwise.hip
 int orx_launch_dedup(orx_ctx* ctx, const DedupArgs& a, int64_t K);

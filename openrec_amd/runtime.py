@@ -88,9 +88,12 @@ class Context:
         check(self._lib.orx_prof_reset(self._h))
 
     def stat(self, what):
-        """orx_ctx_stat: 'pairs' | 'max_dup' | 'nowait_calls' | 'quiet' of the most recent exact pairwise call's plan"""
+        """orx_ctx_stat: 'pairs' | 'max_dup' | 'nowait_calls' | 'quiet' of the most recent exact pairwise call's plan;
+        'topk_prefiltered' | 'topk_dense' | 'topk_candidates' of the most recent recommend_topk call: the users answered from
+        bf16-prefiltered candidates, the users answered densely, the candidates the prefilter kept for the former"""
         v = c_int64()
-        check(self._lib.orx_ctx_stat(self._h, {"pairs": 0, "max_dup": 1, "nowait_calls": 2, "quiet": 3}[what], byref(v)))
+        codes = {"pairs": 0, "max_dup": 1, "nowait_calls": 2, "quiet": 3, "topk_prefiltered": 4, "topk_dense": 5, "topk_candidates": 6}
+        check(self._lib.orx_ctx_stat(self._h, codes[what], byref(v)))
         return int(v.value)
 
     def copy_bandwidth(self, nbytes=1 << 30, reps=10):
@@ -911,12 +914,28 @@ def _excl_lists(excl, n, items):
     return excl.ptr, excl.items
 
 
-def recommend_topk(kind, user, item, bias, uid, k, excl=None, w=None, device=False):
+def _prefilter_flag(prefilter):
+    if prefilter not in (None, "bf16"):
+        raise ValueError(f"prefilter = {prefilter!r}: None or 'bf16'")
+    return _ffi.ORX_TOPK_BF16_PREFILTER if prefilter else 0
+
+
+def topk_geometry(kind, n, items, dim, k, prefilter=None):
+    """orx_topk_geometry (host only): what recommend_topk does for these shapes -> dict(route: 0 dense / 1 fp32 fused / 2 bf16
+    prefilter, sample, capacity, batch_users, user_tile, item_tile, chunk, copy_bytes)"""
+    out = (c_int64 * 8)()
+    check(_ffi.load().orx_topk_geometry(int(n), int(items), int(dim), _topk_k(k), _kind_arg(kind), _prefilter_flag(prefilter), out))
+    return dict(zip(("route", "sample", "capacity", "batch_users", "user_tile", "item_tile", "chunk", "copy_bytes"), map(int, out)))
+
+
+def recommend_topk(kind, user, item, bias, uid, k, excl=None, w=None, device=False, prefilter=None):
     """The k best items of each user -> (item ids int32 [n, k], scores float32 [n, k]), without the [n, item_rows] score
     matrix.  Scores are bit-identical to `score_all_items`; order: score descending, then item id ascending; items in
     `excl` (a SparseMask, or a dense bool mask [n, item_rows]) and NaN scores are skipped, and a row with fewer than k such
-    items ends in item -1 / score -inf.  `device=True`: two torch tensors in HBM instead of host arrays."""
+    items ends in item -1 / score -inf.  `device=True`: two torch tensors in HBM instead of host arrays.  `prefilter="bf16"`:
+    the same bits, found through a bf16 matrix-core pass whose survivors are re-scored in fp32 (ORX_TOPK_BF16_PREFILTER)."""
     lib = user.ctx._lib
+    pf = _prefilter_flag(prefilter)
     ptr, n, keep = _host_uid("recommend_topk", uid)
     k = _topk_k(k)
     kd = _kind_arg(kind)
@@ -929,11 +948,11 @@ def recommend_topk(kind, user, item, bias, uid, k, excl=None, w=None, device=Fal
         items_t = torch.empty((n, k), dtype=torch.int32, device=dv)
         scores_t = torch.empty((n, k), dtype=torch.float32, device=dv)
         user.ctx.after_torch(items_t, scores_t)
-        check(lib.orx_recommend_topk(*head, _ffi.ORX_OUT_DEVICE, items_t.data_ptr(), scores_t.data_ptr()))
+        check(lib.orx_recommend_topk(*head, _ffi.ORX_OUT_DEVICE | pf, items_t.data_ptr(), scores_t.data_ptr()))
         return items_t, scores_t
     items_h = np.empty((n, k), np.int32)
     scores_h = np.empty((n, k), np.float32)
-    check(lib.orx_recommend_topk(*head, 0, items_h.ctypes.data, scores_h.ctypes.data))
+    check(lib.orx_recommend_topk(*head, pf, items_h.ctypes.data, scores_h.ctypes.data))
     return items_h, scores_h
 
 
@@ -2588,11 +2607,12 @@ class SeqRec:
         out = _owned_output(what, self, B, self.H.dim, out)
         return bag_pool(self.H, keep[2:], out, self.pool)           # (the ragged lists: a padded pair is converted once)
 
-    def recommend(self, bags, k, excl=None):
+    def recommend(self, bags, k, excl=None, prefilter=None):
         """the k best items for each history -> (item ids int32 [B, k], scores float32 [B, k]): recommend_topk("dot", ...) on
-        user_table(bags); excl: a SparseMask or a dense bool mask [B, items] of items never returned (the history itself, say)"""
+        user_table(bags); excl: a SparseMask or a dense bool mask [B, items] of items never returned (the history itself, say);
+        prefilter: recommend_topk's"""
         Q = self.user_table(bags)
-        return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl)
+        return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl, prefilter=prefilter)
 
 
 # ---- history-pooled recommender with a dense tower (orx_tower_step / orx_tower_loss / orx_tower_query) -------------------------------
@@ -2732,8 +2752,9 @@ class DeepSeqRec:
         check(self.ctx._lib.orx_tower_query(self.ctx._h, self.H._h, *model, pp, pi, B, n, self._mode, self._denom, out._h, 0, _flags(dev)))
         return out
 
-    def recommend(self, bags, side_ids, k, excl=None):
+    def recommend(self, bags, side_ids, k, excl=None, prefilter=None):
         """the k best items for each history -> (item ids int32 [B, k], scores float32 [B, k]): recommend_topk("dot", ...) on
-        user_table(bags, side_ids); excl: a SparseMask or a dense bool mask [B, items] of items never returned"""
+        user_table(bags, side_ids); excl: a SparseMask or a dense bool mask [B, items] of items never returned; prefilter:
+        recommend_topk's"""
         Q = self.user_table(bags, side_ids)
-        return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl)
+        return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl, prefilter=prefilter)

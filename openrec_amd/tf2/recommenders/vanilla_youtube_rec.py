@@ -204,9 +204,9 @@ class VanillaYouTubeRec(Recommender):
         Q, V, b = self._tables()
         return rt.score_all_items("dot", Q, V, b, uid, device=True)
 
-    def recommend(self, seq_item_id, seq_len, k, excl_mask=None, **user_features):
+    def recommend(self, seq_item_id, seq_len, k, excl_mask=None, prefilter=None, **user_features):
         """the k best items of each history -> (item ids [B, k], scores [B, k]); see Recommender.recommend"""
-        return super().recommend(self._rows(seq_item_id, seq_len, user_features), k, excl_mask)
+        return super().recommend(self._rows(seq_item_id, seq_len, user_features), k, excl_mask, prefilter)
 
     def score(self, seq_item_id, seq_len, candidates, **user_features):
         """the scores of each history's own candidate list; see Recommender.score"""
