@@ -5,7 +5,7 @@ groups (a, c); the next item lies in group (a * c + 3 * gender) mod G -- a produ
 feature the depth-0 model never sees -- and `geo` picks which part of that group.  Both models train on the softmax over all
 items (`train_steps_full`) from the same batches and recommend for held-out histories; the script prints Recall@K for both.
 
-    python examples/youtube_rec_synthetic.py [--steps 400] [--k 20]
+    python examples/youtube_rec_synthetic.py [--steps 400] [--k 20] [--tower-precision bf16]
 """
 import argparse
 import os
@@ -34,9 +34,9 @@ def draw(rng, n, L):
     return seq, lens.astype(np.int32), gender.astype(np.int32), geo.astype(np.int32), label
 
 
-def recall_at(model, held, k, feats):
+def recall_at(model, held, k, feats, tower_precision="fp32"):
     seq, lens, gender, geo, label = held
-    ids, _ = model.recommend(seq, lens, k, **(dict(gender=gender, geo=geo) if feats else {}))
+    ids, _ = model.recommend(seq, lens, k, tower_precision=tower_precision, **(dict(gender=gender, geo=geo) if feats else {}))
     return float((np.asarray(ids) == label[:, None]).any(1).mean())
 
 
@@ -46,7 +46,9 @@ def main():
     ap.add_argument("--batch", type=int, default=2048)
     ap.add_argument("--seq", type=int, default=6)
     ap.add_argument("--k", type=int, default=20)
+    ap.add_argument("--tower-precision", choices=("fp32", "bf16"), default="fp32", help="the precision of the tower's layer products")
     args = ap.parse_args()
+    tp = args.tower_precision
     NI = G * PER
     rng = np.random.default_rng(0)
     held = draw(rng, 4096, args.seq)
@@ -54,16 +56,16 @@ def main():
                       dim_item_embed={"id": 32, "total": 32}, max_seq_len=args.seq, hidden=[128, 32], pool="mean")
     flat = VanillaYouTubeRec(dim_item_embed=32, max_seq_len=args.seq, total_items=NI, use_item_bias=False, pool="mean")
     od, of = rt.Optimizer.adam(0.01), rt.Optimizer.adam(0.01)
-    print(f"{NI} items in {G} groups, histories of up to {args.seq}, B = {args.batch}, Adam(0.01); tower {deep._net.widths}, "
-          f"{rt.tower_geometry(args.batch, deep._net.widths)['scratch_bytes'] / 2 ** 20:.1f} MiB of tower scratch")
-    print(f"  start     : recall@{args.k} tower {recall_at(deep, held, args.k, True):.4f}, depth 0 {recall_at(flat, held, args.k, False):.4f}")
+    print(f"{NI} items in {G} groups, histories of up to {args.seq}, B = {args.batch}, Adam(0.01); tower {deep._net.widths} in {tp}, "
+          f"{rt.tower_geometry(args.batch, deep._net.widths, tp)['scratch_bytes'] / 2 ** 20:.1f} MiB of tower scratch")
+    print(f"  start     : recall@{args.k} tower {recall_at(deep, held, args.k, True, tp):.4f}, depth 0 {recall_at(flat, held, args.k, False):.4f}")
     for step in range(args.steps):
         seq, lens, gender, geo, label = draw(rng, args.batch, args.seq)
         want = (step + 1) % 100 == 0 or step + 1 == args.steps
-        ld = deep.train_steps_full(od, seq, lens, label, want_loss=want, gender=gender, geo=geo)
+        ld = deep.train_steps_full(od, seq, lens, label, want_loss=want, tower_precision=tp, gender=gender, geo=geo)
         lf = flat.train_steps_full(of, seq, lens, label, want_loss=want)
         if want:
-            print(f"  step {step + 1:5d}: loss {ld[0][0]:.4f} / {lf[0][0]:.4f}  recall@{args.k} tower {recall_at(deep, held, args.k, True):.4f}, "
+            print(f"  step {step + 1:5d}: loss {ld[0][0]:.4f} / {lf[0][0]:.4f}  recall@{args.k} tower {recall_at(deep, held, args.k, True, tp):.4f}, "
                   f"depth 0 {recall_at(flat, held, args.k, False):.4f}")
 
 

@@ -82,7 +82,9 @@ enum orx_flags {
     ORX_OUT_DEVICE = 32,  /* orx_recommend_topk, orx_score_candidates: the outputs are device pointers */
     ORX_FS_BF16 = 0x2000, /* the single-label full-softmax calls: the query-against-items products take bf16 operands on the
                              matrix cores; fp32 sums, tables and optimizer state (the block above orx_fullsoftmax_step)      */
-    ORX_TOPK_BF16_PREFILTER = 0x2000  /* orx_recommend_topk: the same bit; a speed option that changes no output bit (see there) */
+    ORX_TOPK_BF16_PREFILTER = 0x2000, /* orx_recommend_topk: the same bit; a speed option that changes no output bit (see there) */
+    ORX_TOWER_BF16 = 0x4000 /* the orx_tower_* calls: the layers' products take bf16 operands on the matrix cores; fp32 sums,
+                             activations, tables and optimizer state (the block above orx_tower_step)                        */
 };
 
 /* kernels whose device time can be sampled with orx_prof_* */
@@ -1266,7 +1268,7 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
  * the launcher's own choice, a function of (B, NI, D) alone -- or a positive multiple of the tile width 64.
  * flags: ORX_IDS_DEVICE, ORX_NO_L2 (the steps), ORX_FS_BF16.  B == 0: ORX_OK, nothing is launched.
  * ORX_FS_BF16 (mixed precision; the six single-label calls orx_fullsoftmax_*, orx_seqrec_full_step / _loss, orx_tower_step /
- * _loss -- the tower's own layers stay fp32).  With bf(x) = x rounded to nearest even to bfloat16:
+ * _loss -- the tower's own layers stay fp32 unless ORX_TOWER_BF16 is set as well, see orx_tower_step).  With bf(x) = x rounded to nearest even to bfloat16:
  *   s_ij   = scale * (sum_d bf(u_id) bf(V_jd) + b_j) + off_j      the sum in fp32 on the matrix cores; bias, offset, scale fp32
  *   lse_i, l_i, tot_i, A_i, c_i as above, in fp32, from these s; the label's score is the same rounded product
  *   g_u[i] = scale * sum_j bf(a_ij) bf(V_jd) + l2_reg u_i
@@ -1338,7 +1340,20 @@ int orx_seqrec_full_loss(orx_ctx* ctx,
  * (rows outside the batch stay as they are), item, bias, W_l and c_l by the optimizer's dense rule.  No float atomics: all results
  * are bit-repeatable; a row of the tower's output has the same bits in any batch.
  * train_mask: ORX_TRAIN_USER (hist) | _ITEM | _BIAS | ORX_TRAIN_SIDE (every side table) | ORX_TRAIN_TOWER (every W_l and c_l);
- * 0 = every table given.  flags: ORX_IDS_DEVICE, ORX_NO_L2 (then l2_reg == l2_mlp == 0).
+ * 0 = every table given.  flags: ORX_IDS_DEVICE, ORX_NO_L2 (then l2_reg == l2_mlp == 0), ORX_FS_BF16, ORX_TOWER_BF16.
+ * ORX_TOWER_BF16 (mixed precision of the layers; orx_tower_step / _loss / _query and orx_tower_sets_step / _loss; independent of
+ * ORX_FS_BF16, all four combinations are valid on the single-label calls).  With bf(x) = x rounded to nearest even to bfloat16:
+ *   z_{l+1}[i][n] = sum_k bf(x_l[i][k]) bf(W_l[k][n]) (+ c_l[n])      the sum in fp32 on the matrix cores, the bias fp32
+ *   x_{l+1}       = act_l(z_{l+1})                                    stored fp32
+ *   gm            = g_{l+1} .* (x_{l+1} > 0)                          fp32, from the stored fp32 activations
+ *   g_l[i][k]     = sum_n bf(gm[i][n]) bf(W_l[k][n])                  (+ l2_reg x0 for l = 0: the unrounded x0, the product rounded once, then the sum)
+ *   dW_l[k][n]    = sum_i bf(x_l[i][k]) bf(gm[i][n]) + l2_mlp W_l[k][n]     the l2 term on the unrounded W_l
+ *   dc_l[n]       = sum_i gm[i][n] + l2_mlp c_l[n]                    the unrounded gm
+ * x0 (the input launch is the same, the pool's bits included), the l2 sums, the master W_l and c_l, the optimizer slots and every
+ * apply use the unrounded fp32 values; the query x_L goes to the full softmax as fp32 (ORX_FS_BF16 rounds it there).  Everything
+ * else is as without the flag: no float atomics, every sum in a fixed order that (B, the widths) determine, bit-repeatable
+ * results, a row of x_L has the same bits in any batch, the forwards give the step's loss and l2 bit for bit at the same flags, a
+ * dead sample and an empty bag behave the same.  Every call without a tower refuses the flag with ORX_ERR_ARG before any device work.
  * ORX_ERR_ARG before any device work, beyond what orx_seqrec_full_step refuses: n_layers outside 1 .. 4, n_side outside 0 .. 4; a
  * width outside 1 .. 256; a layer whose inputs do not chain, a last layer that is not the item table's dim wide; c_l not
  * [1, out_l]; a table passed twice; l2_mlp negative or not finite; ORX_TRAIN_SIDE without a side table; an optimizer that
@@ -1346,7 +1361,12 @@ int orx_seqrec_full_loss(orx_ctx* ctx,
  *   orx_tower_loss       forward only: the step's loss_out / l2_out bit for bit, and l_i per sample if row_loss_out is not NULL
  *   orx_tower_query      q_i of B bags into rows [out_row0, out_row0 + B) of `out` [.., out_{L-1}]: the queries the step uses, bit for bit
  *   orx_tower_geometry   no device: out = { rows per tile, batch chunks of the backward, tiles per chunk, scratch bytes of a step with
- *                        every table trained beyond the lists' and the full softmax's } for B samples and widths[n_layers + 1]
+ *                        every table trained beyond the lists' and the full softmax's } for B samples and widths[n_layers + 1]; it
+ *                        reports the fp32 path
+ *   orx_tower_bf16_geometry   the same under ORX_TOWER_BF16: out = { rows per workgroup of the forward and of the g_l product, batch
+ *                        chunks of the dW product, 64-row tiles per chunk, scratch bytes }.  The flag adds the two bf16 copies of
+ *                        every layer, (out_l up to 16) x (in_l up to 32) and (in_l up to 16) x (out_l up to 32) elements of 2
+ *                        bytes, to the scratch; the chunks' partials are at most 8 MiB + 32 KB per layer whatever B is (at most 32 chunks)
  * Not offered: the sampled-negatives form (orx_seqrec_step with a tower), dropout, batch norm, K-step calls. */
 enum orx_tower_train_mask { ORX_TRAIN_SIDE = 16, ORX_TRAIN_TOWER = 32 };      /* beside orx_train_mask's three (8 is ORX_TRAIN_PROJ) */
 int orx_tower_step(orx_ctx* ctx, orx_opt* opt,
@@ -1371,6 +1391,7 @@ int orx_tower_query(orx_ctx* ctx, orx_table* hist,
                     const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom,
                     orx_table* out, int64_t out_row0, int flags);
 int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* widths /* [n_layers + 1] */, int64_t out[4]);
+int orx_tower_bf16_geometry(int64_t B, int32_t n_layers, const int32_t* widths /* [n_layers + 1] */, int64_t out[4]);
 
 /* ---- LABEL SETS UNDER THE FULL SOFTMAX (api_fullsoftmax.hip, api_seqrec.hip, api_tower.hip, kernels_labelsets.hip): the
  * multinomial likelihood of Mult-DAE / Mult-VAE (Liang et al. 2018) -- a sample's query against every item, scored on the

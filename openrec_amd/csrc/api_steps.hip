@@ -82,6 +82,7 @@ int orx_check_dot_model(const char* fn, orx_ctx* c, orx_table* U, orx_table* V, 
     ORX_ARG(U->ctx == c && V->ctx == c && (!b || b->ctx == c), "%s: the tables belong to a different context", fn);
     ORX_ARG(U->dim == V->dim + extra_dim, "%s: user dim %d != item dim %d (dot scores only)", fn, U->dim, V->dim + extra_dim);
     ORX_ARG(!b || (b->dim == 1 && b->rows == V->rows), "%s: item_bias must be [%lld, 1]", fn, (long long)V->rows);
+    ORX_ARG(!(flags & ORX_TOWER_BF16 & ~allowed), "%s: ORX_TOWER_BF16 belongs to the calls with a dense tower (orx_tower_*)", fn);
     ORX_ARG((flags & ~allowed) == 0, "%s: unknown flags", fn);
     ORX_ARG(!(flags & ORX_HOGWILD), "%s: ORX_HOGWILD is a speed-comparison mode of the plain pairwise step only", fn);
     ORX_ARG(!(flags & ORX_CENSOR), "%s: ORX_CENSOR belongs to UCML; this step scores by dot products only (UCML / L2 scoring is not offered)", fn);

@@ -18,7 +18,7 @@
 
 namespace {
 
-constexpr int TW_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_HOGWILD | ORX_CENSOR;      // (the last two are named to be refused by name)
+constexpr int TW_FLAGS = ORX_IDS_DEVICE | ORX_NO_L2 | ORX_TOWER_BF16 | ORX_HOGWILD | ORX_CENSOR;     // (the last two are named to be refused by name)
 
 struct TowerModel {
     orx_table* hist; orx_table* item; orx_table* b;
@@ -90,13 +90,16 @@ struct TowerLayout {
     BagLayout bag; size_t sid[ORX_TOWER_SIDE];
     size_t x[ORX_TOWER_LAYERS + 1], g[ORX_TOWER_LAYERS], pw[ORX_TOWER_LAYERS], pc[ORX_TOWER_LAYERS], GW[ORX_TOWER_LAYERS], Gc[ORX_TOWER_LAYERS];
     int ldx[ORX_TOWER_LAYERS + 1]; int nch, tpc;
+    bool bf16; size_t wk16[ORX_TOWER_LAYERS], wn16[ORX_TOWER_LAYERS];
 };
 
 // own_out: x_L is carved here (the step and the forward: the full softmax's Q); otherwise it is the caller's table
 void tower_layout(Carve* cv, const int* w, int L, int m, int64_t B, int64_t n, bool host, bool own_out, bool lists, bool below, bool want_g0,
-                  bool trained, TowerLayout* l) {
+                  bool trained, bool bf16, TowerLayout* l) {
     memset(l, 0, sizeof(*l));
-    orx_tower_plan(B, &l->nch, &l->tpc);
+    l->bf16 = bf16;
+    if (bf16) orx_tower16_plan(B, &l->nch, &l->tpc);
+    else orx_tower_plan(B, &l->nch, &l->tpc);
     orx_bag_layout(cv, B, n, host, lists ? ORX_BAG_STEP : ORX_BAG_FORWARD, &l->bag);
     if (host)
         for (int j = 0; j < m; ++j) l->sid[j] = cv->take((size_t)B * sizeof(int32_t));
@@ -111,6 +114,11 @@ void tower_layout(Carve* cv, const int* w, int L, int m, int64_t B, int64_t n, b
             l->pw[k] = cv->take(kn * l->nch * sizeof(float)); l->pc[k] = cv->take(nn * l->nch * sizeof(float));
             l->GW[k] = cv->take(kn * sizeof(float)); l->Gc[k] = cv->take(nn * sizeof(float));
         }
+    }
+    // ORX_TOWER_BF16: the bf16 copies of the layers, behind everything else -- at most 2 x 128 KB + padding per layer
+    for (int k = 0; bf16 && k < L; ++k) {
+        l->wk16[k] = cv->take((size_t)((w[k + 1] + 15) & ~15) * ((w[k] + 31) & ~31) * sizeof(unsigned short));
+        if (below) l->wn16[k] = cv->take((size_t)((w[k] + 15) & ~15) * ((w[k + 1] + 31) & ~31) * sizeof(unsigned short));
     }
 }
 
@@ -132,6 +140,10 @@ int tower_bind(orx_ctx* c, const TowerModel& md, const TowerLayout& l, const int
         t.W[k] = md.W[k]->w; t.c[k] = md.c[k] ? md.c[k]->w : nullptr;
         if (below && (k > 0 || want_g0)) t.g[k] = f(l.g[k]);
         if (trained) { t.pw[k] = f(l.pw[k]); t.pc[k] = f(l.pc[k]); t.GW[k] = f(l.GW[k]); t.Gc[k] = f(l.Gc[k]); }
+        if (l.bf16) {
+            t.wk16[k] = reinterpret_cast<unsigned short*>(base + l.wk16[k]);
+            if (below) t.wn16[k] = reinterpret_cast<unsigned short*>(base + l.wn16[k]);
+        }
     }
     for (int j = 0; j < md.m; ++j) {
         t.S[j] = md.S[j]->w; t.srows[j] = md.S[j]->rows; t.sd[j] = md.S[j]->dim; t.f[j] = md.f[j];
@@ -151,6 +163,14 @@ int tower_input(orx_ctx* c, const TowerModel& md, const TowerArgs& t, uint2* pai
     return orx_bag_produce(c, md.hist, t.bag, pairs, [&]() { return orx_launch_tower_input(c, t); });
 }
 
+// the layers, every one finished and current by now: fp32, or -- the copies bound (ORX_TOWER_BF16) -- the bf16 copies of the master
+// values this call reads, then the products on them
+int tower_forward(orx_ctx* c, const TowerArgs& t) {
+    if (!t.wk16[0]) return orx_launch_tower_forward(c, t);
+    CHECK(orx_launch_tower16_cast(c, t));
+    return orx_launch_tower16_forward(c, t);
+}
+
 // ---- the tower form of the full-softmax drivers: Q = x_L
 struct TowerForm : FullSoftmaxForm {
     TowerModel md; TowerLayout tl; TowerArgs t; uint2* pairs;
@@ -162,7 +182,7 @@ void tower_form(TowerForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt*
                 int32_t n_side, orx_table* const* side, const int32_t* const* side_ids, int32_t n_layers, orx_table* const* W, orx_table* const* cs,
                 int relu_last, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode, float denom, float l2_reg,
                 float l2_mlp, int flags) {
-    const bool host = !(flags & ORX_IDS_DEVICE);
+    const bool host = !(flags & ORX_IDS_DEVICE), bf16 = (flags & ORX_TOWER_BF16) != 0;
     f->fn = fn; f->has_ids = false; f->ids = nullptr; f->index_flag = true; f->n_tab = 0;
     f->query_side = f->tH = f->tS = f->tT = f->gH = f->want_g0 = f->below = false;
     f->check = [=]() -> int {
@@ -173,7 +193,7 @@ void tower_form(TowerForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt*
             ORX_ARG(std::isfinite(l2_mlp) && l2_mlp >= 0.f, "%s: l2_mlp must be finite and >= 0 (got %g)", fn, (double)l2_mlp);
             ORX_ARG(!(flags & ORX_NO_L2) || l2_mlp == 0.f, "%s: ORX_NO_L2 together with l2_mlp = %g (drop the flag, or pass l2_mlp = 0)", fn, (double)l2_mlp);
         } else {
-            CHECK(orx_check_dot_model(fn, c, item, item, b, 0, flags, ORX_IDS_DEVICE | ORX_FS_BF16 | ORX_HOGWILD | ORX_CENSOR));
+            CHECK(orx_check_dot_model(fn, c, item, item, b, 0, flags, ORX_IDS_DEVICE | ORX_FS_BF16 | ORX_TOWER_BF16 | ORX_HOGWILD | ORX_CENSOR));
         }
         TowerModel& md = f->md;
         CHECK(check_tower(fn, c, hist, n_side, side, side_ids, n_layers, W, cs, relu_last, item->dim, "the item table", {item, b}, B, &md));
@@ -198,7 +218,7 @@ void tower_form(TowerForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt*
         return ORX_OK;
     };
     f->carve = [=](Carve* cv, bool grads) {
-        tower_layout(cv, f->md.w, f->md.L, f->md.m, B, n, host, true, grads, f->below, f->want_g0, f->tT, &f->tl);
+        tower_layout(cv, f->md.w, f->md.L, f->md.m, B, n, host, true, grads, f->below, f->want_g0, f->tT, bf16, &f->tl);
     };
     f->bind = [=](bool, FullSoftmaxQuery* q) -> int {
         TowerArgs& t = f->t;
@@ -212,10 +232,10 @@ void tower_form(TowerForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt*
         TowerArgs& t = f->t;
         if (step) { t.g[t.L] = a.gu; t.ldg[t.L] = a.gs; }             // the full softmax's query gradient is the last layer's
         CHECK(tower_input(c, f->md, t, step && f->tH ? f->pairs : nullptr));
-        return orx_launch_tower_forward(c, t);
+        return tower_forward(c, t);
     };
     f->backward = [=]() -> int {
-        if (f->below) CHECK(orx_launch_tower_backward(c, f->t));
+        if (f->below) CHECK(bf16 ? orx_launch_tower16_backward(c, f->t) : orx_launch_tower_backward(c, f->t));
         if (f->tT) CHECK(orx_launch_tower_finish(c, f->t));
         return ORX_OK;
     };
@@ -239,10 +259,8 @@ void tower_form(TowerForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt*
     };
 }
 
-}  // namespace
-
-extern "C" int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* widths, int64_t out[4]) {
-    static const char* fn = "orx_tower_geometry";
+// what the launchers do for B samples and these widths: the fp32 path's numbers, or ORX_TOWER_BF16's
+int tower_geometry(const char* fn, int64_t B, int32_t n_layers, const int32_t* widths, bool bf16, int64_t out[4]) {
     ORX_ARG(out && widths, "%s: NULL argument", fn);
     ORX_ARG(n_layers >= 1 && n_layers <= ORX_TOWER_LAYERS, "%s: %d layers (1 .. %d)", fn, n_layers, ORX_TOWER_LAYERS);
     ORX_ARG(B >= 0 && B <= 0x7fffff00LL, "%s: B = %lld (B must fit 31 bits)", fn, (long long)B);
@@ -253,9 +271,19 @@ extern "C" int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* wi
     }
     Carve cv;
     TowerLayout l;
-    tower_layout(&cv, w, n_layers, 0, B, 0, false, true, true, true, true, true, &l);
-    out[0] = 64; out[1] = l.nch; out[2] = l.tpc; out[3] = (int64_t)cv.off;
+    tower_layout(&cv, w, n_layers, 0, B, 0, false, true, true, true, true, true, bf16, &l);
+    out[0] = bf16 ? orx_tower16_tile() : 64; out[1] = l.nch; out[2] = l.tpc; out[3] = (int64_t)cv.off;
     return ORX_OK;
+}
+
+}  // namespace
+
+extern "C" int orx_tower_geometry(int64_t B, int32_t n_layers, const int32_t* widths, int64_t out[4]) {
+    return tower_geometry("orx_tower_geometry", B, n_layers, widths, false, out);
+}
+
+extern "C" int orx_tower_bf16_geometry(int64_t B, int32_t n_layers, const int32_t* widths, int64_t out[4]) {
+    return tower_geometry("orx_tower_bf16_geometry", B, n_layers, widths, true, out);
 }
 
 extern "C" int orx_tower_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
@@ -321,7 +349,7 @@ extern "C" int orx_tower_query(orx_ctx* c, orx_table* hist, int32_t n_side, orx_
                                orx_table* out, int64_t out_row0, int flags) {
     static const char* fn = "orx_tower_query";
     ORX_ARG(c && hist && out, "%s: NULL context/table", fn);
-    ORX_ARG((flags & ~ORX_IDS_DEVICE) == 0, "%s: flags other than ORX_IDS_DEVICE", fn);
+    ORX_ARG((flags & ~(ORX_IDS_DEVICE | ORX_TOWER_BF16)) == 0, "%s: flags other than ORX_IDS_DEVICE and ORX_TOWER_BF16", fn);
     const bool host = !(flags & ORX_IDS_DEVICE);
     CHECK(orx_bag_check(fn, bag_ptr, bag_items, B, n, mode, denom, host));
     TowerModel md;
@@ -334,13 +362,13 @@ extern "C" int orx_tower_query(orx_ctx* c, orx_table* hist, int32_t n_side, orx_
     for (int l = 0; l < md.L; ++l) { CHECK(orx_table_sync(md.W[l])); CHECK(orx_table_sync(md.c[l])); }
     Carve cv;
     TowerLayout tl;
-    tower_layout(&cv, md.w, md.L, md.m, B, n, host, false, false, false, false, false, &tl);
+    tower_layout(&cv, md.w, md.L, md.m, B, n, host, false, false, false, false, false, (flags & ORX_TOWER_BF16) != 0, &tl);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     TowerArgs t;
     CHECK(tower_bind(c, md, tl, bag_ptr, bag_items, B, n, mode, denom, host, false, false, false, false, &t, nullptr));
     t.x[md.L] = out->w + (size_t)out_row0 * out->dim; t.ldx[md.L] = out->dim;
     CHECK(tower_input(c, md, t, nullptr));
-    CHECK(orx_launch_tower_forward(c, t));
+    CHECK(tower_forward(c, t));
     out->version++;
     if (host) return orx_check_index_error(c);
     return ORX_OK;

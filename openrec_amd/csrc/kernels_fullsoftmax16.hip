@@ -20,13 +20,7 @@
 //                   X[16 s + 4 q + r][16 kb + ln]: two ds_read_b64 of the transposed copy.  Two instructions per 16 columns and tile.
 // No atomics: every sum has a fixed order, and the results are bit-repeatable.
 #include "orx_device.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "orx_mfma16.h"
 
 namespace {
 
@@ -47,14 +41,6 @@ __device__ __forceinline__ void fs_add(float& s, float& c, float x) {
     const float y = x - c, t = s + y;
     c = (t - s) - y;
     s = t;
-}
-
-// eight fp32 -> eight bf16, round to nearest even (v_cvt_pk_bf16_f32), as 16 bytes
-__device__ __forceinline__ u32x4 fs16_pack(f32x4 lo, f32x4 hi) {
-    bf16x8 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { v[j] = (__bf16)lo[j]; v[4 + j] = (__bf16)hi[j]; }
-    return __builtin_bit_cast(u32x4, v);
 }
 
 // one thread per eight elements of a copy: rows [0, Bp) are xq's, rows [Bp, Bp + NIp) xv's.  Dp is a multiple of 16, so a group

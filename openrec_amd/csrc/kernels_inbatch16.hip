@@ -25,14 +25,10 @@
 //                   X[16 s + 4 q + r][16 gb + ln]: two ds_read_b64 of the transposed copy.  Two instructions per 16 columns and tile.
 // No atomics: every sum has a fixed order, and the results are bit-repeatable.
 #include "orx_device.h"
+#include "orx_mfma16.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 

@@ -44,10 +44,7 @@
 #include <algorithm>
 
 #include "orx_device.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "orx_mfma16.h"
 
 namespace {
 

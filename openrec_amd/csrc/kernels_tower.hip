@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "orx_device.h"
+#include "orx_tower_device.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -154,13 +155,6 @@ __global__ __launch_bounds__(256) void tower_input_kernel(TowerArgs t) {
             if (lane + 64 * e < a.D) pr[lane + 64 * e] = c != 0.0f ? c * s[e] : 0.0f;
     }
     for (int cc = t.w[0] + lane; cc < t.ldx[0]; cc += 64) row[cc] = 0.0f;
-}
-
-// round(round(a b) + c): the l2 term as fs_finish_kernel's fmaf(scale, s, l2 x) rounds it at scale 1 -- the product once, then the sum
-__device__ __forceinline__ float tw_l2_add(float a, float b, float c) {
-#pragma clang fp contract(off)
-    const float p = a * b;
-    return c + p;
 }
 
 // rows [row0, row0 + 64) x columns [0, Wp) of X (stride ld, `width` true columns) into LDS [64][pitch], zeros beyond B and width

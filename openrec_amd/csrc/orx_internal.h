@@ -1172,6 +1172,8 @@ struct TowerArgs {
     float* pw[ORX_TOWER_LAYERS]; float* pc[ORX_TOWER_LAYERS];                // [nch][w[l] w[l + 1]], [nch][w[l + 1]] per-batch-chunk partials; NULL: the tower is not trained
     float* GW[ORX_TOWER_LAYERS]; float* Gc[ORX_TOWER_LAYERS];                // the dense gradients
     int nch; int tpc;                                     // batch chunks of tpc tiles of 64 rows
+    unsigned short* wk16[ORX_TOWER_LAYERS]; unsigned short* wn16[ORX_TOWER_LAYERS];      // ORX_TOWER_BF16: the bf16 copies of W_l, [w[l + 1] up to 16][w[l] up to 32]
+                                                          // (k contiguous) and [w[l] up to 16][w[l + 1] up to 32] (n contiguous; NULL: no gradient goes below); else NULL
     float l2x; float l2m;                                 // the coefficient on x[0] (g[0] += l2x x[0]) and on the layers
     const float* S[ORX_TOWER_SIDE]; int64_t srows[ORX_TOWER_SIDE]; int sd[ORX_TOWER_SIDE]; const int32_t* f[ORX_TOWER_SIDE];      // side tables, DEVICE [B] ids
     BagArgs bag;                                          // the history lists (out unused: the pooled row goes to columns [so, w[0]) of x[0])
@@ -1181,6 +1183,13 @@ int orx_launch_tower_input(orx_ctx* ctx, const TowerArgs& a);
 int orx_launch_tower_forward(orx_ctx* ctx, const TowerArgs& a);                 // one launch per layer
 int orx_launch_tower_backward(orx_ctx* ctx, const TowerArgs& a);                // one launch per layer, last to first
 int orx_launch_tower_finish(orx_ctx* ctx, const TowerArgs& a);                  // one launch: the partials of all layers in chunk order, + l2m * (W, c)
+// kernels_tower16.hip: what runs in the place of the forward and the backward launches when a.wk16 is set (ORX_TOWER_BF16).  The
+// chunks of its dW kernel (nch, tpc in the same fields) come from a plan of its own; the finishing launch is the one above
+void orx_tower16_plan(int64_t B, int* nch, int* tpc);     // a function of B alone
+int orx_tower16_tile();                                   // batch rows per workgroup of the forward and of the g_l product
+int orx_launch_tower16_cast(orx_ctx* ctx, const TowerArgs& a);                  // one launch: the bf16 copies of every layer, from the current fp32 W_l
+int orx_launch_tower16_forward(orx_ctx* ctx, const TowerArgs& a);               // one launch per layer
+int orx_launch_tower16_backward(orx_ctx* ctx, const TowerArgs& a);              // per layer, last to first: g_l (a.g[l] set), dW_l and dc_l's partials (a.pw[l] set)
 
 // ---------------------------------- the host driver of the calls on the softmax over all items (api_fullsoftmax.hip) ---
 // A model on this objective is a QUERY FORM: what produces the query matrix Q [NQ][D] and what takes its gradient.  The entry

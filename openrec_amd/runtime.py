@@ -2441,8 +2441,8 @@ def _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_i
 
 
 def _full_step(what, m, fns, lists, tables, opt, coefs, mask, pid, weights, item_offset, scale, chunk_items, chunk_samples, want_loss, labels,
-               label_weights, precision="fp32"):
-    bits = _precision_bits(what, precision, labels)
+               label_weights, precision="fp32", more_bits=0):
+    bits = _precision_bits(what, precision, labels) | more_bits
     B, n, dev, sets, ptrs, scale, ci, cs, keep = _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, chunk_samples,
                                                             labels, label_weights)
     out, lp, l2p = _loss_outputs(1, want_loss)
@@ -2452,8 +2452,9 @@ def _full_step(what, m, fns, lists, tables, opt, coefs, mask, pid, weights, item
     return out
 
 
-def _full_loss(what, m, fns, lists, tables, pid, weights, item_offset, scale, chunk_items, per_row, labels, label_weights, precision="fp32"):
-    bits = _precision_bits(what, precision, labels)
+def _full_loss(what, m, fns, lists, tables, pid, weights, item_offset, scale, chunk_items, per_row, labels, label_weights, precision="fp32",
+               more_bits=0):
+    bits = _precision_bits(what, precision, labels) | more_bits
     B, n, dev, sets, ptrs, scale, ci, _, keep = _full_args(what, m, lists, tables, pid, weights, item_offset, scale, chunk_items, 0, labels,
                                                            label_weights)
     out, lp, l2p = _loss_outputs(1, True)
@@ -2625,15 +2626,25 @@ def _handles(tables):
     return (c_void_p * max(len(tables), 1))(*[None if t is None else t._h for t in tables])
 
 
-def tower_geometry(B, widths):
+def _tower_bits(what, tower_precision):
+    """tower_precision= of DeepSeqRec's calls -> the call's flag bits: "fp32", or "bf16" (ORX_TOWER_BF16: the layers' products take
+    bf16 operands on the matrix cores; fp32 sums, activations, tables and optimizer state)"""
+    if tower_precision not in ("fp32", "bf16"):
+        raise ValueError(f"{what}: tower_precision = {tower_precision!r}; 'fp32' or 'bf16'")
+    return _ffi.ORX_TOWER_BF16 if tower_precision == "bf16" else 0
+
+
+def tower_geometry(B, widths, tower_precision="fp32"):
     """what the launcher of DeepSeqRec's tower does for B samples and the widths (in_0, out_0, ..., out_{L-1}): a dict of the rows
     per tile, the batch chunks of the backward, the tiles per chunk and the scratch bytes of a step with every table trained
-    (beyond the lists' and the full softmax's).  No device is needed."""
+    (beyond the lists' and the full softmax's).  tower_precision="bf16": the rows per workgroup of the forward, the batch chunks
+    of the dW product, its 64-row tiles per chunk, and the scratch with the layers' bf16 copies.  No device is needed."""
+    fn = "orx_tower_bf16_geometry" if _tower_bits("tower_geometry", tower_precision) else "orx_tower_geometry"
     widths = [int(x) for x in widths]
     if not 2 <= len(widths) <= _TOWER_LAYERS + 1:
         raise ValueError(f"tower_geometry: {len(widths) - 1} layers (1 .. {_TOWER_LAYERS})")
     out = (c_int64 * 4)()
-    check(_ffi.load().orx_tower_geometry(int(B), len(widths) - 1, (c_int32 * len(widths))(*widths), out))
+    check(getattr(_ffi.load(), fn)(int(B), len(widths) - 1, (c_int32 * len(widths))(*widths), out))
     return dict(tile=int(out[0]), batch_chunks=int(out[1]), tiles_per_chunk=int(out[2]), scratch_bytes=int(out[3]))
 
 
@@ -2710,7 +2721,7 @@ class DeepSeqRec:
         return lists
 
     def step_full(self, opt, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, l2_reg=0.0, l2_mlp=0.0, train=None,
-                  chunk_items=0, chunk_samples=0, want_loss=True, labels=None, label_weights=None, precision="fp32"):
+                  chunk_items=0, chunk_samples=0, want_loss=True, labels=None, label_weights=None, precision="fp32", tower_precision="fp32"):
         """One train step on the softmax over ALL items (orx_tower_step): SeqRec.step_full's objective with the query computed by
         the tower.  side_ids: one id list [B] per side table, where the bags live.  J = loss + l2_reg * l2_loss + l2_mlp * 1/2
         sum_l (|W_l|^2 + |c_l|^2), l2_loss = 1/2 (sum |x0_i|^2 + sum |V[pid_i]|^2) on the embedding outputs.  The history table
@@ -2718,28 +2729,35 @@ class DeepSeqRec:
         dense rule.  train: None, or a subset of ("history", "item", "bias", "side", "tower").  -> (loss[1], l2[1]) as numpy
         float32, l2 the unscaled l2_loss, when want_loss, else None.  Bad arguments raise ValueError before the library is
         called; a malformed device list or an id outside its table IndexError.  labels= / label_weights= with pid=None
-        (orx_tower_sets_step): a label set per bag, as SeqRec.step_full takes them -- Mult-DAE with hidden layers."""
+        (orx_tower_sets_step): a label set per bag, as SeqRec.step_full takes them -- Mult-DAE with hidden layers.
+        tower_precision="bf16" (ORX_TOWER_BF16): the layers' products -- x_l W_l, gm W_l^T, x_l^T gm -- take bf16 operands on the
+        matrix cores; sums, stored activations, tables and optimizer state stay fp32.  Independent of precision=, and offered
+        with labels= too."""
         what = "DeepSeqRec.step_full"
+        tbits = _tower_bits(what, tower_precision)
         mask = _mask_arg(what, train, _DEEP_ROLES, self.b is not None) or 0
         if mask & _ffi.ORX_TRAIN_SIDE and not self.side:
             raise ValueError(f'{what}: train: "side" named, but the model has no side table')
         l2c, l2m = _coef_arg(what, "l2_reg", l2_reg), _coef_arg(what, "l2_mlp", l2_mlp)
         return _full_step(what, self, self._FULL_STEP, self._full_lists(bags, side_ids), self._tables, opt, (l2c, l2m), mask, pid, weights,
-                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights, precision)
+                          item_offset, scale, chunk_items, chunk_samples, want_loss, labels, label_weights, precision, tbits)
 
     def loss_full(self, bags, pid=None, side_ids=(), weights=None, item_offset=None, scale=1.0, chunk_items=0, per_row=False,
-                  labels=None, label_weights=None, precision="fp32"):
+                  labels=None, label_weights=None, precision="fp32", tower_precision="fp32"):
         """forward only: (loss, l2_loss) of one batch of step_full -- the step's own numbers bit for bit on the same tables; no
         table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B].  labels= /
-        label_weights= as step_full takes them"""
-        return _full_loss("DeepSeqRec.loss_full", self, self._FULL_LOSS, self._full_lists(bags, side_ids), self._tables, pid, weights,
-                          item_offset, scale, chunk_items, per_row, labels, label_weights, precision)
+        label_weights= / tower_precision= as step_full takes them"""
+        what = "DeepSeqRec.loss_full"
+        return _full_loss(what, self, self._FULL_LOSS, self._full_lists(bags, side_ids), self._tables, pid, weights,
+                          item_offset, scale, chunk_items, per_row, labels, label_weights, precision, _tower_bits(what, tower_precision))
 
-    def user_table(self, bags, side_ids=(), out=None):
+    def user_table(self, bags, side_ids=(), out=None, tower_precision="fp32"):
         """-> a Table [B, Dq] of the queries q_i (orx_tower_query) -- the rows the step scores with, bit for bit, and a row's bits
         do not depend on the batch around it.  out: a Table of that shape to write; None: one owned by this object, valid until
-        the next call with another B.  With (V, b) it goes wherever a user table goes, uid = the row number."""
+        the next call with another B.  With (V, b) it goes wherever a user table goes, uid = the row number.  tower_precision: the
+        step's -- the queries of a model trained with "bf16" are the ones its steps scored with."""
         what = "DeepSeqRec.user_table"
+        tbits = _tower_bits(what, tower_precision)
         pp, pi, B, n, dev, ps, keep = self._lists(what, bags, side_ids)
         out = _owned_output(what, self, B, self.V.dim, out, "bags and queries")
         if any(out is t for t in self._tables):
@@ -2749,12 +2767,13 @@ class DeepSeqRec:
             t._sync_pending()
         out._sync_pending()
         model, arrays = self._model_args(ps)
-        check(self.ctx._lib.orx_tower_query(self.ctx._h, self.H._h, *model, pp, pi, B, n, self._mode, self._denom, out._h, 0, _flags(dev)))
+        check(self.ctx._lib.orx_tower_query(self.ctx._h, self.H._h, *model, pp, pi, B, n, self._mode, self._denom, out._h, 0,
+                                            _flags(dev, tbits)))
         return out
 
-    def recommend(self, bags, side_ids, k, excl=None, prefilter=None):
+    def recommend(self, bags, side_ids, k, excl=None, prefilter=None, tower_precision="fp32"):
         """the k best items for each history -> (item ids int32 [B, k], scores float32 [B, k]): recommend_topk("dot", ...) on
         user_table(bags, side_ids); excl: a SparseMask or a dense bool mask [B, items] of items never returned; prefilter:
-        recommend_topk's"""
-        Q = self.user_table(bags, side_ids)
+        recommend_topk's; tower_precision: user_table's"""
+        Q = self.user_table(bags, side_ids, tower_precision=tower_precision)
         return recommend_topk("dot", Q, self.V, self.b, np.arange(Q.rows, dtype=np.int32), k, excl=excl, prefilter=prefilter)

@@ -23,11 +23,13 @@ class MultDAE(VanillaYouTubeRec):
         self._build("MultDAE", dim_embed, _ANY_LEN, total_items, l2_reg_embed, l2_reg_mlp, use_item_bias, pool, ctx, hidden, ())
 
     def train_steps(self, optimizer, in_items, in_len, label_items, label_len, label_weight=None, sample_weight=None,
-                    item_offset=None, want_loss=True, train=None):
+                    item_offset=None, want_loss=True, train=None, tower_precision="fp32"):
         """One train step in one device call: input bags in_items [B, L] of which in_len [B] entries count, label sets
-        label_items [B, Ll] / label_len [B] (data.autoencoder_batches makes both).  -> (loss[1], l2[1]) when want_loss"""
+        label_items [B, Ll] / label_len [B] (data.autoencoder_batches makes both).  tower_precision="bf16" (hidden layers only): their products in bf16 on
+        the matrix cores.  -> (loss[1], l2[1]) when want_loss"""
         return self.train_steps_sets(optimizer, in_items, in_len, label_items, label_len, label_weight=label_weight,
-                                     sample_weight=sample_weight, item_offset=item_offset, want_loss=want_loss, train=train)
+                                     sample_weight=sample_weight, item_offset=item_offset, want_loss=want_loss, train=train,
+                                     tower_precision=tower_precision)
 
     def loss(self, in_items, in_len, label_items, label_len, label_weight=None, sample_weight=None, item_offset=None):
         """the forward of train_steps alone -> (loss, l2)"""

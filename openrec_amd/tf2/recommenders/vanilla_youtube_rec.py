@@ -88,6 +88,16 @@ class VanillaYouTubeRec(Recommender):
             raise ValueError(f"{type(self).__name__}: user features {sorted(user_features)} given; expected {sorted(self.user_features)}")
         return tuple(_ids(user_features[name]) for name in self.user_features)
 
+    def _tower_kw(self, tower_precision):
+        """tower_precision= -> the keyword of the net's call: the precision of the layers' products (rt.DeepSeqRec), which a model
+        without layers does not have"""
+        rt._tower_bits(type(self).__name__, tower_precision)
+        if self._deep:
+            return {"tower_precision": tower_precision}
+        if tower_precision != "fp32":
+            raise ValueError(f"{type(self).__name__}: tower_precision={tower_precision!r} needs hidden layers; this model has none")
+        return {}
+
     def _bags(self, seq_item_id, seq_len):
         seq, ln = _ids(seq_item_id), _ids(seq_len)
         shape = tuple(getattr(seq, "shape", ()))
@@ -118,31 +128,35 @@ class VanillaYouTubeRec(Recommender):
         return self._net.loss(self._bags(seq_item_id, seq_len), _ids(label), _ids(n_item_id), loss=loss, weights=wts, neg_offset=off)
 
     def train_steps_full(self, optimizer, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, want_loss=True,
-                         train=None, precision="fp32", **user_features):
+                         train=None, precision="fp32", tower_precision="fp32", **user_features):
         """One train step on the reference's objective (rt.SeqRec.step_full): the softmax of the label over ALL items, no
         negatives to draw.  item_offset [total_items]: a per-item constant added to every row's logits (-inf removes an item,
         a padding id for one).  The item table and the bias take the optimizer's dense rule on every row.  With hidden layers
         (rt.DeepSeqRec.step_full) the layers take it too, `train` may also name "side" and "tower", and user_features holds one
-        id array [B] per user feature, by name.
+        id array [B] per user feature, by name.  tower_precision="bf16": the layers' products in bf16 on the matrix cores, beside
+        and independent of precision= (the softmax's); a model without layers refuses it.
         -> (loss[1], l2[1]) as float32 arrays when want_loss, else None"""
+        tkw = self._tower_kw(tower_precision)
         opt = optimizer.native(self._net.ctx) if hasattr(optimizer, "native") else optimizer
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(item_offset) if item_offset is not None else None
         if self._deep:
             return self._net.step_full(opt, self._bags(seq_item_id, seq_len), _ids(label), self._side(user_features), weights=wts,
                                        item_offset=off, l2_reg=self.l2_reg, l2_mlp=self.l2_reg_mlp, train=train, want_loss=want_loss,
-                                       precision=precision)
+                                       precision=precision, **tkw)
         self._side(user_features)
         return self._net.step_full(opt, self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off,
                                    l2_reg=self.l2_reg, train=train, want_loss=want_loss, precision=precision)
 
-    def loss_full(self, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, precision="fp32", **user_features):
+    def loss_full(self, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, precision="fp32", tower_precision="fp32",
+                  **user_features):
         """the forward of train_steps_full alone -> (loss, l2)"""
+        tkw = self._tower_kw(tower_precision)
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(item_offset) if item_offset is not None else None
         if self._deep:
             return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), self._side(user_features), weights=wts, item_offset=off,
-                                       precision=precision)
+                                       precision=precision, **tkw)
         self._side(user_features)
         return self._net.loss_full(self._bags(seq_item_id, seq_len), _ids(label), weights=wts, item_offset=off, precision=precision)
 
@@ -154,12 +168,14 @@ class VanillaYouTubeRec(Recommender):
         return (lab, ln), (_ids(label_weight) if label_weight is not None else None)
 
     def train_steps_sets(self, optimizer, seq_item_id, seq_len, label_item_id, label_len, label_weight=None, sample_weight=None,
-                         item_offset=None, want_loss=True, train=None, **user_features):
+                         item_offset=None, want_loss=True, train=None, tower_precision="fp32", **user_features):
         """train_steps_full with a label SET per history (rt.SeqRec.step_full(labels=...) / rt.DeepSeqRec.step_full(labels=...)):
         the multinomial likelihood of the history's whole set of items over ALL items, in one walk of the item table -- the
         objective of Mult-DAE.  label_item_id [B, Ll] of which label_len [B] entries count (an empty set keeps only its l2
-        part); label_weight [B, Ll]: per-entry weights (None: 1).  Everything else as train_steps_full.
+        part); label_weight [B, Ll]: per-entry weights (None: 1).  Everything else as train_steps_full, tower_precision included
+        (the label sets have no precision= of the softmax's).
         -> (loss[1], l2[1]) as float32 arrays when want_loss, else None"""
+        tkw = self._tower_kw(tower_precision)
         opt = optimizer.native(self._net.ctx) if hasattr(optimizer, "native") else optimizer
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(item_offset) if item_offset is not None else None
@@ -167,20 +183,21 @@ class VanillaYouTubeRec(Recommender):
         if self._deep:
             return self._net.step_full(opt, self._bags(seq_item_id, seq_len), None, self._side(user_features), weights=wts,
                                        item_offset=off, l2_reg=self.l2_reg, l2_mlp=self.l2_reg_mlp, train=train, want_loss=want_loss,
-                                       labels=labels, label_weights=lw)
+                                       labels=labels, label_weights=lw, **tkw)
         self._side(user_features)
         return self._net.step_full(opt, self._bags(seq_item_id, seq_len), None, weights=wts, item_offset=off, l2_reg=self.l2_reg,
                                    train=train, want_loss=want_loss, labels=labels, label_weights=lw)
 
     def loss_sets(self, seq_item_id, seq_len, label_item_id, label_len, label_weight=None, sample_weight=None, item_offset=None,
-                  **user_features):
+                  tower_precision="fp32", **user_features):
         """the forward of train_steps_sets alone -> (loss, l2)"""
+        tkw = self._tower_kw(tower_precision)
         wts = _ids(sample_weight) if sample_weight is not None else None
         off = _ids(item_offset) if item_offset is not None else None
         labels, lw = self._label_sets(label_item_id, label_len, label_weight)
         if self._deep:
             return self._net.loss_full(self._bags(seq_item_id, seq_len), None, self._side(user_features), weights=wts, item_offset=off,
-                                       labels=labels, label_weights=lw)
+                                       labels=labels, label_weights=lw, **tkw)
         self._side(user_features)
         return self._net.loss_full(self._bags(seq_item_id, seq_len), None, weights=wts, item_offset=off, labels=labels, label_weights=lw)
 
@@ -189,24 +206,25 @@ class VanillaYouTubeRec(Recommender):
         if self._history is None:
             raise ValueError(f"{type(self).__name__}: no histories to score (pass seq_item_id and seq_len)")
         if self._deep:
-            return self._net.user_table(self._history, self._history_side), self._net.V, self._net.b
+            return self._net.user_table(self._history, self._history_side, **self._history_tower), self._net.V, self._net.b
         return self._net.user_table(self._history), self._net.V, self._net.b
 
-    def _rows(self, seq_item_id, seq_len, user_features=None):
+    def _rows(self, seq_item_id, seq_len, user_features=None, tower_precision="fp32"):
         """the histories become the user table of the call that follows -> their row numbers, the ids that call takes"""
+        self._history_tower = self._tower_kw(tower_precision)
         self._history_side = self._side(user_features or {})
         self._history = self._bags(seq_item_id, seq_len)
         return np.arange(int(self._history[0].shape[0]), dtype=np.int32)
 
-    def inference(self, seq_item_id, seq_len, **user_features):
-        """q(history) @ V^T + b -> [B, total_items]"""
-        uid = self._rows(seq_item_id, seq_len, user_features)
+    def inference(self, seq_item_id, seq_len, tower_precision="fp32", **user_features):
+        """q(history) @ V^T + b -> [B, total_items]; tower_precision: the one the model was trained with"""
+        uid = self._rows(seq_item_id, seq_len, user_features, tower_precision)
         Q, V, b = self._tables()
         return rt.score_all_items("dot", Q, V, b, uid, device=True)
 
-    def recommend(self, seq_item_id, seq_len, k, excl_mask=None, prefilter=None, **user_features):
+    def recommend(self, seq_item_id, seq_len, k, excl_mask=None, prefilter=None, tower_precision="fp32", **user_features):
         """the k best items of each history -> (item ids [B, k], scores [B, k]); see Recommender.recommend"""
-        return super().recommend(self._rows(seq_item_id, seq_len, user_features), k, excl_mask, prefilter)
+        return super().recommend(self._rows(seq_item_id, seq_len, user_features, tower_precision), k, excl_mask, prefilter)
 
     def score(self, seq_item_id, seq_len, candidates, **user_features):
         """the scores of each history's own candidate list; see Recommender.score"""
