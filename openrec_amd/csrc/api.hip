@@ -1,6 +1,6 @@
-// C-ABI entry points (include/openrec_hip.h): contexts, tables, optimizers and
-// the host-side sequencing of the train-step kernels.  No torch, no CPU
-// fallback: every entry point needs a usable HIP device.
+// C-ABI entry points (include/openrec_hip.h): contexts, tables, optimizers, the
+// host side of the exact steps' plan (their driver: api_exact.hip) and profiling.
+// No torch, no CPU fallback: every entry point needs a usable HIP device.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -17,11 +17,12 @@ static thread_local char g_err[1024] = "";
 #include <chrono>
 static bool host_timing() { static const bool on = getenv("ORX_HOST_TIMING") != nullptr; return on; }
 static thread_local double g_ht[16]; static thread_local const char* g_htn[16]; static thread_local int g_htc = 0;
-static void ht_mark(const char* what) {
+void ht_mark(const char* what, bool first) {
+    if (first) g_htc = 0;
     if (!host_timing() || g_htc >= 16) return;
     g_ht[g_htc] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); g_htn[g_htc++] = what;
 }
-static void ht_dump() {
+void ht_dump() {
     if (!host_timing() || g_htc == 0) return;
     fprintf(stderr, "[orx host]");
     for (int i = 1; i < g_htc; ++i) fprintf(stderr, " %s +%.1f", g_htn[i], g_ht[i] - g_ht[i - 1]);
@@ -582,24 +583,7 @@ extern "C" int orx_opt_slot_write(orx_opt* o, orx_table* t, int slot, int64_t ro
     return rows_copy(t->ctx, p, t->rows, t->dim, row0, nrows, (float*)host_src, false);
 }
 
-// ------------------------------------------------------------ the hot path ---
-// b == NULL: BPR without item biases (model < 0: any model may go without, as in orx_pairwise_reserve); UCML and the
-// censor always need the bias
-static int check_pair_tables(orx_table* U, orx_table* V, orx_table* b, int model = -1, int flags = 0) {
-    ORX_ARG(U && V, "pairwise: NULL table");
-    ORX_ARG(b || model != ORX_UCML, "pairwise: UCML needs the item bias table (bias may be NULL with ORX_BPR only)");
-    ORX_ARG(b || !(flags & ORX_CENSOR), "pairwise: ORX_CENSOR needs the item bias table (bias may be NULL with ORX_BPR only)");
-    if (b == nullptr) {
-        ORX_ARG(U->ctx == V->ctx, "pairwise: tables belong to different contexts");
-        ORX_ARG(U->dim == V->dim, "pairwise: user dim %d != item dim %d (every model multiplies them element-wise)", U->dim, V->dim);
-        return ORX_OK;
-    }
-    ORX_ARG(U->ctx == V->ctx && V->ctx == b->ctx, "pairwise: tables belong to different contexts");
-    ORX_ARG(U->dim == V->dim, "pairwise: user dim %d != item dim %d (every model multiplies them element-wise)", U->dim, V->dim);
-    ORX_ARG(b->dim == 1 && b->rows == V->rows, "pairwise: item_bias must be [%lld, 1]", (long long)V->rows);
-    return ORX_OK;
-}
-
+// ------------------------------------------- the plan of the exact steps, host side ---
 int fetch_losses(orx_ctx* c, int64_t K, float* loss_out, float* l2_out) {
     if (!loss_out && !l2_out) return ORX_OK;
     std::vector<double> h((size_t)2 * K);
@@ -829,7 +813,7 @@ int orx_exact_plan_finish(orx_ctx* c, int64_t kc, int64_t B, bool inline_apply, 
 // plan is made with staging off (rows referenced >= 3 times then use fp32 atomics; the in-launch apply is exact at any density):
 // a call whose predecessor's counters were quiet takes that form, enqueues everything without a host wait, and leaves the copy of its
 // own counters behind its last launch for the next call to look at (not quiet any more: that call plans with the read-back again).
-static int plan_stats_poll(orx_ctx* c) {
+int plan_stats_poll(orx_ctx* c) {
     if (!c->stats_pending) return ORX_OK;
     hipError_t e = hipEventQuery(c->stats_ev);
     if (e == hipErrorNotReady) {
@@ -853,7 +837,7 @@ extern "C" int orx_ctx_stat(orx_ctx* c, int what, int64_t* out) {
     *out = what == 0 ? c->stat_pairs : what == 1 ? c->stat_max_dup : what == 2 ? c->stat_nowait_calls : (int64_t)(c->plan_stats.valid && c->plan_stats.quiet);
     return ORX_OK;
 }
-static int plan_stats_leave(orx_ctx* c, int64_t kc, int64_t B, bool pairing_on, const int64_t key[5]) {
+int plan_stats_leave(orx_ctx* c, int64_t kc, int64_t B, bool pairing_on, const int64_t key[5]) {
     c->stat_nowait_calls += 1;
     if (!c->stats_ev) ORX_HIP(hipEventCreateWithFlags(&c->stats_ev, hipEventDisableTiming));
     ORX_HIP(hipMemcpyAsync(c->h_plan, c->d_alloc, (size_t)kc * 8 * sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -935,378 +919,6 @@ int orx_pairing_buffers(orx_ctx* c, int64_t B, int dim, PairPlan* plan) {
     ENSURE(c->d_ids4, c->d_ids4_cap, (size_t)plan->cap * B * sizeof(int4));
     plan->pair_tpw = orx_fused_tpw(dim);
     return ORX_OK;
-}
-
-// ---- host setup that the pairwise and the pointwise step call (api_more.hip) share
-// ORX_FORCE_FALLBACK (debug / tests; read per call): bit 0 = behave as if the tables had >= 2^28 rows (no role bits: every
-// duplicate uses atomics, separate dup_apply launches), bit 1 = no in-launch apply, bit 2 = the censor in separate passes,
-// bit 3 = atomics instead of staging slots, bit 4 = no pairing
-int orx_fallback_bits() {
-    const char* e = getenv("ORX_FORCE_FALLBACK");
-    return e ? atoi(e) : 0;
-}
-
-// epochs are consumed one per step; on wrap-around every table clears its epoch-tagged arrays
-int orx_epochs_reserve(orx_ctx* c, int64_t K, std::initializer_list<orx_table*> tables) {
-    if ((int64_t)c->epoch + K + 16 > 0x7fffffff) { c->epoch = 0; c->epoch_gen += 1; }
-    for (orx_table* t : tables) {
-        if (t->tag_gen != c->epoch_gen) {
-            if (t->ready) ORX_HIP(hipMemsetAsync(t->ready, 0, (size_t)t->rows * sizeof(int), c->stream));
-            if (t->side) ORX_HIP(hipMemsetAsync(t->side, 0, (size_t)t->rows * 2 * sizeof(int), c->stream));
-            t->tag_gen = c->epoch_gen;
-        }
-    }
-    return ORX_OK;
-}
-
-// blocks of a step's launch that apply the duplicated rows of the step before it: one lane group per duplicated row in a single
-// pass for the usual ~0.15*B duplicated rows (the count lives in device memory; surplus blocks exit, a larger count grid-strides)
-int orx_apply_blocks(int64_t B, int D) {
-    return (int)std::min<int64_t>(2048, std::max<int64_t>(16, (B / 4) / (1024 / D) + 1));
-}
-
-// one step of the dense TF-2.0 Adam (MODE_ACCUM): the counter advances, then the decay sweep over every table whole (NULL: skipped)
-int orx_adam_dense_step(orx_ctx* c, orx_opt* opt, std::initializer_list<std::pair<orx_table*, OptSlots>> tables, float* lr_t_out) {
-    opt->t += 1;
-    const double b1 = opt->p0, b2 = opt->p1;
-    const float lr_t = (float)(opt->lr * std::sqrt(1.0 - std::pow(b2, (double)opt->t)) / (1.0 - std::pow(b1, (double)opt->t)));
-    for (const auto& ts : tables) {
-        orx_table* t = ts.first;
-        if (t) CHECK(orx_launch_adam_sweep(c, t->w, ts.second.s0, ts.second.s1, t->gsum, t->rows * t->dim, lr_t, opt->p0, opt->p1, opt->p2));
-    }
-    if (lr_t_out) *lr_t_out = lr_t;
-    return ORX_OK;
-}
-
-extern "C" int orx_pairwise_step(orx_ctx* c, int model, orx_opt* opt,
-                                 orx_table* U, orx_table* V, orx_table* b,
-                                 const int32_t* uid, const int32_t* pid, const int32_t* nid,
-                                 int64_t K, int64_t B, int64_t id_stride, float margin, int flags,
-                                 float* loss_out, float* l2_out) {
-    return orx_pairwise_step_impl(c, model, opt, U, V, b, uid, pid, nid, nullptr, K, B, id_stride, margin, (flags & ORX_NO_L2) ? 0.f : 1.f, flags,
-                                  loss_out, l2_out);
-}
-
-// The form a pairwise call takes, from the optimizer, the tables, the call's flags and the fallback bits alone: the step runs it,
-// orx_pairwise_reserve (flags 0, no fallback bits) sizes the buffers for it.
-struct PairForm {
-    bool lazy_adam;
-    int mode;
-    bool role_bits, fused_censor, censor, inline_apply, staging;
-};
-static PairForm pair_form(const orx_opt* opt, const orx_table* U, const orx_table* V, const orx_table* b, int64_t K, int flags, int fb) {
-    PairForm f;
-    const bool hogwild = (flags & ORX_HOGWILD) != 0, want_censor = (flags & ORX_CENSOR) != 0;
-    const bool fast_dim = orx_fused_can_inline_apply(U->dim) != 0, small_tables = U->rows < (1LL << 28) && V->rows < (1LL << 28);
-    // TF-2.0 Adam decays m, v and moves var on EVERY row every step.  On the float4 dims that is applied lazily and
-    // exactly: a row's gradient-free steps are replayed when the row is next touched (or observed: orx_table_sync);
-    // the dense form (every reference accumulates, then three whole-table sweeps per step) remains for the other
-    // cases and behind ORX_ADAM_DENSE=1.  (Wrapped memory is read behind our back: never lazy.)
-    f.lazy_adam = opt->kind == ORX_ADAM && !hogwild && fast_dim && small_tables && U->owned && V->owned && (!b || b->owned) &&
-                  getenv("ORX_ADAM_DENSE") == nullptr;
-    f.mode = (opt->kind == ORX_ADAM && !f.lazy_adam) ? MODE_ACCUM : (hogwild ? MODE_HOGWILD : MODE_EXACT);
-    // rows referenced exactly twice get plain stores into two scratch rows; the role of a reference
-    // travels in bits 30:29 of its id, which needs tables below 2^29 rows
-    f.role_bits = f.mode == MODE_EXACT && small_tables && !(fb & 1);
-    // censor_vec after every step (ucml.py:44-48): fused into the row write-back for the float4 dims in
-    // exact mode; separate passes otherwise
-    f.fused_censor = want_censor && f.mode == MODE_EXACT && fast_dim && !(fb & 4);
-    f.censor = want_censor && !f.fused_censor;
-    // the previous step's duplicated rows are applied by extra blocks of the next step's launch
-    // (no dup_apply launch, no kernel boundary) -- not with a separate censor pass between the steps
-    f.inline_apply = f.role_bits && !f.censor && K > 1 && fast_dim && !(fb & 2);
-    // rows referenced >= 3 times in a step: private staging slots instead of atomics
-    f.staging = f.role_bits && fast_dim && !(fb & 8);
-    return f;
-}
-
-// one pairwise call on its way from orx_pairwise_step_impl through pair_prepare and pair_args to pair_run_chunk
-struct PairCall {
-    orx_ctx* c; orx_opt* opt; orx_table* U; orx_table* V; orx_table* b;      // b NULL: BPR without item biases
-    int kmodel; int64_t K, B;
-    const int32_t* du; const int32_t* dp; const int32_t* dn; const float* dw; int64_t ds;      // the inputs on the device, elements between steps
-    bool want_loss;
-    PairForm f;
-    bool lazy_resume;           // lazy Adam: the tables were lazy under this optimizer already (their step stamps hold)
-    bool nowait;                // no read-back (see plan_stats_poll): the previous call of this shape was quiet
-    int64_t stats_key[5];
-    OptSlots sU, sV, sb;
-    PairPlan plan;
-    PairArgs a;
-};
-
-// tables and optimizer brought to the call's form, the read-back decision, every buffer of the call
-static int pair_prepare(PairCall& q, int fb) {
-    orx_ctx* c = q.c; orx_opt* opt = q.opt; orx_table *U = q.U, *V = q.V, *b = q.b;
-    PairForm& f = q.f;
-    const int64_t K = q.K, B = q.B;
-    // the three tables are lazy together under one optimizer (the item rows and their biases then share step stamps),
-    // or not at all: anything else first brings every row up to date
-    q.lazy_resume = f.lazy_adam && U->lazy == opt && V->lazy == opt && (!b || b->lazy == opt);
-    if (!q.lazy_resume) for (orx_table* t : {U, V, b}) CHECK(orx_table_sync(t));      // (NULL: nothing to do)
-    { orx_table* mine[3] = {U, V, b}; CHECK(orx_opt_isolate(opt, mine, b ? 3 : 2)); }      // (a shared optimizer: see orx_opt_isolate)
-    // (kmodel: a biased and a bias-free call of one shape run different kernels and keep apart; so do a weighted and an unweighted call)
-    const bool want_censor = f.censor || f.fused_censor;
-    const int64_t key[5] = {B, U->rows, V->rows, (int64_t)q.kmodel * 16 + opt->kind + (q.dw ? 1024 : 0), (int64_t)U->dim * 4 + (want_censor ? 1 : 0) + (f.inline_apply ? 2 : 0)};
-    CHECK(plan_stats_poll(c));
-    const bool plan_wait = getenv("ORX_PLAN_WAIT") != nullptr;      // (experiments / tests: always read back)
-    q.nowait = f.mode == MODE_EXACT && orx_plan_v2(f.role_bits) && f.staging && !f.censor && opt->kind != ORX_ADAM && !plan_wait &&
-               c->plan_stats.valid && c->plan_stats.quiet;
-    for (int k = 0; k < 5; ++k) { q.stats_key[k] = key[k]; q.nowait = q.nowait && c->plan_stats.key[k] == key[k]; }
-    if (q.nowait) f.staging = false;
-    const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-    if (f.mode != MODE_HOGWILD) {
-        CHECK(orx_table_scratch(U, f.role_bits)); CHECK(orx_table_scratch(V, f.role_bits));
-        if (b) CHECK(orx_table_scratch(b, f.role_bits));
-    }
-    CHECK(orx_opt_slots(opt, U, &q.sU)); CHECK(orx_opt_slots(opt, V, &q.sV));
-    if (b) CHECK(orx_opt_slots(opt, b, &q.sb));
-
-    PairPlan& plan = q.plan;
-    CHECK(orx_exact_buffers(c, U, V, K, B, f.mode, f.role_bits, f.inline_apply, f.staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
-    // Adam's normalised update amplifies summation-order noise where an element's summed gradient nearly cancels: its
-    // rows referenced >= 3 times always take staging slots (fixed summation order), never fp32 atomics
-    if (opt->kind == ORX_ADAM) plan.min_late = 1;
-    // pairing (kernels_plan.hip): the two triplets of a row referenced exactly twice share a wavefront and exchange gradients there
-    // (SGD only -- Adagrad with pairing measured slower, profiles/r5_adagrad_pairing_ab.txt -- on the float4 dims with >= 2 triplets per wavefront; fb bit 4 / ORX_NO_PAIR=1: off)
-    // The pairing plan costs ~1.5 us per step (records, decisions, the swaps); it pays where a good share of the batch pairs
-    // (uniform ids over tables ~ 10 x the batch: 11 %).  Tables so small that most duplicated rows have three or more references, or
-    // ids so skewed that the hot rows take them, pair little: the plan of a call tells (accepted pairs per step), and pairing then
-    // pauses for 32 calls before it is tried again.  ORX_PAIR_ALWAYS=1: no pause.
-    const bool pair_ok = orx_pairing_wanted(f.mode, f.role_bits, opt->kind, U->dim, B, fb);
-    if (pair_ok && c->pair_pause > 0) c->pair_pause -= 1;
-    else if (pair_ok) CHECK(orx_pairing_buffers(c, B, U->dim, &plan));
-    return ORX_OK;
-}
-
-// the kernels' arguments that hold for every step of the call
-static int pair_args(PairCall& q, float margin, float l2w) {
-    orx_ctx* c = q.c; orx_opt* opt = q.opt; orx_table *U = q.U, *V = q.V, *b = q.b;
-    const PairForm& f = q.f;
-    const int64_t K = q.K, B = q.B;
-    PairArgs& a = q.a;
-    memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b ? b->w : nullptr;
-    a.gU = U->gsum; a.gV = V->gsum; a.gb = b ? b->gsum : nullptr;
-    if (f.role_bits) { a.gU2 = U->gsum2; a.gV2 = V->gsum2; a.gb2 = b ? b->gsum2 : nullptr; a.role_bits = 1; a.readyU = U->ready; a.readyV = V->ready; }
-    a.aU = q.sU.s0; a.aV = q.sV.s0; a.ab = q.sb.s0;
-    a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
-    a.lr = opt->lr;
-    a.eps = orx_rule_eps(opt);
-    a.margin = margin;
-    a.invB = 1.0f / (float)B;
-    a.l2w = l2w;
-    a.err = c->d_err;
-    // Neither the loss nor the l2 sum is asked for (a training loop between two observations of the loss): the kernels that have a
-    // loss-free form (fused_kernel LOSS = false: exact SGD on the float4 dims, unweighted) skip their partials, and for every kernel
-    // the sums over the partials are not launched -- d_partial and d_loss are read by nothing but the fetch_losses of the call itself
-    a.no_loss = q.want_loss ? 0 : 1;
-    if (f.lazy_adam) {
-        CHECK(orx_lazy_adam_fill(opt, U, V, b, q.sU, q.sV, q.sb, !q.lazy_resume, K, &a));
-        // expected steps between two references of a row = rows / references per step
-        a.long_gap = (U->rows / B > 64 || V->rows / (2 * B) > 64) && getenv("ORX_ADAM_NO_LONGGAP") == nullptr;
-    }
-    CHECK(orx_epochs_reserve(c, K, {U, V}));
-    if (f.fused_censor) { CHECK(orx_table_side(V)); a.censor = 1; a.min_norm = 0.1f; a.sideV = V->side; }
-    return ORX_OK;
-}
-
-// arguments of step i of the chunk that starts at step s0, and its fused launch (with_apply: the launch also applies the duplicated
-// rows of step i - 1)
-static int pair_launch_step(PairCall& q, int64_t s0, int64_t i, bool stage_views, bool with_apply) {
-    orx_ctx* c = q.c;
-    PairArgs& a = q.a;
-    const PairPlan& plan = q.plan;
-    const int64_t s = s0 + i, B = q.B;
-    if (q.f.mode == MODE_EXACT) {       // ids rewritten by the plan (duplicate flag in bit 31)
-        a.uid = c->d_ids2 + (size_t)i * 3 * plan.Bp; a.pid = a.uid + plan.Bp; a.nid = a.uid + 2 * plan.Bp;
-    } else {
-        a.uid = q.du + s * q.ds; a.pid = q.dp + s * q.ds; a.nid = q.dn + s * q.ds;
-    }
-    a.wt = q.dw ? q.dw + s * q.ds : nullptr;      // (the caller's order: the kernel reads it at the triplet's original position)
-    orx_exact_step_views(c, plan, i, B, a.D, stage_views, &a);
-    if (!q.b) { a.stageb = nullptr; a.partb = nullptr; a.prev_stageb = nullptr; }      // (no bias: nothing is staged for it)
-    a.ids4 = plan.pair_tpw > 1 ? c->d_ids4 + (size_t)i * B : nullptr;
-    a.partial = c->d_partial + (size_t)i * plan.nw * 2;
-    a.epoch = ++c->epoch;           // one epoch per step: ready flags and censor side marks are tagged with it
-    if (q.f.lazy_adam) { q.opt->t += 1; a.step_t = (int)q.opt->t; }
-    if (with_apply && i > 0) {
-        a.n_apply_blocks = orx_apply_blocks(B, a.D);
-        a.prev_dlist = c->d_dlist + (size_t)(i - 1) * plan.list_stride; a.prev_dcount = c->d_dcount + (i - 1);
-    } else {
-        a.n_apply_blocks = 0; a.prev_dlist = nullptr; a.prev_dcount = nullptr;
-    }
-    return orx_launch_fused(c, q.kmodel, q.opt->kind, q.f.mode, a);
-}
-
-// steps s0 .. s0 + kc - 1: their plan, their launches, their loss sums
-static int pair_run_chunk(PairCall& q, int64_t s0, int64_t kc) {
-    orx_ctx* c = q.c; orx_opt* opt = q.opt; orx_table *U = q.U, *V = q.V, *b = q.b;
-    const PairForm& f = q.f;
-    PairArgs& a = q.a;
-    const int64_t B = q.B, ds = q.ds;
-    const int32_t *du = q.du + s0 * ds, *dp = q.dp + s0 * ds, *dn = q.dn + s0 * ds;      // step 0 of the chunk
-    const bool exact = f.mode == MODE_EXACT, v2 = exact && orx_plan_v2(f.role_bits);
-    bool first_launched = false;
-    bool tail_done = false;             // the chunk's loss sums left with the last step's duplicate apply
-    ExactChunk ck;                      // (no read-back: in-launch apply where the call allows it, no staging, no tree)
-    if (q.nowait) {
-        CHECK(orx_exact_plan_issue(c, U, V, du, dp, dn, ds, B, B, B, kc, B, f.inline_apply, f.staging, q.plan, 0, nullptr, nullptr));
-        ht_mark("plan_issued");
-    } else if (exact) {
-        // With the bucketed plan the chunk's FIRST fused launch goes out before the host waits for the plan's counters:
-        // step 0 never carries apply blocks, and the kernel built with the staging bookkeeping is right whether or not
-        // any range made a staging plan (references without one carry (-1, 0) and use atomics).
-        const std::function<int()> early = [&]() -> int { first_launched = true; return pair_launch_step(q, s0, 0, f.staging, false); };
-        CHECK(orx_exact_plan_chunk(c, U, V, du, dp, dn, ds, B, B, B, kc, B, f.role_bits, f.inline_apply, f.staging, q.plan, &ck,
-                                   v2 && !f.censor ? &early : nullptr));
-    }
-    if (f.censor) {
-        // one elected reference per distinct row of each of the three id lists, for every step of the chunk
-        ENSURE(c->d_cflag, c->d_cflag_cap, (size_t)3 * kc * B);
-        const int32_t* lists[3] = {du, dp, dn};
-        const int64_t rows[3] = {U->rows, V->rows, V->rows};
-        for (int l = 0; l < 3; ++l) {
-            DedupArgs d;
-            memset(&d, 0, sizeof(d));
-            d.uid = lists[l]; d.pid = lists[l]; d.nid = lists[l]; d.id_stride = ds;
-            d.dflag = c->d_cflag + (size_t)l * kc * B; d.flag_stride = B;
-            d.nU = B; d.NU = rows[l]; d.nbu = orx_dedup_buckets(rows[l]); d.first_only = 1;
-            CHECK(orx_launch_dedup(c, d, kc));
-        }
-    }
-    const ReduceArgs r = {c->d_partial, c->d_loss + 2 * s0, q.plan.nw};
-    // may the duplicated rows of a step be applied by the NEXT step's launch?
-    const bool inl = f.inline_apply && !ck.hot && !ck.dense_dups;
-    for (int64_t i = 0; i < kc; ++i) {
-        const bool defer = exact && inl && i < kc - 1;      // step i's duplicated rows wait for launch i + 1
-        if (!(i == 0 && first_launched)) CHECK(pair_launch_step(q, s0, i, ck.use_stage, i > 0 && inl));
-        for (int l = 0; l < ck.tree_levels; ++l) CHECK(orx_launch_hot_reduce(c, a, l));
-        if (exact && !defer) {
-            // the chunk's last step: its duplicated rows and the chunk's loss sums leave in ONE launch where that is possible
-            if (i == kc - 1 && !f.censor && !f.lazy_adam && q.want_loss) {
-                int rc = ORX_OK;
-                if (orx_launch_tail(c, opt->kind, a, r, kc, &rc)) { CHECK(rc); tail_done = true; }
-            }
-            if (!tail_done) CHECK(orx_launch_dup_apply(c, opt->kind, a));
-        }
-        // Adam, dense form: the decay sweep of TF 2.0 over the whole tables
-        if (f.mode == MODE_ACCUM) CHECK(orx_adam_dense_step(c, opt, {{U, q.sU}, {V, q.sV}, {b, q.sb}}, nullptr));
-        if (f.censor) {                   // ucml.py:44-48: users and pos items (two tables), then neg items
-            const unsigned char* fu = c->d_cflag + (size_t)i * B;
-            const unsigned char* fp = c->d_cflag + (size_t)(kc + i) * B;
-            const unsigned char* fn = c->d_cflag + (size_t)(2 * kc + i) * B;
-            CHECK(orx_launch_censor2(c, U->w, fu, U->rows, du + i * ds, B, V->w, fp, V->rows, dp + i * ds, B, U->dim, 0.1f));
-            CHECK(orx_launch_censor2(c, V->w, fn, V->rows, dn + i * ds, B, nullptr, nullptr, 0, nullptr, 0, U->dim, 0.1f));
-        }
-    }
-    if (!tail_done && q.want_loss) CHECK(orx_launch_loss_reduce(c, r, kc));
-    if (v2) {
-        // what this chunk's plan counted: left behind the last launch for the next call (no read-back), or seen already
-        if (q.nowait) CHECK(plan_stats_leave(c, kc, B, q.plan.pair_tpw > 1, q.stats_key));
-        else {
-            c->plan_stats.valid = true; c->plan_stats.quiet = ck.quiet; c->stats_pending = false;
-            for (int k = 0; k < 5; ++k) c->plan_stats.key[k] = q.stats_key[k];
-        }
-    }
-    return ORX_OK;
-}
-
-// The full pairwise step behind orx_pairwise_step (weight NULL, l2w 0 or 1) and orx_pairwise_step_weighted: `weight` lives where the
-// ids live and has their stride; l2w is the coefficient of l2_loss in the objective.  A weighted call runs the WT instantiations of the fused
-// kernels (kernels_pairwise_weighted.hip) and keeps plan statistics of its own.
-int orx_pairwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
-                           const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
-                           int64_t K, int64_t B, int64_t id_stride, float margin, float l2w, int flags,
-                           float* loss_out, float* l2_out) {
-    ORX_ARG(c && opt, "orx_pairwise_step: NULL context/optimizer");
-    ORX_ARG(model == ORX_BPR || model == ORX_UCML, "orx_pairwise_step: unknown model %d", model);
-    CHECK(check_pair_tables(U, V, b, model, flags));
-    ORX_ARG(U->ctx == c && opt->ctx == c, "orx_pairwise_step: objects belong to a different context");
-    ORX_ARG(K >= 0 && B >= 0, "orx_pairwise_step: negative K or B");
-    ORX_ARG(K == 0 || B == 0 || (uid && pid && nid), "orx_pairwise_step: NULL id pointer");
-    if (K == 0) return ORX_OK;
-    g_htc = 0; ht_mark("enter");
-    ORX_HIP(hipSetDevice(c->device));
-    if (B == 0) {           // empty batch: reduce_mean of nothing is NaN in TF; tables untouched
-        for (int64_t s = 0; s < K; ++s) { if (loss_out) loss_out[s] = model == ORX_BPR ? NAN : 0.f; if (l2_out) l2_out[s] = 0.f; }
-        return ORX_OK;
-    }
-    PairCall q;
-    q.c = c; q.opt = opt; q.U = U; q.V = V; q.b = b; q.K = K; q.B = B;
-    q.kmodel = b ? model : MODEL_BPR_NB;        // b == NULL: the kernels of MODEL_BPR_NB, every use of the bias table is skipped
-    q.want_loss = loss_out != nullptr || l2_out != nullptr;
-    StepInputs in;
-    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &in));
-    q.du = in.id[0]; q.dp = in.id[1]; q.dn = in.id[2]; q.dw = in.f[0]; q.ds = in.ds;
-    ORX_ARG(!(flags & ORX_HOGWILD) || opt->kind != ORX_MOMENTUM, "orx_pairwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
-    const int fb = orx_fallback_bits();
-    q.f = pair_form(opt, U, V, b, K, flags, fb);
-    CHECK(pair_prepare(q, fb));
-    CHECK(pair_args(q, margin, l2w));
-    ht_mark("setup");
-    for (int64_t s0 = 0; s0 < K; s0 += q.plan.chunk) CHECK(pair_run_chunk(q, s0, std::min<int64_t>(K - s0, q.plan.chunk)));
-    ht_mark("launched");
-    CHECK(fetch_losses(c, K, loss_out, l2_out));
-    ht_mark("losses"); ht_dump();
-    if (!(flags & ORX_IDS_DEVICE)) return orx_check_index_error(c);
-    return ORX_OK;
-}
-
-extern "C" int orx_pairwise_reserve(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, int64_t K, int64_t B) {
-    ORX_ARG(c && opt, "orx_pairwise_reserve: NULL context/optimizer");
-    CHECK(check_pair_tables(U, V, b));
-    ORX_ARG(K > 0 && B > 0, "orx_pairwise_reserve: K and B must be positive");
-    ORX_HIP(hipSetDevice(c->device));
-    const PairForm f = pair_form(opt, U, V, b, K, 0, 0);
-    const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-    CHECK(orx_table_scratch(U, f.role_bits)); CHECK(orx_table_scratch(V, f.role_bits));
-    if (b) CHECK(orx_table_scratch(b, f.role_bits));
-    OptSlots s;
-    CHECK(orx_opt_slots(opt, U, &s)); CHECK(orx_opt_slots(opt, V, &s));
-    if (b) CHECK(orx_opt_slots(opt, b, &s));
-    PairPlan plan;
-    CHECK(orx_exact_buffers(c, U, V, K, B, f.mode, f.role_bits, f.inline_apply, f.staging, nb_total, orx_fused_nwaves(U->dim, B), &plan));
-    if (orx_pairing_wanted(f.mode, f.role_bits, opt->kind, U->dim, B, 0)) CHECK(orx_pairing_buffers(c, B, U->dim, &plan));
-    ORX_HIP(hipStreamSynchronize(c->stream));
-    return ORX_OK;
-}
-
-extern "C" int orx_pairwise_loss(orx_ctx* c, int model, orx_table* U, orx_table* V, orx_table* b,
-                                 const int32_t* uid, const int32_t* pid, const int32_t* nid,
-                                 int64_t B, float margin, int flags, float* loss_out, float* l2_out) {
-    return orx_pairwise_loss_impl(c, model, U, V, b, uid, pid, nid, nullptr, B, margin, flags, loss_out, l2_out);
-}
-
-int orx_pairwise_loss_impl(orx_ctx* c, int model, orx_table* U, orx_table* V, orx_table* b,
-                           const int32_t* uid, const int32_t* pid, const int32_t* nid, const float* weight,
-                           int64_t B, float margin, int flags, float* loss_out, float* l2_out) {
-    if (U) CHECK(orx_table_sync(U));
-    if (V) CHECK(orx_table_sync(V));
-    if (b) CHECK(orx_table_sync(b));
-    ORX_ARG(c, "orx_pairwise_loss: NULL context");
-    ORX_ARG(model == ORX_BPR || model == ORX_UCML, "orx_pairwise_loss: unknown model %d", model);
-    CHECK(check_pair_tables(U, V, b, model, flags));
-    ORX_ARG(B > 0 && uid && pid && nid, "orx_pairwise_loss: empty batch or NULL ids");
-    ORX_HIP(hipSetDevice(c->device));
-    StepInputs in;
-    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {pid, 1}, {nid, 1}}, {{weight, 1}}, &in));
-    const int nw = orx_fused_nwaves(U->dim, B);
-    ENSURE(c->d_partial, c->d_partial_cap, (size_t)nw * 2 * sizeof(float));
-    ENSURE(c->d_loss, c->d_loss_cap, 2 * sizeof(double));
-    PairArgs a;
-    memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b ? b->w : nullptr;
-    a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = U->dim;
-    a.margin = margin; a.invB = 1.0f / (float)B; a.l2w = 1.f;
-    a.partial = c->d_partial; a.err = c->d_err;
-    a.uid = in.id[0]; a.pid = in.id[1]; a.nid = in.id[2]; a.wt = in.f[0];
-    CHECK(orx_launch_fused(c, b ? model : MODEL_BPR_NB, ORX_SGD, MODE_LOSS, a));
-    ReduceArgs r;
-    r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nw;
-    CHECK(orx_launch_loss_reduce(c, r, 1));
-    CHECK(fetch_losses(c, 1, loss_out, l2_out));
-    return orx_check_index_error(c);
 }
 
 // ---------------------------------------------------------------- profiling ---

@@ -1,235 +1,11 @@
-// C-ABI entry points of the pointwise step and its loss and of the sharded building blocks (row gather, pair gradients, the
-// applies of gradient rows with lazy Adam and the planned apply, the device-side exchange plan).  The device sampler's are in
-// api_sampler.hip.
+// C-ABI entry points of the building blocks on rows that the sharded engine and the gradient-rows steps are made of: the row
+// gather, the pair gradients of gathered rows, the applies of gradient rows (summed, lazy Adam, the planned apply) and the
+// device-side route of a shard exchange.
 #include <vector>
 #include <cmath>
 #include <cstring>
 
 #include "orx_internal.h"
-
-// ------------------------------------------------------------ pointwise step ---
-static int check_point_tables(int model, orx_table* U, orx_table* V, orx_table* b, orx_table* w) {
-    ORX_ARG(model == ORX_GMF || model == ORX_WRMF, "pointwise: unknown model %d", model);
-    ORX_ARG(U && V && b, "pointwise: NULL table");
-    ORX_ARG(U->dim == V->dim, "pointwise: user dim %d != item dim %d", U->dim, V->dim);
-    ORX_ARG(b->dim == 1 && b->rows == V->rows, "pointwise: item_bias must be [%lld, 1]", (long long)V->rows);
-    ORX_ARG(model != ORX_GMF || (w && w->rows == U->dim && w->dim == 1), "pointwise: GMF needs the Dense kernel w as a [D, 1] table");
-    return ORX_OK;
-}
-
-extern "C" int orx_pointwise_step(orx_ctx* c, int model, orx_opt* opt,
-                                  orx_table* U, orx_table* V, orx_table* b, orx_table* w,
-                                  const int32_t* uid, const int32_t* iid, const float* label,
-                                  int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, int flags,
-                                  float* loss_out, float* l2_out) {
-    return orx_pointwise_step_impl(c, model, opt, U, V, b, w, uid, iid, label, K, B, id_stride, a_w, b_w, (flags & ORX_NO_L2) ? 0.f : 1.f, flags,
-                                   loss_out, l2_out);
-}
-
-// (l2w: the coefficient of l2_loss in the objective -- orx_pointwise_step_l2reg; the plain entry point passes 0 or 1)
-int orx_pointwise_step_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
-                            const int32_t* uid, const int32_t* iid, const float* label,
-                            int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags,
-                            float* loss_out, float* l2_out) {
-    ORX_ARG(c && opt, "orx_pointwise_step: NULL context/optimizer");
-    CHECK(check_point_tables(model, U, V, b, w));
-    ORX_ARG(K >= 0 && B > 0, "orx_pointwise_step: K must be >= 0 and B > 0");
-    ORX_ARG(K == 0 || (uid && iid && label), "orx_pointwise_step: NULL id/label pointer");
-    if (K == 0) return ORX_OK;
-    ORX_HIP(hipSetDevice(c->device));
-    StepInputs in;
-    CHECK(orx_stage_steps(c, K, B, id_stride, flags, {{uid, 1}, {iid, 1}}, {{label, 1}}, &in));
-    const int32_t *du = in.id[0], *di = in.id[1]; const float* dl = in.f[0]; const int64_t ds = in.ds;
-    const bool hogwild = (flags & ORX_HOGWILD) != 0;
-    ORX_ARG(!hogwild || opt->kind != ORX_MOMENTUM, "orx_pointwise_step: ORX_HOGWILD is not supported with momentum (its racy in-place pass has no velocity rule)");
-    const int fb = orx_fallback_bits();
-    // TF-2.0 Adam applied lazily, as in orx_pairwise_step: float4 dims with the exact-step plan; the
-    // Dense(1) kernel of GMF is a dense parameter and takes the plain rule.  Otherwise every reference accumulates
-    // and the tables are swept whole.
-    const bool lazy_adam = opt->kind == ORX_ADAM && !hogwild && orx_fused_can_inline_apply(U->dim) && U->rows < (1LL << 28) &&
-                           V->rows < (1LL << 28) && !(fb & 1) && U->owned && V->owned && b->owned && getenv("ORX_ADAM_DENSE") == nullptr;
-    const int mode = (opt->kind == ORX_ADAM && !lazy_adam) ? MODE_ACCUM : (hogwild ? MODE_HOGWILD : MODE_EXACT);
-    const bool lazy_resume = lazy_adam && U->lazy == opt && V->lazy == opt && b->lazy == opt;
-    if (!lazy_resume) for (orx_table* t : {U, V, b}) CHECK(orx_table_sync(t));
-    { orx_table* mine[3] = {U, V, b}; CHECK(orx_opt_isolate(opt, mine, 3)); }      // (a shared optimizer: api.hip orx_opt_isolate)
-    if (w) CHECK(orx_table_sync(w));
-    CHECK(orx_table_scratch(U)); CHECK(orx_table_scratch(V)); CHECK(orx_table_scratch(b));
-    if (w) CHECK(orx_table_scratch(w));
-    OptSlots sU, sV, sb, sw;
-    CHECK(orx_opt_slots(opt, U, &sU)); CHECK(orx_opt_slots(opt, V, &sV)); CHECK(orx_opt_slots(opt, b, &sb));
-    if (w) CHECK(orx_opt_slots(opt, w, &sw));
-    const int D = U->dim;
-    const int nw = orx_point_nwaves(D, B);
-    const int nslot = nw + (model == ORX_GMF ? 1 : 0);      // + one slot for 0.5*||w||^2
-    ENSURE(c->d_partial, c->d_partial_cap, (size_t)K * nslot * 2 * sizeof(float));
-    ENSURE(c->d_loss, c->d_loss_cap, (size_t)K * 2 * sizeof(double));
-    if (model == ORX_GMF) ENSURE(c->d_wpart, c->d_wpart_cap, (size_t)(nw + 256) * D * sizeof(float));   // + stage-1 rows of dense_reduce
-    const int64_t list_stride = 2 * B;
-    // exact mode on the float4 dims below 2^28 rows: the plan of the pairwise step (roles: rows referenced twice get
-    // plain stores; staging plan + reduction tree for hot rows), made once for all K steps.  Otherwise byte flags +
-    // atomics for every duplicate.
-    const bool role_bits = mode == MODE_EXACT && orx_fused_can_inline_apply(D) && U->rows < (1LL << 28) && V->rows < (1LL << 28) && !(fb & 1);
-    const bool staging = role_bits && !(fb & 8);
-    // the previous step's duplicated rows are applied by extra blocks of the next step's launch, as in the pairwise step
-    // (WRMF 27.1 -> see DESIGN 4.4; fb bit 2: separate dup_apply launches)
-    const bool inline_apply = role_bits && K > 1 && orx_plan_v2(true) && !(fb & 2);
-    PairPlan plan;
-    memset(&plan, 0, sizeof(plan));
-    if (role_bits) {
-        CHECK(orx_table_scratch(U, true)); CHECK(orx_table_scratch(V, true)); CHECK(orx_table_scratch(b, true));
-        const int nb_total = orx_dedup_buckets(U->rows) + orx_dedup_buckets(V->rows);
-        CHECK(orx_exact_buffers(c, U, V, K, B, mode, true, inline_apply, staging, nb_total, nslot, &plan));
-        if (opt->kind == ORX_ADAM) plan.min_late = 1;      // Adam: fixed summation order for every row referenced >= 3 times (api.hip)
-        // pairing (round 6): as in orx_pairwise_step -- SGD, float4 dims with >= 2 samples per wavefront, paused for 32 calls when a plan
-        // accepts few pairs.  ORX_NO_PAIR=1 / ORX_POINT_NO_PAIR=1 / ORX_FORCE_FALLBACK bit 4: off
-        if (orx_pairing_wanted(mode, true, opt->kind, D, B, fb) && getenv("ORX_POINT_NO_PAIR") == nullptr) {
-            if (c->pair_pause > 0) c->pair_pause -= 1;
-            else CHECK(orx_pairing_buffers(c, B, D, &plan));
-        }
-        ENSURE(c->d_partial, c->d_partial_cap, (size_t)K * nslot * 2 * sizeof(float));      // (orx_exact_buffers sized it for its own shape: a chunk)
-    } else if (mode == MODE_EXACT) {
-        ENSURE(c->d_dflag, c->d_dflag_cap, (size_t)K * 2 * B);
-        ENSURE(c->d_dlist, c->d_dlist_cap, (size_t)K * list_stride * sizeof(uint32_t));
-        ENSURE(c->d_dcount, c->d_dcount_cap, (size_t)K * sizeof(int));
-        DedupArgs d;
-        memset(&d, 0, sizeof(d));
-        d.uid = du; d.pid = di; d.nid = di; d.id_stride = ds;
-        d.dflag = c->d_dflag; d.dlist = c->d_dlist; d.dcount = c->d_dcount;
-        d.flag_stride = 2 * B; d.list_stride = list_stride;
-        d.nU = B; d.nP = B; d.nN = 0; d.NU = U->rows; d.NI = V->rows;
-        d.nbu = orx_dedup_buckets(U->rows); d.nbi = orx_dedup_buckets(V->rows);
-        ORX_HIP(hipMemsetAsync(c->d_dcount, 0, (size_t)K * sizeof(int), c->stream));
-        CHECK(orx_launch_dedup(c, d, K));
-    }
-    PointArgs a;
-    memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b->w; a.w = w ? w->w : nullptr;
-    a.gU = U->gsum; a.gV = V->gsum; a.gb = b->gsum;
-    a.aU = sU.s0; a.aV = sV.s0; a.ab = sb.s0;
-    a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = D;
-    a.lr = opt->lr; a.eps = orx_rule_eps(opt);
-    a.invB = 1.0f / (float)B; a.l2w = l2w; a.a_w = a_w; a.b_w = b_w;
-    a.sigmoid = (model == ORX_WRMF && (flags & ORX_POINT_SIGMOID)) ? 1 : 0;
-    a.wpartial = c->d_wpart; a.err = c->d_err;
-    // GMF on the float4 kernels: the Dense(1) gradient is reduced and applied by the last workgroups of the step's own launch
-    const bool dense_tail = model == ORX_GMF && orx_point_dense_tail_ok(D);
-    if (dense_tail) {
-        // the partial rows and the group rows behind them start out EMPTY (all ones); every launch hands them back that way
-        const size_t nrows = (size_t)orx_point_wparts(D, B) + (size_t)orx_point_reducers(D, B) - 1;
-        ORX_HIP(hipMemsetAsync(c->d_wpart, 0xff, nrows * D * sizeof(float), c->stream));
-        a.wt_nred = orx_point_reducers(D, B); a.wt_rows = c->d_wpart + (size_t)orx_point_wparts(D, B) * D;
-        const bool to_gout = mode == MODE_ACCUM || lazy_adam;                        // (Adam: adam_sweep_kernel applies the gradient)
-        a.wt_gout = to_gout ? w->gsum : nullptr; a.wt_acc = to_gout ? nullptr : sw.s0; a.wt_optkind = to_gout ? -1 : opt->kind;
-    }
-    if (role_bits) { a.role_bits = 1; a.gU2 = U->gsum2; a.gV2 = V->gsum2; a.gb2 = b->gsum2; a.readyU = U->ready; a.readyV = V->ready; }
-    PairArgs pa;                                 // view of the same tables for dup_apply_kernel / hot_reduce_kernel / the in-launch apply
-    memset(&pa, 0, sizeof(pa));
-    pa.U = U->w; pa.V = V->w; pa.b = b->w; pa.gU = U->gsum; pa.gV = V->gsum; pa.gb = b->gsum;
-    if (role_bits) { pa.gU2 = U->gsum2; pa.gV2 = V->gsum2; pa.gb2 = b->gsum2; pa.role_bits = 1; pa.readyU = U->ready; pa.readyV = V->ready; }
-    CHECK(orx_epochs_reserve(c, K, {U, V}));      // epochs tag the ready flags: one per step
-    pa.aU = sU.s0; pa.aV = sV.s0; pa.ab = sb.s0; pa.B = B; pa.D = D; pa.lr = a.lr; pa.eps = a.eps;
-    if (lazy_adam) {
-        CHECK(orx_lazy_adam_fill(opt, U, V, b, sU, sV, sb, !lazy_resume, K, &a));
-        // (the view for dup_apply_kernel / the in-launch apply: the same, but its replay loops)
-        pa.a2U = a.a2U; pa.a2V = a.a2V; pa.a2b = a.a2b; pa.lastU = a.lastU; pa.lastV = a.lastV; pa.lastb = a.lastb;
-        pa.lrt = a.lrt; pa.b1 = a.b1; pa.b2 = a.b2; pa.eps = a.eps; pa.newton = a.newton;
-    }
-    const int64_t chunk = role_bits ? plan.chunk : K;
-    for (int64_t s0 = 0; s0 < K; s0 += chunk) {
-    const int64_t kc = (K - s0 < chunk) ? (K - s0) : chunk;
-    ExactChunk ck;
-    if (role_bits) {
-        c->plan_label = plan.pair_tpw > 1 ? dl + s0 * ds : nullptr;
-        const int rc_plan = orx_exact_plan_chunk(c, U, V, du + s0 * ds, di + s0 * ds, di + s0 * ds, ds, B, B, 0, kc, B, true, inline_apply, staging, plan, &ck);
-        c->plan_label = nullptr;
-        CHECK(rc_plan);
-    }
-    const bool inl = inline_apply && !ck.hot && !ck.dense_dups;      // (many duplicated rows / reduction-tree levels: separate launches, api.hip)
-    for (int64_t i = 0; i < kc; ++i) {
-        const int64_t s = s0 + i;
-        a.label = dl + s * ds;
-        a.partial = c->d_partial + (size_t)s * nslot * 2;
-        a.wt_l2slot = a.partial + 2 * nw;
-        if (role_bits) {
-            a.uid = c->d_ids2 + (size_t)i * 3 * plan.Bp; a.iid = a.uid + plan.Bp;
-            a.ids4 = plan.pair_tpw > 1 ? c->d_ids4 + (size_t)i * B : nullptr;      // (with pairing the SoA copy is not written: the records are the input)
-            orx_exact_step_views(c, plan, i, B, D, ck.use_stage, &pa);
-            a.refinfo = pa.refinfo; a.segstart = pa.segstart; a.stage = pa.stage; a.stageb = pa.stageb;
-        } else {
-            a.uid = du + s * ds; a.iid = di + s * ds;
-            a.dflag = c->d_dflag + (size_t)s * 2 * B;
-            pa.dlist = c->d_dlist + (size_t)s * list_stride; pa.dcount = c->d_dcount + s;
-        }
-        if (lazy_adam) { opt->t += 1; a.step_t = pa.step_t = (int)opt->t; }
-        a.n_apply_blocks = 0;
-        if (role_bits) {
-            a.epoch = pa.epoch = ++c->epoch;
-            if (inl && i > 0) {                  // this launch also applies the duplicated rows of step i-1
-                pa.n_apply_blocks = orx_apply_blocks(B, D);
-                pa.prev_dlist = c->d_dlist + (size_t)(i - 1) * plan.list_stride; pa.prev_dcount = c->d_dcount + (i - 1);
-                a.n_apply_blocks = pa.n_apply_blocks;
-                a.ap = pa;
-            }
-        }
-        CHECK(orx_launch_point_fused(c, model, opt->kind, mode, a));
-        if (mode == MODE_EXACT) {
-            for (int l = 0; l < ck.tree_levels; ++l) CHECK(orx_launch_hot_reduce(c, pa, l));
-            if (!inl || i == kc - 1) CHECK(orx_launch_dup_apply(c, opt->kind, pa));
-        }
-        float lr_t = lazy_adam ? opt->h_lrt[(size_t)opt->t] : 0.f;
-        if (mode == MODE_ACCUM) CHECK(orx_adam_dense_step(c, opt, {{U, sU}, {V, sV}, {b, sb}}, &lr_t));
-        if (model == ORX_GMF) {                  // dense Dense(1) kernel: reduce partials, apply the dense rule
-            if (mode == MODE_ACCUM || lazy_adam) {
-                if (!dense_tail) CHECK(orx_launch_dense_reduce(c, c->d_wpart, orx_point_wparts(D, B), D, w->w, a.l2w, w->gsum, a.partial + 2 * nw, nullptr, -1, 0.f, 0.f));
-                CHECK(orx_launch_adam_sweep(c, w->w, sw.s0, sw.s1, w->gsum, D, lr_t, opt->p0, opt->p1, opt->p2));
-            } else if (!dense_tail) {        // reduce + dense SGD / Adagrad rule in one launch
-                CHECK(orx_launch_dense_reduce(c, c->d_wpart, orx_point_wparts(D, B), D, w->w, a.l2w, nullptr, a.partial + 2 * nw, sw.s0, opt->kind, opt->lr, a.eps));
-            }
-        }
-    }
-    }
-    ReduceArgs r;
-    r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nslot;
-    CHECK(orx_launch_loss_reduce(c, r, K));
-    CHECK(fetch_losses(c, K, loss_out, l2_out));
-    if (!(flags & ORX_IDS_DEVICE)) return orx_check_index_error(c);
-    return ORX_OK;
-}
-
-extern "C" int orx_pointwise_loss(orx_ctx* c, int model, orx_table* U, orx_table* V, orx_table* b, orx_table* w,
-                                  const int32_t* uid, const int32_t* iid, const float* label,
-                                  int64_t B, float a_w, float b_w, int flags, float* loss_out, float* l2_out) {
-    if (U) CHECK(orx_table_sync(U));
-    if (V) CHECK(orx_table_sync(V));
-    if (b) CHECK(orx_table_sync(b));
-    if (w) CHECK(orx_table_sync(w));
-    ORX_ARG(c, "orx_pointwise_loss: NULL context");
-    CHECK(check_point_tables(model, U, V, b, w));
-    ORX_ARG(B > 0 && uid && iid && label, "orx_pointwise_loss: empty batch or NULL pointer");
-    ORX_HIP(hipSetDevice(c->device));
-    StepInputs in;
-    CHECK(orx_stage_steps(c, 1, B, B, flags, {{uid, 1}, {iid, 1}}, {{label, 1}}, &in));
-    const int D = U->dim;
-    const int nw = orx_point_nwaves(D, B);
-    const int nslot = nw + (model == ORX_GMF ? 1 : 0);
-    ENSURE(c->d_partial, c->d_partial_cap, (size_t)nslot * 2 * sizeof(float));
-    ENSURE(c->d_loss, c->d_loss_cap, 2 * sizeof(double));
-    PointArgs a;
-    memset(&a, 0, sizeof(a));
-    a.U = U->w; a.V = V->w; a.b = b->w; a.w = w ? w->w : nullptr;
-    a.B = B; a.NU = U->rows; a.NI = V->rows; a.D = D;
-    a.invB = 1.0f / (float)B; a.l2w = 1.f; a.a_w = a_w; a.b_w = b_w;
-    a.sigmoid = (model == ORX_WRMF && (flags & ORX_POINT_SIGMOID)) ? 1 : 0;
-    a.partial = c->d_partial; a.err = c->d_err;
-    a.uid = in.id[0]; a.iid = in.id[1]; a.label = in.f[0];
-    CHECK(orx_launch_point_fused(c, model, ORX_SGD, MODE_LOSS, a));
-    if (model == ORX_GMF) CHECK(orx_launch_dense_reduce(c, nullptr, 0, D, w->w, 0.f, nullptr, c->d_partial + 2 * nw, nullptr, -1, 0.f, 0.f));
-    ReduceArgs r;
-    r.partial = c->d_partial; r.out = c->d_loss; r.nwaves = nslot;
-    CHECK(orx_launch_loss_reduce(c, r, 1));
-    CHECK(fetch_losses(c, 1, loss_out, l2_out));
-    return orx_check_index_error(c);
-}
 
 extern "C" int orx_gather_rows(orx_ctx* ctx, orx_table* t, orx_table* bias, const int32_t* ids, int64_t n,
                                float* out, int64_t out_stride) {

@@ -3,7 +3,7 @@
 // which deliver the weights of a pairwise draw, are in api_sampler.hip.)
 //
 // Nothing is computed here.  The entry points check what only they can refuse and hand over to the bodies of the plain steps
-// (orx_pairwise_step_impl and its kin: api.hip, api_subset.hip, api_more.hip), which carry the two knobs as arguments: the weight
+// (orx_pairwise_step_impl and its kin: api_exact.hip, api_subset.hip), which carry the two knobs as arguments: the weight
 // pointer reaches the fused kernels as PairArgs::wt / SubsetArgs::wt, where a non-NULL pointer selects their compile-time weighted
 // variants -- the plain entry points launch the kernels they always launched --, and l2_reg is the l2w the kernels always had.
 #include <cmath>

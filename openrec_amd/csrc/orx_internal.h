@@ -196,6 +196,12 @@ int orx_table_side(orx_table* t);                               // allocate the 
 int orx_opt_slots(orx_opt* opt, orx_table* t, OptSlots* out);   // allocate optimizer slots
 int stage_ids(orx_ctx* c, const int32_t* host, int64_t n, int64_t off);   // H2D into ctx->d_ids
 int fetch_losses(orx_ctx* c, int64_t K, float* loss_out, float* l2_out);
+// ORX_HOST_TIMING=1: a wall-clock mark on the host's way through a train-step call (first: the call's first mark), and their print-out
+void ht_mark(const char* what, bool first = false);
+void ht_dump();
+// no read-back (api.hip): take in the plan counters an earlier call left behind, if they have arrived; leave this call's behind its last launch
+int plan_stats_poll(orx_ctx* c);
+int plan_stats_leave(orx_ctx* c, int64_t kc, int64_t B, bool pairing_on, const int64_t key[5]);
 
 // ---------------------------------- the host driver of the train steps (api_steps.hip) ---
 struct Carve {                                // consecutive 256-byte aligned pieces of one device buffer
@@ -296,7 +302,7 @@ int orx_pointwise_subset_impl(orx_ctx* c, int model, orx_opt* opt, orx_table* U,
                               const int32_t* uid, const int32_t* iid, const float* label,
                               int64_t K, int64_t B, int64_t id_stride, float a_w, float b_w, float l2w, int flags, int train_mask,
                               float* loss_out, float* l2_out);
-// host setup the pairwise and the pointwise step call share (api.hip)
+// host setup the pairwise and the pointwise step call share (api_exact.hip, the driver of the exact steps: DESIGN 4.5za)
 int orx_fallback_bits();                                          // ORX_FORCE_FALLBACK, read per call
 int orx_epochs_reserve(orx_ctx* c, int64_t K, std::initializer_list<orx_table*> tables);     // K step epochs; on wrap-around the tables clear their tags
 int orx_apply_blocks(int64_t B, int D);                           // blocks of a step's launch that apply the previous step's duplicated rows

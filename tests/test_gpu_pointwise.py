@@ -233,3 +233,39 @@ def test_gmf_dense_gradient_inside_the_launch(optkind, D, B, monkeypatch):
             assert rel_err(a[k], c[k]) < tol, (what, k, rel_err(a[k], c[k]))
     # the kernel MOVED (the test cannot pass on a gradient that never reached w)
     assert np.abs(got["w"] - w).max() > 0
+
+
+@pytest.mark.parametrize("model,optkind", [("wrmf", "sgd"), ("gmf", "adagrad")])
+def test_call_longer_than_a_plan_chunk(model, optkind):
+    """One call of K = 260 steps -- more than the 256 steps one plan chunk holds -- against the oracle, as test_random_batches_vs_oracle
+    compares and with its tolerance.  Tables this small against B = 96 bring every duplicate class (rows referenced once, twice, three
+    times and more) into both chunks.  (Not against the same steps as two calls of 130, bit for bit: rows referenced three times or
+    more in so small a step add with fp32 atomics, in arrival order -- 466 elements of U and 495 of V differed by up to 9.3e-10
+    between the two ways, 3 of the 260 l2 sums by 3.0e-8, before the two step calls shared a host driver, and as many after.)"""
+    from openrec_amd import runtime as rt
+    from oracle import numpy_oracle as orc
+    K, B, D, NU, NI = 260, 96, 32, 500, 400
+    rng = np.random.default_rng(260)
+    U = rng.uniform(-.05, .05, (NU, D)).astype(np.float32); V = rng.uniform(-.05, .05, (NI, D)).astype(np.float32)
+    b = rng.uniform(-.05, .05, (NI, 1)).astype(np.float32); w = rng.uniform(-.3, .3, (D, 1)).astype(np.float32)
+    uid = rng.integers(0, NU, (K, B)).astype(np.int32); iid = rng.integers(0, NI, (K, B)).astype(np.int32)
+    lab = (rng.uniform(size=(K, B)) < 0.4).astype(np.float32)
+    most = np.array([[np.bincount(x[s], minlength=n).max() for s in range(K)] for x, n in ((uid, NU), (iid, NI))])
+    assert (most == 2).any() and (most >= 3).any() and (most >= 3)[:, 256:].any()      # (the short second chunk has them too)
+    tU = rt.Table(NU, D).write(U); tV = rt.Table(NI, D).write(V); tb = rt.Table(NI, 1).write(b)
+    tw = rt.Table(D, 1).write(w) if model == "gmf" else None
+    l, l2 = rt.pointwise_step(model, _opt(rt, optkind), tU, tV, tb, tw, uid, iid, lab, K=K, B=B, a=1.5, b_w=0.7)
+    assert len(l) == K and len(l2) == K
+    oo = {"sgd": orc.SGD, "adagrad": orc.Adagrad}[optkind](**OPT_KW[optkind])
+    for s in range(K):
+        if model == "gmf":
+            lr, l2r = orc.gmf_step(U, V, b, w, uid[s], iid[s], lab[s], oo)
+        else:
+            lr, l2r = orc.wrmf_step(U, V, b, uid[s], iid[s], lab[s], oo, a=1.5, b_w=0.7)
+        print(s, "loss", abs(l[s] - lr) / abs(lr), "l2", abs(l2[s] - l2r) / abs(l2r))
+        assert abs(l[s] - lr) <= TOL * abs(lr) and abs(l2[s] - l2r) <= TOL * abs(l2r), s
+    print("tables", rel_err(tU.read(), U), rel_err(tV.read(), V), rel_err(tb.read(), b))
+    assert rel_err(tU.read(), U) < TOL and rel_err(tV.read(), V) < TOL and rel_err(tb.read(), b) < TOL
+    if model == "gmf":
+        print("w", rel_err(tw.read(), w))
+        assert rel_err(tw.read(), w) < TOL
