@@ -4,8 +4,10 @@
 on the same batches, the sampled-softmax run of that example (`train_steps`, N drawn negatives).  Both are trained on one half
 of the users and recommend for the OTHER half from their histories alone; the script prints Recall@K of the held-out users' last
 item for both.  --precision bf16 runs the full-softmax steps with bf16 operands on the matrix cores (fp32 sums and tables).
+--sampled S trains the second model on ONE list of S uniformly drawn candidates shared by the whole batch
+(`train_steps_sampled`, with the log-Q correction) in the place of N negatives per sample.
 
-    python examples/seqrec_full_softmax.py [--steps 300] [--k 20] [--precision fp32|bf16]
+    python examples/seqrec_full_softmax.py [--steps 300] [--k 20] [--precision fp32|bf16] [--sampled S]
 """
 import argparse
 import os
@@ -29,6 +31,7 @@ def main():
     ap.add_argument("--seq", type=int, default=5)
     ap.add_argument("--k", type=int, default=20)
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32")
+    ap.add_argument("--sampled", type=int, default=0, metavar="S", help="a shared list of S candidates per step in the place of N negatives per sample")
     args = ap.parse_args()
     raw, NU, NI = planted()
     train_half = raw["user_id"] % 2 == 0
@@ -55,11 +58,17 @@ def main():
         want = (step + 1) % 100 == 0
         lf = full.train_steps_full(opt_full, bt["seq_item_id"], bt["seq_len"], bt["label"], want_loss=want,
                                    precision=args.precision)
-        ls = sampled.train_steps(opt_sampled, bt["seq_item_id"], bt["seq_len"], bt["label"], nid, loss="softmax", want_loss=want)
+        if args.sampled:                        # uniform proposal: Q = 1 / NI, so -log(S Q) on the candidates, -log Q on the label
+            cand = rng.integers(0, NI, args.sampled).astype(np.int32)
+            ls = sampled.train_steps_sampled(opt_sampled, bt["seq_item_id"], bt["seq_len"], bt["label"], cand,
+                                             cand_offset=np.full(args.sampled, np.log(NI / args.sampled), np.float32),
+                                             pos_offset=np.full(args.batch, np.log(NI), np.float32), want_loss=want)
+        else:
+            ls = sampled.train_steps(opt_sampled, bt["seq_item_id"], bt["seq_len"], bt["label"], nid, loss="softmax", want_loss=want)
         if want or step + 1 == args.steps:
             tail = f"loss {lf[0][0]:.4f} / {ls[0][0]:.4f}  " if lf is not None else ""
             print(f"  step {step + 1:5d}: {tail}recall@{args.k} for the held-out users: full softmax {recall_at(full, ev, args.k):.4f}, "
-                  f"sampled softmax (N = {args.negatives}) {recall_at(sampled, ev, args.k):.4f}")
+                  f"sampled softmax ({f'S = {args.sampled} shared' if args.sampled else f'N = {args.negatives}'}) {recall_at(sampled, ev, args.k):.4f}")
 
 
 if __name__ == "__main__":

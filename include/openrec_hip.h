@@ -1291,7 +1291,7 @@ int orx_seqrec_loss(orx_ctx* ctx, int loss_kind /* orx_multineg_kind */,
  *                              path (ORX_FS_BF16 adds two bf16 copies, (Bp + NIp) rows of D rounded up to 32, to the scratch)
  * Not offered: ORX_FS_BF16 with label sets (their sparse part scores the label entries from the fp32 rows), fp16 or fp8 operands,
  * bf16 tables or optimizer state; dropout between the query and the item table (hidden layers: orx_tower_step, below); K-step calls; UCML / L2 scoring; hit masking (every
- * item is one column); a sampled or sharded item axis; label sets in the user-table form (orx_seqrec_full_sets_step and
+ * item is one column); a sharded item axis (a SAMPLED one is orx_sampled_softmax_step, below); label sets in the user-table form (orx_seqrec_full_sets_step and
  * orx_tower_sets_step have them). */
 int orx_fullsoftmax_step(orx_ctx* ctx, orx_opt* opt,
                          orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
@@ -1318,6 +1318,78 @@ int orx_seqrec_full_loss(orx_ctx* ctx,
                          const float* weight /* NULL ok */, const float* item_offset /* [NI], NULL ok */,
                          int64_t B, int64_t n, int mode, float denom, float scale, int32_t chunk_items, int flags,
                          float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+
+/* ---- SAMPLED SOFTMAX OVER A SHARED CANDIDATE LIST (api_sampledsoftmax.hip, kernels_sampledsoftmax.hip): one train step in which
+ * every sample of the batch is scored against ONE list of S sampled items -- the objective the YouTube retrieval tower was trained
+ * with, TensorFlow's sampled_softmax_loss with its default of candidates shared across the batch.  The B x S logits are a dense
+ * product on the matrix cores (fp32, v_mfma_f32_16x16x4_f32); no B x S matrix is stored; only B + S item rows are touched.
+ * Sample i has a query q_i and a label pid[i].  q_i = U[uid[i]] (orx_sampled_softmax_*: the user-table form) or the pooled q_i of
+ * bag i with orx_bag_pool's bits (orx_seqrec_sampled_*: the SeqRec form; hist, item, bias, the bags, mode and denom as in
+ * orx_seqrec_step).  cand[S] are int32 item ids; cand_offset[S], pos_offset[B] and weight[B] are optional; all live where the ids live.
+ *   s_i+    = scale * (q_i . V[pid_i]  + b[pid_i])  + pos_off_i
+ *   s_ic    = scale * (q_i . V[cand_c] + b[cand_c]) + cand_off_c         c in [0, S);  no "+ b" with bias == NULL
+ *             removed (-inf) when cand_c == pid_i and ORX_SS_MASK_HITS is set, or when cand_off_c == -inf
+ *   lse_i   = logsumexp(s_i+, live s_ic)                  evaluated with the maximum subtracted
+ *   l_i     = lse_i - s_i+
+ *   loss    = (1/B) sum_i w_i l_i                         w_i = weight[i], 1 when weight == NULL
+ *   l2_loss = 1/2 sum_i (|q_i|^2 + |V[pid_i]|^2)          the looked-up rows, as orx_inbatch_step; candidates are not regularised
+ *   J       = loss + l2_reg * l2_loss
+ * -log(S Q(item)) as cand_offset with -log Q(pid) as pos_offset is the usual correction for a proposal Q.  Repeated ids in cand
+ * are separate columns.  Gradients, on the pre-step tables, with c_i = w_i / B and pi = exp(s - lse_i):
+ *   a_ic = c_i pi_ic,   a_i+ = -c_i sum_c pi_ic                           (the pi themselves, never 1 - pi_+)
+ *   g_q[i]        = scale * (sum_c a_ic V[cand_c] + a_i+ V[pid_i]) + l2_reg q_i
+ *   g_V (entry c) = scale * sum_i a_ic q_i                                g_b (entry c) = scale * sum_i a_ic
+ *   g_V (label i) = scale * a_i+ q_i + l2_reg V[pid_i]                    g_b (label i) = scale * a_i+
+ * The apply.  The item side is ONE row list of B + S entries, the labels and then the candidates, under the sparse rule of
+ * orx_apply_rows on its deterministic route: a row that appears more than once has its entries summed in list order.  The item
+ * table and the bias stay lazy under Adam.  The query side is orx_apply_rows on uid, or orx_seqrec_step's history route.  The
+ * counter advances once per step, after the reads and before the applies.  One step per call.  train_mask: ORX_TRAIN_USER (the
+ * user / history table) | _ITEM | _BIAS, 0 = every table given; a table outside the mask is read and never written; with neither
+ * item nor bias in the mask the candidates' gradient pass is not launched.
+ * A uid or pid outside its table, or a bad id in a bag, drops its sample (c_i = 0: no loss, no l2, no gradient); a candidate id
+ * outside the item table drops its column in every row.  Both report ORX_ERR_INDEX as orx_inbatch_step reports it; no id is ever
+ * an address and the context stays usable.  A row whose candidates are all removed has l_i = 0 and no gradient beyond its l2 terms.
+ * No float atomics: every sum has a fixed order that depends on (B, S, D) alone, so losses, row losses and tables are
+ * bit-repeatable.  The forward-only calls give the step's loss_out / l2_out bit for bit and, if row_loss_out is not NULL, l_i
+ * ([B], where the ids live; 0 for a dropped sample).  loss_out == l2_out == NULL with ORX_IDS_DEVICE: no host synchronisation.
+ * flags: ORX_IDS_DEVICE, ORX_SS_MASK_HITS.  B == 0: ORX_OK, nothing is launched; S == 0 is allowed (every l_i is 0).
+ * ORX_ERR_ARG before any device work, naming the call: what orx_fullsoftmax_step / orx_seqrec_full_step refuse for the same
+ * tables, bags, optimizer, l2_reg and train mask; D > 256; S outside [0, 65536]; scale not finite or <= 0; any other flag
+ * (ORX_FS_BF16 by name).
+ *   orx_sampled_softmax_geometry   no device: out = { query rows per workgroup, candidates per tile, sample chunks of the
+ *                                  candidates' pass, padded dim, scratch bytes of a step with every table trained }
+ * Not offered: bf16 operands; the tower form (orx_tower_step's layers under this objective); label sets; K-step calls; a
+ * candidate sampler (any device int32 list serves; orx_sampler_set_proposal's alias table draws one). */
+enum orx_sampled_softmax_flags { ORX_SS_MASK_HITS = 0x1000 };     /* a candidate equal to the row's own label is no negative */
+int orx_sampled_softmax_step(orx_ctx* ctx, orx_opt* opt,
+                             orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                             const int32_t* uid, const int32_t* pid, const int32_t* cand /* [S] */,
+                             const float* weight /* NULL ok */, const float* pos_offset /* [B], NULL ok */,
+                             const float* cand_offset /* [S], NULL ok */,
+                             int64_t B, int64_t S, float scale, float l2_reg, int train_mask, int flags,
+                             float* loss_out, float* l2_out);
+int orx_sampled_softmax_loss(orx_ctx* ctx,
+                             orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
+                             const int32_t* uid, const int32_t* pid, const int32_t* cand /* [S] */,
+                             const float* weight /* NULL ok */, const float* pos_offset /* [B], NULL ok */,
+                             const float* cand_offset /* [S], NULL ok */,
+                             int64_t B, int64_t S, float scale, int flags,
+                             float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
+int orx_sampled_softmax_geometry(int64_t B, int64_t S, int32_t D, int64_t out[5]);
+int orx_seqrec_sampled_step(orx_ctx* ctx, orx_opt* opt,
+                            orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                            const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */, const int32_t* cand /* [S] */,
+                            const float* weight /* NULL ok */, const float* pos_offset /* [B], NULL ok */,
+                            const float* cand_offset /* [S], NULL ok */,
+                            int64_t B, int64_t n, int64_t S, int mode, float denom, float scale, float l2_reg,
+                            int train_mask, int flags, float* loss_out, float* l2_out);
+int orx_seqrec_sampled_loss(orx_ctx* ctx,
+                            orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
+                            const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */, const int32_t* cand /* [S] */,
+                            const float* weight /* NULL ok */, const float* pos_offset /* [B], NULL ok */,
+                            const float* cand_offset /* [S], NULL ok */,
+                            int64_t B, int64_t n, int64_t S, int mode, float denom, float scale, int flags,
+                            float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
 
 /* ---- THE HISTORY-POOLED RECOMMENDER WITH A DENSE TOWER (api_tower.hip, kernels_tower.hip): the reference's YouTubeRec /
  * VanillaYouTubeRec -- user-feature embeddings beside the pooled history, hidden layers, the softmax over all items.  Sample i:

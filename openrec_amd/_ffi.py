@@ -21,6 +21,7 @@ ORX_TRAIN_SIDE, ORX_TRAIN_TOWER = 16, 32                      # enum orx_tower_t
 ORX_MN_SOFTMAX, ORX_MN_LOGSIG = 0, 1                          # enum orx_multineg_kind
 ORX_BAG_MEAN, ORX_BAG_FIXED = 0, 1                            # enum orx_bag_mode
 ORX_IB_MASK_HITS = 0x1000                                     # enum orx_inbatch_flags
+ORX_SS_MASK_HITS = 0x1000                                     # enum orx_sampled_softmax_flags
 ORX_FS_BF16 = 0x2000                                          # enum orx_flags: the single-label full-softmax calls
 ORX_TOPK_BF16_PREFILTER = 0x2000                              # orx_recommend_topk: the same bit, a speed option that changes no output bit
 ORX_IB_BF16 = 0x2000                                          # enum orx_inbatch_flags: the same bit on the in-batch calls
@@ -131,6 +132,14 @@ SIGNATURES = {
                                      c_int32, c_int32, c_int, c_int, _fp, _fp]),
     "orx_seqrec_full_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64, c_int, c_float, c_float, c_int32, c_int,
                                      _fp, _fp, _fp]),
+    "orx_sampled_softmax_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_float, c_float, c_int, c_int,
+                                         _fp, _fp]),
+    "orx_sampled_softmax_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_float, c_int, _fp, _fp, _fp]),
+    "orx_sampled_softmax_geometry": (c_int, [c_int64, c_int64, c_int32, POINTER(c_int64)]),
+    "orx_seqrec_sampled_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_int64, c_int, c_float,
+                                        c_float, c_float, c_int, c_int, _fp, _fp]),
+    "orx_seqrec_sampled_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_int64, c_int, c_float,
+                                        c_float, c_int, _fp, _fp, _fp]),
     "orx_tower_step": (c_int, [_p, _p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64,
                                c_int, c_float, c_float, c_float, c_float, c_int32, c_int32, c_int, c_int, _fp, _fp]),
     "orx_tower_loss": (c_int, [_p, _p, _p, _p, c_int32, _pp, _pp, c_int32, _pp, _pp, c_int, _ip, _ip, _ip, _fp, _fp, c_int64, c_int64,

@@ -298,6 +298,13 @@ void user_form(FullSoftmaxForm* f, const char* fn, bool is_step, orx_ctx* c, orx
 
 }  // namespace
 
+std::shared_ptr<FullSoftmaxForm> orx_fullsoftmax_user_form(const char* fn, bool is_step, orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V,
+                                                           orx_table* b, const int32_t* uid, int64_t B, float l2_reg, int flags) {
+    auto f = std::make_shared<FullSoftmaxForm>();
+    user_form(f.get(), fn, is_step, c, opt, U, V, b, uid, B, l2_reg, flags);
+    return f;
+}
+
 extern "C" int orx_fullsoftmax_step(orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V, orx_table* b,
                                     const int32_t* uid, const int32_t* pid, const float* weight, const float* item_offset,
                                     int64_t B, float scale, float l2_reg, int32_t chunk_items, int32_t chunk_samples, int train_mask, int flags,

@@ -321,6 +321,14 @@ void bag_form(BagForm* f, const char* fn, bool is_step, orx_ctx* c, orx_opt* opt
 
 }  // namespace
 
+std::shared_ptr<FullSoftmaxForm> orx_seqrec_bag_form(const char* fn, bool is_step, orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item,
+                                                     orx_table* b, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode,
+                                                     float denom, float l2_reg, int flags) {
+    auto f = std::make_shared<BagForm>();
+    bag_form(f.get(), fn, is_step, c, opt, hist, item, b, bag_ptr, bag_items, B, n, mode, denom, l2_reg, flags);
+    return f;
+}
+
 extern "C" int orx_seqrec_full_step(orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item, orx_table* b,
                                     const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid, const float* weight,
                                     const float* item_offset, int64_t B, int64_t n, int mode, float denom, float scale, float l2_reg,

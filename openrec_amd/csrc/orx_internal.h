@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <initializer_list>
 #include <map>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -1233,6 +1234,40 @@ int orx_fullsoftmax_drive_step(orx_ctx* c, orx_opt* opt, FullSoftmaxForm& f, orx
 int orx_fullsoftmax_drive_loss(orx_ctx* c, FullSoftmaxForm& f, orx_table* V, orx_table* b, const int32_t* pid, const LabelLists* sets,
                                const float* weight, const float* item_offset, int64_t B, float scale, int32_t chunk_items, int flags,
                                float* loss_out, float* l2_out, float* row_loss_out);
+
+// the two query forms of the drivers above for a caller in another file (api_sampledsoftmax.hip): the user-table form
+// (api_fullsoftmax.hip) and the bag form (api_seqrec.hip), built as orx_fullsoftmax_step / orx_seqrec_full_step build theirs
+std::shared_ptr<FullSoftmaxForm> orx_fullsoftmax_user_form(const char* fn, bool is_step, orx_ctx* c, orx_opt* opt, orx_table* U, orx_table* V,
+                                                           orx_table* b, const int32_t* uid, int64_t B, float l2_reg, int flags);
+std::shared_ptr<FullSoftmaxForm> orx_seqrec_bag_form(const char* fn, bool is_step, orx_ctx* c, orx_opt* opt, orx_table* hist, orx_table* item,
+                                                     orx_table* b, const int32_t* bag_ptr, const int32_t* bag_items, int64_t B, int64_t n, int mode,
+                                                     float denom, float l2_reg, int flags);
+
+// kernels_sampledsoftmax.hip (orx_sampled_softmax_step / orx_seqrec_sampled_step and their forwards): one step of the softmax of
+// every sample's label against ONE shared list of S candidates.  Bp = B rounded up to 64, Sp = S rounded up to 64 (at least 64),
+// Dp = D rounded up to 16; every [Bp] / [Sp] / [..][Dp] array is scratch carved from the context's d_tmp
+struct SampledSoftmaxArgs {
+    const float* Q; const float* V; const float* b;       // read only; Q [NQ][D]: the user table, or the pooled rows; b NULL: no item bias
+    const int32_t* qid; const int32_t* pid; const int32_t* cand;      // DEVICE [B] rows of Q and labels, [S] candidates
+    const float* wt; const float* poff; const float* coff;            // DEVICE [B] weights, [B] label offsets, [S] candidate offsets (NULL: 1 / 0 / 0)
+    int64_t B; int64_t Bp; int64_t NQ; int64_t NI; int64_t S; int64_t Sp;
+    int D; int Dp; int gs; int ncs; int tps; int mask;    // ncs sample chunks of tps tiles of 64 (the column kernel); mask: ORX_SS_MASK_HITS
+    float scale; float invB; float l2w;
+    float* xq; float* xp; float* xc;                      // [Bp][Dp] query rows, label rows; [Sp][Dp] candidate rows
+    int32_t* key; float* cw; float* sq; float* pb; float* po;         // [Bp] pid or -1, w / B, |q|^2 + |v|^2, the label's bias and offset
+    int32_t* ckey; float* cb; float* co;                  // [Sp] item id or -1 (bad id, offset -inf, padding), bias, offset
+    int32_t* list;                                        // [B + S] the item side's rows: labels, then candidates (-1: dropped); NULL: a forward
+    float* rmax; float* cn; float* rowloss;               // [Bp] the row maximum m_i (+inf: a dead row), c_i / tot_i, l_i
+    float* gpc; float* bpc;                               // [ncs][Sp][Dp], [ncs][Sp] the column kernel's partial tiles and bias sums
+    float* gu; float* gi;                                 // [B][gs] query gradient rows; [B + S][gs] item gradient rows, the bias gradient in column D
+    float* partial;                                       // [orx_sampledsoftmax_npartials(B)][2] loss / l2 partials: one per workgroup of the row kernel
+    int* err;
+};
+struct SampledSoftmaxPlan { int64_t Bp, Sp, Dp, tps, ncs; };
+inline int orx_sampledsoftmax_npartials(int64_t B) { return (int)((B + 63) >> 6); }
+void orx_sampledsoftmax_plan(int64_t B, int64_t S, int32_t D, SampledSoftmaxPlan* p);
+int orx_launch_sampledsoftmax_rows(orx_ctx* ctx, const SampledSoftmaxArgs& a, bool query_grads);      // gather; the row kernel (gi set: the label entries too)
+int orx_launch_sampledsoftmax_cols(orx_ctx* ctx, const SampledSoftmaxArgs& a);                        // the column kernel and its finishing pass
 
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {

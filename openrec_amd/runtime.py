@@ -718,6 +718,74 @@ def fullsoftmax_geometry(B, items, D, chunk_items=0, chunk_samples=0):
                 scratch_bytes=int(out[5]))
 
 
+# ---- sampled softmax over a shared candidate list (orx_sampled_softmax_step / _loss; SeqRec.step_sampled is the pooled-query form) ----
+def _candidates_arg(what, cand, cand_offset, dev):
+    """the shared candidate list of a sampled-softmax call and its optional offsets, where the ids live
+    -> (cand pointer, offset pointer, S, keepalives)"""
+    (pc,), (S,), _, kc = _id_lists(what, (cand,), dev)
+    if S > 65536:
+        raise ValueError(f"{what}: S = {S} candidates; S must be in [0, 65536]")
+    po, ko = _floats_arg(what, "cand_offset", cand_offset, dev, S, "cand")
+    return pc, po, S, (kc, ko)
+
+
+def _sampled_args(what, user, item, bias, uid, pid, cand, weights, cand_offset, pos_offset, scale):
+    """the checks and the pointers sampled_softmax_step and sampled_softmax_loss share; every bad argument is a ValueError
+    raised here, before the library is called"""
+    _dot_tables(what, user.shape[1], item.shape[1], item.shape[0], bias)
+    if user.shape[1] > 256:
+        raise ValueError(f"{what}: dim {user.shape[1]} above 256")
+    scale = _scale_arg(what, scale)
+    _, B, _, dev, (pu, pp, pw, ppo), keep = _list_args(what, ("uid", "pid"), (uid, pid), (("weights", weights, 0), ("pos_offset", pos_offset, 1)))
+    pc, pco, S, kc = _candidates_arg(what, cand, cand_offset, dev)
+    user.ctx.after_torch(*keep, *_flat_keep(kc))
+    return B, S, dev, (pu, pp, pc, pw, ppo, pco), scale, (keep, kc)
+
+
+def sampled_softmax_step(opt, user, item, bias, uid, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0,
+                         mask_hits=True, l2_reg=0.0, train=None, want_loss=True):
+    """One train step on the sampled softmax over a SHARED candidate list (orx_sampled_softmax_step): sample i's label pid[i]
+    against the S items of cand, the same list for every row -- s_ic = scale (u_i . V[cand_c] + b[cand_c]) + cand_offset[c],
+    s_i+ = scale (u_i . V[pid_i] + b[pid_i]) + pos_offset[i], l_i = logsumexp(s_i+, s_i.) - s_i+ -- as a dense product on the
+    matrix cores, without a B x S matrix.  cand: int32 [S], S <= 65536, repeated ids are separate columns; cand_offset [S]
+    (-log(S Q(item)) is the usual correction, -inf removes a column), pos_offset [B] and weights [B] live where the ids live.
+    mask_hits: a candidate equal to the row's own label is no negative.  The objective is loss + l2_reg * l2_loss, l2_loss over
+    the 2B looked-up rows.  Every table takes the sparse rule, the item table and the bias on the B + S rows pid | cand, and
+    stays lazy under Adam.  train: None, or a subset of ("user", "item", "bias").  Returns (loss[1], l2[1]) as numpy float32
+    when want_loss, else None (device ids: no host synchronisation).  Bad arguments raise ValueError before the library is
+    called; an id outside its table IndexError (a bad uid / pid drops its sample, a bad candidate its column)."""
+    what = "sampled_softmax_step"
+    mask = _train_mask(train, bias, what) or 0
+    l2c = _coef_arg(what, "l2_reg", l2_reg)
+    B, S, dev, ptrs, scale, keep = _sampled_args(what, user, item, bias, uid, pid, cand, weights, cand_offset, pos_offset, scale)
+    out, lp, l2p = _loss_outputs(1, want_loss)
+    check(user.ctx._lib.orx_sampled_softmax_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, B, S, scale, l2c, mask,
+                                                 _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0), lp, l2p))
+    _keep_tables(opt, (user, item, bias))
+    return out
+
+
+def sampled_softmax_loss(user, item, bias, uid, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0,
+                         mask_hits=True, per_row=False):
+    """forward only: (loss, l2_loss) of one batch of sampled_softmax_step -- the step's own numbers bit for bit on the same
+    tables; no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+    what = "sampled_softmax_loss"
+    B, S, dev, ptrs, scale, keep = _sampled_args(what, user, item, bias, uid, pid, cand, weights, cand_offset, pos_offset, scale)
+    out, lp, l2p = _loss_outputs(1, True)
+    rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
+    check(user.ctx._lib.orx_sampled_softmax_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, S, scale,
+                                                 _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0), lp, l2p, rp))
+    return _forward_result(out, rows, dev)
+
+
+def sampled_softmax_geometry(B, S, D):
+    """what the launchers of sampled_softmax_step do for (B, S, D): a dict of query rows per workgroup, candidates per tile,
+    sample chunks of the candidates' pass, the padded dim and the scratch bytes of a step.  No device is needed."""
+    out = (c_int64 * 5)()
+    check(_ffi.load().orx_sampled_softmax_geometry(int(B), int(S), int(D), out))
+    return dict(rows=int(out[0]), tile=int(out[1]), sample_chunks=int(out[2]), dim=int(out[3]), scratch_bytes=int(out[4]))
+
+
 _POINT = {"gmf": _ffi.ORX_GMF, "wrmf": _ffi.ORX_WRMF}
 
 
@@ -2599,6 +2667,51 @@ class SeqRec:
         label_weights= as step_full takes them"""
         return _full_loss("SeqRec.loss_full", self, self._FULL_LOSS, self._full_lists(bags), (self.H, self.V, self.b), pid, weights, item_offset,
                           scale, chunk_items, per_row, labels, label_weights, precision)
+
+    def _sampled_args(self, what, bags, pid, cand, weights, cand_offset, pos_offset, scale):
+        scale = _scale_arg(what, scale)
+        pp, pi, B, n, dev, kb = _bags_arg(what, bags)
+        (ppid,), (npid,), _, keep = _id_lists(what, (pid,), dev)          # (on the side the bags are on)
+        if npid != B:
+            raise ValueError(f"{what}: {B} bags and {npid} label ids (one label per bag)")
+        pc, pco, S, kc = _candidates_arg(what, cand, cand_offset, dev)
+        pw, kw = _floats_arg(what, "weights", weights, dev, B, "the bags")
+        ppo, kpo = _floats_arg(what, "pos_offset", pos_offset, dev, B, "the bags")
+        self.ctx.after_torch(*_flat_keep((kb, keep, kc)), kw, kpo)
+        for t in (self.H, self.V, self.b):
+            if t is not None:
+                t._sync_pending()
+        return B, n, S, dev, (pp, pi, ppid, pc, pw, ppo, pco), scale, (kb, keep, kc, kw, kpo)
+
+    def step_sampled(self, opt, bags, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0, mask_hits=True,
+                     l2_reg=0.0, train=None, want_loss=True):
+        """One train step on the sampled softmax over a SHARED candidate list (orx_seqrec_sampled_step): bag i's pooled vector
+        and its label pid[i] against the S items of cand -- rt.sampled_softmax_step's objective with the user row replaced by
+        q.  cand [S], cand_offset [S], pos_offset [B] and weights [B] live where the bags live.  The history table goes `step`'s
+        route; the item table and the bias take the sparse rule on the B + S rows pid | cand.  train: None, or a subset of
+        ("history", "item", "bias").  -> (loss[1], l2[1]) as numpy float32 when want_loss, else None.  Bad arguments raise
+        ValueError before the library is called; a malformed device list or an id outside its table IndexError."""
+        what = "SeqRec.step_sampled"
+        mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
+        l2c = _coef_arg(what, "l2_reg", l2_reg)
+        B, n, S, dev, ptrs, scale, keep = self._sampled_args(what, bags, pid, cand, weights, cand_offset, pos_offset, scale)
+        out, lp, l2p = _loss_outputs(1, want_loss)
+        check(self.ctx._lib.orx_seqrec_sampled_step(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, S, self._mode,
+                                                    self._denom, scale, l2c, mask, _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0),
+                                                    lp, l2p))
+        _keep_tables(opt, (self.H, self.V, self.b))
+        return out
+
+    def loss_sampled(self, bags, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0, mask_hits=True, per_row=False):
+        """forward only: (loss, l2_loss) of one batch of step_sampled -- the step's own numbers bit for bit on the same tables;
+        no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
+        what = "SeqRec.loss_sampled"
+        B, n, S, dev, ptrs, scale, keep = self._sampled_args(what, bags, pid, cand, weights, cand_offset, pos_offset, scale)
+        out, lp, l2p = _loss_outputs(1, True)
+        rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
+        check(self.ctx._lib.orx_seqrec_sampled_loss(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, S, self._mode, self._denom,
+                                                    scale, _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0), lp, l2p, rp))
+        return _forward_result(out, rows, dev)
 
     def user_table(self, bags, out=None):
         """-> a Table [B, D] of the pooled rows q_i of `bags` (out: a Table of that shape to write; None: one owned by this
