@@ -5,7 +5,8 @@ on the same batches, the sampled-softmax run of that example (`train_steps`, N d
 of the users and recommend for the OTHER half from their histories alone; the script prints Recall@K of the held-out users' last
 item for both.  --precision bf16 runs the full-softmax steps with bf16 operands on the matrix cores (fp32 sums and tables).
 --sampled S trains the second model on ONE list of S uniformly drawn candidates shared by the whole batch
-(`train_steps_sampled`, with the log-Q correction) in the place of N negatives per sample.
+(`train_steps_sampled`, with the log-Q correction) in the place of N negatives per sample; with --precision bf16 that step too
+takes bf16 operands.
 
     python examples/seqrec_full_softmax.py [--steps 300] [--k 20] [--precision fp32|bf16] [--sampled S]
 """
@@ -62,7 +63,8 @@ def main():
             cand = rng.integers(0, NI, args.sampled).astype(np.int32)
             ls = sampled.train_steps_sampled(opt_sampled, bt["seq_item_id"], bt["seq_len"], bt["label"], cand,
                                              cand_offset=np.full(args.sampled, np.log(NI / args.sampled), np.float32),
-                                             pos_offset=np.full(args.batch, np.log(NI), np.float32), want_loss=want)
+                                             pos_offset=np.full(args.batch, np.log(NI), np.float32), want_loss=want,
+                                             precision=args.precision)
         else:
             ls = sampled.train_steps(opt_sampled, bt["seq_item_id"], bt["seq_len"], bt["label"], nid, loss="softmax", want_loss=want)
         if want or step + 1 == args.steps:

@@ -1322,7 +1322,7 @@ int orx_seqrec_full_loss(orx_ctx* ctx,
 /* ---- SAMPLED SOFTMAX OVER A SHARED CANDIDATE LIST (api_sampledsoftmax.hip, kernels_sampledsoftmax.hip): one train step in which
  * every sample of the batch is scored against ONE list of S sampled items -- the objective the YouTube retrieval tower was trained
  * with, TensorFlow's sampled_softmax_loss with its default of candidates shared across the batch.  The B x S logits are a dense
- * product on the matrix cores (fp32, v_mfma_f32_16x16x4_f32); no B x S matrix is stored; only B + S item rows are touched.
+ * product on the matrix cores (fp32, v_mfma_f32_16x16x4_f32; bf16 operands under ORX_SS_BF16); no B x S matrix is stored; only B + S item rows are touched.
  * Sample i has a query q_i and a label pid[i].  q_i = U[uid[i]] (orx_sampled_softmax_*: the user-table form) or the pooled q_i of
  * bag i with orx_bag_pool's bits (orx_seqrec_sampled_*: the SeqRec form; hist, item, bias, the bags, mode and denom as in
  * orx_seqrec_step).  cand[S] are int32 item ids; cand_offset[S], pos_offset[B] and weight[B] are optional; all live where the ids live.
@@ -1352,15 +1352,34 @@ int orx_seqrec_full_loss(orx_ctx* ctx,
  * No float atomics: every sum has a fixed order that depends on (B, S, D) alone, so losses, row losses and tables are
  * bit-repeatable.  The forward-only calls give the step's loss_out / l2_out bit for bit and, if row_loss_out is not NULL, l_i
  * ([B], where the ids live; 0 for a dropped sample).  loss_out == l2_out == NULL with ORX_IDS_DEVICE: no host synchronisation.
- * flags: ORX_IDS_DEVICE, ORX_SS_MASK_HITS.  B == 0: ORX_OK, nothing is launched; S == 0 is allowed (every l_i is 0).
+ * flags: ORX_IDS_DEVICE, ORX_SS_MASK_HITS, ORX_SS_BF16.  B == 0: ORX_OK, nothing is launched; S == 0 is allowed (every l_i is 0).
  * ORX_ERR_ARG before any device work, naming the call: what orx_fullsoftmax_step / orx_seqrec_full_step refuse for the same
- * tables, bags, optimizer, l2_reg and train mask; D > 256; S outside [0, 65536]; scale not finite or <= 0; any other flag
- * (ORX_FS_BF16 by name).
+ * tables, bags, optimizer, l2_reg and train mask; D > 256; S outside [0, 65536]; scale not finite or <= 0; any other flag.
+ * ORX_SS_BF16 (mixed precision; all four entry points; kernels_sampledsoftmax16.hip).  With bf(x) = x rounded to nearest even to
+ * bfloat16, the three products run on v_mfma_f32_16x16x32_bf16:
+ *   s_i+  = scale * (sum_d bf(q_id) bf(V[pid_i]_d)  + b[pid_i])  + pos_off_i     an fp32 sum of the same rounded products
+ *   s_ic  = scale * (sum_d bf(q_id) bf(V[cand_c]_d) + b[cand_c]) + cand_off_c    fp32 sums; bias, offsets and scale fp32
+ *   lse_i, l_i, c_i, a_ic, a_i+ and the hit / -inf / bad-id masking: as above, in fp32, from these s
+ *   g_q[i]        = scale * (sum_c bf(a_ic) bf(V[cand_c]) + a_i+ bf(V[pid_i])) + l2_reg q_i      a_i+ unrounded, element-wise fp32
+ *   g_V (label i) = scale * a_i+ bf(q_i) + l2_reg V[pid_i]            g_V (entry c) = scale * sum_i bf(a_ic) bf(q_i)
+ *   g_b (label i) = scale * a_i+                                      g_b (entry c) = scale * sum_i a_ic     (the unrounded coefficients)
+ * l2_loss, the l2 terms, the master tables, the optimizer state, the lazy-Adam bookkeeping, the sort and every apply use the
+ * unrounded fp32 rows; in the SeqRec form the pooled query is produced in fp32 with orx_bag_pool's bits and rounded by this
+ * objective's gather.  Everything promised above holds under the flag: no float atomics, fixed summation orders that depend on
+ * (B, S, D) alone, bit-repeatable losses, row losses and tables, the forward's bits equal to the step's at the same flag, dead
+ * samples and columns, S == 0, B == 0, ORX_ERR_INDEX.  The row side is split over blocks of 64 query rows x candidate chunks:
+ * with ntiles = Sp / 64 and want = max(1, 512 / (Bp / 64)), a chunk has tpc = min(ntiles, max(4, ceil(ntiles / want))) tiles.
  *   orx_sampled_softmax_geometry   no device: out = { query rows per workgroup, candidates per tile, sample chunks of the
- *                                  candidates' pass, padded dim, scratch bytes of a step with every table trained }
- * Not offered: bf16 operands; the tower form (orx_tower_step's layers under this objective); label sets; K-step calls; a
+ *                                  candidates' pass, padded dim, scratch bytes of a step with every table trained } of the fp32 path
+ *   orx_sampled_softmax_bf16_geometry   the same under ORX_SS_BF16: out = { query rows per workgroup, candidates per tile, sample
+ *                                  chunks of the candidates' pass, candidate chunks of the row side, the dim padded to the
+ *                                  instruction's k-block of 32, scratch bytes }
+ * Not offered: fp16 / fp8 operands, bf16 tables or optimizer state; the tower form (orx_tower_step's layers under this objective); label sets; K-step calls; a
  * candidate sampler (any device int32 list serves; orx_sampler_set_proposal's alias table draws one). */
-enum orx_sampled_softmax_flags { ORX_SS_MASK_HITS = 0x1000 };     /* a candidate equal to the row's own label is no negative */
+enum orx_sampled_softmax_flags {
+    ORX_SS_MASK_HITS = 0x1000,    /* a candidate equal to the row's own label is no negative */
+    ORX_SS_BF16 = 0x2000          /* the value of ORX_FS_BF16: bf16 operands on the matrix cores, fp32 sums, tables and optimizer state */
+};
 int orx_sampled_softmax_step(orx_ctx* ctx, orx_opt* opt,
                              orx_table* user, orx_table* item, orx_table* bias /* NULL ok */,
                              const int32_t* uid, const int32_t* pid, const int32_t* cand /* [S] */,
@@ -1376,6 +1395,7 @@ int orx_sampled_softmax_loss(orx_ctx* ctx,
                              int64_t B, int64_t S, float scale, int flags,
                              float* loss_out, float* l2_out, float* row_loss_out /* NULL ok */);
 int orx_sampled_softmax_geometry(int64_t B, int64_t S, int32_t D, int64_t out[5]);
+int orx_sampled_softmax_bf16_geometry(int64_t B, int64_t S, int32_t D, int64_t out[6]);
 int orx_seqrec_sampled_step(orx_ctx* ctx, orx_opt* opt,
                             orx_table* hist, orx_table* item, orx_table* bias /* NULL ok */,
                             const int32_t* bag_ptr, const int32_t* bag_items, const int32_t* pid /* [B] */, const int32_t* cand /* [S] */,

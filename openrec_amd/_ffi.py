@@ -25,6 +25,7 @@ ORX_SS_MASK_HITS = 0x1000                                     # enum orx_sampled
 ORX_FS_BF16 = 0x2000                                          # enum orx_flags: the single-label full-softmax calls
 ORX_TOPK_BF16_PREFILTER = 0x2000                              # orx_recommend_topk: the same bit, a speed option that changes no output bit
 ORX_IB_BF16 = 0x2000                                          # enum orx_inbatch_flags: the same bit on the in-batch calls
+ORX_SS_BF16 = 0x2000                                          # enum orx_sampled_softmax_flags: the same bit on the sampled-softmax calls
 ORX_TOWER_BF16 = 0x4000                                       # enum orx_flags: the orx_tower_* calls, the layers' products in bf16
 ORX_SHARD_OVERLAP, ORX_SHARD_NO_DEDUP, ORX_SHARD_DEDUP, ORX_COMM_ID_BYTES = 0x100, 0x200, 0x400, 128
 ORX_DLRM_INTERACT_ITSELF, ORX_DLRM_SIGMOID_BOT, ORX_DLRM_SIGMOID_TOP, ORX_DLRM_LOSS_BCE, ORX_DLRM_REFERENCE_COMPAT = 1, 2, 4, 8, 16
@@ -136,6 +137,7 @@ SIGNATURES = {
                                          _fp, _fp]),
     "orx_sampled_softmax_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_float, c_int, _fp, _fp, _fp]),
     "orx_sampled_softmax_geometry": (c_int, [c_int64, c_int64, c_int32, POINTER(c_int64)]),
+    "orx_sampled_softmax_bf16_geometry": (c_int, [c_int64, c_int64, c_int32, POINTER(c_int64)]),
     "orx_seqrec_sampled_step": (c_int, [_p, _p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_int64, c_int, c_float,
                                         c_float, c_float, c_int, c_int, _fp, _fp]),
     "orx_seqrec_sampled_loss": (c_int, [_p, _p, _p, _p, _ip, _ip, _ip, _ip, _fp, _fp, _fp, c_int64, c_int64, c_int64, c_int, c_float,

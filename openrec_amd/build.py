@@ -22,11 +22,11 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
             "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value",
             "-Wno-bitwise-instead-of-logical"]
-# per source file: kernels_fullsoftmax16.hip, kernels_inbatch16.hip, kernels_topk16.hip and kernels_tower16.hip are compiled without the packed fp32 VALU instructions
+# per source file: kernels_fullsoftmax16.hip, kernels_inbatch16.hip, kernels_sampledsoftmax16.hip, kernels_topk16.hip and kernels_tower16.hip are compiled without the packed fp32 VALU instructions
 # (v_pk_add / mul / fma_f32), so their fp32 epilogues are the scalar-per-lane code the fp32 walks' are
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"kernels_fullsoftmax16.hip": NO_PACKED_FP32, "kernels_inbatch16.hip": NO_PACKED_FP32,
-               "kernels_topk16.hip": NO_PACKED_FP32, "kernels_tower16.hip": NO_PACKED_FP32}
+               "kernels_sampledsoftmax16.hip": NO_PACKED_FP32, "kernels_topk16.hip": NO_PACKED_FP32, "kernels_tower16.hip": NO_PACKED_FP32}
 
 
 def _sources():

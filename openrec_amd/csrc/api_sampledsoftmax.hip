@@ -1,7 +1,8 @@
 // The sampled softmax over a shared candidate list: the checks, the scratch layout, the staging of host lists and the driver of
 // every call on this objective, and the C-ABI entry points orx_sampled_softmax_step / _loss / _geometry (the user-table form) and
 // orx_seqrec_sampled_step / _loss (the bag form).  include/openrec_hip.h has the semantics, kernels_sampledsoftmax.hip the
-// kernels; the query comes from a FullSoftmaxForm (orx_internal.h), built by the builders the full softmax's entry points use.
+// kernels (kernels_sampledsoftmax16.hip those under ORX_SS_BF16); the query comes from a FullSoftmaxForm (orx_internal.h), built
+// by the builders the full softmax's entry points use.
 //
 // Per step: a table outside the mask is finished first, every other one stays lazy; the form touches its rows and writes Q; the
 // rows of V and b under pid and cand are touched; gather, the row kernel, [the column kernel and its finish]; [Adam: the counter
@@ -18,6 +19,7 @@ namespace {
 struct Layout {
     SampledSoftmaxPlan plan;
     size_t cand, coff, xq, xp, xc, key, cw, sq, pb, po, ckey, cb, co, rmax, cn, rowloss, list, gpc, bpc, gu, gi, sorted;
+    size_t xq16, xc16, spos, apos, pm, pE, gqc;             // ORX_SS_BF16
 };
 
 int check_shape(const char* fn, int64_t B, int64_t S, int32_t D, float scale) {
@@ -29,21 +31,29 @@ int check_shape(const char* fn, int64_t B, int64_t S, int32_t D, float scale) {
 }
 
 int check_flags(const char* fn, int flags) {
-    ORX_ARG(!(flags & ORX_FS_BF16), "%s: ORX_FS_BF16 is not offered (the sampled softmax runs in fp32)", fn);
-    ORX_ARG((flags & ~(ORX_IDS_DEVICE | ORX_SS_MASK_HITS)) == 0, "%s: flags other than ORX_IDS_DEVICE | ORX_SS_MASK_HITS (0x%x)", fn, flags);
+    ORX_ARG((flags & ~(ORX_IDS_DEVICE | ORX_SS_MASK_HITS | ORX_SS_BF16)) == 0, "%s: flags other than ORX_IDS_DEVICE | ORX_SS_MASK_HITS | ORX_SS_BF16 (0x%x)", fn, flags);
     return ORX_OK;
 }
 
-// host_cand / host_coff: a piece for the host list; grads: the step's buffers, query_side / item_side the two gradient sides'
-void layout(Carve* cv, int64_t B, int64_t S, int32_t D, bool host_cand, bool host_coff, bool grads, bool query_side, bool item_side, Layout* l) {
+// host_cand / host_coff: a piece for the host list; grads: the step's buffers, query_side / item_side the two gradient sides';
+// bf16: ORX_SS_BF16 -- the bf16 copies in the place of the candidates' fp32 copy, and what the split row side passes on
+void layout(Carve* cv, int64_t B, int64_t S, int32_t D, bool host_cand, bool host_coff, bool grads, bool query_side, bool item_side, bool bf16, Layout* l) {
     memset(l, 0, sizeof(*l));
     SampledSoftmaxPlan& p = l->plan;
-    orx_sampledsoftmax_plan(B, S, D, &p);
+    if (bf16) orx_sampledsoftmax16_plan(B, S, D, &p); else orx_sampledsoftmax_plan(B, S, D, &p);
     const int gs = (D + 1 + 3) & ~3;
     const size_t row = (size_t)p.Bp * sizeof(float), rows = row * p.Dp, col = (size_t)p.Sp * sizeof(float), cols = col * p.Dp;
     if (host_cand) l->cand = cv->take((size_t)S * sizeof(int32_t));
     if (host_coff) l->coff = cv->take((size_t)S * sizeof(float));
-    l->xq = cv->take(rows); l->xp = cv->take(rows); l->xc = cv->take(cols);
+    l->xq = cv->take(rows); l->xp = cv->take(rows);
+    if (bf16) {
+        l->xq16 = cv->take((size_t)p.Bp * p.Dk * sizeof(unsigned short)); l->xc16 = cv->take((size_t)p.Sp * p.Dk * sizeof(unsigned short));
+        l->spos = cv->take(row); l->apos = cv->take(row);
+        l->pm = cv->take(row * p.ncc); l->pE = cv->take(row * p.ncc);
+        if (grads && query_side) l->gqc = cv->take(rows * p.ncc);
+    } else {
+        l->xc = cv->take(cols);
+    }
     l->key = cv->take(row); l->cw = cv->take(row); l->sq = cv->take(row); l->pb = cv->take(row); l->po = cv->take(row);
     l->ckey = cv->take(col); l->cb = cv->take(col); l->co = cv->take(col);
     l->rmax = cv->take(row); l->cn = cv->take(row); l->rowloss = cv->take(row);
@@ -76,7 +86,8 @@ int prepare(orx_ctx* c, FullSoftmaxForm& f, const Call& k, float l2w, bool grads
     Carve cv;
     f.carve(&cv, grads);
     Layout l;
-    layout(&cv, k.B, k.S, V->dim, host && k.S, host && k.S && k.cand_offset, grads, grads && f.query_side, item_side, &l);
+    const bool bf16 = (k.flags & ORX_SS_BF16) != 0;
+    layout(&cv, k.B, k.S, V->dim, host && k.S, host && k.S && k.cand_offset, grads, grads && f.query_side, item_side, bf16, &l);
     ENSURE(c->d_tmp, c->d_tmp_cap, cv.off);
     FullSoftmaxQuery q;
     memset(&q, 0, sizeof(q));
@@ -103,7 +114,15 @@ int prepare(orx_ctx* c, FullSoftmaxForm& f, const Call& k, float l2w, bool grads
     a.D = V->dim; a.Dp = (int)p.Dp; a.gs = (a.D + 1 + 3) & ~3; a.ncs = (int)p.ncs; a.tps = (int)p.tps;
     a.mask = (k.flags & ORX_SS_MASK_HITS) ? 1 : 0;
     a.scale = k.scale; a.invB = 1.0f / (float)k.B; a.l2w = l2w; a.err = c->d_err;
-    a.xq = fp(l.xq); a.xp = fp(l.xp); a.xc = fp(l.xc);
+    a.xq = fp(l.xq); a.xp = fp(l.xp);
+    if (bf16) {
+        a.xq16 = reinterpret_cast<unsigned short*>(base + l.xq16); a.xc16 = reinterpret_cast<unsigned short*>(base + l.xc16);
+        a.Dk = (int)p.Dk; a.ncc = (int)p.ncc; a.tpc = (int)p.tpc;
+        a.spos = fp(l.spos); a.apos = fp(l.apos); a.pm = fp(l.pm); a.pE = fp(l.pE);
+        if (grads && f.query_side) a.gqc = fp(l.gqc);
+    } else {
+        a.xc = fp(l.xc);
+    }
     a.key = ip(l.key); a.cw = fp(l.cw); a.sq = fp(l.sq); a.pb = fp(l.pb); a.po = fp(l.po);
     a.ckey = ip(l.ckey); a.cb = fp(l.cb); a.co = fp(l.co);
     a.rmax = fp(l.rmax); a.cn = fp(l.cn); a.rowloss = fp(l.rowloss);
@@ -149,8 +168,13 @@ int drive_step(orx_ctx* c, orx_opt* opt, FullSoftmaxForm& f, const Call& k, floa
         a.partial = partial;
         CHECK(f.produce(fa, true));
         CHECK(touch_items(k, a));
-        CHECK(orx_launch_sampledsoftmax_rows(c, a, f.query_side));
-        if (tV || tb) CHECK(orx_launch_sampledsoftmax_cols(c, a));
+        if (k.flags & ORX_SS_BF16) {
+            CHECK(orx_launch_sampledsoftmax16_forward(c, a));
+            CHECK(orx_launch_sampledsoftmax16_grads(c, a));
+        } else {
+            CHECK(orx_launch_sampledsoftmax_rows(c, a, f.query_side));
+            if (tV || tb) CHECK(orx_launch_sampledsoftmax_cols(c, a));
+        }
         if (opt->kind == ORX_ADAM) CHECK(orx_opt_advance(opt, keep, n_keep));      // once per step: after the step's reads, before its applies
         CHECK(f.apply(fa));
         if (tV || tb) {                         // one sort of pid | cand, each table on its own: a row's occurrences are summed in list order
@@ -184,7 +208,8 @@ int drive_loss(orx_ctx* c, FullSoftmaxForm& f, const Call& k, float* loss_out, f
         a.partial = partial;
         CHECK(f.produce(fa, false));
         CHECK(touch_items(k, a));
-        CHECK(orx_launch_sampledsoftmax_rows(c, a, false));
+        if (k.flags & ORX_SS_BF16) CHECK(orx_launch_sampledsoftmax16_forward(c, a));
+        else CHECK(orx_launch_sampledsoftmax_rows(c, a, false));
         if (row_loss_out)
             ORX_HIP(hipMemcpyAsync(row_loss_out, a.rowloss, (size_t)k.B * sizeof(float), host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, c->stream));
         return ORX_OK;
@@ -199,8 +224,19 @@ extern "C" int orx_sampled_softmax_geometry(int64_t B, int64_t S, int32_t D, int
     CHECK(check_shape(fn, B, S, D, 1.0f));
     Carve cv;
     Layout l;
-    layout(&cv, B, S, D, false, false, true, true, true, &l);
+    layout(&cv, B, S, D, false, false, true, true, true, false, &l);
     out[0] = 64; out[1] = 64; out[2] = l.plan.ncs; out[3] = l.plan.Dp; out[4] = (int64_t)cv.off;
+    return ORX_OK;
+}
+
+extern "C" int orx_sampled_softmax_bf16_geometry(int64_t B, int64_t S, int32_t D, int64_t out[6]) {
+    static const char* fn = "orx_sampled_softmax_bf16_geometry";
+    ORX_ARG(out, "%s: NULL out", fn);
+    CHECK(check_shape(fn, B, S, D, 1.0f));
+    Carve cv;
+    Layout l;
+    layout(&cv, B, S, D, false, false, true, true, true, true, &l);
+    out[0] = 64; out[1] = 64; out[2] = l.plan.ncs; out[3] = l.plan.ncc; out[4] = l.plan.Dk; out[5] = (int64_t)cv.off;
     return ORX_OK;
 }
 

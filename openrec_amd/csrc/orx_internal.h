@@ -1262,12 +1262,23 @@ struct SampledSoftmaxArgs {
     float* gu; float* gi;                                 // [B][gs] query gradient rows; [B + S][gs] item gradient rows, the bias gradient in column D
     float* partial;                                       // [orx_sampledsoftmax_npartials(B)][2] loss / l2 partials: one per workgroup of the row kernel
     int* err;
+    // ORX_SS_BF16 (kernels_sampledsoftmax16.hip); otherwise NULL / 0, and xc is NULL under the flag
+    unsigned short* xq16; unsigned short* xc16; int Dk;   // [Bp][Dk], [Sp][Dk] bf16 copies of the query and candidate rows, Dk = D rounded up to 32
+    int ncc; int tpc;                                     // ncc candidate chunks of tpc tiles of 64 (the stats and query-gradient walks)
+    float* spos; float* apos;                             // [Bp] s_i+, a_i+
+    float* pm; float* pE;                                 // [ncc][Bp] a chunk's running maximum and sum
+    float* gqc;                                           // [ncc][Bp][Dp] the query-gradient walk's partial tiles
 };
-struct SampledSoftmaxPlan { int64_t Bp, Sp, Dp, tps, ncs; };
+struct SampledSoftmaxPlan { int64_t Bp, Sp, Dp, tps, ncs, Dk, tpc, ncc; };     // Dk, tpc, ncc: orx_sampledsoftmax16_plan's
 inline int orx_sampledsoftmax_npartials(int64_t B) { return (int)((B + 63) >> 6); }
 void orx_sampledsoftmax_plan(int64_t B, int64_t S, int32_t D, SampledSoftmaxPlan* p);
 int orx_launch_sampledsoftmax_rows(orx_ctx* ctx, const SampledSoftmaxArgs& a, bool query_grads);      // gather; the row kernel (gi set: the label entries too)
 int orx_launch_sampledsoftmax_cols(orx_ctx* ctx, const SampledSoftmaxArgs& a);                        // the column kernel and its finishing pass
+// kernels_sampledsoftmax16.hip (ORX_SS_BF16): the plan above with the candidate chunks of the split row side; gather, the stats
+// walk and the merge; [a.gu: the query-gradient walk] [a.gi: the column walk] and the finishing pass over what is set
+void orx_sampledsoftmax16_plan(int64_t B, int64_t S, int32_t D, SampledSoftmaxPlan* p);
+int orx_launch_sampledsoftmax16_forward(orx_ctx* ctx, const SampledSoftmaxArgs& a);
+int orx_launch_sampledsoftmax16_grads(orx_ctx* ctx, const SampledSoftmaxArgs& a);
 
 // kernels_warp.hip (orx_sampler_pairwise_warp): the pairwise draw of `s`, then candidates one after another until one violates the margin
 struct WarpNegArgs {

@@ -623,7 +623,7 @@ def _scale_arg(what, scale):
 
 
 def _precision_bits(what, precision, labels=None):
-    """precision= of the full-softmax and in-batch calls -> the call's flag bits: "fp32", or "bf16" (ORX_FS_BF16 == ORX_IB_BF16: bf16
+    """precision= of the full-softmax, in-batch and sampled-softmax calls -> the call's flag bits: "fp32", or "bf16" (ORX_FS_BF16 == ORX_IB_BF16 == ORX_SS_BF16: bf16
     operands on the matrix cores, fp32 sums and tables), which the label-set forms do not offer"""
     if precision not in ("fp32", "bf16"):
         raise ValueError(f"{what}: precision = {precision!r}; 'fp32' or 'bf16'")
@@ -743,7 +743,7 @@ def _sampled_args(what, user, item, bias, uid, pid, cand, weights, cand_offset, 
 
 
 def sampled_softmax_step(opt, user, item, bias, uid, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0,
-                         mask_hits=True, l2_reg=0.0, train=None, want_loss=True):
+                         mask_hits=True, l2_reg=0.0, train=None, want_loss=True, precision="fp32"):
     """One train step on the sampled softmax over a SHARED candidate list (orx_sampled_softmax_step): sample i's label pid[i]
     against the S items of cand, the same list for every row -- s_ic = scale (u_i . V[cand_c] + b[cand_c]) + cand_offset[c],
     s_i+ = scale (u_i . V[pid_i] + b[pid_i]) + pos_offset[i], l_i = logsumexp(s_i+, s_i.) - s_i+ -- as a dense product on the
@@ -752,35 +752,45 @@ def sampled_softmax_step(opt, user, item, bias, uid, pid, cand, weights=None, ca
     mask_hits: a candidate equal to the row's own label is no negative.  The objective is loss + l2_reg * l2_loss, l2_loss over
     the 2B looked-up rows.  Every table takes the sparse rule, the item table and the bias on the B + S rows pid | cand, and
     stays lazy under Adam.  train: None, or a subset of ("user", "item", "bias").  Returns (loss[1], l2[1]) as numpy float32
-    when want_loss, else None (device ids: no host synchronisation).  Bad arguments raise ValueError before the library is
-    called; an id outside its table IndexError (a bad uid / pid drops its sample, a bad candidate its column)."""
+    when want_loss, else None (device ids: no host synchronisation).  precision="bf16": the three products take bf16 operands
+    on the matrix cores and the row side is split over candidate chunks (ORX_SS_BF16); sums, tables and optimizer state stay
+    fp32.  Bad arguments raise ValueError before the library is called; an id outside its table IndexError (a bad uid / pid
+    drops its sample, a bad candidate its column)."""
     what = "sampled_softmax_step"
+    bits = _precision_bits(what, precision)
     mask = _train_mask(train, bias, what) or 0
     l2c = _coef_arg(what, "l2_reg", l2_reg)
     B, S, dev, ptrs, scale, keep = _sampled_args(what, user, item, bias, uid, pid, cand, weights, cand_offset, pos_offset, scale)
     out, lp, l2p = _loss_outputs(1, want_loss)
     check(user.ctx._lib.orx_sampled_softmax_step(user.ctx._h, opt._h, user._h, item._h, _bias_h(bias), *ptrs, B, S, scale, l2c, mask,
-                                                 _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0), lp, l2p))
+                                                 _flags(dev, (_ffi.ORX_SS_MASK_HITS if mask_hits else 0) | bits), lp, l2p))
     _keep_tables(opt, (user, item, bias))
     return out
 
 
 def sampled_softmax_loss(user, item, bias, uid, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0,
-                         mask_hits=True, per_row=False):
-    """forward only: (loss, l2_loss) of one batch of sampled_softmax_step -- the step's own numbers bit for bit on the same
-    tables; no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
+                         mask_hits=True, per_row=False, precision="fp32"):
+    """forward only: (loss, l2_loss) of one batch of sampled_softmax_step at the same precision -- the step's own numbers bit
+    for bit on the same tables; no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every sample, a numpy float32 array [B]"""
     what = "sampled_softmax_loss"
+    bits = _precision_bits(what, precision)
     B, S, dev, ptrs, scale, keep = _sampled_args(what, user, item, bias, uid, pid, cand, weights, cand_offset, pos_offset, scale)
     out, lp, l2p = _loss_outputs(1, True)
     rows, rp = _row_loss_buffer(user.ctx, B, dev, per_row)
     check(user.ctx._lib.orx_sampled_softmax_loss(user.ctx._h, user._h, item._h, _bias_h(bias), *ptrs, B, S, scale,
-                                                 _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0), lp, l2p, rp))
+                                                 _flags(dev, (_ffi.ORX_SS_MASK_HITS if mask_hits else 0) | bits), lp, l2p, rp))
     return _forward_result(out, rows, dev)
 
 
-def sampled_softmax_geometry(B, S, D):
+def sampled_softmax_geometry(B, S, D, precision="fp32"):
     """what the launchers of sampled_softmax_step do for (B, S, D): a dict of query rows per workgroup, candidates per tile,
-    sample chunks of the candidates' pass, the padded dim and the scratch bytes of a step.  No device is needed."""
+    sample chunks of the candidates' pass, the padded dim and the scratch bytes of a step; precision="bf16" adds cand_chunks,
+    the candidate chunks of the split row side, and dim is the dim padded to 32.  No device is needed."""
+    if _precision_bits("sampled_softmax_geometry", precision):
+        out = (c_int64 * 6)()
+        check(_ffi.load().orx_sampled_softmax_bf16_geometry(int(B), int(S), int(D), out))
+        return dict(rows=int(out[0]), tile=int(out[1]), sample_chunks=int(out[2]), cand_chunks=int(out[3]), dim=int(out[4]),
+                    scratch_bytes=int(out[5]))
     out = (c_int64 * 5)()
     check(_ffi.load().orx_sampled_softmax_geometry(int(B), int(S), int(D), out))
     return dict(rows=int(out[0]), tile=int(out[1]), sample_chunks=int(out[2]), dim=int(out[3]), scratch_bytes=int(out[4]))
@@ -2684,33 +2694,37 @@ class SeqRec:
         return B, n, S, dev, (pp, pi, ppid, pc, pw, ppo, pco), scale, (kb, keep, kc, kw, kpo)
 
     def step_sampled(self, opt, bags, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0, mask_hits=True,
-                     l2_reg=0.0, train=None, want_loss=True):
+                     l2_reg=0.0, train=None, want_loss=True, precision="fp32"):
         """One train step on the sampled softmax over a SHARED candidate list (orx_seqrec_sampled_step): bag i's pooled vector
         and its label pid[i] against the S items of cand -- rt.sampled_softmax_step's objective with the user row replaced by
         q.  cand [S], cand_offset [S], pos_offset [B] and weights [B] live where the bags live.  The history table goes `step`'s
         route; the item table and the bias take the sparse rule on the B + S rows pid | cand.  train: None, or a subset of
-        ("history", "item", "bias").  -> (loss[1], l2[1]) as numpy float32 when want_loss, else None.  Bad arguments raise
-        ValueError before the library is called; a malformed device list or an id outside its table IndexError."""
+        ("history", "item", "bias").  precision: rt.sampled_softmax_step's (the pooled query is produced in fp32 and rounded by
+        the objective).  -> (loss[1], l2[1]) as numpy float32 when want_loss, else None.  Bad arguments raise ValueError
+        before the library is called; a malformed device list or an id outside its table IndexError."""
         what = "SeqRec.step_sampled"
+        bits = _precision_bits(what, precision)
         mask = _mask_arg(what, train, _SEQ_ROLES, self.b is not None) or 0
         l2c = _coef_arg(what, "l2_reg", l2_reg)
         B, n, S, dev, ptrs, scale, keep = self._sampled_args(what, bags, pid, cand, weights, cand_offset, pos_offset, scale)
         out, lp, l2p = _loss_outputs(1, want_loss)
         check(self.ctx._lib.orx_seqrec_sampled_step(self.ctx._h, opt._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, S, self._mode,
-                                                    self._denom, scale, l2c, mask, _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0),
+                                                    self._denom, scale, l2c, mask, _flags(dev, (_ffi.ORX_SS_MASK_HITS if mask_hits else 0) | bits),
                                                     lp, l2p))
         _keep_tables(opt, (self.H, self.V, self.b))
         return out
 
-    def loss_sampled(self, bags, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0, mask_hits=True, per_row=False):
-        """forward only: (loss, l2_loss) of one batch of step_sampled -- the step's own numbers bit for bit on the same tables;
-        no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
+    def loss_sampled(self, bags, pid, cand, weights=None, cand_offset=None, pos_offset=None, scale=1.0, mask_hits=True, per_row=False,
+                     precision="fp32"):
+        """forward only: (loss, l2_loss) of one batch of step_sampled at the same precision -- the step's own numbers bit for bit
+        on the same tables; no table changes.  per_row=True: (loss, l2_loss, l) with l_i of every bag, a numpy float32 array [B]"""
         what = "SeqRec.loss_sampled"
+        bits = _precision_bits(what, precision)
         B, n, S, dev, ptrs, scale, keep = self._sampled_args(what, bags, pid, cand, weights, cand_offset, pos_offset, scale)
         out, lp, l2p = _loss_outputs(1, True)
         rows, rp = _row_loss_buffer(self.ctx, B, dev, per_row)
         check(self.ctx._lib.orx_seqrec_sampled_loss(self.ctx._h, self.H._h, self.V._h, _bias_h(self.b), *ptrs, B, n, S, self._mode, self._denom,
-                                                    scale, _flags(dev, _ffi.ORX_SS_MASK_HITS if mask_hits else 0), lp, l2p, rp))
+                                                    scale, _flags(dev, (_ffi.ORX_SS_MASK_HITS if mask_hits else 0) | bits), lp, l2p, rp))
         return _forward_result(out, rows, dev)
 
     def user_table(self, bags, out=None):

@@ -400,14 +400,15 @@ class PairwiseRecommender(Recommender):
                                    l2_reg=self.l2_reg, train=train, want_loss=want_loss, precision=precision)
 
     def train_steps_sampled(self, optimizer, user_id, p_item_id, cand_item_id, want_loss=True, sample_weight=None, cand_offset=None,
-                            pos_offset=None, scale=1.0, mask_hits=True, train=None):
+                            pos_offset=None, scale=1.0, mask_hits=True, train=None, precision="fp32"):
         """Beyond the reference API: one step on the sampled softmax over a SHARED candidate list in one device call
         (rt.sampled_softmax_step): every sample's positive against the S items of cand_item_id [S], the same list for every
         row.  user_id / p_item_id shaped [B].  cand_offset [S] (-log(S Q(item)) is the usual correction, -inf removes a
         column) and pos_offset [B] (-log Q(positive)) are added to the logits; sample_weight: per-sample weights.  mask_hits:
         a candidate equal to the row's own positive is no negative.  Every table takes the sparse rule.  train: None, or a
         subset of ("user", "item", "bias").  The objective is loss + l2_reg * l2_loss with the model's l2_reg; the returned l2
-        is the unscaled l2_loss.  Dot-product models only: it goes through no tape, and UCML raises NotImplementedError."""
+        is the unscaled l2_loss.  precision: rt.sampled_softmax_step's ("bf16": bf16 operands on the matrix cores, fp32 sums and
+        tables).  Dot-product models only: it goes through no tape, and UCML raises NotImplementedError."""
         if self._model != "bpr":
             raise NotImplementedError(f"{type(self).__name__}.train_steps_sampled: the sampled-softmax step scores by dot products "
                                       "(u.v + b); UCML's squared-distance scores are not supported by it")
@@ -416,4 +417,4 @@ class PairwiseRecommender(Recommender):
         wts, coff, poff = (_ids(x) if x is not None else None for x in (sample_weight, cand_offset, pos_offset))
         return rt.sampled_softmax_step(opt, U, V, b, _ids(user_id), _ids(p_item_id), _ids(cand_item_id), weights=wts, cand_offset=coff,
                                        pos_offset=poff, scale=scale, mask_hits=mask_hits, l2_reg=self.l2_reg, train=train,
-                                       want_loss=want_loss)
+                                       want_loss=want_loss, precision=precision)

@@ -128,18 +128,20 @@ class VanillaYouTubeRec(Recommender):
         return self._net.loss(self._bags(seq_item_id, seq_len), _ids(label), _ids(n_item_id), loss=loss, weights=wts, neg_offset=off)
 
     def train_steps_sampled(self, optimizer, seq_item_id, seq_len, label, cand_item_id, sample_weight=None, cand_offset=None,
-                            pos_offset=None, scale=1.0, mask_hits=True, want_loss=True, train=None):
+                            pos_offset=None, scale=1.0, mask_hits=True, want_loss=True, train=None, precision="fp32"):
         """One train step on the sampled softmax over a SHARED candidate list (rt.SeqRec.step_sampled): every history's label
         against the S items of cand_item_id [S], the same list for every row -- the objective the YouTube tower was trained
         with.  cand_offset [S] (-log(S Q(item)); -inf removes a column), pos_offset [B] (-log Q(label)), sample_weight [B].
         Every table takes the sparse rule; train: None, or a subset of ("history", "item", "bias").  The objective is
-        loss + l2_reg_embed * l2_loss.  -> (loss[1], l2[1]) as float32 arrays when want_loss, else None"""
+        loss + l2_reg_embed * l2_loss.  precision: rt.SeqRec.step_sampled's.  -> (loss[1], l2[1]) as float32 arrays when
+        want_loss, else None"""
         if self._deep:
             raise NotImplementedError(f"{type(self).__name__}: with hidden layers the shared-candidate step is not offered; use train_steps_full")
         opt = optimizer.native(self._net.ctx) if hasattr(optimizer, "native") else optimizer
         wts, coff, poff = (_ids(x) if x is not None else None for x in (sample_weight, cand_offset, pos_offset))
         return self._net.step_sampled(opt, self._bags(seq_item_id, seq_len), _ids(label), _ids(cand_item_id), weights=wts, cand_offset=coff,
-                                      pos_offset=poff, scale=scale, mask_hits=mask_hits, l2_reg=self.l2_reg, train=train, want_loss=want_loss)
+                                      pos_offset=poff, scale=scale, mask_hits=mask_hits, l2_reg=self.l2_reg, train=train, want_loss=want_loss,
+                                      precision=precision)
 
     def train_steps_full(self, optimizer, seq_item_id, seq_len, label, sample_weight=None, item_offset=None, want_loss=True,
                          train=None, precision="fp32", tower_precision="fp32", **user_features):
